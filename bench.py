@@ -14,16 +14,28 @@ widths from scripts/train-vae.sh (encoder 256 x 2 layers x 8 heads, decoder 128 
 --data resident (default): the batches are in HBM before the timed region (`value` is defined on this);
 --data host: every step's batch travels pinned host -> HBM through PinnedBatchPipeline inside the timed region.
 Rank 0 prints ONE JSON line. `value` follows the contract (K steps between barrier + synchronize, max over ranks);
-`ms_per_step_median` is the median of the same K steps timed one by one with HIP events on the step's stream.
+`ms_per_step` = the wall time of those K steps / K; `ms_per_step_median` is the median of the same K steps timed one by one
+with HIP events on the step's stream.
 
-The line also carries
+--dump-outputs DIR: after the timed steps, what the last one handed its caller goes to DIR/<name>.npy in float32 (the
+per-sample losses of that step and the fp32 weights Adam left behind; see dump_outputs). Inputs, weights and ε are seeded:
+the same arguments give the same inputs on every run, so two builds compare file for file. On the default configs[1] step
+two runs of one build end on bit-identical weights and KL (tests/test_step_gpu.py::
+test_identical_benchmark_steps_give_bit_identical_gradients_and_weights checks every gradient over two steps); loss_recon
+and loss_total still sum per-sample pieces with fp32 atomics and agree to fp32 rounding (1.8e-7 relative measured after
+571 steps). Other configurations and paths still add some gradients with fp32 atomics (the token path's embedding
+gradients, LayerNorm launches without a partials buffer, the bias of wgrad batches below the two-pass size): their last
+bits may differ between runs.
+
+A plain run sets up, warms up, times the K steps, [dumps] and prints its line. With --full the line also carries
   roofline     : the step's heavy kernel families, each re-launched on the step's own operands and timed with HIP
                  events on its stream (`families`), and the one with the largest share of the step as the headline:
                  algorithmic bytes (or FLOPs) per launch / average launch duration against the gfx950 peak
                  (profiles/ holds the rocprofv3 summary of the same command)
   cpu_baseline : the CPU oracle (oracle/vae_oracle.py, a restatement of the reference — the MXNet reference itself
                  cannot run here) timed on this node's host cores on a bounded sample of the same workload, same
-                 dropout. A reported baseline, not the optimisation target.
+                 dropout. A reported baseline, not the optimisation target (--no-cpu-baseline leaves it out).
+--decode with --full adds the device-only replay of the captured positions (device_us_per_position, host_share, roofline).
 """
 import argparse
 import json
@@ -294,6 +306,34 @@ def roofline(plan, o, config_id):
             "families": [{k: v for k, v in f.items() if k != "pmc_key"} for f in sorted(fams, key=lambda f: -f["share_ms"])]}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(plan, out_dir, limit_bytes=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files — the per-sample losses of that
+    step (loss_total = reconstruction + kl_weight * KL, loss_recon, loss_kl: [B]) and the flat fp32 master weights the
+    optimizer left behind (weights: [n], ParamStore order, what the next step starts from). An array that would take the
+    files past limit_bytes is replaced by a fixed, seeded sample of its elements (weights_sample, float32, and
+    weights_sample_index, float64)."""
+    import torch
+    if plan.store.w.is_cuda:
+        torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss_total": plan.total, "loss_recon": plan.recon, "loss_kl": plan.kl, "weights": plan.store.w}
+    arrays = {k: v.detach().float().cpu().numpy().astype(np.float32) for k, v in arrays.items()}
+    small = sum(a.nbytes for k, a in arrays.items() if k != "weights")
+    w = arrays.pop("weights")
+    if small + w.nbytes > limit_bytes:
+        k = (limit_bytes - small) // 12  # (a float32 value + its float64 index)
+        idx = np.sort(np.random.default_rng(0).choice(w.size, size=k, replace=False))
+        arrays["weights_sample"], arrays["weights_sample_index"] = w[idx], idx.astype(np.float64)
+    else:
+        arrays["weights"] = w
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return sorted(arrays)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -312,6 +352,11 @@ def parse_args(argv=None):
                     help="with --gpus N > 1 and no launcher: start the N rank processes, have each print its rendezvous environment "
                          "as one JSON line and exit (no GPU, no torch): a test of the launcher itself")
     ap.add_argument("--launch-timeout", type=float, default=1500.0, help="seconds before the self-launcher gives up on its ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the roofline of the step's kernel families (re-launched on "
+                         "their own), the CPU oracle baseline; with --decode, the device-only replay of the captured positions")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed for its caller as DIR/<name>.npy (float32)")
     return ap.parse_args(argv)
 
 
@@ -403,6 +448,8 @@ def main(argv=None):
     if args.dry_launch:
         return dry_rank()
     if args.decode:
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs writes the training step's outputs; it does not apply to --decode")
         return run_decode(args)
     return run_rank(args)
 
@@ -457,30 +504,34 @@ def run_decode(args):
             reps += 1
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
-        # the device part alone: the captured positions (decode step + ranking + cache gather) replayed back to back
         bs = m.beam_search_plan(B, K, 2 * (T + 1), "query")
-        with torch.cuda.stream(bs.plan.stream):
-            ts = sorted(bs._graphs)
-            e0, e1 = o.Event(), o.Event()
-            e0.record()
-            for t in ts:
-                bs._graphs[t].launch()
-            e1.record()
-            e1.sync()
-            dev_us = e0.elapsed_ms(e1) * 1e3 / max(len(ts), 1)
+        if args.full:
+            # the device part alone: the captured positions (decode step + ranking + cache gather) replayed back to back
+            with torch.cuda.stream(bs.plan.stream):
+                ts = sorted(bs._graphs)
+                e0, e1 = o.Event(), o.Event()
+                e0.record()
+                for t in ts:
+                    bs._graphs[t].launch()
+                e1.record()
+                e1.sync()
+                dev_us = e0.elapsed_ms(e1) * 1e3 / max(len(ts), 1)
     tok_s = n_tok / elapsed
-    # the decode step's roof: a position streams the cache rows it re-gathers (K and V of every hypothesis, positions 0..t, read +
-    # written), attends over them (read once more) and reads the layer's weights; everything else is per-hypothesis rows
-    dcfg = bs.plan.cfg
-    Dd, V = dcfg.d_model, dcfg.out_dim
-    t_avg = (max(ts) + 1) / 2.0 if ts else 1.0
-    cache_bytes = dcfg.d_layers * B * K * t_avg * 2 * Dd * 2 * 3           # gather read + write + attention read, 16-bit K | V
-    weight_bytes = 2.0 * (dcfg.d_layers * 12 * Dd * Dd + V * Dd * 2)        # the layers' 16-bit shadows + embedding and output tables
-    pos_bytes = cache_bytes + weight_bytes + B * K * (V * 4 * 2 + Dd * 2 * 12)
-    roof = {"bound": "hbm", "kernel": "one decoded position (decode step + beam ranking + cache gather: one captured graph)",
-            "achieved": pos_bytes / (dev_us * 1e-6) / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": pos_bytes / (dev_us * 1e-6) / 1e9 / PEAK_HBM_GBS,
-            "traffic": None, "algorithmic_bytes_per_position": pos_bytes,
-            "note": "latency-bound: ~20 dependent launches of 4-64 workgroups per position (profiles/README.md, decode)"}
+    full = {}
+    if args.full:
+        # the decode step's roof: a position streams the cache rows it re-gathers (K and V of every hypothesis, positions 0..t, read +
+        # written), attends over them (read once more) and reads the layer's weights; everything else is per-hypothesis rows
+        dcfg = bs.plan.cfg
+        Dd, V = dcfg.d_model, dcfg.out_dim
+        t_avg = (max(ts) + 1) / 2.0 if ts else 1.0
+        cache_bytes = dcfg.d_layers * B * K * t_avg * 2 * Dd * 2 * 3           # gather read + write + attention read, 16-bit K | V
+        weight_bytes = 2.0 * (dcfg.d_layers * 12 * Dd * Dd + V * Dd * 2)        # the layers' 16-bit shadows + embedding and output tables
+        pos_bytes = cache_bytes + weight_bytes + B * K * (V * 4 * 2 + Dd * 2 * 12)
+        roof = {"bound": "hbm", "kernel": "one decoded position (decode step + beam ranking + cache gather: one captured graph)",
+                "achieved": pos_bytes / (dev_us * 1e-6) / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": pos_bytes / (dev_us * 1e-6) / 1e9 / PEAK_HBM_GBS,
+                "traffic": None, "algorithmic_bytes_per_position": pos_bytes,
+                "note": "latency-bound: ~20 dependent launches of 4-64 workgroups per position (profiles/README.md, decode)"}
+        full = {"device_us_per_position": dev_us, "host_share": 1.0 - dev_us * 1e-6 * n_pos / elapsed, "roofline": roof}
     out = {"metric": "decoded tokens/s (beam search, KV-cache decode step)", "value": tok_s, "unit": "tokens/s", "n_gpus": 1,
            "steps": n_pos, "warmup": warm, "ms_per_step": elapsed / n_pos * 1e3, "higher_is_better": True, "scaling": "weak",
            "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
@@ -491,8 +542,7 @@ def run_decode(args):
                       "hypotheses": B * K, "beam": K, "positions_per_sequence": smp.positions_decoded,
                       "tokens_counted": "live continuations per position (device counters); PAD continuations of finished hypotheses excluded"},
            "hypothesis_positions_per_s": B * K * n_pos / elapsed,
-           "device_us_per_position": dev_us, "host_share": 1.0 - dev_us * 1e-6 * n_pos / elapsed,
-           "graphs_captured": len(bs._graphs), "ranking": "device" if smp.on_device else "host", "roofline": roof}
+           "graphs_captured": len(bs._graphs), "ranking": "device" if smp.on_device else "host", **full}
     print(json.dumps(out), flush=True)
     return 0
 
@@ -719,6 +769,9 @@ def run_rank(args):
         # as one graph). It is measured and WRITTEN OUT (stderr + a file) before anything else touches RCCL.
         base_name = "one all-reduce between backward and Adam, default communicator" if world > 1 else "one captured graph"
         best_name, best = base_name, timed_run(False, None)
+        if args.dump_outputs and rank == 0:
+            # (here, before anything else runs on the step's buffers: N > 1 dumps the baseline schedule's last step)
+            log(f"outputs of the last timed step: {', '.join(dump_outputs(plan, args.dump_outputs))} -> {args.dump_outputs}")
         dp_report = None
         final_lock, final_done = threading.Lock(), [False]
         if world > 1:
@@ -786,7 +839,7 @@ def run_rank(args):
         m = plan.metrics()
         if args.data == "host":
             plan.bind_inputs(blobs[0])
-        roof = roofline(plan, o, args.config) if rank == 0 else None
+        roof = roofline(plan, o, args.config) if rank == 0 and args.full else None
 
     rccl = None
     if dist is not None:
@@ -829,8 +882,9 @@ def run_rank(args):
         # no epsilon and sigma straddles 0 at Xavier init, where a handful of |sigma| < 1e-2 elements carry the error
         "elbo_tolerance": {"bf16_raw_init": 4e-3, "fp16_raw_init": 1e-3, "bf16_conditioned": 1e-3, "fp16_conditioned": 1e-3,
                            "reconstruction_loss_any": 1e-3, "this_run": dtype + "_raw_init"},
-        "roofline": roof,
     })
+    if args.full:
+        out["roofline"] = roof
     if nonfinite:
         out["invalid"] = f"{nonfinite} steps were skipped by the non-finite guard: the timed region did less work than {args.steps} steps"
         out["value_if_all_steps_counted"], out["value"] = out["value"], None
@@ -838,7 +892,7 @@ def run_rank(args):
         out["rccl"] = rccl
     if best["host_pipeline"] is not None:
         out["host_pipeline"] = best["host_pipeline"]
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(c, args.dropout)
     print(json.dumps(out), flush=True)
     leave()

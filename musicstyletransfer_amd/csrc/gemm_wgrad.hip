@@ -26,6 +26,8 @@ struct WgradBatch {
                                   // gets ONE slab instead of `split` workgroups of which all but one exit at once
   int64_t item_prefix[WG_MAXP + 1];  // prefix sums of tiles_p * split_p: work items of problem p are [prefix[p], prefix[p+1])
   float* partial;                 // optional scratch [items][BN*BKO]: the slabs' tiles go there instead of into dW by atomics
+  float* partial_bias;            // optional, with partial: [items][BN] behind the tiles, the slabs' bias column sums (summed in
+                                  // slab order by the reduction pass); null: the bias goes to db by fp32 atomics
   mst_wgrad_args p[WG_MAXP];
   int64_t tile_prefix[WG_MAXP + 1];  // prefix sums of (tiles_n * tiles_k) per problem
 };
@@ -423,12 +425,17 @@ __device__ __forceinline__ void wgrad_body(const WgradBatch& b, unsigned char* s
   }
 
   if (bias_wave && li == 0) {
+    // two-pass form: this slab's column sums go to its own row of partial_bias, wgrad_reduce_kernel adds the rows in slab order
+    // (with more than two slabs per tile, fp32 atomics on db made the bias gradients depend on arrival order in the last bits)
+    float* brow = b.partial_bias ? b.partial_bias + item * (int64_t)BN : nullptr;
 #pragma unroll
     for (int j = 0; j < TN; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int64_t n = n0 + wn * WTN + j * 16 + 4 * g + r;
-        if (n < a.N) atomicAdd(a.db + n, acc_b[j][r] * a.scale);
+        const int nl = wn * WTN + j * 16 + 4 * g + r;
+        const int64_t n = n0 + nl;
+        if (brow) brow[nl] = acc_b[j][r];
+        else if (n < a.N) atomicAdd(a.db + n, acc_b[j][r] * a.scale);
       }
   }
   WG_STAMP(3);
@@ -507,13 +514,21 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(WgradBatch b, Partial
   // slabs that own rows of this problem (wgrad_kernel returns early, writing nothing, for the others)
   const int sp = b.split_p[pi];
   const int64_t m_chunk = (int64_t)((((uint32_t)a.M + (uint32_t)sp - 1) / (uint32_t)sp + BMR - 1) / BMR * BMR);
+  // the bias rides on the first k column's thread of each row n: its slab rows are loaded in the same iterations as the tile's
+  // (a loop of their own after this one was a second chain of dependent round trips for the whole workgroup)
+  const bool bias_here = a.db != nullptr && k == 0 && b.partial_bias != nullptr;  // (else wgrad_kernel added it atomically)
+  const float* pb = bias_here ? b.partial_bias + (b.item_prefix[pi] + local) * BN + nl : nullptr;
   f32x4 sum = {0.f, 0.f, 0.f, 0.f};
-  for (int s = 0; s < sp && (int64_t)s * m_chunk < a.M; ++s)
+  float sb = 0.f;
+  for (int s = 0; s < sp && (int64_t)s * m_chunk < a.M; ++s) {
     sum += *reinterpret_cast<const f32x4*>(b.partial + (b.item_prefix[pi] + (int64_t)s * tiles_p + local) * (BN * BKO) + e);
+    if (bias_here) sb += pb[(int64_t)s * tiles_p * BN];
+  }
   float* d = a.dW + n * a.ldw + k;
 #pragma unroll
   for (int c = 0; c < 4; ++c)
     if (k + c < a.K) d[c] += sum[c] * a.scale;
+  if (bias_here) a.db[n] += sb * a.scale;  // (slabs in order, as the tile)
 }
 
 static_assert(sizeof(WgradBatch) + sizeof(PartialSumBatch) + sizeof(OuterBatch) <= 4096, "kernel arguments of the reduction pass");
@@ -687,8 +702,13 @@ extern "C" int mst_gemm_wgrad_batch_flush(const mst_wgrad_args* list, int n, flo
   for (int i = n + 1; i <= WG_MAXP; ++i) b.item_prefix[i] = b.item_prefix[n];
   // two-pass reduction through the caller's scratch buffer when it is big enough (256x256 tiles only: that is where
   // 4 N K split bytes of atomics are tens of microseconds)
-  b.partial = nullptr;
-  if (scratch && big == 3 && n_items * (int64_t)(256 * 256) * 4 <= scratch_bytes) b.partial = scratch;
+  // The bias rows behind the tiles need n_items * 1 KiB more: a buffer that holds the tiles only keeps the two-pass tiles and adds
+  // the bias atomically, as before the rows existed (ParamStore.wgrad_scratch is sized for both).
+  b.partial = b.partial_bias = nullptr;
+  if (scratch && big == 3 && n_items * (int64_t)(256 * 256) * 4 <= scratch_bytes) {
+    b.partial = scratch;
+    if (n_items * (int64_t)(256 * 256 + 256) * 4 <= scratch_bytes) b.partial_bias = scratch + n_items * (int64_t)(256 * 256);  // (BN = 256)
+  }
   hipStream_t s = (hipStream_t)stream;
   bool ps_done = false;
   int rc = dispatch_act(list[0].dtype, [&](auto tag) -> int {

@@ -290,9 +290,67 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_bwd_vec_kernel(int De, int
 }
 
 // (batch_outer: outer_jobs.hpp)
+// dcls[class_b, j] += t[b, j] (the decoder class table's gradient) without fp32 atomics, whose arrival order made the table's
+// gradient — and, through Adam, whole training runs — differ in the last bits from run to run. A 256-thread block owns 64
+// columns; as in batch_outer its four waves take a quarter of the batch each, 16 rows of loads in flight, and the quarters are
+// added in order through LDS. Classes go four at a time in registers (the class index selects, so nothing is indexed
+// dynamically); the table here has two.
+constexpr int CT_ROWS = 16, CT_CLS = 4;
+__device__ __forceinline__ void class_table_block(int blk, int tid, int64_t B, int Dd, const float* __restrict__ tvec,
+                                                  const int32_t* __restrict__ classes, float* __restrict__ dcls, int64_t ld_cls) {
+  __shared__ int s_ncls;
+  __shared__ float red[CT_CLS][4][64];
+  const int o = tid & 63, part = tid >> 6, j = blk * 64 + o;
+  const bool col = j < Dd;
+  const int64_t per = (B + 3) / 4, b0 = part * per, b1 = b0 + per < B ? b0 + per : B;
+  if (tid == 0) s_ncls = 0;
+  __syncthreads();
+  // the number of classes comes out of the first pass's own loads (an integer max in LDS: order-free); a table of more than
+  // CT_CLS classes takes more passes over the batch
+  for (int c0 = 0, n_cls = CT_CLS; c0 < n_cls; c0 += CT_CLS) {
+    float acc[CT_CLS];
+#pragma unroll
+    for (int q = 0; q < CT_CLS; ++q) acc[q] = 0.f;
+    int mx = 0;
+    int64_t b = b0;
+    for (; b + CT_ROWS <= b1; b += CT_ROWS) {  // whole chunks: every load of the chunk in flight at once
+      float v[CT_ROWS];
+      int cl[CT_ROWS];
+#pragma unroll
+      for (int u = 0; u < CT_ROWS; ++u) {
+        cl[u] = classes[b + u];
+        v[u] = col ? tvec[(b + u) * Dd + j] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < CT_ROWS; ++u) {
+        mx = max(mx, cl[u] + 1);
+#pragma unroll
+        for (int q = 0; q < CT_CLS; ++q) acc[q] += cl[u] - c0 == q ? v[u] : 0.f;  // (rows in batch order; x + 0 is exact)
+      }
+    }
+    for (; b < b1; ++b) {
+      const int cl = classes[b];
+      const float v = col ? tvec[b * Dd + j] : 0.f;
+      mx = max(mx, cl + 1);
+#pragma unroll
+      for (int q = 0; q < CT_CLS; ++q) acc[q] += cl - c0 == q ? v : 0.f;
+    }
+    if (c0 == 0) atomicMax(&s_ncls, mx);
+#pragma unroll
+    for (int q = 0; q < CT_CLS; ++q) red[q][part][o] = acc[q];
+    __syncthreads();
+    n_cls = s_ncls;
+    if (part == 0 && col)
+#pragma unroll
+      for (int q = 0; q < CT_CLS; ++q)
+        if (c0 + q < n_cls) dcls[(int64_t)(c0 + q) * ld_cls + j] += ((red[q][0][o] + red[q][1][o]) + red[q][2][o]) + red[q][3][o];
+    __syncthreads();
+  }
+}
+
 // ONE launch for the three parameter-gradient pieces of the latent block (they were three ~5-14 us launches):
 // blocks [0, n_wl): dWl[2Z, De] += dlat^T h0, dbl; blocks [n_wl, n_wl + n_wh): dWh[Dd, Z] += t^T z, dbh;
-// the rest: dcls_d[class_b, :] += t[b, :]
+// the rest: dcls_d[class_b, :] += t[b, :] in a fixed order (class_table_block)
 template <typename T>
 __global__ __launch_bounds__(256) void latent_param_grads_kernel(int64_t B, int De, int Z, int Dd, const float* __restrict__ dlat,
                                                                  const T* __restrict__ enc_out, int64_t enc_stride,
@@ -308,12 +366,15 @@ __global__ __launch_bounds__(256) void latent_param_grads_kernel(int64_t B, int 
   } else if (blk < n_wl + n_wh) {
     batch_outer<float>(blk - n_wl, threadIdx.x, B, Dd, Z, tvec, z, Z, dWh, dbh, red);
   } else {
-    const int64_t idx = (int64_t)(blk - n_wl - n_wh) * 256 + threadIdx.x;
-    if (idx < B * Dd) {
-      const uint32_t bq = (uint32_t)idx / (uint32_t)Dd, dr = (uint32_t)idx - bq * (uint32_t)Dd;
-      atomicAdd(dcls + (int64_t)classes[bq] * ld_cls + dr, tvec[idx]);
-    }
+    class_table_block(blk - n_wl - n_wh, threadIdx.x, B, Dd, tvec, classes, dcls, ld_cls);
   }
+}
+
+// the class table's gradient as a launch of its own (mst_latent_bwd_vec): grid cdiv(Dd, 64), 256 threads
+__global__ __launch_bounds__(256) void class_table_grad_kernel(int64_t B, int Dd, const float* __restrict__ tvec,
+                                                               const int32_t* __restrict__ classes, float* __restrict__ dcls,
+                                                               int64_t ld_cls) {
+  class_table_block((int)blockIdx.x, threadIdx.x, B, Dd, tvec, classes, dcls, ld_cls);
 }
 
 }  // namespace mst
@@ -383,7 +444,7 @@ extern "C" int mst_latent_bwd(int dtype, int64_t B, int64_t De, int64_t Z, int64
   MST_CHECK_ARG(Z <= LAT_THREADS, "mst_latent_bwd: latent size above %d", LAT_THREADS);
   MST_CHECK_ARG(2 * Z * De < (1ll << 31) && Dd * Z < (1ll << 31) && B * Dd < (1ll << 31), "mst_latent_bwd: sizes above 2^31 elements");
   const size_t lds = sizeof(float) * (Dd + 2 * Z + (latent_bwd_pre_shape(De, Z, Dd) ? 1 : 4) * LAT_THREADS + 4);  // (+ 4: the float4 view's alignment)
-  const int n_wl = (int)cdiv(2 * Z * De, 64), n_wh = (int)cdiv(Dd * Z, 64), n_cls = (int)cdiv(B * Dd, 256);
+  const int n_wl = (int)cdiv(2 * Z * De, 64), n_wh = (int)cdiv(Dd * Z, 64), n_cls = (int)cdiv(Dd, 64);
   return dispatch_act(dtype, [&](auto tag) -> int {
     typedef decltype(tag) T;
     if (latent_bwd_pre_shape(De, Z, Dd))
@@ -419,12 +480,16 @@ static int latent_bwd_vec_impl(int dtype, int64_t B, int64_t De, int64_t Z, int6
     if (latent_bwd_pre_shape(De, Z, Dd))
       hipLaunchKernelGGL((latent_bwd_vec_kernel<T, true>), dim3((unsigned)B), dim3(LAT_THREADS), lds, (hipStream_t)stream, (int)De, (int)Z,
                          (int)Dd, Wl, eps, Wh, mu, sigma, (const T*)d_dec_in, dec_sample_stride, alpha_d, kl_weight, gscale, enc_scale,
-                         scratch, scratch + B * Dd, (T*)d_enc_out, denc_sample_stride, classes, dcls_d, ld_cls, x0);
+                         scratch, scratch + B * Dd, (T*)d_enc_out, denc_sample_stride, classes, (float*)nullptr, ld_cls, x0);
     else
       hipLaunchKernelGGL((latent_bwd_vec_kernel<T, false>), dim3((unsigned)B), dim3(LAT_THREADS), lds, (hipStream_t)stream, (int)De, (int)Z,
                          (int)Dd, Wl, eps, Wh, mu, sigma, (const T*)d_dec_in, dec_sample_stride, alpha_d, kl_weight, gscale, enc_scale,
-                         scratch, scratch + B * Dd, (T*)d_enc_out, denc_sample_stride, classes, dcls_d, ld_cls, x0);
+                         scratch, scratch + B * Dd, (T*)d_enc_out, denc_sample_stride, classes, (float*)nullptr, ld_cls, x0);
     MST_CHECK_LAUNCH("latent_bwd_vec_kernel");
+    // the class table's gradient from the rows the kernel left in scratch (tvec), in batch order
+    hipLaunchKernelGGL(class_table_grad_kernel, dim3((unsigned)cdiv(Dd, 64)), dim3(256), 0, (hipStream_t)stream, B, (int)Dd,
+                       (const float*)scratch, classes, dcls_d, ld_cls);
+    MST_CHECK_LAUNCH("class_table_grad_kernel");
     return MST_OK;
   });
 }

@@ -184,3 +184,51 @@ def test_rccl_logging_is_opt_in_and_cleans_up(tmp_path, monkeypatch):
     finally:
         for k in ("NCCL_DEBUG", "NCCL_DEBUG_SUBSYS", "NCCL_DEBUG_FILE", "MST_RCCL_LOG_DIR", "MST_RCCL_LOG_TMP"):
             os.environ.pop(k, None)
+
+
+# ---------------------------------------------------------------------------------- a plain run, --full, --dump-outputs
+def test_full_is_off_by_default_and_dump_outputs_takes_a_directory():
+    b = _bench()
+    a = b.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    a = b.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_outputs_with_decode_is_refused():
+    r = subprocess.run([sys.executable, BENCH, "--decode", "--dump-outputs", "x"], env=_env(), capture_output=True, text=True, timeout=60)
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr
+
+
+def _fake_plan(B, n):
+    from types import SimpleNamespace
+    g = torch.Generator().manual_seed(0)
+    recon, kl = torch.rand(B, generator=g), torch.rand(B, generator=g)
+    return SimpleNamespace(recon=recon, kl=kl, total=recon + kl, store=SimpleNamespace(w=torch.randn(n, generator=g)))
+
+
+def test_dump_outputs_writes_the_losses_and_weights_as_float32(tmp_path):
+    b = _bench()
+    import numpy as np
+    plan = _fake_plan(8, 1000)
+    names = b.dump_outputs(plan, str(tmp_path / "d"))
+    assert names == ["loss_kl", "loss_recon", "loss_total", "weights"]
+    for name, t in (("loss_kl", plan.kl), ("loss_recon", plan.recon), ("loss_total", plan.total), ("weights", plan.store.w)):
+        a = np.load(tmp_path / "d" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, t.numpy())
+
+
+def test_dump_outputs_samples_the_weights_past_the_limit_the_same_way_every_time(tmp_path):
+    b = _bench()
+    import numpy as np
+    plan = _fake_plan(8, 4000)
+    limit = 3 * 8 * 4 + 1200  # the losses + room for 100 sampled weights (4-byte value + 8-byte index)
+    for d in ("a", "b"):
+        names = b.dump_outputs(plan, str(tmp_path / d), limit_bytes=limit)
+        assert names == ["loss_kl", "loss_recon", "loss_total", "weights_sample", "weights_sample_index"]
+    files = {f: np.load(tmp_path / "a" / f"{f}.npy") for f in names}
+    assert sum(a.nbytes for a in files.values()) <= limit
+    idx, w = files["weights_sample_index"], files["weights_sample"]
+    assert idx.dtype == np.float64 and w.dtype == np.float32 and len(idx) == 100 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(w, plan.store.w.numpy()[idx.astype(np.int64)])
+    assert all(np.array_equal(files[f], np.load(tmp_path / "b" / f"{f}.npy")) for f in names)

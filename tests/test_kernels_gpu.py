@@ -882,7 +882,7 @@ def roundup8(x):
 
 def test_gemm_wgrad_two_pass_reduction_is_deterministic_and_equal(gpu):
     """a batch big enough for 256x256 tiles: with a scratch buffer the M-slabs are summed in slab order by a second
-    launch instead of fp32 atomics — same result to fp32 rounding, and bit-identical run to run"""
+    launch instead of fp32 atomics — same result to fp32 rounding, and bit-identical run to run (weights and biases)"""
     o = ops()
     M = 4096
     shapes = [(256, 1024), (1024, 256), (768, 256), (256, 256), (300, 200), (1024, 256), (256, 1024), (512, 512)]  # 2.1 M outputs
@@ -911,12 +911,13 @@ def test_gemm_wgrad_two_pass_reduction_is_deterministic_and_equal(gpu):
         return outs
 
     atomic, two_a, two_b = run(False), run(True), run(True)
-    for (A, B, N, K), (dWa, dba), (dW1, db1), (dW2, _) in zip(probs, atomic, two_a, two_b):
+    for (A, B, N, K), (dWa, dba), (dW1, db1), (dW2, db2) in zip(probs, atomic, two_a, two_b):
         ref = 0.5 * (A[:, :N].float().t() @ B[:, :K].float())
         close(dW1, ref, 1e-4, 1e-3 * ref.abs().max().item(), "two-pass dW")
         close(dW1, dWa, 1e-5, 1e-4 * ref.abs().max().item(), "two-pass vs atomic")
         close(db1, 0.5 * A[:, :N].float().sum(0), 1e-4, 1e-2, "db")
         assert torch.equal(dW1, dW2), "the two-pass reduction must be run-to-run deterministic"
+        assert torch.equal(db1, db2), "the bias column sums of the two-pass reduction must be run-to-run deterministic"
     for dsts in colsums:
         for (n, off, length), d in zip(sum_specs, dsts):
             assert torch.equal(d, 1.0 + part[:n, off:off + length].sum(0))

@@ -756,3 +756,37 @@ def test_identical_runs_agree_on_full_length_batches(gpu):
     for w in ws[1:]:
         d = np.abs(w - ws[0])
         assert d.max() <= 2.1 * 1e-2 * 3 and (d > 2e-5).mean() < 0.05, (d.max(), (d > 2e-5).mean())
+
+
+@pytest.mark.gpu
+def test_identical_benchmark_steps_give_bit_identical_gradients_and_weights(gpu):
+    """bench.py's configs[1] step (B 64, T 256, 128 pitches, latent 64, bf16, dropout 0.2), built twice from the same seeds:
+    after each of two steps every parameter gradient, the weights and the KL are bit-identical between the two. The bias
+    column sums (the wgrad launch's slab rows, summed in slab order) and the decoder class table's gradient are the sums that
+    fp32 atomics used to take in arrival order; 17 of the 58 gradients then differed in the last bits on every run."""
+    from musicstyletransfer_amd import engine as E
+    dims = dict(kind="pianoroll", in_dim=128, out_dim=128, num_classes=2, latent_dim=64, e_model=256, e_layers=2, e_heads=8,
+                d_model=128, d_layers=1, d_heads=8)
+    B, T = 64, 256
+    rng = np.random.default_rng(1234)
+    roll = (rng.random((B, T + 1, 128)) < 0.04).astype(np.uint8)
+    x = roll[:, :T].copy()
+    x[:, 0, :] = 0
+    x[:, 0, 0] = 1
+    classes = rng.integers(0, 2, size=B).astype(np.int32)
+    runs = []
+    for _ in range(2):
+        store = E.ParamStore(E.VAEConfig(e_dropout=0.2, d_dropout=0.2, **dims), gpu, torch.bfloat16, seed=1234)
+        plan = E.StepPlan(store, B, T, lr=3e-4, clip_gradient=1.0, kl_weight=1.0, global_batch=B, internal_eps=True, seed=1000)
+        plan.bind_inputs(plan.pack_batch(x, np.full(B, T, np.int32), classes, roll[:, 1:].copy()).to(gpu))
+        steps = []
+        for _ in range(2):
+            plan.step_kernels(True)
+            torch.cuda.synchronize()
+            steps.append((store.to_numpy("g"), store.w.cpu().numpy().copy(), plan.kl.cpu().numpy().copy()))
+        runs.append(steps)
+        del plan, store
+    for i, ((ga, wa, kla), (gb, wb, klb)) in enumerate(zip(*runs)):
+        differ = [n for n in ga if not np.array_equal(ga[n], gb[n])]
+        assert not differ, f"step {i + 1}: gradients that differ between identical runs: {differ}"
+        assert np.array_equal(wa, wb) and np.array_equal(kla, klb), f"step {i + 1}"

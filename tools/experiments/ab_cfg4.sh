@@ -1,4 +1,4 @@
-run() { python bench.py --config 4 --steps 60 --warmup 10 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+run() { python bench.py --config 4 --steps 60 --warmup 10 --full --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('$1', d['ms_per_step'], [ (f['kernel'][:22], round(f['avg_launch_ms']*1e3,1)) for f in d['roofline']['families']])"; }
 run default

@@ -9,7 +9,7 @@ root="${GRAFT_REPO_ROOT:-$(pwd)}"
 out="$root/gpurun_out/$tag"
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -o r -- python3 "$root/bench.py" --steps 60 --warmup 10 --no-cpu-baseline "$@" > "$out/bench.json" 2> "$out/bench.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -o r -- python3 "$root/bench.py" --steps 60 --warmup 10 --full --no-cpu-baseline "$@" > "$out/bench.json" 2> "$out/bench.err"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$out/fetch" -o r -- python3 "$root/bench.py" --steps 3 --warmup 1 --no-cpu-baseline "$@" > /dev/null 2> "$out/fetch.err"
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$out/write" -o r -- python3 "$root/bench.py" --steps 3 --warmup 1 --no-cpu-baseline "$@" > /dev/null 2> "$out/write.err"
 cd "$root"
