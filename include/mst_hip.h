@@ -358,6 +358,25 @@ int mst_attn_keysoftmax_bwd(int dtype, int64_t B, int64_t S, int64_t H, int64_t 
                             mst_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Causal self-attention with a conventional softmax over the KEY axis (the decoder's opt-in causal mode; the
+ * model mst_attn_decode mode 1 samples from). Per (batch b, head h), with keymask[b,k] the decoder's mask:
+ *   logit[q,k] = Q[q]·K[k]/sqrt(dh) for k <= q and keymask[b,k], excluded (probability exactly 0) otherwise;
+ *   P[q,:] = softmax over k; O[q] = sum_k P[q,k] V[k].
+ * Same layouts as mst_attn_keysoftmax_fwd/bwd: lse fp32 [2, B, H, S] now holds per-QUERY statistics (plane 0 =
+ * row max, plane 1 = log row sum of the non-excluded logits); the backward writes delta fp32 [B, H, S] =
+ * rowsum(dO * O) and dQ | dK | dV into dqkv (the qkv layout). Key blocks above the diagonal are skipped,
+ * nothing S x S reaches HBM, no atomics: identical calls give identical bits. dh in {16, 32, 64}; qkv, out,
+ * dout and dqkv 16-byte aligned with leading dimensions that are multiples of 8.
+ * ------------------------------------------------------------------------ */
+int mst_attn_causal_fwd(int dtype, int64_t B, int64_t S, int64_t H, int64_t dh,
+                        const void* qkv, int64_t ld_qkv, int64_t k_off, int64_t q_off, int64_t v_off,
+                        const uint8_t* keymask, float* lse, void* out, int64_t ld_out, mst_stream_t stream);
+int mst_attn_causal_bwd(int dtype, int64_t B, int64_t S, int64_t H, int64_t dh,
+                        const void* qkv, int64_t ld_qkv, int64_t k_off, int64_t q_off, int64_t v_off,
+                        const uint8_t* keymask, const float* lse, const void* dout, int64_t ld_dout,
+                        void* dqkv, int64_t ld_dqkv, float* delta, mst_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * K6: y = LayerNorm(x) * gamma + beta over the last axis (eps, biased variance;
  * gluon.nn.LayerNorm at transformer.py:142,147,175,180). The residual add is fused
  * into the producing GEMM's epilogue, so x is the pre-norm sum.

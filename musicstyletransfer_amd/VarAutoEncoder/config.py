@@ -59,6 +59,8 @@ _FLAGS = [
     ("MI355X", ("--pianoroll",), dict(action="store_true")),
     ("MI355X", ("--dtype",), dict(choices=["bf16", "fp16"], default="bf16")),
     ("MI355X", ("--max-steps",), dict(type=int, default=0)),
+    # a causal decoder (softmax over the keys): a model the incremental samplers decode as trained. Off: the reference's decoder
+    ("MI355X", ("--d-causal",), dict(action="store_true")),
 ]
 
 

@@ -66,7 +66,8 @@ def create_model_config(args, dataset):
         decoder_config=model.DecoderConfig(
             transformer_config=TransformerConfig(model_size=args.d_rnn_hidden_dim, dropout=args.d_dropout, num_layers=args.d_n_layers,
                                                  vocab_size=dataset.num_tokens(), num_heads=d_heads),
-            latent_dim=args.latent_dim, num_classes=dataset.num_classes(), output_dim=dataset.num_tokens()),
+            latent_dim=args.latent_dim, num_classes=dataset.num_classes(), output_dim=dataset.num_tokens(),
+            causal=getattr(args, "d_causal", False)),
         kind="pianoroll" if args.pianoroll else "token")
 
 

@@ -25,10 +25,14 @@ class LSTMConfig(Config):  # kept for config files that name it (model.py:11-19)
 
 
 class DecoderConfig(Config):
-    def __init__(self, transformer_config, latent_dim: int, num_classes: int, output_dim: int):
+    """causal: the decoder's self-attention sees only past rows, with a softmax over the keys — the model the incremental
+    samplers decode (attention="key"). Off by default: the reference's decoder is not causal (transformer.py:174)."""
+
+    def __init__(self, transformer_config, latent_dim: int, num_classes: int, output_dim: int, causal: bool = False):
         super().__init__()
         self.transformer_config = transformer_config
         self.latent_dim, self.num_classes, self.output_dim = latent_dim, num_classes, output_dim
+        self.causal = bool(causal)
 
 
 class EncoderConfig(Config):
@@ -49,7 +53,20 @@ class ModelConfig(Config):
         te, td = e.transformer_config, d.transformer_config
         assert e.latent_dim == d.latent_dim and e.num_classes == d.num_classes
         return E.VAEConfig(self.kind, e.input_dim, d.output_dim, e.num_classes, e.latent_dim, te.model_size, te.num_layers,
-                           te.num_heads, td.model_size, td.num_layers, td.num_heads, te.dropout, td.dropout)
+                           te.num_heads, td.model_size, td.num_layers, td.num_heads, te.dropout, td.dropout,
+                           d_causal=getattr(d, "causal", False))  # (configs written before the field: not causal)
+
+
+def resolve_attention(engine_config, attention):
+    """the decode attention mode: None = the model's own ('key' for a causal decoder, else the reference's 'query').
+    A causal decoder never saw the query-axis softmax in training, so asking for it is an error."""
+    causal = getattr(engine_config, "d_causal", False)
+    if attention is None:
+        return "key" if causal else "query"
+    if causal and attention == "query":
+        raise ValueError("this model's decoder is causal (trained with the softmax over the keys): decode it with "
+                         "attention='key' or None, not 'query'")
+    return attention
 
 
 class DecoderState:
@@ -92,12 +109,13 @@ class _Decoder:
         row0 = plan.x0_d.view(B, T + 1, -1)[:, 0, :]
         return (row0.repeat_interleave(beam, dim=0) if beam > 1 else row0).contiguous()
 
-    def get_initial_state(self, tokens, seq_lens, classes, t_max, attention="query", beam=1):
+    def get_initial_state(self, tokens, seq_lens, classes, t_max, attention=None, beam=1):
         """encode the batch, take z = the latent MEANS (sampler.py:146-148: latent_vector = means), build position 0 of the
         decoder input from it (model.py:229-232) and feed it: returns a DecoderState whose caches hold row 0.
-        beam > 1: every sample is repeated `beam` times (beam search's hypotheses, sampler.py:211-213)."""
-        from .. import decode
+        beam > 1: every sample is repeated `beam` times (beam search's hypotheses, sampler.py:211-213).
+        attention None: the model's own mode (resolve_attention)."""
         m = self._model
+        attention = resolve_attention(m.engine_config, attention)
         x = np.asarray(tokens.cpu() if torch.is_tensor(tokens) else tokens)
         B, T = x.shape[0], x.shape[1]
         plan = m.plan(B, T, want_probs=False, internal_eps=False)
@@ -191,10 +209,11 @@ class Model:
 
     DECODE_PLAN_MAX = 8
 
-    def decode_plan(self, n_hyp, t_max, attention="query"):
+    def decode_plan(self, n_hyp, t_max, attention=None):
         """the DecodePlan (caches + one captured graph per position) of this many hypotheses / positions, kept across
         batches: a sampler that decodes batch after batch of one shape captures its graphs once"""
         from .. import decode
+        attention = resolve_attention(self.engine_config, attention)
         if not hasattr(self, "_decode_plans") or getattr(self, "_decode_store", None) is not self.store:
             self._decode_plans, self._decode_store = OrderedDict(), self.store
         key = (n_hyp, t_max, attention)
@@ -208,9 +227,10 @@ class Model:
         self._decode_plans[key] = plan
         return plan
 
-    def beam_search_plan(self, B, K, i_max, attention="query"):
+    def beam_search_plan(self, B, K, i_max, attention=None):
         """decode.BeamSearch of this shape (caches, token rows, one captured graph per position), kept across batches"""
         from .. import decode
+        attention = resolve_attention(self.engine_config, attention)
         if not hasattr(self, "_beam_plans") or getattr(self, "_beam_store", None) is not self.store:
             self._beam_plans, self._beam_store = OrderedDict(), self.store
         key = (B, K, i_max, attention)

@@ -14,9 +14,9 @@ from ..MIDIUtil.midi_io import MelodyWriter
 
 
 class SamplerBase:
-    def __init__(self, model_folder=None, context=None, checkpoint=None, verbose=False, attention="query", seed=0):
+    def __init__(self, model_folder=None, context=None, checkpoint=None, verbose=False, attention=None, seed=0):
         self.model_folder, self.context, self.verbose = model_folder, context, verbose
-        self.attention = attention
+        self._attention = attention  # None: the model's own mode ('key' for a causal decoder, else 'query')
         self.rng = np.random.default_rng(seed)
         self.writer = MelodyWriter()
         self.model = None
@@ -25,6 +25,13 @@ class SamplerBase:
 
     def update_parameters(self, model):
         self.model = model
+
+    @property
+    def attention(self):
+        from .model import resolve_attention
+        if self.model is None:
+            return self._attention
+        return resolve_attention(self.model.engine_config, self._attention)
 
     def sample(self, batch):
         raise NotImplementedError

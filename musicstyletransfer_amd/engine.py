@@ -42,7 +42,7 @@ class VAEConfig:
     kind='pianoroll' (multi-hot frame x table in, sigmoid + BinaryCrossEntropy out)."""
 
     def __init__(self, kind, in_dim, out_dim, num_classes, latent_dim, e_model, e_layers, e_heads, d_model, d_layers,
-                 d_heads, e_dropout=0.0, d_dropout=0.0):
+                 d_heads, e_dropout=0.0, d_dropout=0.0, d_causal=False):
         assert kind in ("token", "pianoroll")
         assert e_model % e_heads == 0 and d_model % d_heads == 0  # transformer.py:134,167
         self.kind = kind
@@ -51,6 +51,9 @@ class VAEConfig:
         self.e_model, self.e_layers, self.e_heads = e_model, e_layers, e_heads
         self.d_model, self.d_layers, self.d_heads = d_model, d_layers, d_heads
         self.e_dropout, self.d_dropout = float(e_dropout), float(d_dropout)
+        # d_causal: the decoder's self-attention is causal with a softmax over the keys (mst_attn_causal_fwd/bwd), the model
+        # DecodePlan(attention="key") samples from. Off: the reference's non-causal query-axis softmax (transformer.py:174,100).
+        self.d_causal = bool(d_causal)
 
     def as_dict(self):
         return dict(self.__dict__)
@@ -859,8 +862,12 @@ class StepPlan:
         dh = D // H
         if side == "encoder" and i == self.cfg.e_layers - 1:
             return self._top_encoder_layer_fwd(i, L, x_in)
+        causal = side == "decoder" and self.cfg.d_causal
         if side == "decoder" and i == 0 and self._ride_fwd:  # (projected by the forward tail's riders + the latent block's launch)
-            o.attn_fwd(L.qkv, keymask, L.lse, L.att, self.B, S, H, dh, 0, D, 2 * D)
+            (o.attn_causal_fwd if causal else o.attn_fwd)(L.qkv, keymask, L.lse, L.att, self.B, S, H, dh, 0, D, 2 * D)
+        elif causal:  # the projection GEMM, then the causal attention launch
+            o.gemm_nt(x_in, st.fused(st.w16, pre, "weight"), L.qkv, N=3 * D, K=D, bias=st.fused(st.w, pre, "bias"))
+            o.attn_causal_fwd(L.qkv, keymask, L.lse, L.att, self.B, S, H, dh, 0, D, 2 * D)
         else:
             o.attn_qkv_fwd(x_in, st.fused(st.w16, pre, "weight"), st.fused(st.w, pre, "bias"), L.qkv, keymask, L.lse, L.att, self.B, S, H, dh,
                            0, D, 2 * D)
@@ -1107,7 +1114,10 @@ class StepPlan:
                                 **ln1)
         dproj = t.dh1m if p > 0 else t.dh1
         o.gemm_nt(dproj, st.t(f"{pre}.att.W_proj.weight"), t.datt, N=D, K=D)
-        o.attn_bwd(L.qkv, keymask, L.lse, t.datt, t.dqkv, t.delta, self.B, S, H, dhd, 0, D, 2 * D)
+        if side == "decoder" and self.cfg.d_causal:
+            o.attn_causal_bwd(L.qkv, keymask, L.lse, t.datt, t.dqkv, t.delta, self.B, S, H, dhd, 0, D, 2 * D)
+        else:
+            o.attn_bwd(L.qkv, keymask, L.lse, t.datt, t.dqkv, t.delta, self.B, S, H, dhd, 0, D, 2 * D)
         if next_ln is not None:  # the layer below starts its backward pass with a LayerNorm backward: run it here
             kw, t_below = next_ln
             o.gemm_nt_ln_bwd(t.dqkv, st.t(f"{pre}.att.W_kqv"), t_below.dh, N=D, K=3 * D, resid=t.dh1, **kw)

@@ -459,6 +459,17 @@ def attn_bwd(qkv, keymask, lse, dout, dqkv, delta, B, S, H, dh, k_off, q_off, v_
          ptr(lse), ptr(dout), ld(dout), ptr(dqkv), ld(dqkv), ptr(delta), q_limit, stream())
 
 
+def attn_causal_fwd(qkv, keymask, lse, out, B, S, H, dh, k_off, q_off, v_off):
+    """causal attention with the softmax over the keys (mst_attn_causal_fwd): lse gets per-query statistics"""
+    call("mst_attn_causal_fwd", dt(qkv), B, S, H, dh, ptr(qkv), ld(qkv), k_off, q_off, v_off, ptr(keymask), ptr(lse), ptr(out),
+         ld(out), stream())
+
+
+def attn_causal_bwd(qkv, keymask, lse, dout, dqkv, delta, B, S, H, dh, k_off, q_off, v_off):
+    call("mst_attn_causal_bwd", dt(qkv), B, S, H, dh, ptr(qkv), ld(qkv), k_off, q_off, v_off, ptr(keymask), ptr(lse), ptr(dout),
+         ld(dout), ptr(dqkv), ld(dqkv), ptr(delta), stream())
+
+
 def attn_decode(cache3, n_keys, H, dh, k_off, q_off, v_off, out, mode=0):
     """cache3: [B, t_max, ld] K|Q|V rows fed so far (row n_keys - 1 = the new position); out [B, ld_out]"""
     B, t_max = cache3.shape[0], cache3.shape[1]
