@@ -272,8 +272,8 @@ int mst_gemm_wgrad_batch_sums(const mst_wgrad_args* list, int n, float* scratch,
 /* Deferred batch outer products: out[j, i] += sum_b L[b, j] * R[b, i] (out fp32 [J, I] contiguous, accumulated into) and, with
  * obias, obias[j] += sum_b L[b, j]. L fp32 [B, J] contiguous; R [B, >= I] of r_dtype (MST_F32 / MST_BF16 / MST_F16) with row stride
  * r_stride elements. The parameter gradients of a layer that sees one row per sample — the latent block's latent_proj and
- * latent2hid (model.py:97-103,229-232; what mst_latent_bwd's second launch computes from mst_latent_bwd_vec's `scratch`) — which
- * nothing downstream but the optimizer reads. Up to 2 jobs per call. */
+ * latent2hid (model.py:97-103,229-232; computed from mst_latent_bwd_vec's `scratch`) — which nothing downstream but the optimizer
+ * reads. Up to 2 jobs per call. */
 typedef struct mst_outer_job {
   const float* L; const void* R; int32_t r_dtype; int64_t r_stride;
   int64_t B, J, I;
@@ -440,20 +440,10 @@ int mst_latent_fwd_proj(int dtype, int64_t B, int64_t De, int64_t Z, int64_t Dd,
                         const void* Wq, int64_t ld_wq, const float* bq, void* qkv0, int64_t qkv_sample_stride, int64_t nq,
                         mst_stream_t stream);
 
-int mst_latent_bwd(int dtype, int64_t B, int64_t De, int64_t Z, int64_t Dd,
-                   const void* enc_out, int64_t enc_sample_stride,
-                   const float* Wl, const float* eps, const float* Wh,
-                   const int32_t* classes,
-                   const float* mu, const float* sigma, const float* z,
-                   const void* d_dec_in, int64_t dec_sample_stride, float alpha_d,
-                   float kl_weight, float gscale /* encoder-side loss scale */,
-                   float enc_scale /* gscale / decoder-side loss scale */,
-                   float* dWl, float* dbl, float* dWh, float* dbh, float* dcls_d, int64_t ld_cls,
-                   void* d_enc_out, int64_t denc_sample_stride, float* scratch /* fp32 [B*(Dd+2Z)] */,
-                   mst_stream_t stream);
-/* mst_latent_bwd's first launch on its own, with the decoder class table's gradient (dcls_d[classes[b], :] += t[b, :]) folded in:
- * leaves t = alpha_d * d(dec_in[b, 0, :]) at scratch[0 .. B*Dd) and d[mu | sigma] at scratch[B*Dd .. B*(Dd + 2Z)), writes d(enc_out)
- * row 0. The remaining parameter gradients are two mst_outer_job of the caller's weight-gradient flush:
+/* The latent block's backward pass: the per-sample vectors, then the decoder class table's gradient (dcls_d[classes[b], :] += t[b, :]).
+ * gscale is the encoder-side loss scale, enc_scale = gscale / the decoder-side loss scale. Leaves t = alpha_d * d(dec_in[b, 0, :]) at
+ * scratch[0 .. B*Dd) and d[mu | sigma] at scratch[B*Dd .. B*(Dd + 2Z)) (fp32), writes d(enc_out) row 0. The remaining parameter
+ * gradients are two mst_outer_job of the caller's weight-gradient flush:
  *   dWl[2Z, De] += dlat^T enc_out[:, 0, :], dbl += sum_b dlat;   dWh[Dd, Z] += t^T z, dbh += sum_b t. */
 int mst_latent_bwd_vec(int dtype, int64_t B, int64_t De, int64_t Z, int64_t Dd, const float* Wl, const float* eps, const float* Wh,
                        const int32_t* classes, const float* mu, const float* sigma, const void* d_dec_in, int64_t dec_sample_stride,

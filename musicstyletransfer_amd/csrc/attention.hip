@@ -1628,8 +1628,6 @@ static int attn_check(int64_t B, int64_t S, int64_t H, int64_t dh, int64_t ld, i
 template <typename T>
 static int launch_fwd_qkv(const AttnArgs& a, hipStream_t s) {
   constexpr int DH = 32;
-  const char* off = getenv("MST_ATTN_QKV");
-  if (off && off[0] == '0') return 0;
   const size_t lds = res_lds_fwd<DH>(a.S);  // (the projection's slices borrow the Q / K / V tiles)
   const int NB = (int)cdiv(a.S, 32);
   const int nw = choose_resident(a.S, a.B * a.H, lds, 16, false);
@@ -1656,11 +1654,10 @@ static int launch_fwd(const AttnArgs& a_in, hipStream_t s) {
   const int waves_cu = DH == 16 ? 4 * MST_ATT16_WAVES_FWD : 16;
   int nw = choose_resident(a.S, a.B * a.H, lds, waves_cu, lone_f);
   if (!nw) {  // Q | K | V do not fit together: two tiles, K and V staged over Q between the phases (configs[4]'s decoder: S 1025, dh 16)
-    static const bool off = getenv("MST_ATTN_RESTAGE") && getenv("MST_ATTN_RESTAGE")[0] == '0';
     const size_t lds2 = res_lds_fwd<DH>(a.S, 2);
-    const int nw2 = off ? 0 : choose_resident(a.S, a.B * a.H, lds2, waves_cu, lone_f);
+    const int nw2 = choose_resident(a.S, a.B * a.H, lds2, waves_cu, lone_f);
     if (nw2) { nw = nw2; lds = lds2; a.restage = 1; }
-    else if (!off && !lone_f && DH >= 32) {
+    else if (!lone_f && DH >= 32) {
       // ... nor K | V alone: one tile, the output phase in two chunks of keys (configs[4]'s encoder: S 1024, head size 32)
       const int NB = (int)cdiv(a.S, 32);
       const size_t lds1 = res_lds_fwd<DH>(a.S, 1);
@@ -1725,10 +1722,9 @@ static int launch_bwd(const AttnArgs& a, hipStream_t s) {
   else hipLaunchKernelGGL((attn_bwd_kv_kernel<T, DH, false>), grid, dim3(256), 0, s, a);
   MST_CHECK_LAUNCH("attn_bwd_kv_kernel");
   {  // dQ: one workgroup per (batch, head) with the keys staged in chunks where the constants and two chunk tiles fit LDS
-    static const bool off = getenv("MST_ATTN_QCHUNK") && getenv("MST_ATTN_QCHUNK")[0] == '0';
     constexpr int OBM = 4, NWQ = 8;
     const int NB = (int)cdiv(a.S, 32);
-    if (!off && DH == 32 && NB <= OBM * NWQ) {  // (head size 32: at 64 four blocks' accumulators and fragments do not fit 256 registers)
+    if (DH == 32 && NB <= OBM * NWQ) {  // (head size 32: at 64 four blocks' accumulators and fragments do not fit 256 registers)
       for (int nc = 1; nc <= 4; nc *= 2) {
         if (NB % nc != 0) break;
         const size_t lds = (size_t)2 * (NB * 32 / nc) * LdsLd<DH>::V * 2 + (size_t)6 * NB * 32 * 4;

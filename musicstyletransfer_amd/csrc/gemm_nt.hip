@@ -1291,8 +1291,7 @@ extern "C" int mst_gemm_sigmoid_bce_dgrad_ln(const mst_gemm_args* args, const ms
   if (rc == MST_OK) rc = check_gemm_ln(g2, l);
   if (rc) return rc;
   // one launch: 128 pitches, width 128, whole 64-row tiles, and the second GEMM's A operand IS the first one's logit gradient
-  static const bool off = getenv("MST_BCE_DGRAD") && getenv("MST_BCE_DGRAD")[0] == '0';
-  const bool one = !off && a.N == 128 && g2.N == 128 && g2.K == 128 && g2.M == a.M && a.M % 64 == 0 && l.mode == 2 && a.C && g2.A == a.C &&
+  const bool one = a.N == 128 && g2.N == 128 && g2.K == 128 && g2.M == a.M && a.M % 64 == 0 && l.mode == 2 && a.C && g2.A == a.C &&
                    g2.lda == a.ldc && g2.dtype == a.dtype && g2.a_rows_per_group <= 0 && !g2.a_u8;
   if (!one) {
     rc = mst_gemm_sigmoid_bce(args, bce, stream);
@@ -1340,8 +1339,7 @@ extern "C" int mst_gemm_nt(const mst_gemm_args* args, mst_stream_t stream) {
     // (a launch whose rows are whole 64-row tiles but not whole 128-row tiles — the decoder's 64 x 257 — keeps the
     // fast-epilogue kernel with 64x64 tiles)
     const bool ragged128 = a.M % 128 != 0 && a.M % 64 == 0 && a.N % 128 == 0 && !a.c_f32;
-    static const bool three = !(getenv("MST_GEMM_3CU") && getenv("MST_GEMM_3CU")[0] == '0');
-    if (three && big_tiles > 512 && big_tiles <= 768 && a.N >= 128 && !ragged128) {
+    if (big_tiles > 512 && big_tiles <= 768 && a.N >= 128 && !ragged128) {
       const int rc = launch_gemm_3cu<T>(a, s);
       if (rc <= 0) return rc;
     }
@@ -1369,8 +1367,7 @@ extern "C" int mst_gemm_nt_pair_begin(const mst_gemm_args* args0, const mst_gemm
            a.act == 0 && a.dropout_p == 0.f && !a.self_resid && ((!a.rowadd && !a.grpadd) || a.rowadd_period > 0) &&
            (!a.grpadd || a.grp_index) && gemm_fast_form<64, 64>(a) && a.K % 64 == 0 && cdiv(a.M, 64) * cdiv(a.N, 64) < (1 << 20);
   };
-  static const bool off = getenv("MST_GEMM_PAIR") && getenv("MST_GEMM_PAIR")[0] == '0';
-  if (off || a0.dtype != a1.dtype || !plain(a0) || !plain(a1) || (begin && begin->sh_w && begin->sh_dtype != a0.dtype)) {
+  if (a0.dtype != a1.dtype || !plain(a0) || !plain(a1) || (begin && begin->sh_w && begin->sh_dtype != a0.dtype)) {
     int rc = begin ? mst_step_begin_v(begin, stream) : MST_OK;  // (runs the shadow refresh as a launch of its own)
     if (rc == MST_OK) rc = mst_gemm_nt(args0, stream);
     return rc != MST_OK ? rc : mst_gemm_nt(args1, stream);
@@ -1390,8 +1387,7 @@ extern "C" int mst_gemm_nt_pair_begin(const mst_gemm_args* args0, const mst_gemm
     // long contractions (configs[2]: 2048 pitch columns per frame): 128 x 128 tiles — the uint8 frames cross L2 -> LDS once per
     // 128 output columns instead of once per 64 (three times instead of six for the two tables), 33 K stages amortise the tile's
     // prologue and epilogue; at configs[1]'s K = 128 the 64 x 64 form stays (1 536 short tiles fill the chip, 384 long ones do not)
-    static const bool big_off = getenv("MST_GEMM_PAIR_BIG") && getenv("MST_GEMM_PAIR_BIG")[0] == '0';
-    if (!big_off && a0.K >= 1024 && a1.K >= 1024 && gemm_fast_form<128, 128>(a0) && gemm_fast_form<128, 128>(a1)) {
+    if (a0.K >= 1024 && a1.K >= 1024 && gemm_fast_form<128, 128>(a0) && gemm_fast_form<128, 128>(a1)) {
       const int t0 = (int)((a0.M / 128) * (a0.N / 128)), t1 = (int)((a1.M / 128) * (a1.N / 128));
       const size_t lds_b = (size_t)2 * (128 + 128) * 64 * 2;  // (epilogue: one 64-row block of the tile at a time, PATH 4: 34 KB)
       static bool opted = false;

@@ -659,12 +659,11 @@ extern "C" int mst_gemm_wgrad_batch_flush(const mst_wgrad_args* list, int n, flo
   // fl(0 + s1) + s2 == fl(0 + s2) + s1; no slab scratch, no reduction pass — measured 170 us against 70 + 17: with one 4-wave
   // workgroup per CU a 64-row stage is a dependent chain of ~1.3 us whatever the tile size. docs/kernel_notes.md, round 4)
   const int bn = big >= 2 ? 256 : (big ? 128 : 64), bk = big == 3 ? 256 : (big ? 128 : 64);
-  static const bool mixed = !(getenv("MST_WGRAD_MIXED") && getenv("MST_WGRAD_MIXED")[0] == '0');
   b.tile_prefix[0] = 0;
   int bk_p[WG_MAXP];
   b.narrow = 0u;
   for (int i = 0; i < n; ++i) {
-    bk_p[i] = (big == 3 && mixed && list[i].K <= 128) ? 128 : bk;
+    bk_p[i] = (big == 3 && list[i].K <= 128) ? 128 : bk;
     if (bk_p[i] != bk) b.narrow |= 1u << i;
     b.tile_prefix[i + 1] = b.tile_prefix[i] + cdiv(list[i].N, bn) * cdiv(list[i].K, bk_p[i]);
   }

@@ -6,9 +6,9 @@
 //   z = mu + eps * sigma                                       model.py:292   (eps injected by the caller)
 //   kl[b] = 0.5 * sum(sigma^2 + mu^2 - 1 - log(sigma^2))       loss.py:8-12   (no epsilon inside the log)
 //   dec_in[b,0,:] = alpha_d * (z · Wh^T + bh + cls_d[c_b]) + pos_d[0]   model.py:229-232,244; transformer.py:237
-// Backward: per-sample vectors in one kernel, then the parameter gradients as batch reductions
-// (no atomics: each output element is owned by one thread that loops over the batch) — a second launch (mst_latent_bwd), or,
-// in the training step, two mst_outer_job that ride on the weight-gradient reduction pass (mst_latent_bwd_vec + outer_jobs.hpp).
+// Backward: per-sample vectors in one kernel (mst_latent_bwd_vec), then the parameter gradients as batch reductions
+// (no atomics: each output element is owned by one thread that loops over the batch): two mst_outer_job that ride on the
+// weight-gradient reduction pass (outer_jobs.hpp).
 //
 // These are B x {De, 2Z, Dd} problems (64 x 256 x 128): far too small for MFMA tiles to matter;
 // they are kept in fp32 because the KL term's log(sigma^2) is the most precision-sensitive
@@ -348,28 +348,6 @@ __device__ __forceinline__ void class_table_block(int blk, int tid, int64_t B, i
   }
 }
 
-// ONE launch for the three parameter-gradient pieces of the latent block (they were three ~5-14 us launches):
-// blocks [0, n_wl): dWl[2Z, De] += dlat^T h0, dbl; blocks [n_wl, n_wl + n_wh): dWh[Dd, Z] += t^T z, dbh;
-// the rest: dcls_d[class_b, :] += t[b, :] in a fixed order (class_table_block)
-template <typename T>
-__global__ __launch_bounds__(256) void latent_param_grads_kernel(int64_t B, int De, int Z, int Dd, const float* __restrict__ dlat,
-                                                                 const T* __restrict__ enc_out, int64_t enc_stride,
-                                                                 const float* __restrict__ tvec, const float* __restrict__ z,
-                                                                 const int32_t* __restrict__ classes, float* __restrict__ dWl,
-                                                                 float* __restrict__ dbl, float* __restrict__ dWh,
-                                                                 float* __restrict__ dbh, float* __restrict__ dcls, int64_t ld_cls,
-                                                                 int n_wl, int n_wh) {
-  __shared__ float red[8][64];
-  const int blk = blockIdx.x;
-  if (blk < n_wl) {
-    batch_outer<T>(blk, threadIdx.x, B, 2 * Z, De, dlat, enc_out, enc_stride, dWl, dbl, red);
-  } else if (blk < n_wl + n_wh) {
-    batch_outer<float>(blk - n_wl, threadIdx.x, B, Dd, Z, tvec, z, Z, dWh, dbh, red);
-  } else {
-    class_table_block(blk - n_wl - n_wh, threadIdx.x, B, Dd, tvec, classes, dcls, ld_cls);
-  }
-}
-
 // the class table's gradient as a launch of its own (mst_latent_bwd_vec): grid cdiv(Dd, 64), 256 threads
 __global__ __launch_bounds__(256) void class_table_grad_kernel(int64_t B, int Dd, const float* __restrict__ tvec,
                                                                const int32_t* __restrict__ classes, float* __restrict__ dcls,
@@ -425,43 +403,6 @@ extern "C" int mst_latent_fwd_proj(int dtype, int64_t B, int64_t De, int64_t Z, 
   MST_CHECK_ARG(Wq != nullptr, "mst_latent_fwd_proj: null projection weight");
   return latent_fwd_impl(dtype, B, De, Z, Dd, enc_out, enc_sample_stride, Wl, bl, eps, Wh, bh, classes, cls_d, ld_cls, pos_d, alpha_d, mu, sigma, z,
                          kl, dec_in, dec_sample_stride, Wq, ld_wq, bq, qkv0, qkv_sample_stride, nq, stream);
-}
-
-extern "C" int mst_latent_bwd(int dtype, int64_t B, int64_t De, int64_t Z, int64_t Dd, const void* enc_out,
-                              int64_t enc_sample_stride, const float* Wl, const float* eps, const float* Wh,
-                              const int32_t* classes, const float* mu, const float* sigma, const float* z,
-                              const void* d_dec_in, int64_t dec_sample_stride, float alpha_d, float kl_weight,
-                              float gscale, float enc_scale, float* dWl, float* dbl, float* dWh, float* dbh, float* dcls_d,
-                              int64_t ld_cls, void* d_enc_out, int64_t denc_sample_stride, float* scratch,
-                              mst_stream_t stream) {
-  MST_CHECK_ARG(B > 0 && De > 0 && Z > 0 && Dd > 0, "mst_latent_bwd: sizes must be positive");
-  MST_CHECK_ARG(enc_out && Wl && eps && Wh && classes && mu && sigma && z && d_dec_in && dWl && dbl && dWh && dbh &&
-                    dcls_d && d_enc_out && scratch,
-                "mst_latent_bwd: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  float* tvec = scratch;            // [B, Dd]
-  float* dlat = scratch + B * Dd;   // [B, 2Z]
-  MST_CHECK_ARG(Z <= LAT_THREADS, "mst_latent_bwd: latent size above %d", LAT_THREADS);
-  MST_CHECK_ARG(2 * Z * De < (1ll << 31) && Dd * Z < (1ll << 31) && B * Dd < (1ll << 31), "mst_latent_bwd: sizes above 2^31 elements");
-  const size_t lds = sizeof(float) * (Dd + 2 * Z + (latent_bwd_pre_shape(De, Z, Dd) ? 1 : 4) * LAT_THREADS + 4);  // (+ 4: the float4 view's alignment)
-  const int n_wl = (int)cdiv(2 * Z * De, 64), n_wh = (int)cdiv(Dd * Z, 64), n_cls = (int)cdiv(Dd, 64);
-  return dispatch_act(dtype, [&](auto tag) -> int {
-    typedef decltype(tag) T;
-    if (latent_bwd_pre_shape(De, Z, Dd))
-      hipLaunchKernelGGL((latent_bwd_vec_kernel<T, true>), dim3((unsigned)B), dim3(LAT_THREADS), lds, s, (int)De, (int)Z, (int)Dd, Wl,
-                         eps, Wh, mu, sigma, (const T*)d_dec_in, dec_sample_stride, alpha_d, kl_weight, gscale, enc_scale, tvec,
-                         dlat, (T*)d_enc_out, denc_sample_stride, (const int32_t*)nullptr, (float*)nullptr, (int64_t)0, LatentDx0{});
-    else
-      hipLaunchKernelGGL((latent_bwd_vec_kernel<T, false>), dim3((unsigned)B), dim3(LAT_THREADS), lds, s, (int)De, (int)Z, (int)Dd, Wl,
-                         eps, Wh, mu, sigma, (const T*)d_dec_in, dec_sample_stride, alpha_d, kl_weight, gscale, enc_scale, tvec,
-                         dlat, (T*)d_enc_out, denc_sample_stride, (const int32_t*)nullptr, (float*)nullptr, (int64_t)0, LatentDx0{});
-    MST_CHECK_LAUNCH("latent_bwd_vec_kernel");
-    hipLaunchKernelGGL((latent_param_grads_kernel<T>), dim3((unsigned)(n_wl + n_wh + n_cls)), dim3(256), 0, s, B, (int)De, (int)Z,
-                       (int)Dd, dlat, (const T*)enc_out, enc_sample_stride, tvec, z, classes, dWl, dbl, dWh, dbh, dcls_d, ld_cls,
-                       n_wl, n_wh);
-    MST_CHECK_LAUNCH("latent_param_grads_kernel");
-    return MST_OK;
-  });
 }
 
 static int latent_bwd_vec_impl(int dtype, int64_t B, int64_t De, int64_t Z, int64_t Dd, const float* Wl, const float* eps,

@@ -188,11 +188,10 @@ class ParamStore:
         # Deferred shadow refresh (piano-roll ends): the transposed shadows of the matrices only the BACKWARD pass reads are rebuilt by
         # extra workgroups of the NEXT step's first launch (mst_gemm_nt_pair_begin, sh_*) instead of a launch of their own behind the
         # optimizer; the two embedding tables, which that first launch itself reads, are kept current by the optimizer launch
-        # (mst_adam_flat_emb). MST_SHADOW_RIDE=0: the separate launch.
+        # (mst_adam_flat_emb). Token ends keep the separate launch.
         emb_names = [n for n in ("encoder.embedding.weight", "decoder.embedding.weight") if n in self.t_specs]
         late = [n for n in self.t_specs if n not in emb_names]
-        self.shadows_deferred = (cfg.kind == "pianoroll" and len(emb_names) == 2 and len(late) > 0 and
-                                 os.environ.get("MST_SHADOW_RIDE", "1") != "0" and os.environ.get("MST_BEGIN_RIDE", "1") != "0")
+        self.shadows_deferred = cfg.kind == "pianoroll" and len(emb_names) == 2 and len(late) > 0
         ldesc, lprefix = [], [0]
         for name in late:
             so, r, c = self.t_specs[name]
@@ -545,10 +544,9 @@ class StepPlan:
             # The class-embedding gradient is a column sum of d(x0) per class = onehot(class)^T d(x0): with the one-hot class id
             # of a frame in C extra columns behind its pitches, and the class table behind the embedding table in the flat
             # buffers, it is rows in_dim.. of the encoder embedding's weight-gradient problem — whose 256-row tile has the
-            # room — instead of a launch of its own (MST_CLS_WGRAD=0: the group_colsum launch)
+            # room — instead of a launch of its own (otherwise: the group_colsum launch)
             C_ = cfg.num_classes
-            self.cls_fold = (os.environ.get("MST_CLS_WGRAD", "1") != "0" and cfg.in_dim % 8 == 0 and
-                             roundup(cfg.in_dim + C_, 256) == roundup(cfg.in_dim, 256) and
+            self.cls_fold = (cfg.in_dim % 8 == 0 and roundup(cfg.in_dim + C_, 256) == roundup(cfg.in_dim, 256) and
                              store.offsets["encoder.class2hid.weight"] == store.offsets["encoder.embedding.weight"] + cfg.in_dim * De)
             self.ld_roll = roundup(cfg.in_dim + (C_ if self.cls_fold else 0), 8)
             seg = [("roll", B * T * self.ld_roll), ("labels", B * T * cfg.out_dim)]
@@ -561,7 +559,6 @@ class StepPlan:
         self.bind_inputs(self.own_inbuf)
         self.eps = torch.zeros(B, Z, **f32)
         self.rng_state = store.rng_state(seed)
-        self.defer_latent_grads = os.environ.get("MST_DEFER_LATENT", "1") != "0"
         self._outers = []
 
         self.pos_e = torch.from_numpy(positional_table(De, Se)).to(dev)
@@ -599,28 +596,27 @@ class StepPlan:
         self.metric_acc = store.metric_acc  # [sum kl, sum total, count]  (trainer.py:115-116)
         self.track_token_metrics = False  # Trainer: accumulate ppl / acc / topk sums on the device in the CE launch
         # output layer + BCE in one launch when a tile can hold whole rows of pitches of one sample (configs[1]: P 128, T 256)
-        fb = os.environ.get("MST_FUSE_BCE", "1")  # "0": never, "all": wherever the launch exists (A/B runs), default: where it pays
-        self.fuse_bce = (cfg.kind == "pianoroll" and o.can_fuse_bce(cfg.out_dim, T, negative_label_downscaling) and fb != "0" and
-                         (fb == "all" or o.bce_fusion_pays(cfg.out_dim)))
-        # the attention output projection + LayerNorm-1 in front of the forward feed-forward launch (two launches less per layer
-        # at equal time; its dgrad behind the backward block measured +14 us and was removed): MST_FUSE_PROJ=0 keeps them apart
-        self.fuse_tail_bwd = os.environ.get("MST_TAIL_BWD", "1") != "0"  # the top layer's position-0 backward chain in one launch
-        self.fuse_proj = os.environ.get("MST_FUSE_PROJ", "1") != "0"
+        self.fuse_bce = (cfg.kind == "pianoroll" and o.can_fuse_bce(cfg.out_dim, T, negative_label_downscaling) and
+                         o.bce_fusion_pays(cfg.out_dim))
+        # ... and the output layer's input gradient + the last decoder layer's LayerNorm-3 backward in the same workgroups
+        self.bce_dgrad = self.fuse_bce and o.ln_bwd_fusion_pays(Dd)
         # The LAST decoder layer's row-wise part (W_proj, LayerNorm-1, feed-forward, LayerNorm-3 and their backward) skips every
         # sample's position-0 row: its output is dropped before the loss (model.py:253), so nothing it computes there is ever
         # read and every gradient there is zero — the buffers' position-0 rows simply stay at the zeros they were allocated with.
         # B x T rows are B T / 64 tiles of the one-workgroup-per-CU feed-forward launches: ONE resident round at configs[1]
         # (256 tiles) where B (T + 1) rows were 257 (measured: forward 22.8 -> 18.9 us, backward 24.6 -> 20.3).
-        self.skip_row0 = (cfg.d_layers > 0 and T % 64 == 0 and o.ffn_fusion_pays(Dd, 4 * Dd) and
-                          os.environ.get("MST_SKIP_ROW0", "1") != "0")
+        self.skip_row0 = cfg.d_layers > 0 and T % 64 == 0 and o.ffn_fusion_pays(Dd, 4 * Dd)
         # RIDERS on the one-launch position-0 tails (which keep ONE XCD busy for ~26 us each while seven idle): the decoder's first
         # K | Q | V projection of rows 1..T — its input exists since the step's first launch — is computed by the forward tail
         # launch's workgroups on the other XCDs (row 0 by the latent block's launch), and the input gradient of that projection for
         # rows 1..T — which only the decoder embedding's weight gradient reads — by the backward tail's (row 0 inside the latent
         # block's backward launch): two GEMM launches (12 + 10 us at configs[1]) leave the step's dependent chain. Piano-roll ends.
         self.ride = (cfg.kind != "token" and cfg.d_layers >= 1 and cfg.e_layers >= 1 and Dd in (128, 256) and
-                     o.can_ride(B * T, 3 * Dd, Dd, T) and o.can_ride(B * T, Dd, 3 * Dd, T) and os.environ.get("MST_TAIL_RIDERS", "1") != "0")
+                     o.can_ride(B * T, 3 * Dd, Dd, T) and o.can_ride(B * T, Dd, 3 * Dd, T))
         self._ride_fwd = self._ride_bwd = False
+        # the deferred shadow refresh (ParamStore.shadows_deferred) behind the forward tail's riders where that launch has them;
+        # False: behind the tiles of the step's first launch
+        self.shadows_on_tail = True
         self.logits = None if self.fuse_bce else act(B * T, cfg.out_dim)
         self.dlogits = act(B * T, cfg.out_dim)
         if cfg.kind == "token":
@@ -660,7 +656,7 @@ class StepPlan:
         self.lat_scratch = torch.zeros(B * (Dd + 2 * Z), **f32)
         # Sparse gradient carriers, never used as ping-pong targets so their untouched rows stay zero:
         #   d_dec_out: d(decoder output) - rows 1..T written by the output-layer dgrad, row 0 always 0 (model.py:253)
-        #   d_enc_out: d(encoder output) - only row 0 of each sample written, by latent_bwd (model.py:97)
+        #   d_enc_out: d(encoder output) - only row 0 of each sample written, by latent_bwd_vec (model.py:97)
         self.d_dec_out = act(self.Md, Dd)
         self.d_enc_out = act(self.Me, De)
         # Top encoder layer, backward: the loss reads the encoder only at position 0 (model.py:97), so the gradient
@@ -877,7 +873,7 @@ class StepPlan:
         # as much. The backward forms, where the LayerNorm launch is 16 us, do pay: _layer_bwd.)
         proj = dict(N=D, K=D, bias=st.p(f"{pre}.att.W_proj.bias"), resid=x_in, **self._drop(p, site0))
         fused = o.ffn_fusion_pays(D, 4 * D)
-        if not (fused and self.fuse_proj):
+        if not fused:
             o.gemm_nt(L.att, st.h(f"{pre}.att.W_proj.weight"), L.h1, **proj)
             o.layernorm_fwd(L.h1, st.p(f"{pre}.ln1.gamma"), st.p(f"{pre}.ln1.beta"), L.x1, L.mean1, L.rstd1, D=D)
         ff1 = dict(K=D, bias=st.p(f"{pre}.ff1.bias"), act=o.ACT_RELU, **self._drop(p, site0 + 1))
@@ -885,11 +881,11 @@ class StepPlan:
         ln = "ln2" if side == "encoder" else "ln3"
         ff2 = dict(K=4 * D, bias=st.p(f"{pre}.ff2.bias"), **self._drop(p, site0 + 2))
         ff2.update(dict(resid=L.x1) if side == "encoder" else dict(self_resid=True))
-        if fused:  # the whole feed-forward block + LayerNorm in one launch (same results, bit for bit in a / h2)
-            head = None
-            if self.fuse_proj:  # ... and the attention output projection + LayerNorm-1 in front of it (mst_proj_ffn_ln_fwd)
-                head = dict(att=L.att, W=st.h(f"{pre}.att.W_proj.weight"), h1=L.h1, gamma=st.p(f"{pre}.ln1.gamma"),
-                            beta=st.p(f"{pre}.ln1.beta"), mean=L.mean1, rstd=L.rstd1, **proj)
+        if fused:  # the attention output projection + LayerNorm-1, the whole feed-forward block and its LayerNorm in one launch
+            # (mst_proj_ffn_ln_fwd; same results, bit for bit in a / h2. The projection's dgrad behind the backward block measured +14 us
+            # and was removed.)
+            head = dict(att=L.att, W=st.h(f"{pre}.att.W_proj.weight"), h1=L.h1, gamma=st.p(f"{pre}.ln1.gamma"),
+                        beta=st.p(f"{pre}.ln1.beta"), mean=L.mean1, rstd=L.rstd1, **proj)
             o.ffn_ln_fwd(L.x1, st.h(f"{pre}.ff1.weight"), L.a, st.h(f"{pre}.ff2.weight"), L.h2, st.p(f"{pre}.{ln}.gamma"),
                          st.p(f"{pre}.{ln}.beta"), L.x2, L.mean2, L.rstd2, ff1=ff1, ff2=ff2, proj=head,
                          row_groups=self._row0_groups(side, i))
@@ -901,7 +897,7 @@ class StepPlan:
 
     def _ride_bwd_planned(self):
         """the backward tail will run as one launch in this step and can take a rider (decided before it is issued)"""
-        return self.ride and self._tail_on(self.cfg.e_model) and self.fuse_tail_bwd and self.defer_latent_grads
+        return self.ride and self._tail_on(self.cfg.e_model)
 
     def _row0_groups(self, side, i):
         """row groups of the last decoder layer's row-wise launches (skip_row0): rows 1..T of every T + 1, else None"""
@@ -931,16 +927,16 @@ class StepPlan:
                      mask_e=self.keymask_e if cfg.kind != "token" else None, add_e=0, mask_d=self.keymask_d, add_d=1,
                      zero_a=self._recon_buf, zero_b=st.g if tick else None)
         self._tail_shadows = None
-        if st.shadows_deferred and cfg.kind != "token" and os.environ.get("MST_BEGIN_RIDE", "1") != "0":
+        if st.shadows_deferred:
             late = dict(w=st.w, wt16=st.wt16, desc=st.t_desc_late, prefix=st.t_prefix_late, n_mat=st.t_n_late, tiles=st.t_tiles_late)
             # the refresh of the transposed shadows (read by the backward pass only): behind the forward tail's riders where that launch
             # has them — compute units that idle until the position-0 chain ends — else behind the tiles of the step's first launch (+4.9 us)
-            if self.ride and self._tail_on(cfg.e_model) and cfg.e_layers >= 1 and os.environ.get("MST_SHADOW_TAIL", "1") != "0":
+            if self.shadows_on_tail and self.ride and self._tail_on(cfg.e_model):
                 self._tail_shadows = late
             else:
                 begin["shadows"] = late
         # (piano-roll ends: nothing in the embedding GEMMs reads what the bookkeeping writes — it rides on their launch)
-        ride = cfg.kind != "token" and os.environ.get("MST_BEGIN_RIDE", "1") != "0"
+        ride = cfg.kind != "token"
         if not ride:
             o.step_begin(**begin)
         # ---- encoder input (model.py:81-91, transformer.py:270)
@@ -993,7 +989,7 @@ class StepPlan:
                          tok_parts=self.store.tok_parts if self.track_token_metrics else None)
         elif self.fuse_bce:
             dgrad = None
-            if with_grad and o.ln_bwd_fusion_pays(cfg.d_model) and os.environ.get("MST_BCE_DGRAD", "1") != "0":
+            if with_grad and self.bce_dgrad:
                 # the first launch of the backward pass — the output layer's input gradient + the last decoder layer's LayerNorm-3
                 # backward (backward_early) — consumes exactly the logit-gradient tile this launch produces: same workgroup
                 last, Dd, Sd = cfg.d_layers - 1, cfg.d_model, T + 1
@@ -1152,7 +1148,7 @@ class StepPlan:
             return buf.view(B, S, -1)[:, 0, :]
 
         dy = row0(self.d_enc_out)
-        self._tail_used["bwd"] = self._tail_on(D) and self.fuse_tail_bwd
+        self._tail_used["bwd"] = self._tail_on(D)
         if self._tail_used["bwd"]:
             # LayerNorm-2 backward, both FFN dgrads, LayerNorm-1 backward and the W_proj dgrad of the B rows in one launch
             o.row_tail_bwd(dy, row0(L.h2), row0(L.h1), row0(L.a), L.mean1, L.rstd1, L.mean2, L.rstd2, st.p(f"{pre}.ln1.gamma"),
@@ -1268,24 +1264,15 @@ class StepPlan:
                                                 K=Dd, scale=sq_d, b_remap=(T, Sd, 1)))
         # gradient w.r.t. the encoder output: zero except position 0 of every sample
         d_enc = self.d_enc_out
-        if self.defer_latent_grads:
-            # nothing but the optimizer reads the latent block's parameter gradients: they ride on the weight-gradient flush (extra
-            # workgroups of its reduction pass) instead of being a launch in the middle of the backward pass's dependent chain
-            o.latent_bwd_vec(st.p("encoder.latent_proj.weight"), self.eps, st.p("decoder.latent2hid.weight"), self.classes, self.mu,
-                             self.sigma, d_x0_d.view(B, Sd, -1), sq_d, self.kl_weight, self.gscale_enc,
-                             st.grad("decoder.class2hid.weight"), d_enc.view(B, Se, -1), self.lat_scratch,
-                             enc_scale=self.gscale_enc / self.gscale, proj=self._bwd_dx0)
-            self._outers += o.latent_outer_jobs(self.lat_scratch, self.enc_out.view(B, Se, -1), self.z,
-                                                st.grad("encoder.latent_proj.weight"), st.grad("encoder.latent_proj.bias"),
-                                                st.grad("decoder.latent2hid.weight"), st.grad("decoder.latent2hid.bias"))
-        else:
-            o.latent_bwd(self.enc_out.view(B, Se, -1), st.p("encoder.latent_proj.weight"), self.eps,
-                         st.p("decoder.latent2hid.weight"), self.classes, self.mu, self.sigma, self.z,
-                         d_x0_d.view(B, Sd, -1), sq_d, self.kl_weight, self.gscale_enc,
-                         st.grad("encoder.latent_proj.weight"), st.grad("encoder.latent_proj.bias"),
-                         st.grad("decoder.latent2hid.weight"), st.grad("decoder.latent2hid.bias"),
+        # nothing but the optimizer reads the latent block's parameter gradients: they ride on the weight-gradient flush (extra
+        # workgroups of its reduction pass) instead of being a launch in the middle of the backward pass's dependent chain
+        o.latent_bwd_vec(st.p("encoder.latent_proj.weight"), self.eps, st.p("decoder.latent2hid.weight"), self.classes, self.mu,
+                         self.sigma, d_x0_d.view(B, Sd, -1), sq_d, self.kl_weight, self.gscale_enc,
                          st.grad("decoder.class2hid.weight"), d_enc.view(B, Se, -1), self.lat_scratch,
-                         enc_scale=self.gscale_enc / self.gscale)
+                         enc_scale=self.gscale_enc / self.gscale, proj=self._bwd_dx0)
+        self._outers += o.latent_outer_jobs(self.lat_scratch, self.enc_out.view(B, Se, -1), self.z,
+                                            st.grad("encoder.latent_proj.weight"), st.grad("encoder.latent_proj.bias"),
+                                            st.grad("decoder.latent2hid.weight"), st.grad("decoder.latent2hid.bias"))
         top = cfg.e_layers - 1
         x_in = self.enc[top - 1].x2 if top > 0 else self.x0_e
         below = (self._out_ln_bwd("encoder", top - 1, self.enc[top - 1], De, cfg.e_dropout, self._site_e(top - 1), self.be_l[top - 1], self.Me),
@@ -1334,7 +1321,7 @@ class StepPlan:
                         rescale=1.0 / (self.global_batch * self.gscale), clip=clip, advance_step=False, metrics=mt, emb=emb(0), **self.opt)
         else:
             # encoder.* tensors come first in the flat buffers; everything from decoder.latent2hid on is decoder-side.
-            # NOTE the latent_proj gradients are produced by latent_bwd at the encoder-side scale.
+            # NOTE the latent_proj gradients are produced by latent_bwd_vec at the encoder-side scale.
             cut = st.offsets["decoder.latent2hid.weight"]
             rng = [(0, cut, self.gscale_enc, False), (cut, st.n, self.gscale, False)]
             for a, b, gs, adv in rng:

@@ -567,19 +567,9 @@ def latent_fwd(enc_out3, Wl, bl, eps, Wh, bh, classes, cls_d, pos_d, alpha_d, mu
         call("mst_latent_fwd_proj", *args, ptr(Wq), ld(Wq), ptr(bq), ptr(qkv3), qkv3.stride(0), Wq.shape[0], stream())
 
 
-def latent_bwd(enc_out3, Wl, eps, Wh, classes, mu, sigma, z, d_dec_in3, alpha_d, kl_weight, gscale, dWl, dbl, dWh, dbh,
-               dcls_d, d_enc_out3, scratch, enc_scale=1.0):
-    B = enc_out3.shape[0]
-    De, Z, Dd = Wl.shape[1], Wh.shape[1], Wh.shape[0]
-    call("mst_latent_bwd", dt(enc_out3), B, De, Z, Dd, ptr(enc_out3), enc_out3.stride(0), ptr(Wl), ptr(eps), ptr(Wh),
-         ptr(classes), ptr(mu), ptr(sigma), ptr(z), ptr(d_dec_in3), d_dec_in3.stride(0), alpha_d, kl_weight, gscale,
-         enc_scale, ptr(dWl), ptr(dbl), ptr(dWh), ptr(dbh), ptr(dcls_d), dcls_d.stride(0), ptr(d_enc_out3), d_enc_out3.stride(0),
-         ptr(scratch), stream())
-
-
 def latent_bwd_vec(Wl, eps, Wh, classes, mu, sigma, d_dec_in3, alpha_d, kl_weight, gscale, dcls_d, d_enc_out3, scratch, enc_scale=1.0,
                    proj=None):
-    """latent_bwd's first launch with the decoder class table's gradient folded in (mst_latent_bwd_vec); the other parameter
+    """the latent block's backward pass with the decoder class table's gradient folded in (mst_latent_bwd_vec); the other parameter
     gradients are latent_outer_jobs(...) of the caller's weight-gradient flush.
     proj = (dqkv3 [B, S, >= nq], Wt [Dd, nq] the transposed 16-bit weight, resid3 [B, S, Dd] or None): d(dec_in[:, 0, :]) is computed
     here from the projection's gradient at position 0 instead of being read from d_dec_in3 (mst_latent_bwd_vec_proj)"""

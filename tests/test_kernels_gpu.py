@@ -1277,7 +1277,7 @@ def test_group_colsum(gpu, B, T, D, s_off):
 
 
 # ------------------------------------------------------------------------------------------ latent
-def test_latent_fwd_bwd(gpu):
+def test_latent_fwd_and_deferred_bwd(gpu):
     o = ops()
     B, S, De, Z, Dd, Cn, Sd = 5, 6, 64, 16, 32, 3, 7
     enc = rnd((B, S, De), gpu, seed=60)
@@ -1312,28 +1312,21 @@ def test_latent_fwd_bwd(gpu):
 
     g0 = rnd((B, Sd, Dd), gpu, seed=68, scale=0.1)
     beta = 0.7
-    dWl = torch.zeros_like(Wl); dbl = torch.zeros_like(bl); dWh = torch.zeros_like(Wh); dbh = torch.zeros_like(bh)
-    dcls = torch.zeros_like(cls_d)
-    denc = torch.zeros(B, S, De, dtype=BF, device=gpu)
-    scratch = torch.zeros(B * (Dd + 2 * Z), device=gpu)
-    o.latent_bwd(enc, Wl, eps, Wh, classes, mu, sigma, z, g0, alpha_d, beta, 1.0, dWl, dbl, dWh, dbh, dcls, denc, scratch)
-    torch.cuda.synchronize()
     total = (d0 * g0[:, 0].float()).sum() + beta * kl_r.sum()
     total.backward()
-    for got, ref, name in zip((dWl, dbl, dWh, dbh, dcls), (p.grad for p in P), ("dWl", "dbl", "dWh", "dbh", "dcls")):
-        close(got, ref, 1e-4, 1e-4 * max(1.0, ref.abs().max().item()), name)
-    close(denc[:, 0], h0.grad, 1e-2, 1e-2 * h0.grad.abs().max().item(), "d enc row 0")
 
-    # the deferred form (mst_latent_bwd_vec + two mst_outer_job): identical arithmetic, (a) as one mst_outer_jobs launch,
-    # (b) as extra workgroups of a weight-gradient flush that has a reduction pass, (c) behind a flush that has none
+    # the backward pass (mst_latent_bwd_vec + two mst_outer_job) against fp32 autograd and, bit for bit, against itself: (a) as one
+    # mst_outer_jobs launch, (b) as extra workgroups of a weight-gradient flush that has a reduction pass, (c) behind a flush that has none
     M, N, K = 1024, 256, 256  # a problem of the whole-step tile form (two-pass reduction through the scratch buffer)
     A, Bm = rnd((M, N), gpu, seed=69), rnd((M, K), gpu, seed=70)
+    names = ("dWl", "dbl", "dWh", "dbh", "dcls")
+    first = None
     for mode in ("own launch", "reduction pass", "no reduction pass"):
         g = [torch.zeros_like(t) for t in (Wl, bl, Wh, bh, cls_d)]
-        denc2 = torch.zeros(B, S, De, dtype=BF, device=gpu)
-        scratch2 = torch.zeros(B * (Dd + 2 * Z), device=gpu)
-        o.latent_bwd_vec(Wl, eps, Wh, classes, mu, sigma, g0, alpha_d, beta, 1.0, g[4], denc2, scratch2)
-        jobs = o.latent_outer_jobs(scratch2, enc, z, g[0], g[1], g[2], g[3])
+        denc = torch.zeros(B, S, De, dtype=BF, device=gpu)
+        scratch = torch.zeros(B * (Dd + 2 * Z), device=gpu)
+        o.latent_bwd_vec(Wl, eps, Wh, classes, mu, sigma, g0, alpha_d, beta, 1.0, g[4], denc, scratch)
+        jobs = o.latent_outer_jobs(scratch, enc, z, g[0], g[1], g[2], g[3])
         dW = torch.zeros(N, K, device=gpu)
         if mode == "own launch":
             o.outer_jobs(jobs)
@@ -1341,10 +1334,16 @@ def test_latent_fwd_bwd(gpu):
             ws = torch.zeros(16 * 1024 * 1024, device=gpu) if mode == "reduction pass" else None
             o.gemm_wgrad_batch([o.wgrad_problem(A, Bm, dW)], scratch=ws, outers=jobs)
         torch.cuda.synchronize()
-        assert torch.equal(scratch2, scratch) and torch.equal(denc2, denc), mode
-        for got, want, name in zip(g[:4], (dWl, dbl, dWh, dbh), ("dWl", "dbl", "dWh", "dbh")):
-            assert torch.equal(got, want), f"{name} ({mode})"
-        close(g[4], dcls, 1e-6, 1e-6, f"dcls ({mode})")  # (atomics: the order of the adds is free)
+        for got, ref, name in zip(g, (p.grad for p in P), names):
+            close(got, ref, 1e-4, 1e-4 * max(1.0, ref.abs().max().item()), f"{name} ({mode})")
+        close(denc[:, 0], h0.grad, 1e-2, 1e-2 * h0.grad.abs().max().item(), f"d enc row 0 ({mode})")
+        if first is None:
+            first = (scratch, denc, g)
+        else:
+            assert torch.equal(scratch, first[0]) and torch.equal(denc, first[1]), mode
+            for got, want, name in zip(g[:4], first[2][:4], names):
+                assert torch.equal(got, want), f"{name} ({mode})"
+            close(g[4], first[2][4], 1e-6, 1e-6, f"dcls ({mode})")
         if mode != "own launch":
             close(dW, A.float().t() @ Bm.float(), 1e-3, 1e-3 * math.sqrt(M), f"the flush's own problem ({mode})")
 

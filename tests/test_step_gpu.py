@@ -646,11 +646,10 @@ def test_a_step_with_a_non_finite_loss_leaves_the_model_alone(gpu):
     assert torch.isfinite(store.w).all() and not torch.equal(store.w, w_before)
 
 
-def test_transposed_shadows_follow_the_weights_without_their_own_launch(gpu):
+def test_deferred_shadow_refresh_matches_the_separate_launch(gpu):
     """Piano-roll ends: the optimizer launch keeps the two embedding tables' transposed shadows current (mst_adam_flat_emb) and the NEXT
     step's first launch rebuilds the backward-only ones (mst_gemm_nt_pair_begin, sh_*): after the optimizer the embedding shadows
     equal the weights, after the next forward pass all of them do — and the run equals one with the separate refresh launch."""
-    import os
     O, E, ocfg, ecfg, params, batch, eps = _setup("pianoroll", (48, 48, 2, 16, 64, 2, 2, 32, 1, 2), 4, 16, 61)
 
     def fresh(st, names):
@@ -662,13 +661,10 @@ def test_transposed_shadows_follow_the_weights_without_their_own_launch(gpu):
         return ok
 
     res = {}
-    for ride in ("1", "0"):
-        os.environ["MST_SHADOW_RIDE"] = ride
-        try:
-            store = E.ParamStore(ecfg, gpu, torch.bfloat16, params_np=params)
-        finally:
-            os.environ.pop("MST_SHADOW_RIDE", None)
-        assert store.shadows_deferred == (ride == "1")
+    for ride in (True, False):
+        store = E.ParamStore(ecfg, gpu, torch.bfloat16, params_np=params)
+        assert store.shadows_deferred
+        store.shadows_deferred = ride  # False: the refresh launch of its own behind the optimizer
         plan = E.StepPlan(store, 4, 16, lr=1e-2)
         plan.load_batch(batch["x"], batch["seq_lens"], batch["classes"], batch["labels"], eps)
         for _ in range(3):
@@ -677,7 +673,7 @@ def test_transposed_shadows_follow_the_weights_without_their_own_launch(gpu):
         emb = ["encoder.embedding.weight", "decoder.embedding.weight"]
         late = [n for n in store.t_specs if n not in emb]
         assert fresh(store, emb)
-        if ride == "1":
+        if ride:
             assert not fresh(store, late), "the backward-only shadows are one optimizer step behind until the next forward pass"
             plan._tick_adam = False
             plan.forward()
@@ -687,14 +683,13 @@ def test_transposed_shadows_follow_the_weights_without_their_own_launch(gpu):
     # (not bit for bit: the small configuration's LayerNorm parameter gradients and loss sums are fp32 atomics, order-dependent in
     # the last bits from run to run whatever the path)
     from test_parallel_gpu import _close_after_adam
-    _close_after_adam(res["1"], res["0"], 1e-2, 3)
+    _close_after_adam(res[True], res[False], 1e-2, 3)
 
 
-def test_shadow_refresh_rides_on_the_forward_tail(gpu):
+def test_shadow_refresh_on_the_forward_tail_matches_the_first_launch(gpu):
     """Widths at which the position-0 tails have riders (decoder width 128, T a multiple of 128): the backward-only transposed shadows are
     rebuilt by the forward tail's riders behind their GEMM tiles (mst_row_tail_fwd_ride_shadows) instead of on the step's first launch —
     after a forward pass every shadow equals its weights, and training equals the run that keeps the refresh on the first launch."""
-    import os
     # (full-length sequences: with padded keys this model sits in the reference's mask-flip regime — DESIGN section 4 —, where two runs one
     # rounding apart part ways by whole grid steps of the -1e9 mask: 3 of 24 identical runs ended 35 % of the weights away from the others,
     # whichever launch refreshed the shadows; tools/experiments/diag_sporadic.py, diag_shadow_grads.py)
@@ -708,31 +703,28 @@ def test_shadow_refresh_rides_on_the_forward_tail(gpu):
         return ok
 
     res = {}
-    for mode in ("1", "0"):
-        os.environ["MST_SHADOW_TAIL"] = mode
-        try:
-            store = E.ParamStore(ecfg, gpu, torch.bfloat16, params_np=params)
-            plan = E.StepPlan(store, 4, 128, lr=1e-2)
-            plan.load_batch(batch["x"], batch["seq_lens"], batch["classes"], batch["labels"], eps)
-            assert store.shadows_deferred and plan.ride
-            for _ in range(3):
-                plan.step_kernels(True)
-            torch.cuda.synchronize()
-            assert (plan._tail_shadows is not None) == (mode == "1")
-            assert int(store.step_status.cpu()[0]) == 0
-            emb = ["encoder.embedding.weight", "decoder.embedding.weight"]
-            late = [n for n in store.t_specs if n not in emb]
-            assert fresh(store, emb) and not fresh(store, late)
-            plan._tick_adam = False
-            plan.forward()
-            torch.cuda.synchronize()
-            assert fresh(store, emb + late)
-        finally:
-            os.environ.pop("MST_SHADOW_TAIL", None)
+    for mode in (True, False):
+        store = E.ParamStore(ecfg, gpu, torch.bfloat16, params_np=params)
+        plan = E.StepPlan(store, 4, 128, lr=1e-2)
+        plan.load_batch(batch["x"], batch["seq_lens"], batch["classes"], batch["labels"], eps)
+        assert store.shadows_deferred and plan.ride and plan.shadows_on_tail
+        plan.shadows_on_tail = mode  # False: the refresh on the step's first launch
+        for _ in range(3):
+            plan.step_kernels(True)
+        torch.cuda.synchronize()
+        assert (plan._tail_shadows is not None) == mode
+        assert int(store.step_status.cpu()[0]) == 0
+        emb = ["encoder.embedding.weight", "decoder.embedding.weight"]
+        late = [n for n in store.t_specs if n not in emb]
+        assert fresh(store, emb) and not fresh(store, late)
+        plan._tick_adam = False
+        plan.forward()
+        torch.cuda.synchronize()
+        assert fresh(store, emb + late)
         res[mode] = store.w.cpu().numpy().copy()
     # (three Adam steps at lr 1e-2 from gradients that differ in the order of their fp32 atomics: equal except where a near-zero
     # gradient flips sign; a stale shadow would move every weight)
-    d = np.abs(res["1"] - res["0"])
+    d = np.abs(res[True] - res[False])
     assert d.max() <= 2.1 * 1e-2 * 3 and (d > 2e-5).mean() < 0.05, (d.max(), (d > 2e-5).mean())
 
 

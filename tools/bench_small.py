@@ -39,8 +39,8 @@ def main():
     d_dec = r(B, T + 1, Dd).to(BF); d_enc = torch.zeros(B, T, De, dtype=BF, device=dev)
     dWl, dbl, dWh, dbh, dcls = torch.zeros_like(Wl), torch.zeros_like(bl), torch.zeros_like(Wh), torch.zeros_like(bh), torch.zeros_like(cls_d)
     scratch = torch.zeros(B * (Dd + 2 * Z), device=dev)
-    timeit("latent_bwd (all launches)", lambda: o.latent_bwd(enc, Wl, eps, Wh, classes, mu, sigma, z, d_dec, 11.3, 1.0, 1.0, dWl, dbl,
-                                                             dWh, dbh, dcls, d_enc, scratch))
+    timeit("latent_bwd_vec + outer_jobs", lambda: (o.latent_bwd_vec(Wl, eps, Wh, classes, mu, sigma, d_dec, 11.3, 1.0, 1.0, dcls, d_enc, scratch),
+                                                    o.outer_jobs(o.latent_outer_jobs(scratch, enc, z, dWl, dbl, dWh, dbh))))
     logits = r(B * T, P).to(BF); labels = (torch.rand(B * T, P, generator=g) < 0.05).to(torch.uint8).to(dev)
     recon = torch.zeros(B, device=dev); dlog = torch.zeros(B * T, P, dtype=BF, device=dev)
     timeit("sigmoid_bce (+dlogits)", lambda: o.sigmoid_bce(logits, labels, recon, B, T, P, dlogits=dlog))

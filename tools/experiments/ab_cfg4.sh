@@ -2,7 +2,6 @@ run() { python bench.py --config 4 --steps 60 --warmup 10 --full --no-cpu-baseli
 import json,sys
 d=json.loads(sys.stdin.read()); print('$1', d['ms_per_step'], [ (f['kernel'][:22], round(f['avg_launch_ms']*1e3,1)) for f in d['roofline']['families']])"; }
 run default
-MST_FUSE_PROJ=0 run noproj
 export MST_EXTRA_FLAGS="gemm_wgrad.hip=-DMST_WGRAD_IL=0"
 python -m musicstyletransfer_amd.csrc.build --force > /dev/null 2>&1
 run wgrad_il0

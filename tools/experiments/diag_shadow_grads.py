@@ -6,15 +6,13 @@ import numpy as np, torch
 from test_step_gpu import _setup
 gpu = torch.device("cuda", 0)
 mode = sys.argv[1] if len(sys.argv) > 1 else "begin"
-if mode == "begin":
-    os.environ["MST_SHADOW_TAIL"] = "0"
-if mode == "own":
-    os.environ["MST_SHADOW_RIDE"] = "0"
 O, E, ocfg, ecfg, params, batch, eps = _setup("pianoroll", (64, 64, 2, 16, 128, 2, 4, 128, 1, 4), 4, 128, 67)
 runs = []
 for rep in range(int(sys.argv[2]) if len(sys.argv) > 2 else 10):
     store = E.ParamStore(ecfg, gpu, torch.bfloat16, params_np=params)
+    store.shadows_deferred = mode != "own"
     plan = E.StepPlan(store, 4, 128, lr=1e-2)
+    plan.shadows_on_tail = mode == "tail"
     plan.load_batch(batch["x"], batch["seq_lens"], batch["classes"], batch["labels"], eps)
     gs = []
     for _ in range(2):
