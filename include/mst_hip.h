@@ -439,6 +439,29 @@ int mst_latent_fwd_proj(int dtype, int64_t B, int64_t De, int64_t Z, int64_t Dd,
                         void* dec_in, int64_t dec_sample_stride,
                         const void* Wq, int64_t ld_wq, const float* bq, void* qkv0, int64_t qkv_sample_stride, int64_t nq,
                         mst_stream_t stream);
+/* Decoder row 0 from a latent RECIPE — generation from the latent space (prior draws, posterior draws, interpolation between two
+ * melodies, a blend of two class embeddings). For every output row n < N, fp32 math, one rounding to the act dtype at the store:
+ *   base  = interp(zsrc[a[n]], zsrc[b[n]], w[n])                a[n] < 0 (or M = 0): base = 0, scale = 1 — a draw from the prior
+ *   scale = ssrc ? (1 - w[n]) * ssrc[a[n]] + w[n] * ssrc[b[n]] : 1
+ *   z     = base + tau * eps(seed, site, (row0 + n) * Z + k) * scale            (tau = 0: no random number is made)
+ *   dec_in[n * dec_stride + :] = alpha_d * (z . Wh^T + bh + (1 - cw[n]) * cls_d[ca[n]] + cw[n] * cls_d[cb[n]]) + pos_d[0 .. Dd)
+ *   z_out[n, :] = z
+ * zsrc / ssrc: fp32 [M, Z] (the mu / sigma of an encode, or any vectors); a, b, ca, cb: int32 [N]; w, cw: fp32 [N]; z_out fp32 [N, Z].
+ * mode 0: interp is linear, (1 - w) * za + w * zb. mode 1: spherical, sin((1 - w) om) / sin(om) * za + sin(w om) / sin(om) * zb with
+ * om the angle between the two; w <= 0 and w >= 1 return za / zb themselves, and where either vector is zero or |cos om| >= 1 - 2^-16
+ * the linear form is used (never a NaN from a vanishing sine).
+ * eps: the Gaussian of mst_randn / mst_step_begin (Box-Muller over the counter hash; element g is the cosine (g even) or sine (g odd)
+ * branch of pair g >> 1) at the GLOBAL element index (row0 + n) * Z + k, effective seed = seed ^ (seed_ptr ? *seed_ptr : 0): N rows in
+ * one call, or in chunks that pass their first row number as row0, are the same vectors.
+ * The identity recipe (a = b = n, w = cw = tau = 0 on an encode's mu, ca = the batch's classes) is mst_latent_fwd's row 0.
+ * Indices are clamped into their tables (source rows to M - 1, classes to n_classes - 1): validate a recipe where it is built. */
+int mst_latent_rows(int dtype, int64_t N, int64_t M, int64_t Z, int64_t Dd,
+                    const float* zsrc, const float* ssrc, const int32_t* a, const int32_t* b, const float* w, int mode,
+                    float tau, uint64_t seed, const uint64_t* seed_ptr, uint32_t site, int64_t row0,
+                    const float* Wh, const float* bh,
+                    const int32_t* ca, const int32_t* cb, const float* cw, const float* cls_d, int64_t ld_cls, int64_t n_classes,
+                    const float* pos_d, float alpha_d,
+                    float* z_out, void* dec_in, int64_t dec_stride, mst_stream_t stream);
 
 /* The latent block's backward pass: the per-sample vectors, then the decoder class table's gradient (dcls_d[classes[b], :] += t[b, :]).
  * gscale is the encoder-side loss scale, enc_scale = gscale / the decoder-side loss scale. Leaves t = alpha_d * d(dec_in[b, 0, :]) at
@@ -583,6 +606,17 @@ int mst_beam_gather_cols(const void* in, void* out, const int32_t* src, int64_t 
  * host constants (seed, i) only. */
 int mst_sample_step(int64_t N, int64_t V, int64_t i, int64_t L, const float* probs, int64_t ldp, int32_t* seqs, float* scores,
                     int32_t* word, int32_t* active, uint64_t seed, int32_t eos, int32_t pad, mst_stream_t stream);
+/* The same for the piano-roll ends: position i's frame of every sequence n of N from the position's LOGITS (act dtype, [N, ldl >= P]),
+ * with x = logit / tau and p = sigmoid(x) in fp32.
+ *   mode 0 (draw)     : frame[n, j] = u < p, u = (counter hash of (*seed_ptr, i, n * P + j) >> 8) * 2^-24 in [0, 1)
+ *   mode 1 (threshold): frame[n, j] = x > log(thr / (1 - thr)), thr in (0, 1) — no random number; thr = 0.5 is logit > 0
+ * frame -> frames[n, :P] (uint8 rows of ldf: the next position's input; columns >= P are not touched) and roll[n, i - 1, :P] (uint8
+ * [N, L, ldr]: the piece stays on the device); scores[n] += -sum_j log max(frame ? p : 1 - p, 1e-30); probs_out (optional, fp32
+ * [N, L, P]) gets p at [n, i - 1, :]. 1 <= i < L. The seed is read through a device pointer (one 8-byte word the host rewrites
+ * between runs), so a graph captured with this launch replays unchanged for every seed; tau, mode and thr are launch constants. */
+int mst_frame_step(int dtype, int64_t N, int64_t P, int64_t i, int64_t L, const void* logits, int64_t ldl, float tau, int mode, float thr,
+                   const uint64_t* seed_ptr, uint8_t* frames, int64_t ldf, uint8_t* roll, int64_t ldr, float* scores, float* probs_out,
+                   mst_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * K12/K13: softmax over V + SoftmaxCrossEntropy (model.py:256; loss.py:15-23).

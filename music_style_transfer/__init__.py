@@ -18,11 +18,13 @@ class _AliasFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):
             return None
         real = _IMPL + fullname[len(__name__):]
         try:
-            if importlib.util.find_spec(real) is None:
+            real_spec = importlib.util.find_spec(real)
+            if real_spec is None:
                 return None
         except ModuleNotFoundError:
             return None
-        return importlib.util.spec_from_loader(fullname, self, is_package=True)
+        # a package only where the real module is one: `python -m music_style_transfer.VarAutoEncoder.main` must find a module to run
+        return importlib.util.spec_from_loader(fullname, self, origin=real_spec.origin, is_package=real_spec.submodule_search_locations is not None)
 
     def create_module(self, spec):
         real = _IMPL + spec.name[len(__name__):]
@@ -30,6 +32,11 @@ class _AliasFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):
 
     def exec_module(self, module):
         pass
+
+    def get_code(self, fullname):
+        """for `python -m`: the code of the real module (runpy executes it as __main__ under the aliased package)"""
+        real = _IMPL + fullname[len(__name__):]
+        return importlib.util.find_spec(real).loader.get_code(real)
 
 
 if not any(isinstance(f, _AliasFinder) for f in sys.meta_path):

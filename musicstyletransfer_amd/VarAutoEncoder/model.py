@@ -243,6 +243,22 @@ class Model:
         self._beam_plans[key] = bs
         return bs
 
+    def frame_sampling_plan(self, N, L, attention=None, keep_probs=False):
+        """decode.FrameSampling of this shape (piano-roll ends: caches, the roll, one captured graph per position), kept across batches"""
+        from .. import decode
+        attention = resolve_attention(self.engine_config, attention)
+        if not hasattr(self, "_frame_plans") or getattr(self, "_frame_store", None) is not self.store:
+            self._frame_plans, self._frame_store = OrderedDict(), self.store
+        key = (N, L, attention, bool(keep_probs))
+        fs = self._frame_plans.pop(key, None)
+        if fs is None:
+            fs = decode.FrameSampling(self.store, N, L, attention=attention, keep_probs=keep_probs)
+            while len(self._frame_plans) >= self.DECODE_PLAN_MAX:
+                torch.cuda.synchronize(self.store.device)
+                self._frame_plans.popitem(last=False)
+        self._frame_plans[key] = fs
+        return fs
+
     def on_plan_evicted(self, callback):
         """callback(plan) when the cache drops a plan (holders of per-plan state — graphs, input rings — forget it)"""
         self._evict_hooks.append(callback)
@@ -265,6 +281,20 @@ class Model:
         V = cfg.out_dim
         probs = plan.probs[:, :V].float().view(B, T, V)
         return probs, plan.mu, plan.sigma
+
+    def encode(self, tokens, seq_lens, classes):
+        """the encoder and the latent launch only, in inference mode: (mu, sigma) as device fp32 [B, Z] — bit for bit what
+        __call__ returns for the batch, with no decoder-layer, output-layer or loss launch and the training RNG stream left alone"""
+        if self.store is None:
+            raise RuntimeError("call initialize(ctx) first")
+        x = np.asarray(tokens.cpu() if torch.is_tensor(tokens) else tokens)
+        B, T = x.shape[0], x.shape[1]
+        plan = self.plan(B, T, want_probs=False, internal_eps=False)
+        cfg = self.engine_config
+        dummy = np.zeros((B, T), np.int64) if cfg.kind == "token" else np.zeros((B, T, cfg.out_dim), np.uint8)
+        plan.load_batch(x, seq_lens, classes, dummy, np.zeros((B, cfg.latent_dim), np.float32))
+        plan.forward(inference=True, upto="latent")
+        return plan.mu.clone(), plan.sigma.clone()
 
     # -- checkpoints (utils.save_model / load_model_parameters)
     def save_parameters(self, fname):

@@ -80,6 +80,12 @@ class Sampling(SamplerBase):
     """ancestral sampling (sampler.py:155-190): draw the next token from the decoder's distribution until every sequence
     has ended or twice the input length is reached. Piano-roll ends: every pitch of the next frame is a Bernoulli draw."""
 
+    def __init__(self, *args, frames_on_device=False, **kw):
+        """frames_on_device: the piano-roll ends' draw as a device kernel inside every position's captured graph
+        (decode.FrameSampling) instead of the host loop below and its numpy random stream (the default, unchanged)"""
+        super().__init__(*args, **kw)
+        self.frames_on_device = bool(frames_on_device)
+
     def sample(self, batch):
         tokens, seq_lens, classes = batch.data
         tokens = np.asarray(tokens)
@@ -97,6 +103,11 @@ class Sampling(SamplerBase):
             seqs, scores = self._dev.run(dec.initial_rows(tokens, seq_lens, classes))
             self.scores = scores.astype(np.float64)
             return seqs.astype(np.int64)
+        if kind != "token" and self.frames_on_device:
+            fs = self.model.frame_sampling_plan(B, i_max, self.attention)
+            roll, scores = fs.run(dec.initial_rows(tokens, seq_lens, classes), seed=int(self.rng.integers(1 << 62)))
+            self.scores = scores.astype(np.float64)
+            return roll
         state = dec.get_initial_state(tokens, seq_lens, classes, t_max=i_max + 1, attention=self.attention)
         if kind == "token":
             done = np.zeros(B, bool)
@@ -215,6 +226,64 @@ class ReconstructionSampler(SamplerBase):
         return files
 
 
+class _GeneratorSampler(SamplerBase):
+    """samplers over generate.LatentGenerator: one encode of the batch, every requested row decoded together"""
+
+    def __init__(self, *args, decoder="sampling", beam_size=4, temperature=1.0, steps=8, **kw):
+        super().__init__(*args, **kw)
+        self.decoder, self.beam_size, self.temperature, self.steps = decoder, beam_size, temperature, steps
+        self._gen = None
+
+    @property
+    def generator(self):
+        from ..generate import LatentGenerator
+        if self._gen is None or self._gen.model is not self.model:
+            self._gen = LatentGenerator(self.model, attention=self._attention, seed=int(self.rng.integers(1 << 62)),
+                                        temperature=self.temperature, decoder=self.decoder, beam_size=self.beam_size)
+        return self._gen
+
+
+class TransferSampler(_GeneratorSampler):
+    """what Sampling.process_batch writes — the originals, then every melody in every class — from ONE encoder pass"""
+
+    def process_batch(self, batch, output_suffix, num_classes):
+        os.makedirs(output_suffix, exist_ok=True)
+        files = []
+        if self.model.engine_config.kind == "token":
+            for i, seq in enumerate(np.asarray(batch.data[0])):
+                files.append(os.path.join(output_suffix, "out-{}.original.mid".format(i)))
+                self.writer.write_to_file(files[-1], self._melody(seq))
+        out = self.generator.transfer(batch, np.arange(num_classes))
+        self.scores = out.scores
+        order = sorted(range(len(out)), key=lambda r: (out.rows[r]["cls"], out.rows[r]["melody"]))  # class by class, as Sampling writes
+        melodies = out.melodies()
+        for r in order:
+            files.append(os.path.join(output_suffix, "out-{}.class-{}.mid".format(out.rows[r]["melody"], out.rows[r]["cls"])))
+            self.writer.write_to_file(files[-1], melodies[r])
+        return files
+
+
+class PriorSampler(_GeneratorSampler):
+    """one draw from the prior per sample of the batch and class (the batch only sets how many and how long)"""
+
+    def process_batch(self, batch, output_suffix, num_classes):
+        B, T = np.asarray(batch.data[0]).shape[:2]
+        out = self.generator.prior(B * num_classes, np.tile(np.arange(num_classes), B), 2 * T)
+        self.scores = out.scores
+        return out.write(output_suffix)
+
+
+class InterpolationSampler(_GeneratorSampler):
+    """`steps` points between every melody of the batch and the next one"""
+
+    def process_batch(self, batch, output_suffix, num_classes):
+        B = np.asarray(batch.data[0]).shape[0]
+        files = []
+        for i in range(B - 1):
+            files += self.generator.interpolate(batch, i, i + 1, self.steps).write(output_suffix)
+        return files
+
+
 def load_inference_model(model_folder, context, checkpoint):
     """sampler.py:17-38: the saved YAML configuration, a Model built from it, the checkpoint's parameters (-1: latest)"""
     from . import model, utils
@@ -230,7 +299,8 @@ def load_inference_model(model_folder, context, checkpoint):
 
 
 def get_sampler(type, model_folder, context, checkpoint, args):
-    """sampler.py:41-53, plus 'reconstruction' (what the trainer's periodic hook uses by default here)"""
+    """sampler.py:41-53, plus 'reconstruction' (what the trainer's periodic hook uses by default here) and the latent-space
+    generators 'prior', 'interpolation', 'transfer' (generate.LatentGenerator)"""
     verbose = bool(getattr(args, "verbose", False))
     if type == "sampling":
         return Sampling(model_folder, context, checkpoint, verbose=verbose)
@@ -238,4 +308,8 @@ def get_sampler(type, model_folder, context, checkpoint, args):
         return BeamSearchSampler(model_folder, context, checkpoint, beam_size=int(getattr(args, "beam_size", 4) or 4), verbose=verbose)
     if type == "reconstruction":
         return ReconstructionSampler()
+    generators = {"prior": PriorSampler, "interpolation": InterpolationSampler, "transfer": TransferSampler}
+    if type in generators:
+        return generators[type](model_folder, context, checkpoint, verbose=verbose, decoder=getattr(args, "decoder", "sampling") or "sampling",
+                                beam_size=int(getattr(args, "beam_size", 4) or 4))
     raise ValueError("Sampler {} is not implemented".format(type))

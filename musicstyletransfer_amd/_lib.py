@@ -218,6 +218,9 @@ SIGNATURES = {
                                  vp, c_f32, vp, vp, vp, vp, vp, c_i64, vp]),
     "mst_latent_fwd_proj": (C.c_int, [C.c_int, c_i64, c_i64, c_i64, c_i64, vp, c_i64, vp, vp, vp, vp, vp, vp, vp, c_i64,
                                       vp, c_f32, vp, vp, vp, vp, vp, c_i64, vp, c_i64, vp, vp, c_i64, c_i64, vp]),
+    "mst_latent_rows": (C.c_int, [C.c_int, c_i64, c_i64, c_i64, c_i64, vp, vp, vp, vp, vp, C.c_int, c_f32, c_u64, vp, c_u32, c_i64, vp, vp,
+                                  vp, vp, vp, vp, c_i64, c_i64, vp, c_f32, vp, vp, c_i64, vp]),
+    "mst_frame_step": (C.c_int, [C.c_int, c_i64, c_i64, c_i64, c_i64, vp, c_i64, c_f32, C.c_int, c_f32, vp, vp, c_i64, vp, c_i64, vp, vp, vp]),
     "mst_reparam_kl_fwd": (C.c_int, [c_i64, c_i64, vp, vp, vp, vp, vp, vp]),
     "mst_reparam_kl_bwd": (C.c_int, [c_i64, c_i64, vp, vp, vp, vp, c_f32, vp, vp, vp]),
     "mst_softmax_ce": (C.c_int, [C.c_int, c_i64, c_i64, c_i64, vp, c_i64, vp, vp, vp, c_i64, vp, c_i64, c_f32, C.c_int, vp,

@@ -2,6 +2,8 @@
 //   mst_beam_step   : per sample, the K best of its K x V continuations (score = summed -log p; a finished hypothesis continues
 //                     with PAD only, at no cost: sampler.py:218-221), the re-ranked token rows, the words fed to the next position
 //   mst_beam_gather : the decoder layers' K | Q | V cache rows of the re-ranked hypotheses (sampler.py:236-238)
+//   mst_sample_step / mst_frame_step : ancestral sampling's draw of a position — a token by inverse CDF, a piano-roll frame by a
+//                     Bernoulli draw (or a threshold) per pitch from the position's logits
 // With these two the whole position — decoder step, ranking, cache reorder — is device work inside ONE captured graph; the host
 // version spent 98 % of a position in its own top-k over beam x V and the copies around it (2.6 ms against 55 us of device time).
 // Ranking is deterministic: candidates are ordered by (score, hypothesis * V + word), i.e. the stable argsort of the host form.
@@ -187,9 +189,68 @@ __global__ __launch_bounds__(256) void sample_step_kernel(int64_t N, int64_t V, 
   }
 }
 
+// The piano-roll ends' draw (sampler.py:155-190 with a Bernoulli per pitch): one wave per sequence walks the P logits of the position.
+// x = logit / tau; p = sigmoid(x) and 1 - p = sigmoid(-x) are each formed from their own exponential, so the score of an unlikely
+// frame does not lose its digits in 1 - p. mode 0 draws frame = u < p with u = (dropout_hash(seed, i, n * P + j) >> 8) * 2^-24 in
+// [0, 1); mode 1 thresholds x > thr_logit (no random number). The frame goes to frames[n, :P] (the next position's input) and to
+// roll[n, i - 1, :P]; scores[n] += -sum_j log max(frame ? p : 1 - p, 1e-30) (one wave owns a sequence: no atomics, a fixed order).
+template <typename T>
+__global__ __launch_bounds__(256) void frame_step_kernel(int64_t N, int64_t P, int64_t i, int64_t L, const T* __restrict__ logits, int64_t ldl,
+                                                         float tau, int mode, float thr_logit, const uint64_t* __restrict__ seed_ptr,
+                                                         uint8_t* __restrict__ frames, int64_t ldf, uint8_t* __restrict__ roll, int64_t ldr,
+                                                         float* __restrict__ scores, float* __restrict__ probs_out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t n = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (n >= N) return;
+  const uint64_t seed = mode == 0 ? seed_ptr[0] : 0ull;
+  const T* __restrict__ row = logits + n * ldl;
+  uint8_t* __restrict__ fr = frames + n * ldf;
+  uint8_t* __restrict__ rl = roll + (n * L + (i - 1)) * ldr;
+  float* __restrict__ po = probs_out ? probs_out + (n * L + (i - 1)) * P : nullptr;
+  float nll = 0.f;
+  for (int64_t j = lane; j < P; j += 64) {
+    const float x = to_f32(row[j]) / tau;
+    const float p = 1.f / (1.f + expf(-x)), q = 1.f / (1.f + expf(x));
+    bool on;
+    if (mode == 0) {
+      const float u = (float)(dropout_hash(seed, (uint32_t)i, (uint64_t)(n * P + j)) >> 8) * (1.0f / 16777216.0f);
+      on = u < p;
+    } else {
+      on = x > thr_logit;
+    }
+    const uint8_t f = on ? 1 : 0;
+    fr[j] = f;
+    rl[j] = f;
+    if (po) po[j] = p;
+    nll -= logf(fmaxf(on ? p : q, 1e-30f));
+  }
+  nll = wave_sum(nll);
+  if (lane == 0) scores[n] += nll;
+}
+
 }  // namespace mst
 
 using namespace mst;
+
+extern "C" int mst_frame_step(int dtype, int64_t N, int64_t P, int64_t i, int64_t L, const void* logits, int64_t ldl, float tau, int mode,
+                              float thr, const uint64_t* seed_ptr, uint8_t* frames, int64_t ldf, uint8_t* roll, int64_t ldr, float* scores,
+                              float* probs_out, mst_stream_t stream) {
+  MST_CHECK_ARG(N > 0 && P > 0 && L > 1, "mst_frame_step: sizes must be positive (L >= 2)");
+  MST_CHECK_ARG(i >= 1 && i < L, "mst_frame_step: position i outside [1, L)");
+  MST_CHECK_ARG(tau > 0.f && tau <= 3.0e38f, "mst_frame_step: tau must be positive and finite");
+  MST_CHECK_ARG(mode == 0 || mode == 1, "mst_frame_step: mode must be 0 (draw) or 1 (threshold)");
+  MST_CHECK_ARG(mode == 0 || (thr > 0.f && thr < 1.f), "mst_frame_step: thr outside (0, 1)");
+  MST_CHECK_ARG(logits && frames && roll && scores && (mode == 1 || seed_ptr), "mst_frame_step: null pointer (draw mode needs the seed word)");
+  MST_CHECK_ARG(ldl >= P && ldf >= P && ldr >= P, "mst_frame_step: a row stride below P");
+  const float thr_logit = mode == 1 ? (float)log((double)thr / (1.0 - (double)thr)) : 0.f;
+  return dispatch_act(dtype, [&](auto tag) -> int {
+    typedef decltype(tag) T;
+    hipLaunchKernelGGL((frame_step_kernel<T>), dim3((unsigned)cdiv(N, 4)), dim3(256), 0, (hipStream_t)stream, N, P, i, L, (const T*)logits, ldl,
+                       tau, mode, thr_logit, seed_ptr, frames, ldf, roll, ldr, scores, probs_out);
+    MST_CHECK_LAUNCH("frame_step_kernel");
+    return MST_OK;
+  });
+}
 
 extern "C" int mst_sample_step(int64_t N, int64_t V, int64_t i, int64_t L, const float* probs, int64_t ldp, int32_t* seqs, float* scores,
                                int32_t* word, int32_t* active, uint64_t seed, int32_t eos, int32_t pad, mst_stream_t stream) {

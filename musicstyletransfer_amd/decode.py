@@ -131,8 +131,9 @@ class DecodePlan:
         self._leave()
         self.t = 0
 
-    def _position(self, t):
-        """the kernel sequence of position t >= 0 on inputs already in self.x (t = 0) / self.tokens / self.frames"""
+    def _position(self, t, probs=True):
+        """the kernel sequence of position t >= 0 on inputs already in self.x (t = 0) / self.tokens / self.frames
+        (probs=False: stop at the logits — FrameSampling's draw reads those)"""
         cfg, st, B = self.cfg, self.store, self.B
         D = cfg.d_model
         if t == 0:
@@ -145,6 +146,8 @@ class DecodePlan:
             o.gemm_nt(self.frames, st.t("decoder.embedding.weight"), self.x, N=D, alpha=sq, rowadd=self.pos[t:], rowadd_period=1)
         x = self._layers(self.x, t)
         o.gemm_nt(x, st.h("decoder.output_layer.weight"), self.logits, K=D, bias=st.p("decoder.output_layer.bias"))
+        if not probs:
+            return
         if cfg.kind == "token":
             # (pre_zeroed: only the probabilities are used here — no 4.7 us memset of a loss nobody reads in every position)
             o.softmax_ce(self.logits, self.zero_labels, self.loss, B, 1, cfg.out_dim, probs=self.probs, pre_zeroed=True)
@@ -316,3 +319,74 @@ class AncestralSampling:
         p._leave()
         self.positions = last
         return seqs, scores
+
+
+class FrameSampling:
+    """Sampling for the piano-roll ends with the whole position on the device (sampler.py:155-190 with a Bernoulli draw per pitch):
+    the decode step of position i and mst_frame_step — which reads the position's logits, writes the frame where the next position's
+    embedding GEMM reads it and into the roll, and adds the frame's -log p to the scores — are ONE captured graph per position. The
+    draw's seed is a device word the host rewrites before a run, so the graphs captured by one run replay for every later one; the
+    host sees nothing until the roll is copied back at the end. (The draw forms sigmoid(logit / tau) itself: these graphs have no
+    sigmoid_bce launch.) tau, mode and thr are launch constants of mst_frame_step: a graph is kept per (position, tau, mode, thr)."""
+
+    def __init__(self, store, N, L, attention="query", keep_probs=False):
+        """L positions: the start row + up to L - 1 frames. keep_probs: the per-position probabilities stay in self.probs
+        (fp32 [N, L, P]; tests and diagnostics)"""
+        cfg = store.cfg
+        if cfg.kind == "token":
+            raise ValueError("FrameSampling draws piano-roll frames; the token ends have AncestralSampling")
+        if L < 2:
+            raise ValueError("FrameSampling needs at least two positions")
+        self.N, self.L, self.P = N, L, cfg.out_dim
+        assert cfg.in_dim == cfg.out_dim, "a drawn frame is the next position's input"
+        self.plan = DecodePlan(store, N, L, attention=attention)
+        dev = store.device
+        self.roll = torch.zeros(N, L, roundup(self.P, 8), dtype=torch.uint8, device=dev)
+        self.scores = torch.zeros(N, dtype=torch.float32, device=dev)
+        self.probs = torch.zeros(N, L, self.P, dtype=torch.float32, device=dev) if keep_probs else None
+        self.seed_word = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._seed_host = torch.zeros(1, dtype=torch.int64).pin_memory()
+        self._graphs, self._warm = {}, False
+
+    def _position(self, i, tau, mode, thr):
+        p = self.plan
+        p._position(i, probs=False)
+        o.frame_step(p.logits, self.P, i, self.seed_word, p.frames, self.roll, self.scores, tau=tau, mode=mode, thr=thr, probs_out=self.probs)
+
+    def run(self, row0, length=None, tau=1.0, mode="draw", thr=0.5, seed=0):
+        """row0: [N, >= D] initial decoder rows. Decodes positions 1 .. length - 1 (default: all L - 1) and returns
+        (roll uint8 [N, length - 1, P], scores [N]) as host arrays: frame i - 1 is the draw of position i."""
+        p = self.plan
+        length = self.L if length is None else int(length)
+        if not 2 <= length <= self.L:
+            raise ValueError(f"length {length} outside [2, {self.L}]")
+        tau, thr = float(tau), float(thr)
+        p.reset()
+        seed &= 0xFFFFFFFFFFFFFFFF
+        self._seed_host[0] = seed - (1 << 64) if seed >= (1 << 63) else seed
+        with p._enter():
+            self.seed_word.copy_(self._seed_host, non_blocking=True)
+            p.x.copy_(row0[:, : p.x.shape[1]])
+            p._run_position(0)
+            p.t = 0
+            o.zero(self.scores)
+            o.zero(p.frames)
+            p.frames[:, 0] = 1  # the start row (pianoroll.pianoroll_arrays)
+            for i in range(1, length):
+                key = (i, tau, mode, thr)
+                g = self._graphs.get(key) if p.use_graphs else None
+                if g is None and p.use_graphs and self._warm:
+                    g = self._graphs[key] = o.Graph().capture(lambda: self._position(i, tau, mode, thr))
+                if g is not None:
+                    g.launch()
+                else:
+                    self._position(i, tau, mode, thr)  # (the first position ever runs eagerly: lazy HIP module loads ...
+                    self._warm = True
+                    if p.use_graphs:                   # ... and is captured behind that, so the next run replays it too)
+                        self._graphs[key] = o.Graph().capture(lambda: self._position(i, tau, mode, thr))
+                p.t = i
+            roll = self.roll[:, : length - 1, : self.P].cpu().numpy()
+            scores = self.scores.cpu().numpy()
+        p._leave()
+        self.positions = length - 1
+        return roll, scores

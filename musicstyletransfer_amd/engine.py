@@ -905,10 +905,14 @@ class StepPlan:
             return (self.T, self.T + 1, 1)
         return None
 
-    def forward(self, inference=False):
+    def forward(self, inference=False, upto=None):
         """inference=True: the forward pass as the reference runs it OUTSIDE autograd.record() (Model(...) called directly, the
         samplers: sampler.py:146-148) — every Dropout is the identity and the training RNG stream is left alone (an eps the
-        caller did not supply is drawn from the store's inference stream)."""
+        caller did not supply is drawn from the store's inference stream).
+        upto="latent" (inference only): stop behind the latent launch — mu, sigma, z and decoder row 0 are there, no decoder layer,
+        output layer or loss launch is issued (Model.encode)."""
+        if upto not in (None, "latent") or (upto and not inference):
+            raise ValueError("forward(upto=...) takes 'latent', in inference mode only")
         cfg, st, B, T = self.cfg, self.store, self.B, self.T
         self._infer = bool(inference)
         self._tail_used = dict(fwd=False, bwd=False)
@@ -965,6 +969,8 @@ class StepPlan:
         if self._ride_fwd:  # ... and position 0 of that projection, on the launch that produces the row
             proj0 = (st.fused(st.w16, "decoder.layer0", "weight"), st.fused(st.w, "decoder.layer0", "bias"), self.dec[0].qkv.view(B, Sd, -1))
         o.latent_fwd(*lat, proj=proj0)
+        if upto == "latent":
+            return
         # ---- decoder positions 1..T (model.py:241-245, transformer.py:237)
         if cfg.kind == "token":
             o.embed_fwd(self.tokens, st.p("decoder.embedding.weight"), self.pos_d, self.x0_d.view(B, Sd, -1), 1, sq_d)

@@ -1,0 +1,372 @@
+"""Generation from the latent space: draws from the prior, posterior draws at a temperature, interpolation between two melodies,
+style transfer from ONE encode, and blends of two class embeddings.
+
+A request is a RECIPE — per output row which source vectors to mix (a, b, w), how much noise to add (tau, optionally scaled by the
+encoder's sigma) and which class embeddings to mix (ca, cb, cw) — built on the host by the functions below (pure numpy: they are what
+the CPU tests check), turned into latent vectors and decoder start rows by ONE launch per chunk (ops.latent_rows: mst_latent_rows),
+and decoded by what the samplers use: decode.AncestralSampling / decode.BeamSearch for the token ends, decode.FrameSampling for the
+piano-roll ends. The reference stops at `latent_vector = means` (sampler.py:146-148); nothing here has a counterpart there.
+
+    python -m music_style_transfer.VarAutoEncoder.generate --model-output DIR --mode transfer --data MIDI_DIR --out OUT_DIR
+"""
+import argparse
+import math
+import os
+
+import numpy as np
+
+MODES = ("prior", "posterior", "interpolate", "transfer", "blend")
+DECODERS = ("sampling", "greedy", "beam")
+
+
+class Recipe:
+    """N rows of mst_latent_rows' inputs, what each row is (`rows`: one dict per row) and the name of the file it is written to"""
+
+    def __init__(self, name, a, b, w, ca, cb, cw, rows, files, tau=0.0, use_sigma=False, mode="lerp"):
+        self.name = name
+        self.a, self.b = np.asarray(a, np.int32).reshape(-1), np.asarray(b, np.int32).reshape(-1)
+        self.ca, self.cb = np.asarray(ca, np.int32).reshape(-1), np.asarray(cb, np.int32).reshape(-1)
+        self.w, self.cw = np.asarray(w, np.float32).reshape(-1), np.asarray(cw, np.float32).reshape(-1)
+        self.rows, self.files = list(rows), list(files)
+        self.tau, self.use_sigma, self.mode = float(tau), bool(use_sigma), mode
+        n = len(self.a)
+        if not all(len(x) == n for x in (self.b, self.w, self.ca, self.cb, self.cw, self.rows, self.files)):
+            raise ValueError("recipe arrays differ in length")
+        if mode not in ("lerp", "slerp"):
+            raise ValueError("interpolation mode must be 'lerp' or 'slerp', got {!r}".format(mode))
+        if self.tau < 0:
+            raise ValueError("temperature must not be negative")
+
+    def __len__(self):
+        return len(self.a)
+
+    def validate(self, n_sources, n_classes):
+        """the kernel clamps indices into its tables; a recipe that would need the clamp is refused here"""
+        src = np.concatenate([self.a, self.b])
+        if (src >= n_sources).any() or (self.b[self.a >= 0] < 0).any():
+            raise ValueError("recipe {!r} names a source row outside [0, {})".format(self.name, n_sources))
+        cls = np.concatenate([self.ca, self.cb])
+        if (cls < 0).any() or (cls >= n_classes).any():
+            raise ValueError("recipe {!r} names a class outside [0, {})".format(self.name, n_classes))
+        if not (np.isfinite(self.w).all() and np.isfinite(self.cw).all()):
+            raise ValueError("recipe {!r} has a weight that is not finite".format(self.name))
+
+
+def _classes(classes, n, what):
+    c = np.asarray(classes, np.int64).reshape(-1)
+    if c.size == 1:
+        c = np.full(n, int(c[0]), np.int64)
+    if c.size != n:
+        raise ValueError("{}: {} classes for {} rows".format(what, c.size, n))
+    return c
+
+
+def recipe_prior(n, classes, temperature=1.0):
+    """z ~ N(0, temperature^2 I), one class per row (one class for all rows if a single one is given)"""
+    if n <= 0:
+        raise ValueError("prior: n must be positive")
+    c = _classes(classes, n, "prior")
+    rows = [dict(n=k, cls=int(c[k])) for k in range(n)]
+    files = ["prior-{}.class-{}.mid".format(k, int(c[k])) for k in range(n)]
+    z = np.zeros(n)
+    return Recipe("prior", z - 1, z - 1, z, c, c, z, rows, files, tau=temperature)
+
+
+def recipe_posterior(batch_classes, n_per_sample, temperature=1.0):
+    """z = mu + temperature * eps * sigma, n_per_sample draws of every melody (melody-major), the melody's own class"""
+    c = np.asarray(batch_classes, np.int64).reshape(-1)
+    if n_per_sample <= 0:
+        raise ValueError("posterior: n_per_sample must be positive")
+    a = np.repeat(np.arange(len(c)), n_per_sample)
+    d = np.tile(np.arange(n_per_sample), len(c))
+    rows = [dict(melody=int(i), draw=int(k), cls=int(c[i])) for i, k in zip(a, d)]
+    files = ["posterior-{}.draw-{}.mid".format(int(i), int(k)) for i, k in zip(a, d)]
+    z = np.zeros(len(a))
+    return Recipe("posterior", a, a, z, c[a], c[a], z, rows, files, tau=temperature, use_sigma=True)
+
+
+def recipe_interpolate(i, j, steps, class_i, class_j, classes=None, mode="slerp"):
+    """`steps` points from melody i (weight 0) to melody j (weight 1), both included; the class is i's up to and including the
+    middle step and j's behind it, or `classes` (one per step)"""
+    if steps < 2:
+        raise ValueError("interpolate: at least the two end points (steps >= 2)")
+    w = np.linspace(0.0, 1.0, steps).astype(np.float32)
+    if classes is None:
+        c = np.where(2 * np.arange(steps) <= steps - 1, int(class_i), int(class_j))
+    else:
+        c = _classes(classes, steps, "interpolate")
+    rows = [dict(melody_a=int(i), melody_b=int(j), step=s, weight=float(w[s]), cls=int(c[s])) for s in range(steps)]
+    files = ["interp-{}-{}.{:02d}.mid".format(int(i), int(j), s) for s in range(steps)]
+    z = np.zeros(steps)
+    return Recipe("interpolate", z + i, z + j, w, c, c, z, rows, files, mode=mode)
+
+
+def recipe_transfer(n_melodies, target_classes):
+    """every melody x every target class (melody-major): z = mu of the melody, the class embedding of the target"""
+    t = np.asarray(target_classes, np.int64).reshape(-1)
+    if n_melodies <= 0 or t.size == 0:
+        raise ValueError("transfer: no melody or no target class")
+    a = np.repeat(np.arange(n_melodies), t.size)
+    c = np.tile(t, n_melodies)
+    rows = [dict(melody=int(i), cls=int(k)) for i, k in zip(a, c)]
+    files = ["transfer-{}.class-{}.mid".format(int(i), int(k)) for i, k in zip(a, c)]
+    z = np.zeros(len(a))
+    return Recipe("transfer", a, a, z, c, c, z, rows, files)
+
+
+def recipe_class_blend(n_melodies, class_a, class_b, weights):
+    """z = mu of the melody, class embedding (1 - weight) * class_a + weight * class_b, for every melody x weight (melody-major)"""
+    wts = np.asarray(weights, np.float32).reshape(-1)
+    if n_melodies <= 0 or wts.size == 0:
+        raise ValueError("class_blend: no melody or no weight")
+    a = np.repeat(np.arange(n_melodies), wts.size)
+    k = np.tile(np.arange(wts.size), n_melodies)
+    rows = [dict(melody=int(i), cls_a=int(class_a), cls_b=int(class_b), step=int(s), weight=float(wts[s])) for i, s in zip(a, k)]
+    files = ["blend-{}.class-{}-{}.{:02d}.mid".format(int(i), int(class_a), int(class_b), int(s)) for i, s in zip(a, k)]
+    z = np.zeros(len(a))
+    return Recipe("blend", a, a, z, z + class_a, z + class_b, wts[k], rows, files)
+
+
+def chunks(n_rows, max_rows):
+    """[lo, hi) ranges of at most max_rows rows; the noise of row r is a function of r, so the chunking does not change it"""
+    if max_rows <= 0:
+        raise ValueError("max_rows must be positive")
+    return [(lo, min(lo + max_rows, n_rows)) for lo in range(0, n_rows, max_rows)]
+
+
+def ids_to_melody(ids):
+    """token row -> Melody: PAD / SOS dropped, cut at the first EOS (what the samplers write)"""
+    from .MIDIUtil.defaults import EOS_ID, PAD_ID, SOS_ID
+    from .MIDIUtil.Melody import get_melody_from_ids
+    ids = [int(i) for i in np.asarray(ids).reshape(-1) if int(i) not in (PAD_ID, SOS_ID)]
+    if EOS_ID in ids:
+        ids = ids[: ids.index(EOS_ID)]
+    return get_melody_from_ids(np.asarray(ids, np.int64))
+
+
+class Generated:
+    """what a LatentGenerator call returns: `z` (host fp32 [N, Z]), `rows` (what every row is), `sequences` (token ids [N, L], token
+    ends) or `rolls` (uint8 [N, frames, P], piano-roll ends), `scores` (summed -log p of what was decoded), `start_rows` (the decoder
+    rows of position 0, host copy in the activation type), `probs` (piano-roll ends with keep_probs: fp32 [N, frames, P])"""
+
+    def __init__(self, recipe, z, start_rows, scores, sequences=None, rolls=None, probs=None, slices_per_quarter=4):
+        self.name, self.rows, self.files = recipe.name, recipe.rows, recipe.files
+        self.z, self.start_rows, self.scores = z, start_rows, scores
+        self.sequences, self.rolls, self.probs = sequences, rolls, probs
+        self.slices_per_quarter = slices_per_quarter
+
+    def __len__(self):
+        return len(self.rows)
+
+    def melodies(self):
+        if self.sequences is not None:
+            return [ids_to_melody(s) for s in self.sequences]
+        from .pianoroll import pianoroll_to_melody
+        return [pianoroll_to_melody(r, self.slices_per_quarter) for r in self.rolls]
+
+    def write(self, folder, names=None):
+        """one .mid per row into `folder` (names: the recipe's, e.g. transfer-0.class-1.mid); returns the paths"""
+        from .MIDIUtil.midi_io import MelodyWriter
+        os.makedirs(folder, exist_ok=True)
+        writer, out = MelodyWriter(), []
+        for name, melody in zip(names or self.files, self.melodies()):
+            out.append(os.path.join(folder, name))
+            writer.write_to_file(out[-1], melody)
+        return out
+
+
+class LatentGenerator:
+    """model: an initialised VarAutoEncoder.model.Model. decoder: 'sampling' (ancestral draws), 'greedy' (the most likely token /
+    every pitch above one half) or 'beam' (token ends only). temperature: the scale of the latent noise (prior and posterior draws);
+    frame_temperature: the piano-roll draw's own (logits are divided by it). More than max_rows rows are decoded in chunks."""
+
+    def __init__(self, model, attention=None, seed=0, temperature=1.0, decoder="sampling", beam_size=4, max_rows=256,
+                 frame_temperature=1.0, keep_probs=False):
+        if decoder not in DECODERS:
+            raise ValueError("decoder must be one of {}, got {!r}".format(DECODERS, decoder))
+        if max_rows <= 0:
+            raise ValueError("max_rows must be positive")
+        self.model, self._attention, self.seed = model, attention, int(seed)
+        self.temperature, self.decoder, self.beam_size, self.max_rows = float(temperature), decoder, int(beam_size), int(max_rows)
+        self.frame_temperature, self.keep_probs = float(frame_temperature), bool(keep_probs)
+        self.calls = 0
+        self._samplers, self._pos0 = {}, None
+        if model is not None and decoder == "beam" and model.engine_config.kind != "token":
+            raise ValueError("beam search ranks token sequences; the piano-roll ends decode with 'sampling' or 'greedy'")
+
+    # ------------------------------------------------------------------ the modes
+    def encode(self, batch):
+        """(mu, sigma) of a batch (device fp32 [B, Z]): the encoder and the latent launch only (Model.encode)"""
+        tokens, seq_lens, classes = batch.data[:3]
+        return self.model.encode(tokens, seq_lens, classes)
+
+    def prior(self, n, classes, length):
+        return self._run(recipe_prior(n, classes, self.temperature), None, None, length)
+
+    def posterior(self, batch, n_per_sample, length=None):
+        mu, sigma = self.encode(batch)
+        return self._run(recipe_posterior(batch.data[2], n_per_sample, self.temperature), mu, sigma, self._length(batch, length))
+
+    def interpolate(self, batch, i, j, steps, mode="slerp", classes=None, length=None):
+        cls = np.asarray(batch.data[2]).reshape(-1)
+        mu, _ = self.encode(batch)
+        return self._run(recipe_interpolate(i, j, steps, cls[i], cls[j], classes, mode), mu, None, self._length(batch, length))
+
+    def transfer(self, batch, target_classes=None, length=None):
+        """every melody of the batch in every target class (default: all of the model's) from ONE encode"""
+        if target_classes is None:
+            target_classes = np.arange(self.model.engine_config.num_classes)
+        mu, _ = self.encode(batch)
+        return self._run(recipe_transfer(len(np.asarray(batch.data[2])), target_classes), mu, None, self._length(batch, length))
+
+    def class_blend(self, batch, class_a, class_b, weights, length=None):
+        mu, _ = self.encode(batch)
+        return self._run(recipe_class_blend(len(np.asarray(batch.data[2])), class_a, class_b, weights), mu, None,
+                         self._length(batch, length))
+
+    # ------------------------------------------------------------------ recipe -> rows -> decoded pieces
+    @staticmethod
+    def _length(batch, length):
+        return int(length) if length is not None else 2 * np.asarray(batch.data[0]).shape[1]  # (sampler.py:163)
+
+    def _decode(self, row0, length, seed):
+        """-> (sequences or rolls, scores, probs) of one chunk as host arrays"""
+        from . import decode
+        from .VarAutoEncoder.model import resolve_attention
+        m, n = self.model, row0.shape[0]
+        attention = resolve_attention(m.engine_config, self._attention)
+        if m.engine_config.kind != "token":
+            fs = m.frame_sampling_plan(n, length, attention, keep_probs=self.keep_probs)
+            roll, scores = fs.run(row0, length, tau=self.frame_temperature, mode="draw" if self.decoder == "sampling" else "threshold",
+                                  thr=0.5, seed=seed)
+            return roll, scores, (fs.probs[:, : length - 1].cpu().numpy() if self.keep_probs else None)
+        from .MIDIUtil.defaults import PAD_ID
+        if self.decoder == "sampling":
+            key = (n, length, attention, id(m.store))
+            smp = self._samplers.get(key)
+            if smp is None:
+                if len(self._samplers) >= 4:
+                    self._samplers.pop(next(iter(self._samplers)))
+                smp = self._samplers[key] = decode.AncestralSampling(m.store, n, length, attention, seed=seed)
+            got, scores = smp.run(row0)
+            seqs = np.full((n, length), PAD_ID, np.int64)
+            seqs[:, : got.shape[1]] = got
+            return seqs, scores, None
+        K = self.beam_size if self.decoder == "beam" else 1  # (one beam is greedy decoding)
+        bs = m.beam_search_plan(n, K, length, attention)
+        seqs, scores = bs.run(row0.repeat_interleave(K, dim=0).contiguous() if K > 1 else row0)
+        return seqs.astype(np.int64).reshape(n, K, -1)[:, 0], scores.reshape(n, K)[:, 0], None
+
+    def _rows(self, recipe, mu, ssrc, lo, hi, seed=0):
+        """rows [lo, hi) of a recipe through mst_latent_rows -> (z fp32 [n, Z], decoder start rows [n, >= Dd]) on the device"""
+        import torch
+        from . import ops as o
+        from .engine import positional_table, roundup
+        st, cfg = self.model.store, self.model.engine_config
+        dev, Dd, n = st.device, cfg.d_model, hi - lo
+        if self._pos0 is None or self._pos0.device != dev:
+            self._pos0 = torch.from_numpy(np.ascontiguousarray(positional_table(Dd, 1)[:1])).to(dev)
+        up = lambda x: torch.from_numpy(np.ascontiguousarray(x[lo:hi])).to(dev)
+        z_out = torch.empty(n, cfg.latent_dim, dtype=torch.float32, device=dev)
+        row0 = torch.zeros(n, roundup(Dd, 8), dtype=st.act_dtype, device=dev)
+        o.latent_rows(mu, ssrc, up(recipe.a), up(recipe.b), up(recipe.w), up(recipe.ca), up(recipe.cb), up(recipe.cw),
+                      st.p("decoder.latent2hid.weight"), st.p("decoder.latent2hid.bias"), st.p("decoder.class2hid.weight"), self._pos0,
+                      math.sqrt(float(Dd)), z_out, row0, mode=recipe.mode, tau=recipe.tau, seed=seed, row0=lo)
+        return z_out, row0
+
+    def _run(self, recipe, mu, sigma, length):
+        import torch
+        cfg = self.model.engine_config
+        recipe.validate(0 if mu is None else mu.shape[0], cfg.num_classes)
+        if length < 2:
+            raise ValueError("length must be at least 2 positions")
+        self.calls += 1
+        seed = (self.seed * 0x9E3779B97F4A7C15 + self.calls) & 0xFFFFFFFFFFFFFFFF
+        zs, rows, outs, scores, probs = [], [], [], [], []
+        for lo, hi in chunks(len(recipe), self.max_rows):
+            z_out, row0 = self._rows(recipe, mu, sigma if recipe.use_sigma else None, lo, hi, seed)
+            out, sc, pr = self._decode(row0, length, seed ^ (lo * 0xD1B54A32D192ED03 & 0xFFFFFFFFFFFFFFFF))
+            zs.append(z_out.cpu().numpy())
+            rows.append(row0[:, : cfg.d_model].cpu())
+            outs.append(out)
+            scores.append(np.asarray(sc, np.float64))
+            probs.append(pr)
+        token = cfg.kind == "token"
+        return Generated(recipe, np.concatenate(zs), torch.cat(rows), np.concatenate(scores),
+                         sequences=np.concatenate(outs) if token else None, rolls=None if token else np.concatenate(outs),
+                         probs=np.concatenate(probs) if probs[0] is not None else None)
+
+
+# ---------------------------------------------------------------------- command line
+def build_parser():
+    p = argparse.ArgumentParser(prog="python -m music_style_transfer.VarAutoEncoder.generate",
+                                description="Generate .mid files from the latent space of a trained model.")
+    p.add_argument("--model-output", required=True, help="the model folder of the training run (config + params.N)")
+    p.add_argument("--checkpoint", type=int, default=-1, help="checkpoint index (-1: the latest)")
+    p.add_argument("--mode", required=True, choices=MODES)
+    src = p.add_mutually_exclusive_group()
+    src.add_argument("--data", default=None, help="MIDI folder (one sub-folder per class); the first batch is used")
+    src.add_argument("--toy", action="store_true", help="the three toy sequences instead of --data")
+    p.add_argument("--out", required=True, help="folder the .mid files are written to")
+    p.add_argument("--n", type=int, default=4, help="prior: number of pieces; posterior: draws per melody")
+    p.add_argument("--steps", type=int, default=8, help="interpolate / blend: number of points, end points included")
+    p.add_argument("--pair", type=int, nargs=2, default=(0, 1), metavar=("I", "J"), help="interpolate: the two melodies of the batch")
+    p.add_argument("--classes", type=int, nargs="*", default=None, help="prior / transfer: classes (default: all); blend: the two to mix")
+    p.add_argument("--interpolation", default="slerp", choices=("slerp", "lerp"))
+    p.add_argument("--temperature", type=float, default=1.0)
+    p.add_argument("--decoder", default="sampling", choices=DECODERS)
+    p.add_argument("--beam-size", type=int, default=4)
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--length", type=int, default=None, help="positions to decode (default: twice the input length; prior: 2 * --max-seq-len)")
+    p.add_argument("--batch-size", type=int, default=8)
+    p.add_argument("--max-seq-len", type=int, default=64)
+    p.add_argument("--slices-per-quarter-note", type=int, default=4)
+    p.add_argument("--max-rows", type=int, default=256)
+    p.add_argument("--device", type=int, default=0, help="index of the HIP device")
+    return p
+
+
+def _first_batch(args, kind):
+    from .VarAutoEncoder.data import Loader, ToyData, load_dataset
+    if args.toy:
+        return next(iter(ToyData()))
+    if args.data is None:
+        raise SystemExit("--mode {} needs --data DIR or --toy".format(args.mode))
+    loader = Loader(path=args.data, max_sequence_length=args.max_seq_len, slices_per_quarter_note=args.slices_per_quarter_note)
+    kw = {}
+    if kind != "token":
+        from .pianoroll import PianoRollDataset
+        kw = dict(dataset_cls=lambda bs, L, mel, **k: PianoRollDataset(bs, L, mel, slices_per_quarter=args.slices_per_quarter_note))
+    train, _ = load_dataset(loader, args.batch_size, None, None, **kw)
+    return next(iter(train))
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    from .VarAutoEncoder.sampler import load_inference_model
+    from .VarAutoEncoder.utils import gpu
+    model = load_inference_model(args.model_output, gpu(args.device), args.checkpoint)
+    cfg = model.engine_config
+    gen = LatentGenerator(model, seed=args.seed, temperature=args.temperature, decoder=args.decoder, beam_size=args.beam_size,
+                          max_rows=args.max_rows)
+    if args.mode == "prior":
+        classes = args.classes if args.classes else np.arange(args.n) % cfg.num_classes
+        out = gen.prior(args.n, classes, args.length or 2 * args.max_seq_len)
+    else:
+        batch = _first_batch(args, cfg.kind)
+        if args.mode == "posterior":
+            out = gen.posterior(batch, args.n, length=args.length)
+        elif args.mode == "interpolate":
+            out = gen.interpolate(batch, args.pair[0], args.pair[1], args.steps, mode=args.interpolation, length=args.length)
+        elif args.mode == "transfer":
+            out = gen.transfer(batch, args.classes or None, length=args.length)
+        else:
+            ca, cb = (args.classes if args.classes and len(args.classes) == 2 else (0, cfg.num_classes - 1))
+            out = gen.class_blend(batch, ca, cb, np.linspace(0.0, 1.0, args.steps), length=args.length)
+    files = out.write(args.out)
+    print("wrote {} files to {}".format(len(files), args.out))
+    return files
+
+
+if __name__ == "__main__":
+    main()

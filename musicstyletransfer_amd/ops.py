@@ -492,6 +492,18 @@ def sample_step(probs, seqs, scores, word, i, seed, eos, pad, active=None):
          ptr(active), seed, eos, pad, stream())
 
 
+FRAME_MODES = {"draw": 0, "threshold": 1}
+
+
+def frame_step(logits, P, i, seed_ptr, frames, roll, scores, tau=1.0, mode="draw", thr=0.5, probs_out=None):
+    """the piano-roll frame of position i for every sequence (mst_frame_step): logits [N, >= P] 16-bit; frames uint8 [N, >= P];
+    roll uint8 [N, L, >= P]; probs_out fp32 [N, L, P] or None; seed_ptr: a device int64 / uint64 word"""
+    N, L = roll.shape[0], roll.shape[1]
+    assert roll.is_contiguous() and (probs_out is None or (probs_out.is_contiguous() and tuple(probs_out.shape) == (N, L, P)))
+    call("mst_frame_step", dt(logits), N, P, i, L, ptr(logits), ld(logits), tau, FRAME_MODES[mode], thr, ptr(seed_ptr), ptr(frames), ld(frames),
+         ptr(roll), roll.stride(1), ptr(scores), ptr(probs_out), stream())
+
+
 def beam_gather(cache_in, cache_out, src, n_rows, skip_cols=None):
     """cache_out[j, :n_rows] = cache_in[src[j], :n_rows] for [N, t_max, width] caches (mst_beam_gather);
     skip_cols = (first, count): those columns of every row are left alone (mst_beam_gather_cols)"""
@@ -565,6 +577,25 @@ def latent_fwd(enc_out3, Wl, bl, eps, Wh, bh, classes, cls_d, pos_d, alpha_d, mu
     else:
         Wq, bq, qkv3 = proj
         call("mst_latent_fwd_proj", *args, ptr(Wq), ld(Wq), ptr(bq), ptr(qkv3), qkv3.stride(0), Wq.shape[0], stream())
+
+
+LATENT_ROWS_SITE = 0x7FFE0000  # the generator's eps stream (the training step's eps site is 0x7FFF0000)
+INTERP = {"lerp": 0, "slerp": 1}
+
+
+def latent_rows(zsrc, ssrc, a, b, w, ca, cb, cw, Wh, bh, cls_d, pos_d, alpha_d, z_out, dec_in, mode="lerp", tau=0.0, seed=0, seed_ptr=None,
+                row0=0, site=LATENT_ROWS_SITE):
+    """decoder row 0 of N recipe rows (mst_latent_rows): zsrc / ssrc fp32 [M, Z] or None (prior draws only); a, b, ca, cb int32 [N];
+    w, cw fp32 [N]; z_out fp32 [N, Z]; dec_in [N, >= Dd] 16-bit"""
+    N, (Dd, Z) = z_out.shape[0], Wh.shape
+    M = zsrc.shape[0] if zsrc is not None else 0
+    assert z_out.is_contiguous() and z_out.shape[1] == Z and (zsrc is None or (zsrc.is_contiguous() and zsrc.shape[1] == Z))
+    assert ssrc is None or (zsrc is not None and ssrc.shape == zsrc.shape and ssrc.is_contiguous())
+    for t in (a, b, w, ca, cb, cw):
+        assert t is None or (t.numel() == N and t.is_contiguous())
+    call("mst_latent_rows", dt(dec_in), N, M, Z, Dd, ptr(zsrc), ptr(ssrc), ptr(a), ptr(b), ptr(w), INTERP[mode], tau,
+         seed & 0xFFFFFFFFFFFFFFFF, ptr(seed_ptr), site, row0, ptr(Wh), ptr(bh), ptr(ca), ptr(cb), ptr(cw), ptr(cls_d), cls_d.stride(0),
+         cls_d.shape[0], ptr(pos_d), alpha_d, ptr(z_out), ptr(dec_in), ld(dec_in), stream())
 
 
 def latent_bwd_vec(Wl, eps, Wh, classes, mu, sigma, d_dec_in3, alpha_d, kl_weight, gscale, dcls_d, d_enc_out3, scratch, enc_scale=1.0,
