@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import ops as o
-from .engine import positional_table, roundup
+from .engine import ALL_ROWS, NO_DROPOUT, positional_table, roundup, row_block_fwd
 
 
 class DecodePlan:
@@ -53,11 +53,14 @@ class DecodePlan:
         self.cache = self.cache_sets[0]
         self.x, self.att, self.h1, self.x1, self.h2, self.x2 = (act(B, D) for _ in range(6))
         self.a = act(B, 4 * D)
-        self.mean, self.rstd = torch.zeros(B, dtype=torch.float32, device=dev), torch.zeros(B, dtype=torch.float32, device=dev)
-        self.mean1, self.rstd1 = torch.zeros(B, dtype=torch.float32, device=dev), torch.zeros(B, dtype=torch.float32, device=dev)
         # W_proj + LN1 + feed-forward + LN3 of a position as ONE launch (the training step's mst_proj_ffn_ln_fwd) instead of
         # five: a decoded position is launch-floor bound (MST_DECODE_FFN=0: the five launches)
         self.fuse_ffn = o.can_fuse_ffn(D, 4 * D) and os.environ.get("MST_DECODE_FFN", "1") != "0"
+        stat = lambda: torch.zeros(B, dtype=torch.float32, device=dev)
+        self.mean2, self.rstd2 = stat(), stat()
+        # (LayerNorm statistics, which nothing in decoding reads: a pair per LayerNorm for the one launch, which writes both; the five
+        # launches write one pair after the other)
+        self.mean1, self.rstd1 = (stat(), stat()) if self.fuse_ffn else (self.mean2, self.rstd2)
         self.logits = act(B, cfg.out_dim)
         self.loss = torch.zeros(B, dtype=torch.float32, device=dev)
         self.npos = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -81,27 +84,14 @@ class DecodePlan:
         cfg, st, B = self.cfg, self.store, self.B
         D, H = cfg.d_model, cfg.d_heads
         for i in range(cfg.d_layers):
-            pre = f"decoder.layer{i}"
+            P = st.layer("decoder", i)
             cache = self.cache_sets[(t & 1) if self.pingpong else 0][i]
             # K | Q | V of the new row, written to row t of every sample's cache (C row remap: logical row b -> b * t_max + t)
-            o.gemm_nt(x, st.fused(st.w16, pre, "weight"), cache.view(B * self.t_max, 3 * D), M=B, K=D, bias=st.fused(st.w, pre, "bias"),
-                      c_remap=(1, self.t_max, t))
+            o.gemm_nt(x, P.kqv.w, cache.view(B * self.t_max, 3 * D), M=B, K=D, bias=P.kqv.b, c_remap=(1, self.t_max, t))
             o.attn_decode(cache, t + 1, H, D // H, 0, D, 2 * D, self.att, mode=self.mode)
-            proj = dict(N=D, K=D, bias=st.p(f"{pre}.att.W_proj.bias"), resid=x)
-            ff1 = dict(K=D, bias=st.p(f"{pre}.ff1.bias"), act=o.ACT_RELU)
+            # the training step's row-wise block on this plan's one-row buffers (att, h1, x1, a, h2, x2, mean1/2, rstd1/2);
             # transformer.py:199-200: LN3(ff + dropout(ff)) — dropout is the identity here, so 2 * ff
-            ff2 = dict(K=4 * D, bias=st.p(f"{pre}.ff2.bias"), self_resid=True)
-            if self.fuse_ffn:
-                head = dict(att=self.att, W=st.h(f"{pre}.att.W_proj.weight"), h1=self.h1, gamma=st.p(f"{pre}.ln1.gamma"),
-                            beta=st.p(f"{pre}.ln1.beta"), mean=self.mean1, rstd=self.rstd1, **proj)
-                o.ffn_ln_fwd(self.x1, st.h(f"{pre}.ff1.weight"), self.a, st.h(f"{pre}.ff2.weight"), self.h2, st.p(f"{pre}.ln3.gamma"),
-                             st.p(f"{pre}.ln3.beta"), self.x2, self.mean, self.rstd, ff1=ff1, ff2=ff2, proj=head)
-            else:
-                o.gemm_nt(self.att, st.h(f"{pre}.att.W_proj.weight"), self.h1, **proj)
-                o.layernorm_fwd(self.h1, st.p(f"{pre}.ln1.gamma"), st.p(f"{pre}.ln1.beta"), self.x1, self.mean, self.rstd, D=D)
-                o.gemm_nt(self.x1, st.h(f"{pre}.ff1.weight"), self.a, **ff1)
-                o.gemm_nt(self.a, st.h(f"{pre}.ff2.weight"), self.h2, **ff2)
-                o.layernorm_fwd(self.h2, st.p(f"{pre}.ln3.gamma"), st.p(f"{pre}.ln3.beta"), self.x2, self.mean, self.rstd, D=D)
+            row_block_fwd(P, self, x, ALL_ROWS, NO_DROPOUT, "fused" if self.fuse_ffn else "launches")
             x = self.x2 if i == cfg.d_layers - 1 else self._keep(self.x2)
         return x
 

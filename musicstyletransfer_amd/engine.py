@@ -18,21 +18,14 @@ out by hand below, mirroring the forward line by line.
 import math
 import os
 import warnings
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
 
 from . import ops as o
-
-
-def roundup(a, b):
-    return (a + b - 1) // b * b
-
-
-def _lib_ce_rows():
-    from . import _lib
-    return _lib.CE_MAX_WORKGROUPS
+from ._lib import CE_MAX_WORKGROUPS
+from .ops import roundup
 
 
 class VAEConfig:
@@ -141,7 +134,7 @@ class ParamStore:
                 order.append(name)
         if cfg.kind == "pianoroll":
             # the class table right behind the input embedding: [in_dim + C, De] is then ONE matrix, and the class-embedding
-            # gradient is the last C rows of the embedding's weight-gradient problem (StepPlan.cls_fold)
+            # gradient is the last C rows of the embedding's weight-gradient problem (Forms.cls_fold)
             order.remove("encoder.class2hid.weight")
             order.insert(order.index("encoder.embedding.weight") + 1, "encoder.class2hid.weight")
         self.shapes, self.offsets = shapes, OrderedDict()
@@ -201,6 +194,9 @@ class ParamStore:
         self.t_prefix_late = torch.tensor(lprefix, dtype=torch.int64, device=device)
         self.t_n_late, self.t_tiles_late = len(late), lprefix[-1]
         self.emb_specs = [(self.t_specs[n][0], self.t_off[n], self.t_specs[n][1], self.t_specs[n][2]) for n in emb_names]
+        # the views of every layer's parameters, built once: the flat buffers never move (captured graphs rely on that)
+        self._layers = {(side, i): self._layer_params(side, i)
+                        for side, n_l in (("encoder", cfg.e_layers), ("decoder", cfg.d_layers)) for i in range(n_l)}
 
         # shared by every StepPlan of this store (plans run one after the other on one stream): the per-step RNG state
         # — ONE stream of seeds however many (B, T) shapes a run goes through — and the weight-gradient work buffer
@@ -222,7 +218,7 @@ class ParamStore:
         self.tail_failures = []       # (flags, skipped steps) of every failure seen
         self._tail_listeners = []
         self._rng_state_infer = None
-        self.tok_parts = torch.zeros(_lib_ce_rows(), 4, **f32) if cfg.kind == "token" else None
+        self.tok_parts = torch.zeros(CE_MAX_WORKGROUPS, 4, **f32) if cfg.kind == "token" else None
         if params_np is None:
             params_np = xavier_init(cfg, np.random.default_rng(seed))
         self.load_numpy(params_np)
@@ -363,6 +359,27 @@ class ParamStore:
         off = self.t_off[name]
         return self.wt16[off: off + c * roundup(r, 8)].view(c, roundup(r, 8))
 
+    def _layer_params(self, side, i):
+        pre = f"{side}.layer{i}"
+
+        def dense(name):
+            w, b = f"{pre}.{name}.weight", f"{pre}.{name}.bias"
+            return Dense(self.h(w), self.p(b), self.t(w), self.grad(w), self.grad(b))
+
+        def norm(name):
+            g, b = f"{pre}.{name}.gamma", f"{pre}.{name}.beta"
+            return Norm(self.p(g), self.p(b), self.grad(g), self.grad(b), f"{pre}.{name}")
+
+        kqv = Dense(self.fused(self.w16, pre, "weight"), self.fused(self.w, pre, "bias"), self.t(f"{pre}.att.W_kqv"),
+                    self.fused(self.g, pre, "weight"), self.fused(self.g, pre, "bias"))
+        dec = side == "decoder"
+        return LayerParams(kqv, dense("att.W_proj"), dense("ff1"), dense("ff2"), norm("ln1"), norm("ln3" if dec else "ln2"),
+                           self_resid=dec, mask_mode=2 if dec else 1)
+
+    def layer(self, side, i):
+        """the LayerParams record of layer i of the 'encoder' / 'decoder' stack"""
+        return self._layers[side, i]
+
     # ---- host <-> device
     def load_numpy(self, params_np):
         host = np.zeros(self.n, np.float32)
@@ -409,83 +426,215 @@ class _Layer:
     pass
 
 
+# Parameter views of one transformer layer as the kernels take them (ParamStore.layer). Dense: w the 16-bit shadow (GEMM B operand), b the
+# fp32 bias, t the transposed 16-bit shadow (dgrad B operand), dw / db their views of the gradient bucket; kqv is the layer's K | Q | V
+# projection as ONE [3D, D] Dense. Norm: site is the LayerNorm's key in StepPlan._ln_part. What an encoder and a decoder layer differ in
+# is data here: ln2 is the layer's LAST LayerNorm (the decoder's ln3); self_resid: the second residual is the feed-forward output itself
+# (decoder, transformer.py:199-200: LN3(ff + dropout(ff))) instead of x1 (encoder: LN2(x1 + dropout(ff))); mask_mode: what the backward
+# of that last LayerNorm does with the dropout mask (1: a masked copy of dx next to dx, 2: dx * (1 + mask)).
+Dense = namedtuple("Dense", "w b t dw db")
+Norm = namedtuple("Norm", "gamma beta dgamma dbeta site")
+LayerParams = namedtuple("LayerParams", "kqv proj ff1 ff2 ln1 ln2 self_resid mask_mode")
+
+# Which rows of a layer's [M, ld] buffers a row-wise block works on. view(buf): the operand a launch reads, or a LayerNorm writes; a
+# GEMM writes the whole buffer through the output row remap c_remap; ln: the row arguments of the LayerNorm launches.
+Rows = namedtuple("Rows", "view c_remap ln")
+ALL_ROWS = Rows(lambda buf: buf, (0, 0, 0), {})
+
+
+def position0_rows(B, S):
+    """position 0 of every sample of a [B * S, ld] buffer: B rows, logical row b -> physical row b * S"""
+    return Rows(lambda buf: buf.view(B, S, -1)[:, 0, :], (1, S, 0), dict(M=B, row_id_stride=S))
+
+
+class Dropout(namedtuple("Dropout", "p seed_ptr site0")):
+    """dropout of a layer's row-wise block: probability, the device seed word (None at p = 0), the first of the block's three site ids
+    (attention output, FFN hidden, FFN output)"""
+
+    def at(self, k):
+        """gemm_nt / layernorm_bwd keywords of site k of the block"""
+        return dict(dropout_p=self.p, dropout_site=self.site0 + k, dropout_seed_ptr=self.seed_ptr) if self.p > 0 else {}
+
+
+NO_DROPOUT = Dropout(0.0, None, 0)
+
+
+def row_block_fwd(P, L, x_in, rows, drop, form, row_groups=None, tail=None):
+    """The row-wise block of a transformer layer behind the attention mix: W_proj + residual -> LayerNorm-1 -> FF1 + ReLU -> FF2 +
+    residual -> LayerNorm-2/3, on `rows` of the layer's buffers L (att in; h1, x1, a, h2, x2, mean1/2, rstd1/2 out). form:
+      'launches'  the five launches (any rows: the recovery path of the position-0 tail, and every width without a fused kernel)
+      'fused'     one launch, mst_proj_ffn_ln_fwd (all rows; row_groups: ops.ffn_ln_fwd's, the last decoder layer without position 0)
+      'tail'      one launch, mst_row_tail_fwd (position-0 rows; tail: its sync / stat_stride / phys_stride / status / rider / queue /
+                  shadows keywords)"""
+    D, v = P.proj.w.shape[0], rows.view
+    if form == "tail":
+        o.row_tail_fwd(v(L.att), v(x_in), P.proj.w, P.proj.b, P.ln1.gamma, P.ln1.beta, P.ff1.w, P.ff1.b, P.ff2.w, P.ff2.b, P.ln2.gamma,
+                       P.ln2.beta, v(L.h1), v(L.x1), v(L.a), v(L.h2), v(L.x2), L.mean1, L.rstd1, L.mean2, L.rstd2, dropout_p=drop.p,
+                       dropout_seed_ptr=drop.seed_ptr, site0=drop.site0, **tail)
+        return L.x2
+    proj = dict(N=D, K=D, bias=P.proj.b, resid=v(x_in), **drop.at(0))
+    ff1 = dict(K=D, bias=P.ff1.b, act=o.ACT_RELU, **drop.at(1))
+    ff2 = dict(K=4 * D, bias=P.ff2.b, **drop.at(2))
+    ff2.update(dict(self_resid=True) if P.self_resid else dict(resid=v(L.x1)))
+    if form == "fused":  # (same results as the five launches, bit for bit in a / h2. The projection's dgrad behind the backward block
+        # measured +14 us and was removed.)
+        head = dict(att=L.att, W=P.proj.w, h1=L.h1, gamma=P.ln1.gamma, beta=P.ln1.beta, mean=L.mean1, rstd=L.rstd1, **proj)
+        o.ffn_ln_fwd(L.x1, P.ff1.w, L.a, P.ff2.w, L.h2, P.ln2.gamma, P.ln2.beta, L.x2, L.mean2, L.rstd2, ff1=ff1, ff2=ff2, proj=head,
+                     row_groups=row_groups)
+        return L.x2
+    # (Dense + LayerNorm in one launch, ops.gemm_nt_ln_fwd, does not pay in the forward pass: graph-replay timings at
+    # M = 16384 are 17.8 vs 19.9 us for N 256 K 256 but 30.3 vs 30.2 for K 1024 and 16.6 vs 13.0 / 21.3 vs 16.5 for
+    # N 128, and nothing at step level — the forward LayerNorm is a 7 us launch and the full-row tile costs the GEMM
+    # as much. The backward forms, where the LayerNorm launch is 16 us, do pay: row_block_bwd.)
+    o.gemm_nt(v(L.att), P.proj.w, L.h1, c_remap=rows.c_remap, **proj)
+    o.layernorm_fwd(v(L.h1), P.ln1.gamma, P.ln1.beta, v(L.x1), L.mean1, L.rstd1, D=D, **rows.ln)
+    o.gemm_nt(v(L.x1), P.ff1.w, L.a, c_remap=rows.c_remap, **ff1)
+    o.gemm_nt(v(L.a), P.ff2.w, L.h2, c_remap=rows.c_remap, **ff2)
+    o.layernorm_fwd(v(L.h2), P.ln2.gamma, P.ln2.beta, v(L.x2), L.mean2, L.rstd2, D=D, **rows.ln)
+    return L.x2
+
+
+def _lead_mask(P, t, drop):
+    """mask keywords of the LayerNorm backward a layer's backward pass starts with (LN2 of an encoder layer, LN3 of a decoder layer)"""
+    if P.mask_mode == 2:
+        return dict(mask_mode=2, **drop.at(2))
+    return dict(mask_mode=1, dx_masked=t.dhm, **drop.at(2)) if drop.p > 0 else {}
+
+
+def no_partials(norm, parts):
+    """row_block_bwd's `partials` for a block of few rows: the LayerNorm parameter gradients go straight into the bucket (atomics)"""
+    return None
+
+
+def row_block_bwd(P, L, t, dy, rows, drop, form, partials, dy_done=False, row_groups=None, tail=None):
+    """Backward of row_block_fwd on the same rows: LayerNorm-2/3 backward of dy, both FFN dgrads, LayerNorm-1 backward, the W_proj
+    dgrad. t: the layer's backward buffers — dh, dhm, dx1, dh1m, dpre indexed by the block's own rows, dh1 and datt by the layer's
+    (written through `rows`). partials(norm, n_workgroups) -> the partials buffer of one LayerNorm-backward launch, or None
+    (StepPlan._ln_partials). Returns (dff, dproj): the A operands of the FF2 and W_proj weight gradients. form:
+      'launches'  five launches
+      'ln_fused'  FF1 dgrad + LayerNorm-1 backward in one launch (mst_gemm_nt_ln; the gradient in between is never stored): four
+      'fused'     both dgrads + LayerNorm-1 backward in one launch (mst_ffn_ln_bwd); an encoder layer's LayerNorm-2 backward rides in
+                  its prologue (mst_ffn_ln_bwd_lead; the prologue has no mask_mode 2). row_groups as in row_block_fwd
+      'tail'      one launch, mst_row_tail_bwd (position-0 rows; tail: its keywords)
+    dy_done: the producer of dy already ran the leading LayerNorm backward (t.dh / t.dhm are filled; not with 'tail')."""
+    D, v = P.proj.w.shape[0], rows.view
+    if form == "tail":
+        o.row_tail_bwd(v(dy), v(L.h2), v(L.h1), v(L.a), L.mean1, L.rstd1, L.mean2, L.rstd2, P.ln1.gamma, P.ln2.gamma, P.ff2.t, P.ff1.t,
+                       P.proj.t, t.dh, t.dhm, t.dx1, t.dh1m, t.dpre, v(t.dh1), v(t.datt), P.ln1.dgamma, P.ln1.dbeta, P.ln2.dgamma,
+                       P.ln2.dbeta, dropout_p=drop.p, dropout_seed_ptr=drop.seed_ptr, site0=drop.site0, **tail)
+        return t.dhm, t.dh1m  # (the launch writes the masked copies at p = 0 too)
+    M = L.h1.shape[0]
+    lead = None
+    if not dy_done and form == "fused" and P.mask_mode == 1:
+        lead = dict(dy=dy, x=L.h2, gamma=P.ln2.gamma, mean=L.mean2, rstd=L.rstd2, dx=t.dh, dgamma=P.ln2.dgamma, dbeta=P.ln2.dbeta,
+                    partials=partials(P.ln2, o.gemm_nt_ln_parts(M)), **_lead_mask(P, t, drop))
+    elif not dy_done:
+        mask = _lead_mask(P, t, drop)
+        if P.mask_mode == 2:
+            mask["dropout_site"] = drop.site0 + 2  # (this launch has always been given the site id at p = 0 too, where nothing reads it)
+        o.layernorm_bwd(v(L.h2), P.ln2.gamma, L.mean2, L.rstd2, v(dy), t.dh, P.ln2.dgamma, P.ln2.dbeta, D=D,
+                        partials=partials(P.ln2, o.layernorm_bwd_parts(M, D)), **rows.ln, **mask)
+    # encoder: dx feeds the residual branch, its masked copy the feed-forward branch; decoder: one branch (mask_mode 2)
+    dff = t.dhm if (drop.p > 0 and not P.self_resid) else t.dh
+    resid_ff = None if P.self_resid else t.dh
+    # FFN: d(pre-relu) = (dff W2) * 1[a > 0] / (1-p)   (a is stored post-dropout, so a > 0 <=> relu on and kept)
+    inv_keep = 1.0 / (1.0 - drop.p) if drop.p > 0 else 1.0
+    ln1 = dict(dx_masked=t.dh1m, mask_mode=1, **drop.at(0)) if drop.p > 0 else {}
+    if form == "fused":
+        n = M if row_groups is None else M // row_groups[1] * row_groups[0]
+        o.ffn_ln_bwd(dff, P.ff2.t, t.dpre, L.a, P.ff1.t, t.dh1, L.h1, P.ln1.gamma, L.mean1, L.rstd1, P.ln1.dgamma, P.ln1.dbeta,
+                     alpha=inv_keep, resid=resid_ff, partials=partials(P.ln1, o.gemm_nt_ln_parts(n)), lead=lead, row_groups=row_groups,
+                     **ln1)
+    else:
+        o.gemm_nt(dff, P.ff2.t, t.dpre, N=4 * D, K=D, gate=v(L.a), alpha=inv_keep)
+        if form == "ln_fused":
+            o.gemm_nt_ln_bwd(t.dpre, P.ff1.t, t.dh1, L.h1, P.ln1.gamma, L.mean1, L.rstd1, P.ln1.dgamma, P.ln1.dbeta, N=D, K=4 * D,
+                             resid=resid_ff, partials=partials(P.ln1, o.gemm_nt_ln_parts(M)), **ln1)
+        else:
+            o.gemm_nt(t.dpre, P.ff1.t, t.dx1, N=D, K=4 * D, resid=resid_ff)
+            o.layernorm_bwd(v(L.h1), P.ln1.gamma, L.mean1, L.rstd1, t.dx1, v(t.dh1), P.ln1.dgamma, P.ln1.dbeta, D=D,
+                            partials=partials(P.ln1, o.layernorm_bwd_parts(M, D)), **rows.ln, **ln1)
+    dproj = t.dh1m if drop.p > 0 else v(t.dh1)
+    o.gemm_nt(dproj, P.proj.t, t.datt, N=D, K=D, c_remap=rows.c_remap)
+    return dff, dproj
+
+
+def layer_wgrads(P, L, t, x_in, dff, dproj, rows):
+    """a layer's four weight-gradient problems (FF2, FF1, W_proj on `rows`; K | Q | V on every row), for the step's ONE wgrad launch"""
+    D, v = P.proj.w.shape[0], rows.view
+    return [o.wgrad_problem(dff, v(L.a), P.ff2.dw, P.ff2.db, N=D, K=4 * D),
+            o.wgrad_problem(t.dpre, v(L.x1), P.ff1.dw, P.ff1.db, N=4 * D, K=D),
+            o.wgrad_problem(dproj, v(L.att), P.proj.dw, P.proj.db, N=D, K=D),
+            o.wgrad_problem(t.dqkv, x_in, P.kqv.dw, P.kqv.db, N=3 * D, K=D)]
+
+
 def row_tail_selfcheck(store, B=64, S=2):
     """One-time start-up check of the one-launch position-0 tails (mst_row_tail_fwd / _bwd) on THIS device, process and
-    partition mode: both are run against the five launches they replace, on random rows and the store's own top-layer
-    weights. Their grid barrier rests on properties no API guarantees (enough workgroups of an oversubscribed launch landing
-    on one XCD, L1 behaviour of write-through lines — csrc/row_tail.hip), so shape alone does not decide whether the fused
-    form is used: a mismatch, an unfinished barrier or a status flag pins the store to the five-launch form."""
+    partition mode: both are run against the five launches the engine falls back to — row_block_fwd / row_block_bwd in both forms —
+    on random rows and the store's own top-layer weights. Their grid barrier rests on properties no API guarantees (enough workgroups
+    of an oversubscribed launch landing on one XCD, L1 behaviour of write-through lines — csrc/row_tail.hip), so shape alone does not
+    decide whether the fused form is used: a mismatch, an unfinished barrier or a status flag pins the store to the five-launch form."""
     store.tail_checked = True
     cfg, dev, adt = store.cfg, store.device, store.act_dtype
     D, F = cfg.e_model, 4 * cfg.e_model
     if not (o.can_row_tail(B, D) and store.tail_fused and cfg.e_layers >= 1):
         return True
-    pre = f"encoder.layer{cfg.e_layers - 1}"
     f32 = dict(dtype=torch.float32, device=dev)
+    P = store.layer("encoder", cfg.e_layers - 1)
+    # (the check's LayerNorm parameter gradients go to scratch, not into the store's bucket)
+    scratch = lambda n: n._replace(dgamma=torch.zeros(D, **f32), dbeta=torch.zeros(D, **f32))
+    P = P._replace(ln1=scratch(P.ln1), ln2=scratch(P.ln2))
 
-    def rnd(rows, width, site, scale=1.0, relu=False):
-        a = torch.zeros(rows, width, **f32)
+    def rnd(n, width, site):
+        a = torch.zeros(n, width, **f32)
         o.randn(a, seed=0x7A11, site=site)
-        t = torch.zeros(rows, width, dtype=adt, device=dev)
-        o.cast_to_act(a, t)  # (values ~ N(0, 1); `scale` only documents intent: LayerNorm makes the chain scale-free)
+        t = torch.zeros(n, width, dtype=adt, device=dev)
+        o.cast_to_act(a, t)  # (values ~ N(0, 1): LayerNorm makes the chain scale-free)
         return t
 
-    row0 = lambda t: t.view(B, S, -1)[:, 0, :]
+    z = lambda n, w: torch.zeros(n, w, dtype=adt, device=dev)
     att, xin = rnd(B * S, D, 1), rnd(B * S, D, 2)
-    Wp, W1, W2 = store.h(f"{pre}.att.W_proj.weight"), store.h(f"{pre}.ff1.weight"), store.h(f"{pre}.ff2.weight")
-    par = {k: store.p(f"{pre}.{k}") for k in ("att.W_proj.bias", "ln1.gamma", "ln1.beta", "ff1.bias", "ff2.bias", "ln2.gamma", "ln2.beta")}
     status = torch.zeros(2, dtype=torch.int32, device=dev)
     sync = torch.zeros(8, dtype=torch.int32, device=dev)
+    rows = position0_rows(B, S)
 
     def fbufs():
-        z = lambda w: torch.zeros(B * S, w, dtype=adt, device=dev)
-        return dict(h1=z(D), x1=z(D), a=z(F), h2=z(D), x2=z(D), m1=torch.zeros(B * S, **f32), r1=torch.zeros(B * S, **f32),
-                    m2=torch.zeros(B * S, **f32), r2=torch.zeros(B * S, **f32))
+        L = _Layer()
+        L.att, L.h1, L.x1, L.a, L.h2, L.x2 = att, z(B * S, D), z(B * S, D), z(B * S, F), z(B * S, D), z(B * S, D)
+        L.mean1, L.rstd1, L.mean2, L.rstd2 = (torch.zeros(B * S, **f32) for _ in range(4))
+        return L
 
-    u, f, rows = fbufs(), fbufs(), (1, S, 0)
-    o.gemm_nt(row0(att), Wp, u["h1"], M=B, N=D, K=D, bias=par["att.W_proj.bias"], resid=row0(xin), c_remap=rows)
-    o.layernorm_fwd(row0(u["h1"]), par["ln1.gamma"], par["ln1.beta"], row0(u["x1"]), u["m1"], u["r1"], D=D, M=B, row_id_stride=S)
-    o.gemm_nt(row0(u["x1"]), W1, u["a"], M=B, K=D, bias=par["ff1.bias"], act=o.ACT_RELU, c_remap=rows)
-    o.gemm_nt(row0(u["a"]), W2, u["h2"], M=B, K=F, bias=par["ff2.bias"], resid=row0(u["x1"]), c_remap=rows)
-    o.layernorm_fwd(row0(u["h2"]), par["ln2.gamma"], par["ln2.beta"], row0(u["x2"]), u["m2"], u["r2"], D=D, M=B, row_id_stride=S)
-    o.row_tail_fwd(row0(att), row0(xin), Wp, par["att.W_proj.bias"], par["ln1.gamma"], par["ln1.beta"], W1, par["ff1.bias"], W2,
-                   par["ff2.bias"], par["ln2.gamma"], par["ln2.beta"], row0(f["h1"]), row0(f["x1"]), row0(f["a"]), row0(f["h2"]),
-                   row0(f["x2"]), f["m1"], f["r1"], f["m2"], f["r2"], sync[0:3], stat_stride=S, phys_stride=S, status=status[0:1])
+    u, f = fbufs(), fbufs()
+    tail = dict(stat_stride=S, phys_stride=S, status=status[0:1])
+    row_block_fwd(P, u, xin, rows, NO_DROPOUT, "launches")
+    row_block_fwd(P, f, xin, rows, NO_DROPOUT, "tail", tail=dict(tail, sync=sync[0:3]))
     # backward chain on the forward's own activations
     dy = rnd(B * S, D, 3)
-    W2t, W1t, Wpt = store.t(f"{pre}.ff2.weight"), store.t(f"{pre}.ff1.weight"), store.t(f"{pre}.att.W_proj.weight")
 
     def bbufs():
-        z = lambda n, w: torch.zeros(n, w, dtype=adt, device=dev)
-        return dict(dh=z(B, D), dhm=z(B, D), dx1=z(B, D), dh1m=z(B, D), dpre=z(B, F), dh1=z(B * S, D), datt=z(B * S, D),
-                    dg1=torch.zeros(D, **f32), db1=torch.zeros(D, **f32), dg2=torch.zeros(D, **f32), db2=torch.zeros(D, **f32))
+        t = _Layer()
+        t.dh, t.dhm, t.dx1, t.dh1m, t.dpre, t.dh1, t.datt = z(B, D), z(B, D), z(B, D), z(B, D), z(B, F), z(B * S, D), z(B * S, D)
+        return t
 
     ub, fb = bbufs(), bbufs()
-    g1, g2 = par["ln1.gamma"], par["ln2.gamma"]
-    o.layernorm_bwd(row0(u["h2"]), g2, u["m2"], u["r2"], row0(dy), ub["dh"], ub["dg2"], ub["db2"], D=D, M=B, row_id_stride=S)
-    o.gemm_nt(ub["dh"], W2t, ub["dpre"], N=F, K=D, gate=row0(u["a"]), alpha=1.0)
-    o.gemm_nt(ub["dpre"], W1t, ub["dx1"], N=D, K=F, resid=ub["dh"])
-    o.layernorm_bwd(row0(u["h1"]), g1, u["m1"], u["r1"], ub["dx1"], row0(ub["dh1"]), ub["dg1"], ub["db1"], D=D, M=B, row_id_stride=S)
-    o.gemm_nt(row0(ub["dh1"]), Wpt, ub["datt"], M=B, N=D, K=D, c_remap=(1, S, 0))
-    o.row_tail_bwd(row0(dy), row0(u["h2"]), row0(u["h1"]), row0(u["a"]), u["m1"], u["r1"], u["m2"], u["r2"], g1, g2, W2t, W1t, Wpt,
-                   fb["dh"], fb["dhm"], fb["dx1"], fb["dh1m"], fb["dpre"], row0(fb["dh1"]), row0(fb["datt"]), fb["dg1"], fb["db1"],
-                   fb["dg2"], fb["db2"], sync[4:7], stat_stride=S, phys_stride=S, status=status[0:1])
+    row_block_bwd(P, u, ub, dy, rows, NO_DROPOUT, "launches", no_partials)
+    row_block_bwd(P, u, fb, dy, rows, NO_DROPOUT, "tail", no_partials, tail=dict(tail, sync=sync[4:7]))
     torch.cuda.current_stream().synchronize()
-    G = D // 16
+    want_f, want_b = o.row_tail_barriers(D)
     sy, stv = sync.cpu().tolist(), status.cpu().tolist()
     why = []
     if stv[0]:
         why.append(f"status flags {stv[0]:#x}")
-    if sy[0] != 3 * G or sy[4] != 2 * G:
-        why.append(f"barrier counters {sy[0]} / {sy[4]} instead of {3 * G} / {2 * G}")
+    if sy[0] != want_f or sy[4] != want_b:
+        why.append(f"barrier counters {sy[0]} / {sy[4]} instead of {want_f} / {want_b}")
     ulp = 2.0 ** -7 if adt == torch.bfloat16 else 2.0 ** -10
     host = lambda t: t.float().cpu().numpy()
     for k in ("h1", "x1", "a", "h2", "x2"):
-        a, b = host(row0(f[k])), host(row0(u[k]))
+        a, b = host(rows.view(getattr(f, k))), host(rows.view(getattr(u, k)))
         if not np.all(np.abs(a - b) <= 4 * ulp * np.maximum(np.abs(b), 1.0)):
             why.append(f"forward {k}: max difference {np.abs(a - b).max():.3g}")
     for k in ("dh", "dpre", "dx1", "dh1", "datt"):
-        a, b = host(fb[k]), host(ub[k])
+        a, b = host(getattr(fb, k)), host(getattr(ub, k))
         if not np.abs(a - b).max() <= 4 * ulp * max(float(np.abs(b).max()), 1e-6) + 1e-6:
             why.append(f"backward {k}: max difference {np.abs(a - b).max():.3g} (scale {np.abs(b).max():.3g})")
     if why:
@@ -493,6 +642,11 @@ def row_tail_selfcheck(store, B=64, S=2):
         warnings.warn("the one-launch position-0 tail failed its start-up check on this device (" + "; ".join(why) +
                       "): using the five-launch form", RuntimeWarning)
     return not why
+
+
+# The launch forms of one issued kernel sequence (StepPlan._resolve_forms): tails — the position-0 tails as one launch; riders — GEMMs
+# riding on them; shadows — where the transposed-shadow refresh goes ('own' / 'begin' / 'tail'); the rest as named there.
+Forms = namedtuple("Forms", "tails riders shadows fuse_bce bce_dgrad skip_row0 cls_fold ffn_e ffn_d ln_bwd_e ln_bwd_d")
 
 
 class StepPlan:
@@ -535,20 +689,26 @@ class StepPlan:
         def act(rows, width):
             return torch.zeros(rows, roundup(width, 8), dtype=adt, device=dev)
 
+        # RIDERS on the one-launch position-0 tails (which keep ONE XCD busy for ~26 us each while seven idle): the decoder's first
+        # K | Q | V projection of rows 1..T — its input exists since the step's first launch — is computed by the forward tail
+        # launch's workgroups on the other XCDs (row 0 by the latent block's launch), and the input gradient of that projection for
+        # rows 1..T — which only the decoder embedding's weight gradient reads — by the backward tail's (row 0 inside the latent
+        # block's backward launch): two GEMM launches (12 + 10 us at configs[1]) leave the step's dependent chain. Piano-roll ends.
+        self.ride = (cfg.kind != "token" and cfg.d_layers >= 1 and cfg.e_layers >= 1 and Dd in (128, 256) and
+                     o.can_ride(B * T, 3 * Dd, Dd, T) and o.can_ride(B * T, Dd, 3 * Dd, T))
+        # the deferred shadow refresh (ParamStore.shadows_deferred) behind the forward tail's riders where that launch has them;
+        # False: behind the tiles of the step's first launch
+        self.shadows_on_tail = True
+        # the launch forms of the sequence issued last (resolved again by every forward(); here: the buffers below follow from them)
+        self.forms = self._resolve_forms()
         # ---- inputs: ONE static device blob (so a batch arrives with a single copy) viewed as typed tensors
         if cfg.kind == "token":
             seg = [("tokens", B * T * 4), ("labels", B * T * 4)]
         else:
             # piano-roll frames stay uint8 in HBM, exactly as the batcher delivers them (1 byte per pitch; rows padded to 8):
-            # the embedding GEMMs and their weight gradients widen them while staging tiles into LDS (a_u8)
-            # The class-embedding gradient is a column sum of d(x0) per class = onehot(class)^T d(x0): with the one-hot class id
-            # of a frame in C extra columns behind its pitches, and the class table behind the embedding table in the flat
-            # buffers, it is rows in_dim.. of the encoder embedding's weight-gradient problem — whose 256-row tile has the
-            # room — instead of a launch of its own (otherwise: the group_colsum launch)
-            C_ = cfg.num_classes
-            self.cls_fold = (cfg.in_dim % 8 == 0 and roundup(cfg.in_dim + C_, 256) == roundup(cfg.in_dim, 256) and
-                             store.offsets["encoder.class2hid.weight"] == store.offsets["encoder.embedding.weight"] + cfg.in_dim * De)
-            self.ld_roll = roundup(cfg.in_dim + (C_ if self.cls_fold else 0), 8)
+            # the embedding GEMMs and their weight gradients widen them while staging tiles into LDS (a_u8); with Forms.cls_fold
+            # the one-hot class id of a frame sits in C extra columns behind its pitches
+            self.ld_roll = roundup(cfg.in_dim + (cfg.num_classes if self.forms.cls_fold else 0), 8)
             seg = [("roll", B * T * self.ld_roll), ("labels", B * T * cfg.out_dim)]
         seg += [("seq_lens", B * 4), ("classes", B * 4)]
         self.in_layout, off = {}, 0
@@ -595,29 +755,7 @@ class StepPlan:
         self.ride_queues = self._recon_buf[nb4 + 32:].view(torch.int32)  # [0]: forward tail's riders, [32]: backward tail's
         self.metric_acc = store.metric_acc  # [sum kl, sum total, count]  (trainer.py:115-116)
         self.track_token_metrics = False  # Trainer: accumulate ppl / acc / topk sums on the device in the CE launch
-        # output layer + BCE in one launch when a tile can hold whole rows of pitches of one sample (configs[1]: P 128, T 256)
-        self.fuse_bce = (cfg.kind == "pianoroll" and o.can_fuse_bce(cfg.out_dim, T, negative_label_downscaling) and
-                         o.bce_fusion_pays(cfg.out_dim))
-        # ... and the output layer's input gradient + the last decoder layer's LayerNorm-3 backward in the same workgroups
-        self.bce_dgrad = self.fuse_bce and o.ln_bwd_fusion_pays(Dd)
-        # The LAST decoder layer's row-wise part (W_proj, LayerNorm-1, feed-forward, LayerNorm-3 and their backward) skips every
-        # sample's position-0 row: its output is dropped before the loss (model.py:253), so nothing it computes there is ever
-        # read and every gradient there is zero — the buffers' position-0 rows simply stay at the zeros they were allocated with.
-        # B x T rows are B T / 64 tiles of the one-workgroup-per-CU feed-forward launches: ONE resident round at configs[1]
-        # (256 tiles) where B (T + 1) rows were 257 (measured: forward 22.8 -> 18.9 us, backward 24.6 -> 20.3).
-        self.skip_row0 = cfg.d_layers > 0 and T % 64 == 0 and o.ffn_fusion_pays(Dd, 4 * Dd)
-        # RIDERS on the one-launch position-0 tails (which keep ONE XCD busy for ~26 us each while seven idle): the decoder's first
-        # K | Q | V projection of rows 1..T — its input exists since the step's first launch — is computed by the forward tail
-        # launch's workgroups on the other XCDs (row 0 by the latent block's launch), and the input gradient of that projection for
-        # rows 1..T — which only the decoder embedding's weight gradient reads — by the backward tail's (row 0 inside the latent
-        # block's backward launch): two GEMM launches (12 + 10 us at configs[1]) leave the step's dependent chain. Piano-roll ends.
-        self.ride = (cfg.kind != "token" and cfg.d_layers >= 1 and cfg.e_layers >= 1 and Dd in (128, 256) and
-                     o.can_ride(B * T, 3 * Dd, Dd, T) and o.can_ride(B * T, Dd, 3 * Dd, T))
-        self._ride_fwd = self._ride_bwd = False
-        # the deferred shadow refresh (ParamStore.shadows_deferred) behind the forward tail's riders where that launch has them;
-        # False: behind the tiles of the step's first launch
-        self.shadows_on_tail = True
-        self.logits = None if self.fuse_bce else act(B * T, cfg.out_dim)
+        self.logits = None if self.forms.fuse_bce else act(B * T, cfg.out_dim)  # (fused: the logits never reach HBM)
         self.dlogits = act(B * T, cfg.out_dim)
         if cfg.kind == "token":
             self.probs = torch.zeros(B * T, cfg.out_dim, **f32) if want_probs else None
@@ -641,8 +779,7 @@ class StepPlan:
         # stream instead bought nothing: hipGraph on ROCm 7.2 replays fork/join branches back to back on one queue.)
         self.be_l = [bwd_bufs(self.Me, De, cfg.e_heads, Se) for _ in range(cfg.e_layers)]
         self.bd_l = [bwd_bufs(self.Md, Dd, cfg.d_heads, Sd) for _ in range(cfg.d_layers)]
-        self.be, self.bd = self.be_l[0], self.bd_l[0]
-        self._wgrads, self._psums, self._out_dgrad_done = [], [], False
+        self._wgrads = []
         self.wgrad_scratch = store.wgrad_scratch()
         # LayerNorm parameter gradients: every LayerNorm-backward workgroup leaves one row of column sums here and ONE
         # launch per flush adds them into the bucket (256 workgroups x one atomic per column on the same 2D addresses
@@ -666,9 +803,10 @@ class StepPlan:
         c = _Layer()
         c.dh, c.dhm, c.dx1, c.dh1m = act(B, De), act(B, De), act(B, De), act(B, De)
         c.dpre = act(B, 4 * De)
+        self.sp_dh1 = c.dh1 = act(self.Me, De)
+        self.sp_datt = c.datt = act(self.Me, De)
+        c.dqkv, c.delta = self.be_l[-1].dqkv, self.be_l[-1].delta  # (attention mixes rows: the layer's own full-size buffers)
         self.top = c
-        self.sp_dh1 = act(self.Me, De)
-        self.sp_datt = act(self.Me, De)
         self.graph = None
         self.graph_late = None
         self.graph_opt = None
@@ -687,18 +825,52 @@ class StepPlan:
     def d_p(self):
         return 0.0 if self._infer else self.cfg.d_dropout
 
-    def _tail_on(self, D):
-        return o.can_row_tail(self.B, D) and self.store.tail_fused
+    def _resolve_forms(self):
+        """Which form every launch of the sequence about to be issued takes: from the shape, and from the four attributes diagnostics
+        set before the first forward() / capture() (store.tail_fused — which a failed tail also clears —, store.shadows_deferred,
+        plan.ride, plan.shadows_on_tail). forward() resolves them; every phase of the step reads this record and nothing else."""
+        cfg, st, B, T = self.cfg, self.store, self.B, self.T
+        De, Dd = cfg.e_model, cfg.d_model
+        roll = cfg.kind == "pianoroll"
+        # position-0 tails of the top encoder layer as one launch each (mst_row_tail_*), else five
+        tails = bool(o.can_row_tail(B, De) and st.tail_fused)
+        riders = bool(self.ride and tails)
+        # the refresh of the transposed shadows (read by the backward pass only): 'own' launch behind the optimizer; deferred to the
+        # next step, behind the forward 'tail''s riders where that launch has them — compute units that idle until the position-0
+        # chain ends — else behind the tiles of the step's first launch ('begin', +4.9 us)
+        shadows = "own" if not st.shadows_deferred else ("tail" if self.shadows_on_tail and riders else "begin")
+        # output layer + BCE in one launch when a tile can hold whole rows of pitches of one sample (configs[1]: P 128, T 256)
+        fuse_bce = roll and o.can_fuse_bce(cfg.out_dim, T, self.nld) and o.bce_fusion_pays(cfg.out_dim)
+        ffn_d, ln_bwd_d = o.ffn_fusion_pays(Dd, 4 * Dd), o.ln_bwd_fusion_pays(Dd)
+        return Forms(
+            tails=tails, riders=riders, shadows=shadows, fuse_bce=fuse_bce,
+            # ... and the output layer's input gradient + the last decoder layer's LayerNorm-3 backward in the same workgroups
+            bce_dgrad=fuse_bce and ln_bwd_d,
+            # The LAST decoder layer's row-wise part (W_proj, LayerNorm-1, feed-forward, LayerNorm-3 and their backward) skips every
+            # sample's position-0 row: its output is dropped before the loss (model.py:253), so nothing it computes there is ever
+            # read and every gradient there is zero — the buffers' position-0 rows simply stay at the zeros they were allocated with.
+            # B x T rows are B T / 64 tiles of the one-workgroup-per-CU feed-forward launches: ONE resident round at configs[1]
+            # (256 tiles) where B (T + 1) rows were 257 (measured: forward 22.8 -> 18.9 us, backward 24.6 -> 20.3).
+            skip_row0=cfg.d_layers > 0 and T % 64 == 0 and ffn_d,
+            # The class-embedding gradient is a column sum of d(x0) per class = onehot(class)^T d(x0): with the one-hot class id
+            # of a frame in C extra columns behind its pitches, and the class table behind the embedding table in the flat
+            # buffers, it is rows in_dim.. of the encoder embedding's weight-gradient problem — whose 256-row tile has the
+            # room — instead of a launch of its own (otherwise: the group_colsum launch)
+            cls_fold=(roll and cfg.in_dim % 8 == 0 and roundup(cfg.in_dim + cfg.num_classes, 256) == roundup(cfg.in_dim, 256) and
+                      st.offsets["encoder.class2hid.weight"] == st.offsets["encoder.embedding.weight"] + cfg.in_dim * De),
+            # the row-wise block of a layer as one launch forward / backward (row_block_fwd / _bwd 'fused'), and Dense dgrad +
+            # LayerNorm backward in one launch (row_block_bwd 'ln_fused', the chain of leading LayerNorm backwards: _out_ln_bwd)
+            ffn_e=o.ffn_fusion_pays(De, 4 * De), ffn_d=ffn_d, ln_bwd_e=o.ln_bwd_fusion_pays(De), ln_bwd_d=ln_bwd_d)
 
     def _guard(self):
         """step guard of the launches that close a step (optimizer / loss_combine): the barrier counters of the one-launch
-        tails issued in this step must have reached their final values (G = D / 16 workgroups: 3 barriers forward, 2 backward)"""
-        G = self.cfg.e_model // 16
+        tails issued in this step must have reached their final values"""
+        fwd, bwd = o.row_tail_barriers(self.cfg.e_model)
         exp = []
         if self._tail_used["fwd"]:
-            exp.append((self.sync_words[0:1], 3 * G))
+            exp.append((self.sync_words[0:1], fwd))
         if self._tail_used["bwd"]:
-            exp.append((self.sync_words[4:5], 2 * G))
+            exp.append((self.sync_words[4:5], bwd))
         g = dict(status=self.store.step_status, expect=exp)
         if self.global_batch == self.B:
             # one rank: the optimizer also skips a step whose loss is not finite (its gradients are NaN: an update would destroy the
@@ -746,7 +918,7 @@ class StepPlan:
             self.labels.copy_(dev(labels, torch.uint8).view(B * T, cfg.out_dim))
         self.seq_lens.copy_(dev(seq_lens, torch.int32))
         self.classes.copy_(dev(classes, torch.int32))
-        if cfg.kind != "token" and self.cls_fold:
+        if self.forms.cls_fold:
             w = self.ld_roll - cfg.in_dim
             onehot = (self.classes.view(B, 1).to(torch.int64) == torch.arange(w, device=self.dev).view(1, w)).to(torch.uint8)
             self.roll_cls.view(B, T, -1)[:, :, cfg.in_dim:].copy_(onehot.view(B, 1, w).expand(B, T, w))
@@ -777,7 +949,7 @@ class StepPlan:
             ldp = self.ld_roll
             roll = seg("roll", np.uint8, B * T, ldp)
             np.copyto(roll[:, : cfg.in_dim], as_np(x).reshape(B * T, cfg.in_dim), casting="unsafe")
-            if self.cls_fold:
+            if self.forms.cls_fold:
                 w = ldp - cfg.in_dim
                 roll.reshape(B, T, ldp)[:, :, cfg.in_dim:] = (as_np(classes).reshape(B, 1, 1).astype(np.int64) ==
                                                               np.arange(w).reshape(1, 1, w)).astype(np.uint8)
@@ -800,6 +972,9 @@ class StepPlan:
     def _drop(self, p, site):
         return dict(dropout_p=p, dropout_site=site, dropout_seed_ptr=self.rng_state) if p > 0 else {}
 
+    def _dropout(self, p, site0):
+        return Dropout(p, self.rng_state if p > 0 else None, site0)
+
     def _site_e(self, i):
         """first of the three dropout site ids of encoder layer i (attention output, FFN hidden, FFN output)"""
         return self.site_base + 3 * i
@@ -807,101 +982,56 @@ class StepPlan:
     def _site_d(self, i):
         return self.site_base + 3 * (self.cfg.e_layers + i)
 
+    def _late_shadows(self):
+        """the deferred refresh of the transposed shadows only the backward pass reads (ParamStore.shadows_deferred)"""
+        st = self.store
+        return dict(w=st.w, wt16=st.wt16, desc=st.t_desc_late, prefix=st.t_prefix_late, n_mat=st.t_n_late, tiles=st.t_tiles_late)
+
     def _top_encoder_layer_fwd(self, i, L, x_in):
         """Last encoder layer: the model reads its output at position 0 only (model.py:97) and everything after the
         attention mix is row-wise, so after the dense K/Q/V projection and the softmax row statistics (which
         normalise over ALL queries) only query 0 is attended and only B rows go through W_proj, LN1, the FFN and LN2.
         The other rows of these buffers are never produced nor read (backward: _top_encoder_layer_bwd)."""
-        cfg, st, B, S = self.cfg, self.store, self.B, self.T
-        D, H, p, site0 = cfg.e_model, cfg.e_heads, self.e_p, self._site_e(i)
-        pre = f"encoder.layer{i}"
-
-        def row0(buf):
-            return buf.view(B, S, -1)[:, 0, :]
-
+        cfg, st, B, S, F = self.cfg, self.store, self.B, self.T, self.forms
+        D, H = cfg.e_model, cfg.e_heads
+        P = st.layer("encoder", i)
         # (the K | Q | V projection runs inside the attention launch where the shape allows: mst_attn_qkv_fwd)
-        o.attn_qkv_fwd(x_in, st.fused(st.w16, pre, "weight"), st.fused(st.w, pre, "bias"), L.qkv, self.keymask_e, L.lse, L.att, B, S, H,
-                       D // H, 0, D, 2 * D, q_limit=1)
-        self._tail_used["fwd"] = self._tail_on(D)
-        self._ride_fwd = self.ride and self._tail_used["fwd"]
-        if self._tail_used["fwd"]:  # W_proj, LN1, FFN1, FFN2, LN2 on the B position-0 rows in one launch (mst_row_tail_fwd)
-            rider = None
-            if self._ride_fwd:  # the decoder's first K | Q | V projection, rows 1..T of every sample (see __init__: ride)
-                Dd, Sd = cfg.d_model, S + 1
-                rider = dict(A=self.x0_d, B=st.fused(st.w16, "decoder.layer0", "weight"), C_out=self.dec[0].qkv, M=B * S, N=3 * Dd, K=Dd,
-                             bias=st.fused(st.w, "decoder.layer0", "bias"), a_remap=(S, Sd, 1), c_remap=(S, Sd, 1))
-            o.row_tail_fwd(row0(L.att), row0(x_in), st.h(f"{pre}.att.W_proj.weight"), st.p(f"{pre}.att.W_proj.bias"),
-                           st.p(f"{pre}.ln1.gamma"), st.p(f"{pre}.ln1.beta"), st.h(f"{pre}.ff1.weight"), st.p(f"{pre}.ff1.bias"),
-                           st.h(f"{pre}.ff2.weight"), st.p(f"{pre}.ff2.bias"), st.p(f"{pre}.ln2.gamma"), st.p(f"{pre}.ln2.beta"),
-                           row0(L.h1), row0(L.x1), row0(L.a), row0(L.h2), row0(L.x2), L.mean1, L.rstd1, L.mean2, L.rstd2,
-                           self.sync_words[0:3], stat_stride=S, phys_stride=S, dropout_p=p,
-                           dropout_seed_ptr=self.rng_state if p > 0 else None, site0=site0, status=st.step_status[0:1], rider=rider,
-                           queue=self.ride_queues[0:1], shadows=self._tail_shadows if rider is not None else None)
-            assert self._tail_shadows is None or rider is not None, "the shadow refresh was planned onto a tail without riders"
-            return L.x2
-        rows = (1, S, 0)  # output row b -> physical row b*S
-        o.gemm_nt(row0(L.att), st.h(f"{pre}.att.W_proj.weight"), L.h1, M=B, N=D, K=D, bias=st.p(f"{pre}.att.W_proj.bias"),
-                  resid=row0(x_in), c_remap=rows, **self._drop(p, site0))
-        o.layernorm_fwd(row0(L.h1), st.p(f"{pre}.ln1.gamma"), st.p(f"{pre}.ln1.beta"), row0(L.x1), L.mean1, L.rstd1, D=D, M=B,
-                        row_id_stride=S)
-        o.gemm_nt(row0(L.x1), st.h(f"{pre}.ff1.weight"), L.a, M=B, K=D, bias=st.p(f"{pre}.ff1.bias"), act=o.ACT_RELU,
-                  c_remap=rows, **self._drop(p, site0 + 1))
-        o.gemm_nt(row0(L.a), st.h(f"{pre}.ff2.weight"), L.h2, M=B, K=4 * D, bias=st.p(f"{pre}.ff2.bias"), resid=row0(L.x1),
-                  c_remap=rows, **self._drop(p, site0 + 2))
-        o.layernorm_fwd(row0(L.h2), st.p(f"{pre}.ln2.gamma"), st.p(f"{pre}.ln2.beta"), row0(L.x2), L.mean2, L.rstd2, D=D, M=B,
-                        row_id_stride=S)
-        return L.x2
+        o.attn_qkv_fwd(x_in, P.kqv.w, P.kqv.b, L.qkv, self.keymask_e, L.lse, L.att, B, S, H, D // H, 0, D, 2 * D, q_limit=1)
+        self._tail_used["fwd"] = F.tails
+        tail = None
+        if F.tails:
+            tail = dict(sync=self.sync_words[0:3], stat_stride=S, phys_stride=S, status=st.step_status[0:1], queue=self.ride_queues[0:1])
+            if F.riders:  # the decoder's first K | Q | V projection, rows 1..T of every sample (see __init__: ride)
+                Pd, Dd, Sd = st.layer("decoder", 0), cfg.d_model, S + 1
+                tail["rider"] = dict(A=self.x0_d, B=Pd.kqv.w, C_out=self.dec[0].qkv, M=B * S, N=3 * Dd, K=Dd, bias=Pd.kqv.b,
+                                     a_remap=(S, Sd, 1), c_remap=(S, Sd, 1))
+                if F.shadows == "tail":
+                    tail["shadows"] = self._late_shadows()
+        return row_block_fwd(P, L, x_in, position0_rows(B, S), self._dropout(self.e_p, self._site_e(i)),
+                             "tail" if F.tails else "launches", tail=tail)
 
     def _layer_fwd(self, side, i, L, x_in, keymask, D, H, S, p, site0):
-        st = self.store
-        pre = f"{side}.layer{i}"
+        F = self.forms
         dh = D // H
         if side == "encoder" and i == self.cfg.e_layers - 1:
             return self._top_encoder_layer_fwd(i, L, x_in)
+        P = self.store.layer(side, i)
         causal = side == "decoder" and self.cfg.d_causal
-        if side == "decoder" and i == 0 and self._ride_fwd:  # (projected by the forward tail's riders + the latent block's launch)
+        if side == "decoder" and i == 0 and F.riders:  # (projected by the forward tail's riders + the latent block's launch)
             (o.attn_causal_fwd if causal else o.attn_fwd)(L.qkv, keymask, L.lse, L.att, self.B, S, H, dh, 0, D, 2 * D)
         elif causal:  # the projection GEMM, then the causal attention launch
-            o.gemm_nt(x_in, st.fused(st.w16, pre, "weight"), L.qkv, N=3 * D, K=D, bias=st.fused(st.w, pre, "bias"))
+            o.gemm_nt(x_in, P.kqv.w, L.qkv, N=3 * D, K=D, bias=P.kqv.b)
             o.attn_causal_fwd(L.qkv, keymask, L.lse, L.att, self.B, S, H, dh, 0, D, 2 * D)
         else:
-            o.attn_qkv_fwd(x_in, st.fused(st.w16, pre, "weight"), st.fused(st.w, pre, "bias"), L.qkv, keymask, L.lse, L.att, self.B, S, H, dh,
-                           0, D, 2 * D)
-        # (Dense + LayerNorm in one launch, ops.gemm_nt_ln_fwd, does not pay in the forward pass: graph-replay timings at
-        # M = 16384 are 17.8 vs 19.9 us for N 256 K 256 but 30.3 vs 30.2 for K 1024 and 16.6 vs 13.0 / 21.3 vs 16.5 for
-        # N 128, and nothing at step level — the forward LayerNorm is a 7 us launch and the full-row tile costs the GEMM
-        # as much. The backward forms, where the LayerNorm launch is 16 us, do pay: _layer_bwd.)
-        proj = dict(N=D, K=D, bias=st.p(f"{pre}.att.W_proj.bias"), resid=x_in, **self._drop(p, site0))
-        fused = o.ffn_fusion_pays(D, 4 * D)
-        if not fused:
-            o.gemm_nt(L.att, st.h(f"{pre}.att.W_proj.weight"), L.h1, **proj)
-            o.layernorm_fwd(L.h1, st.p(f"{pre}.ln1.gamma"), st.p(f"{pre}.ln1.beta"), L.x1, L.mean1, L.rstd1, D=D)
-        ff1 = dict(K=D, bias=st.p(f"{pre}.ff1.bias"), act=o.ACT_RELU, **self._drop(p, site0 + 1))
-        # encoder: LN2(x1 + dropout(ff)); decoder (transformer.py:199-200): LN3(ff + dropout(ff))
-        ln = "ln2" if side == "encoder" else "ln3"
-        ff2 = dict(K=4 * D, bias=st.p(f"{pre}.ff2.bias"), **self._drop(p, site0 + 2))
-        ff2.update(dict(resid=L.x1) if side == "encoder" else dict(self_resid=True))
-        if fused:  # the attention output projection + LayerNorm-1, the whole feed-forward block and its LayerNorm in one launch
-            # (mst_proj_ffn_ln_fwd; same results, bit for bit in a / h2. The projection's dgrad behind the backward block measured +14 us
-            # and was removed.)
-            head = dict(att=L.att, W=st.h(f"{pre}.att.W_proj.weight"), h1=L.h1, gamma=st.p(f"{pre}.ln1.gamma"),
-                        beta=st.p(f"{pre}.ln1.beta"), mean=L.mean1, rstd=L.rstd1, **proj)
-            o.ffn_ln_fwd(L.x1, st.h(f"{pre}.ff1.weight"), L.a, st.h(f"{pre}.ff2.weight"), L.h2, st.p(f"{pre}.{ln}.gamma"),
-                         st.p(f"{pre}.{ln}.beta"), L.x2, L.mean2, L.rstd2, ff1=ff1, ff2=ff2, proj=head,
-                         row_groups=self._row0_groups(side, i))
-            return L.x2
-        o.gemm_nt(L.x1, st.h(f"{pre}.ff1.weight"), L.a, **ff1)
-        o.gemm_nt(L.a, st.h(f"{pre}.ff2.weight"), L.h2, **ff2)
-        o.layernorm_fwd(L.h2, st.p(f"{pre}.{ln}.gamma"), st.p(f"{pre}.{ln}.beta"), L.x2, L.mean2, L.rstd2, D=D)
-        return L.x2
-
-    def _ride_bwd_planned(self):
-        """the backward tail will run as one launch in this step and can take a rider (decided before it is issued)"""
-        return self.ride and self._tail_on(self.cfg.e_model)
+            o.attn_qkv_fwd(x_in, P.kqv.w, P.kqv.b, L.qkv, keymask, L.lse, L.att, self.B, S, H, dh, 0, D, 2 * D)
+        fused = F.ffn_e if side == "encoder" else F.ffn_d
+        return row_block_fwd(P, L, x_in, ALL_ROWS, self._dropout(p, site0), "fused" if fused else "launches",
+                             row_groups=self._row0_groups(side, i))
 
     def _row0_groups(self, side, i):
-        """row groups of the last decoder layer's row-wise launches (skip_row0): rows 1..T of every T + 1, else None"""
-        if side == "decoder" and i == self.cfg.d_layers - 1 and self.skip_row0:
+        """row groups of the last decoder layer's row-wise launches (Forms.skip_row0, which implies their fused form): rows 1..T of
+        every T + 1, else None"""
+        if side == "decoder" and i == self.cfg.d_layers - 1 and self.forms.skip_row0:
             return (self.T, self.T + 1, 1)
         return None
 
@@ -915,11 +1045,14 @@ class StepPlan:
             raise ValueError("forward(upto=...) takes 'latent', in inference mode only")
         cfg, st, B, T = self.cfg, self.store, self.B, self.T
         self._infer = bool(inference)
+        # (every forward: handle_step_status() may have cleared store.tail_fused since the last one. losses(), the backward phases and
+        # optimizer() — also when captured as graphs of their own — read the record this forward leaves.)
+        F = self.forms = self._resolve_forms()
         self._tail_used = dict(fwd=False, bwd=False)
         De, Dd = cfg.e_model, cfg.d_model
         Se, Sd = T, T + 1
         sq_e, sq_d = math.sqrt(float(De)), math.sqrt(float(Dd))
-        self._wgrads, self._psums, self._outers, self._out_dgrad_done = [], [], [], False  # deferred gradient work of this step
+        self._wgrads, self._psums, self._outers = [], [], []  # deferred gradient work of this step
         # one bookkeeping launch: RNG seed of this step, Adam's step count / lr_t, eps, both padding masks
         need_rng = self.e_p > 0 or self.d_p > 0 or self.internal_eps
         rng = st.rng_state_inference() if self._infer else self.rng_state
@@ -930,15 +1063,8 @@ class StepPlan:
                      eps_index0=self.sample_offset * cfg.latent_dim, lens=self.seq_lens,
                      mask_e=self.keymask_e if cfg.kind != "token" else None, add_e=0, mask_d=self.keymask_d, add_d=1,
                      zero_a=self._recon_buf, zero_b=st.g if tick else None)
-        self._tail_shadows = None
-        if st.shadows_deferred:
-            late = dict(w=st.w, wt16=st.wt16, desc=st.t_desc_late, prefix=st.t_prefix_late, n_mat=st.t_n_late, tiles=st.t_tiles_late)
-            # the refresh of the transposed shadows (read by the backward pass only): behind the forward tail's riders where that launch
-            # has them — compute units that idle until the position-0 chain ends — else behind the tiles of the step's first launch (+4.9 us)
-            if self.shadows_on_tail and self.ride and self._tail_on(cfg.e_model):
-                self._tail_shadows = late
-            else:
-                begin["shadows"] = late
+        if F.shadows == "begin":
+            begin["shadows"] = self._late_shadows()
         # (piano-roll ends: nothing in the embedding GEMMs reads what the bookkeeping writes — it rides on their launch)
         ride = cfg.kind != "token"
         if not ride:
@@ -966,8 +1092,9 @@ class StepPlan:
         # (the decoder's first K | Q | V projection riding on this launch — rows 1..T exist since the step's first launch — was
         # built and measured at parity: 16-wave workgroups make poor GEMM tiles at K = 128; removed, docs/kernel_notes.md)
         proj0 = None
-        if self._ride_fwd:  # ... and position 0 of that projection, on the launch that produces the row
-            proj0 = (st.fused(st.w16, "decoder.layer0", "weight"), st.fused(st.w, "decoder.layer0", "bias"), self.dec[0].qkv.view(B, Sd, -1))
+        if F.riders:  # ... and position 0 of that projection, on the launch that produces the row
+            Pd = st.layer("decoder", 0)
+            proj0 = (Pd.kqv.w, Pd.kqv.b, self.dec[0].qkv.view(B, Sd, -1))
         o.latent_fwd(*lat, proj=proj0)
         if upto == "latent":
             return
@@ -981,29 +1108,28 @@ class StepPlan:
         self.dec_out = x
         # ---- output layer on positions 1..T (model.py:253-256); with a whole row of pitches per tile it runs inside the loss
         # launch (losses(): mst_gemm_sigmoid_bce) and the logits never reach HBM
-        if not self.fuse_bce:
+        if not F.fuse_bce:
             o.gemm_nt(x, st.h("decoder.output_layer.weight"), self.logits, M=B * T, K=Dd, bias=st.p("decoder.output_layer.bias"),
                       a_remap=(T, Sd, 1))
 
     def losses(self, with_grad=True, combine=True):
         """combine=False: the total loss / running metric sums are left to optimizer() (they ride on the Adam launch)"""
-        cfg, B, T = self.cfg, self.B, self.T
+        cfg, B, T, F = self.cfg, self.B, self.T, self.forms
         dl = self.dlogits if with_grad else None
         if cfg.kind == "token":
             o.softmax_ce(self.logits, self.labels, self.recon, B, T, cfg.out_dim, probs=self.probs, dlogits=dl,
                          gscale=self.gscale, pre_zeroed=True,
                          tok_parts=self.store.tok_parts if self.track_token_metrics else None)
-        elif self.fuse_bce:
+        elif F.fuse_bce:
             dgrad = None
-            if with_grad and self.bce_dgrad:
+            if with_grad and F.bce_dgrad:
                 # the first launch of the backward pass — the output layer's input gradient + the last decoder layer's LayerNorm-3
                 # backward (backward_early) — consumes exactly the logit-gradient tile this launch produces: same workgroup
                 last, Dd, Sd = cfg.d_layers - 1, cfg.d_model, T + 1
                 dgrad = dict(A=self.dlogits, B=self.store.t("decoder.output_layer.weight"), dX_out=self.bd_l[last].dh, M=B * T, N=Dd,
                              K=self.dlogits.shape[1], c_remap=(T, Sd, 1),
-                             **self._out_ln_bwd("decoder", last, self.dec[last], Dd, cfg.d_dropout, self._site_d(0) + 3 * last,
+                             **self._out_ln_bwd("decoder", last, self.dec[last], cfg.d_dropout, self._site_d(0) + 3 * last,
                                                 self.bd_l[last], B * T))
-                self._out_dgrad_done = True
             o.gemm_sigmoid_bce(self.dec_out, self.store.h("decoder.output_layer.weight"), self.labels, self.recon, T, dgrad=dgrad,
                                dlogits=dl, probs=self.probs, label_smoothing=self.ls, downweight=self.nld, gscale=self.gscale, M=B * T,
                                K=cfg.d_model, bias=self.store.p("decoder.output_layer.bias"), a_remap=(T, T + 1, 1))
@@ -1017,13 +1143,12 @@ class StepPlan:
     # ------------------------------------------------------------------------------ backward
     LN_PARTIALS_MIN = 32  # fewer workgroups than this: their atomics are cheaper than a row of partials each
 
-    def _ln_partials(self, site, parts):
-        """partials buffer of one LayerNorm-backward launch (None: few workgroups, keep the atomics); registers the
-        deferred column sums into dgamma / dbeta, executed by _flush_grads()"""
+    def _ln_partials(self, norm, parts):
+        """partials buffer of one LayerNorm-backward launch of `parts` workgroups (None: few workgroups, keep the atomics); registers
+        the deferred column sums into dgamma / dbeta, executed by _flush_grads()"""
         if parts < self.LN_PARTIALS_MIN:
             return None
-        st, buf = self.store, self._ln_part[site]
-        dg, db = st.grad(f"{site}.gamma"), st.grad(f"{site}.beta")
+        buf, dg, db = self._ln_part[norm.site], norm.dgamma, norm.dbeta
         D = dg.numel()
         if db.data_ptr() == dg.data_ptr() + 4 * D:  # adjacent in the flat bucket: one job
             self._psums.append(o.partial_sum_job(buf, parts, dg, length=2 * D))
@@ -1037,182 +1162,69 @@ class StepPlan:
         self.last_wgrad_launch = (self._wgrads, self._psums)  # (bench.py re-launches the step's own wgrad batch to time it)
         self._wgrads, self._psums, self._outers = [], [], []
 
-    def _out_ln_bwd(self, side, i, L, D, p, site0, t, M):
+    def _out_ln_bwd(self, side, i, L, p, site0, t, M):
         """The LayerNorm backward a layer's backward pass STARTS with (LN2 of an encoder layer, LN3 of a decoder layer),
         as keyword arguments for ops.gemm_nt_ln_bwd: the GEMM (of M rows) that produces the layer's incoming gradient runs
         it in its epilogue (dX_out = t.dh) when the row width allows, see _layer_bwd(dy_done=...)."""
-        st = self.store
-        pre = f"{side}.layer{i}"
-        ln = "ln2" if side == "encoder" else "ln3"
-        kw = dict(x=L.h2, gamma=st.p(f"{pre}.{ln}.gamma"), mean=L.mean2, rstd=L.rstd2, dgamma=st.grad(f"{pre}.{ln}.gamma"),
-                  dbeta=st.grad(f"{pre}.{ln}.beta"), partials=self._ln_partials(f"{pre}.{ln}", o.gemm_nt_ln_parts(M)))
-        if side == "encoder":
-            kw.update(dict(mask_mode=1, dx_masked=t.dhm) if p > 0 else dict(mask_mode=0))
-        else:
-            kw.update(mask_mode=2)
-        if p > 0:
-            kw.update(dropout_p=p, dropout_seed_ptr=self.rng_state, dropout_site=site0 + 2)
-        return kw
+        P = self.store.layer(side, i)
+        return dict(x=L.h2, gamma=P.ln2.gamma, mean=L.mean2, rstd=L.rstd2, dgamma=P.ln2.dgamma, dbeta=P.ln2.dbeta,
+                    partials=self._ln_partials(P.ln2, o.gemm_nt_ln_parts(M)), **_lead_mask(P, t, self._dropout(p, site0)))
 
-    def _layer_bwd(self, side, i, L, x_in, dy, dx_in, keymask, D, H, S, p, site0, t, dy_done=False, next_ln=None):
+    def _layer_bwd(self, side, i, L, x_in, dy, dx_in, keymask, D, H, S, p, site0, t, dy_done=False, next_ln=None, ride=False):
         """dy: gradient w.r.t. the layer output x2; writes the gradient w.r.t. x_in into dx_in.
         dy_done: the producer of dy already ran this layer's leading LayerNorm backward (t.dh / t.dhm are filled).
         next_ln: (_out_ln_bwd(...) of the layer below, its scratch): run THAT layer's leading LayerNorm backward in the
-        epilogue of this layer's last GEMM instead of writing dx_in."""
-        st = self.store
-        pre = f"{side}.layer{i}"
-        dhd = D // H
-        inv_keep = 1.0 / (1.0 - p) if p > 0 else 1.0
-        dk = dict(dropout_p=p, dropout_seed_ptr=self.rng_state) if p > 0 else {}
-        fuse = o.ln_bwd_fusion_pays(D)
-        M = L.h1.shape[0]
-        ffn_fused = o.ffn_fusion_pays(D, 4 * D)
-        lead = None
-        if side == "encoder" and not dy_done and ffn_fused:
-            # LayerNorm-2 backward rides in the prologue of the fused feed-forward backward (mst_ffn_ln_bwd_lead)
-            lead = dict(dy=dy, x=L.h2, gamma=st.p(f"{pre}.ln2.gamma"), mean=L.mean2, rstd=L.rstd2, dx=t.dh,
-                        dgamma=st.grad(f"{pre}.ln2.gamma"), dbeta=st.grad(f"{pre}.ln2.beta"),
-                        partials=self._ln_partials(f"{pre}.ln2", o.gemm_nt_ln_parts(M)))
-            if p > 0:
-                lead.update(dx_masked=t.dhm, dropout_site=site0 + 2, **dk)
-            dy_done = True
-        if side == "encoder":
-            if not dy_done:
-                part = self._ln_partials(f"{pre}.ln2", o.layernorm_bwd_parts(M, D))
-                if p > 0:
-                    o.layernorm_bwd(L.h2, st.p(f"{pre}.ln2.gamma"), L.mean2, L.rstd2, dy, t.dh, st.grad(f"{pre}.ln2.gamma"),
-                                    st.grad(f"{pre}.ln2.beta"), D=D, dx_masked=t.dhm, mask_mode=1, dropout_site=site0 + 2,
-                                    partials=part, **dk)
-                else:
-                    o.layernorm_bwd(L.h2, st.p(f"{pre}.ln2.gamma"), L.mean2, L.rstd2, dy, t.dh, st.grad(f"{pre}.ln2.gamma"),
-                                    st.grad(f"{pre}.ln2.beta"), D=D, partials=part)
-            dff = t.dhm if p > 0 else t.dh
-            resid_ff = t.dh
-        else:
-            if not dy_done:
-                o.layernorm_bwd(L.h2, st.p(f"{pre}.ln3.gamma"), L.mean2, L.rstd2, dy, t.dh, st.grad(f"{pre}.ln3.gamma"),
-                                st.grad(f"{pre}.ln3.beta"), D=D, mask_mode=2, dropout_site=site0 + 2,
-                                partials=self._ln_partials(f"{pre}.ln3", o.layernorm_bwd_parts(M, D)), **dk)
-            dff = t.dh
-            resid_ff = None
-        # FFN: d(pre-relu) = (dff W2) * 1[a > 0] / (1-p)   (a is stored post-dropout, so a > 0 <=> relu on and kept)
-        ln1 = dict(dx_masked=t.dh1m, mask_mode=1, dropout_site=site0, **dk) if p > 0 else {}
-        if ffn_fused:  # both dgrads of the block + LayerNorm-1 backward in one launch (mst_ffn_ln_bwd)
-            rows = self._row0_groups(side, i)
-            o.ffn_ln_bwd(dff, st.t(f"{pre}.ff2.weight"), t.dpre, L.a, st.t(f"{pre}.ff1.weight"), t.dh1, L.h1, st.p(f"{pre}.ln1.gamma"),
-                         L.mean1, L.rstd1, st.grad(f"{pre}.ln1.gamma"), st.grad(f"{pre}.ln1.beta"), alpha=inv_keep, resid=resid_ff,
-                         partials=self._ln_partials(f"{pre}.ln1", o.gemm_nt_ln_parts(self.B * self.T if rows else M)), lead=lead,
-                         row_groups=rows, **ln1)
-        else:
-            o.gemm_nt(dff, st.t(f"{pre}.ff2.weight"), t.dpre, N=4 * D, K=D, gate=L.a, alpha=inv_keep)
-            if fuse:  # FFN1 dgrad + LayerNorm-1 backward in one launch (the gradient in between is never stored)
-                o.gemm_nt_ln_bwd(t.dpre, st.t(f"{pre}.ff1.weight"), t.dh1, L.h1, st.p(f"{pre}.ln1.gamma"), L.mean1, L.rstd1,
-                                 st.grad(f"{pre}.ln1.gamma"), st.grad(f"{pre}.ln1.beta"), N=D, K=4 * D, resid=resid_ff,
-                                 partials=self._ln_partials(f"{pre}.ln1", o.gemm_nt_ln_parts(M)), **ln1)
-            else:
-                o.gemm_nt(t.dpre, st.t(f"{pre}.ff1.weight"), t.dx1, N=D, K=4 * D, resid=resid_ff)
-                o.layernorm_bwd(L.h1, st.p(f"{pre}.ln1.gamma"), L.mean1, L.rstd1, t.dx1, t.dh1, st.grad(f"{pre}.ln1.gamma"),
-                                st.grad(f"{pre}.ln1.beta"), D=D, partials=self._ln_partials(f"{pre}.ln1", o.layernorm_bwd_parts(M, D)),
-                                **ln1)
-        dproj = t.dh1m if p > 0 else t.dh1
-        o.gemm_nt(dproj, st.t(f"{pre}.att.W_proj.weight"), t.datt, N=D, K=D)
+        epilogue of this layer's last GEMM instead of writing dx_in.
+        ride (decoder layer 0 when the backward tail takes a rider): rows 1..T of dx_in — which only the decoder embedding's weight
+        gradient reads — are left to that launch and row 0 to the latent block's backward launch; returns (the rider's GEMM,
+        latent_bwd_vec's proj= triple) for backward_early to hand them on. Else returns None."""
+        F, P = self.forms, self.store.layer(side, i)
+        ffn, ln = (F.ffn_e, F.ln_bwd_e) if side == "encoder" else (F.ffn_d, F.ln_bwd_d)
+        dff, dproj = row_block_bwd(P, L, t, dy, ALL_ROWS, self._dropout(p, site0), "fused" if ffn else ("ln_fused" if ln else "launches"),
+                                   self._ln_partials, dy_done=dy_done, row_groups=self._row0_groups(side, i))
         if side == "decoder" and self.cfg.d_causal:
-            o.attn_causal_bwd(L.qkv, keymask, L.lse, t.datt, t.dqkv, t.delta, self.B, S, H, dhd, 0, D, 2 * D)
+            o.attn_causal_bwd(L.qkv, keymask, L.lse, t.datt, t.dqkv, t.delta, self.B, S, H, D // H, 0, D, 2 * D)
         else:
-            o.attn_bwd(L.qkv, keymask, L.lse, t.datt, t.dqkv, t.delta, self.B, S, H, dhd, 0, D, 2 * D)
+            o.attn_bwd(L.qkv, keymask, L.lse, t.datt, t.dqkv, t.delta, self.B, S, H, D // H, 0, D, 2 * D)
+        handed = None
         if next_ln is not None:  # the layer below starts its backward pass with a LayerNorm backward: run it here
             kw, t_below = next_ln
-            o.gemm_nt_ln_bwd(t.dqkv, st.t(f"{pre}.att.W_kqv"), t_below.dh, N=D, K=3 * D, resid=t.dh1, **kw)
-        elif side == "decoder" and i == 0 and self._ride_bwd_planned():
-            # rows 1..T ride on the backward tail's launch (only the decoder embedding's weight gradient reads them), row 0 is
-            # computed inside the latent block's backward launch: backward_early / _top_encoder_layer_bwd
+            o.gemm_nt_ln_bwd(t.dqkv, P.kqv.t, t_below.dh, N=D, K=3 * D, resid=t.dh1, **kw)
+        elif ride:
             T_ = self.T
-            self._bwd_rider = dict(A=t.dqkv, B=st.t(f"{pre}.att.W_kqv"), C_out=dx_in, M=self.B * T_, N=D, K=3 * D, resid=t.dh1, resid_phys=True,
-                                   a_remap=(T_, T_ + 1, 1), c_remap=(T_, T_ + 1, 1))
-            self._bwd_dx0 = (t.dqkv.view(self.B, S, -1), st.t(f"{pre}.att.W_kqv"), t.dh1.view(self.B, S, -1))
+            handed = (dict(A=t.dqkv, B=P.kqv.t, C_out=dx_in, M=self.B * T_, N=D, K=3 * D, resid=t.dh1, resid_phys=True,
+                           a_remap=(T_, T_ + 1, 1), c_remap=(T_, T_ + 1, 1)),
+                      (t.dqkv.view(self.B, S, -1), P.kqv.t, t.dh1.view(self.B, S, -1)))
         else:
-            o.gemm_nt(t.dqkv, st.t(f"{pre}.att.W_kqv"), dx_in, N=D, K=3 * D, resid=t.dh1)
+            o.gemm_nt(t.dqkv, P.kqv.t, dx_in, N=D, K=3 * D, resid=t.dh1)
         # the layer's four weight gradients: deferred to the ONE wgrad launch at the end of backward() (their operands
         # live in this layer's own scratch `t` and in the forward activations, so nothing is overwritten meanwhile)
-        self._wgrads += [
-            o.wgrad_problem(dff, L.a, st.grad(f"{pre}.ff2.weight"), st.grad(f"{pre}.ff2.bias"), N=D, K=4 * D),
-            o.wgrad_problem(t.dpre, L.x1, st.grad(f"{pre}.ff1.weight"), st.grad(f"{pre}.ff1.bias"), N=4 * D, K=D),
-            o.wgrad_problem(dproj, L.att, st.grad(f"{pre}.att.W_proj.weight"), st.grad(f"{pre}.att.W_proj.bias"), N=D, K=D),
-            o.wgrad_problem(t.dqkv, x_in, st.fused(st.g, pre, "weight"), st.fused(st.g, pre, "bias"), N=3 * D, K=D),
-        ]
+        self._wgrads += layer_wgrads(P, L, t, x_in, dff, dproj, ALL_ROWS)
+        return handed
 
-    def _top_encoder_layer_bwd(self, i, L, x_in, dx_in, t, next_ln=None):
-        """_layer_bwd for the LAST encoder layer, on the B rows (position 0 of each sample) that carry gradient."""
-        cfg, st, B, S = self.cfg, self.store, self.B, self.T
-        D, H, p, site0 = cfg.e_model, cfg.e_heads, cfg.e_dropout, self._site_e(i)
-        pre = f"encoder.layer{i}"
-        c = self.top
-        inv_keep = 1.0 / (1.0 - p) if p > 0 else 1.0
-        dk = dict(dropout_p=p, dropout_seed_ptr=self.rng_state) if p > 0 else {}
-
-        def row0(buf):  # [B, ld] view of position 0 of every sample (row stride S*ld)
-            return buf.view(B, S, -1)[:, 0, :]
-
-        dy = row0(self.d_enc_out)
-        self._tail_used["bwd"] = self._tail_on(D)
-        if self._tail_used["bwd"]:
-            # LayerNorm-2 backward, both FFN dgrads, LayerNorm-1 backward and the W_proj dgrad of the B rows in one launch
-            o.row_tail_bwd(dy, row0(L.h2), row0(L.h1), row0(L.a), L.mean1, L.rstd1, L.mean2, L.rstd2, st.p(f"{pre}.ln1.gamma"),
-                           st.p(f"{pre}.ln2.gamma"), st.t(f"{pre}.ff2.weight"), st.t(f"{pre}.ff1.weight"), st.t(f"{pre}.att.W_proj.weight"),
-                           c.dh, c.dhm, c.dx1, c.dh1m, c.dpre, row0(self.sp_dh1), row0(self.sp_datt), st.grad(f"{pre}.ln1.gamma"),
-                           st.grad(f"{pre}.ln1.beta"), st.grad(f"{pre}.ln2.gamma"), st.grad(f"{pre}.ln2.beta"), self.sync_words[4:7],
-                           stat_stride=S, phys_stride=S, dropout_p=p, dropout_seed_ptr=self.rng_state if p > 0 else None, site0=site0,
-                           status=st.step_status[0:1], rider=getattr(self, "_bwd_rider", None), queue=self.ride_queues[32:33])
-            dff, dproj = c.dhm, c.dh1m
-            return self._top_encoder_layer_bwd_rest(i, L, x_in, dx_in, t, next_ln, dff, dproj)
-        if p > 0:
-            o.layernorm_bwd(row0(L.h2), st.p(f"{pre}.ln2.gamma"), L.mean2, L.rstd2, dy, c.dh, st.grad(f"{pre}.ln2.gamma"),
-                            st.grad(f"{pre}.ln2.beta"), D=D, M=B, row_id_stride=S, dx_masked=c.dhm, mask_mode=1,
-                            dropout_site=site0 + 2, **dk)
-            dff = c.dhm
-        else:
-            o.layernorm_bwd(row0(L.h2), st.p(f"{pre}.ln2.gamma"), L.mean2, L.rstd2, dy, c.dh, st.grad(f"{pre}.ln2.gamma"),
-                            st.grad(f"{pre}.ln2.beta"), D=D, M=B, row_id_stride=S)
-            dff = c.dh
-        o.gemm_nt(dff, st.t(f"{pre}.ff2.weight"), c.dpre, N=4 * D, K=D, gate=row0(L.a), alpha=inv_keep)
-        o.gemm_nt(c.dpre, st.t(f"{pre}.ff1.weight"), c.dx1, N=D, K=4 * D, resid=c.dh)
-        dh1_rows = row0(self.sp_dh1)
-        if p > 0:
-            o.layernorm_bwd(row0(L.h1), st.p(f"{pre}.ln1.gamma"), L.mean1, L.rstd1, c.dx1, dh1_rows, st.grad(f"{pre}.ln1.gamma"),
-                            st.grad(f"{pre}.ln1.beta"), D=D, M=B, row_id_stride=S, dx_masked=c.dh1m, mask_mode=1,
-                            dropout_site=site0, **dk)
-            dproj = c.dh1m
-        else:
-            o.layernorm_bwd(row0(L.h1), st.p(f"{pre}.ln1.gamma"), L.mean1, L.rstd1, c.dx1, dh1_rows, st.grad(f"{pre}.ln1.gamma"),
-                            st.grad(f"{pre}.ln1.beta"), D=D, M=B, row_id_stride=S)
-            dproj = dh1_rows
-        # d(attention output): rows b*S of a buffer that is zero elsewhere
-        o.gemm_nt(dproj, st.t(f"{pre}.att.W_proj.weight"), self.sp_datt, M=B, N=D, K=D, c_remap=(1, S, 0))
-        return self._top_encoder_layer_bwd_rest(i, L, x_in, dx_in, t, next_ln, dff, dproj)
-
-    def _top_encoder_layer_bwd_rest(self, i, L, x_in, dx_in, t, next_ln, dff, dproj):
-        """attention backward (dO is zero outside position 0), the K | Q | V dgrad and the layer's deferred weight gradients"""
-        cfg, st, B = self.cfg, self.store, self.B
-        S = self.T
+    def _top_encoder_layer_bwd(self, i, L, x_in, dx_in, next_ln=None, rider=None):
+        """_layer_bwd for the LAST encoder layer, on the B rows (position 0 of each sample) that carry gradient: LayerNorm-2 backward,
+        both FFN dgrads, LayerNorm-1 backward and the W_proj dgrad of those rows as one launch (with `rider`, a GEMM for its idle
+        workgroups) or five; then attention backward (dO is zero outside position 0), the K | Q | V dgrad and the layer's deferred
+        weight gradients."""
+        cfg, st, B, S, F = self.cfg, self.store, self.B, self.T, self.forms
         D, H = cfg.e_model, cfg.e_heads
-        pre = f"encoder.layer{i}"
-        c = self.top
-
-        def row0(buf):
-            return buf.view(B, S, -1)[:, 0, :]
-
-        o.attn_bwd(L.qkv, self.keymask_e, L.lse, self.sp_datt, t.dqkv, t.delta, B, S, H, D // H, 0, D, 2 * D, q_limit=1)
+        P, c, rows = st.layer("encoder", i), self.top, position0_rows(B, S)
+        self._tail_used["bwd"] = F.tails
+        tail = None
+        if F.tails:
+            tail = dict(sync=self.sync_words[4:7], stat_stride=S, phys_stride=S, status=st.step_status[0:1], rider=rider,
+                        queue=self.ride_queues[32:33])
+        dff, dproj = row_block_bwd(P, L, c, self.d_enc_out, rows, self._dropout(cfg.e_dropout, self._site_e(i)),
+                                   "tail" if F.tails else "launches", no_partials, tail=tail)
+        # d(attention output): rows b*S of a buffer that is zero elsewhere
+        o.attn_bwd(L.qkv, self.keymask_e, L.lse, c.datt, c.dqkv, c.delta, B, S, H, D // H, 0, D, 2 * D, q_limit=1)
         if next_ln is not None:  # as in _layer_bwd: the layer below's LayerNorm-2 backward rides on this GEMM
             kw, t_below = next_ln
-            o.gemm_nt_ln_bwd(t.dqkv, st.t(f"{pre}.att.W_kqv"), t_below.dh, N=D, K=3 * D, resid=self.sp_dh1, **kw)
+            o.gemm_nt_ln_bwd(c.dqkv, P.kqv.t, t_below.dh, N=D, K=3 * D, resid=c.dh1, **kw)
         else:
-            o.gemm_nt(t.dqkv, st.t(f"{pre}.att.W_kqv"), dx_in, N=D, K=3 * D, resid=self.sp_dh1)
-        self._wgrads += [
-            o.wgrad_problem(dff, row0(L.a), st.grad(f"{pre}.ff2.weight"), st.grad(f"{pre}.ff2.bias"), M=B, N=D, K=4 * D),
-            o.wgrad_problem(c.dpre, row0(L.x1), st.grad(f"{pre}.ff1.weight"), st.grad(f"{pre}.ff1.bias"), M=B, N=4 * D, K=D),
-            o.wgrad_problem(dproj, row0(L.att), st.grad(f"{pre}.att.W_proj.weight"), st.grad(f"{pre}.att.W_proj.bias"), M=B, N=D, K=D),
-            o.wgrad_problem(t.dqkv, x_in, st.fused(st.g, pre, "weight"), st.fused(st.g, pre, "bias"), N=3 * D, K=D),
-        ]
+            o.gemm_nt(c.dqkv, P.kqv.t, dx_in, N=D, K=3 * D, resid=c.dh1)
+        self._wgrads += layer_wgrads(P, L, c, x_in, dff, dproj, rows)
 
     def backward(self):
         self.backward_early(flush=False)
@@ -1228,40 +1240,48 @@ class StepPlan:
             return 0
         return st.offsets[f"encoder.layer{cfg.e_layers - 1}.att.W_k.weight"]
 
+    def _below(self, side, i, fuse):
+        """_layer_bwd's next_ln for layer i of a stack: the leading LayerNorm backward of layer i - 1, where the fusion pays"""
+        if not (fuse and i > 0):
+            return None
+        if side == "encoder":
+            layers, bufs, p, site0, M = self.enc, self.be_l, self.cfg.e_dropout, self._site_e(i - 1), self.Me
+        else:
+            layers, bufs, p, site0, M = self.dec, self.bd_l, self.cfg.d_dropout, self._site_d(i - 1), self.Md
+        return self._out_ln_bwd(side, i - 1, layers[i - 1], p, site0, bufs[i - 1], M), bufs[i - 1]
+
     def backward_early(self, flush):
         """Output layer, decoder, latent block and the TOP encoder layer. With `flush` the weight gradients collected so
         far get their own wgrad launch, so that the [grad_cut(), n) part of the bucket can be all-reduced while
         backward_late() runs (data parallel); without it they wait for the single launch at the end."""
-        cfg, st, B, T = self.cfg, self.store, self.B, self.T
+        cfg, st, B, T, F = self.cfg, self.store, self.B, self.T, self.forms
         De, Dd = cfg.e_model, cfg.d_model
         Se, Sd = T, T + 1
         sq_d = math.sqrt(float(Dd))
         # (the gradient bucket was cleared by forward()'s bookkeeping, which also emptied the lists of deferred gradient work)
         # ---- output layer (rows 1..T of the decoder output; row 0 of dx_a stays zero)
         ldv = self.dlogits.shape[1]
-        fuse_d, fuse_e = o.ln_bwd_fusion_pays(Dd), o.ln_bwd_fusion_pays(De)
         site_d = self._site_d(0)
         last = cfg.d_layers - 1
-        if self._out_dgrad_done:  # (it rode on the loss launch: losses())
-            self._out_dgrad_done = False
-        elif fuse_d:  # output-layer dgrad + the last decoder layer's LayerNorm-3 backward (rows 1..T; row 0 of dh stays 0)
+        if F.bce_dgrad:  # (it rode on the loss launch: losses())
+            pass
+        elif F.ln_bwd_d:  # output-layer dgrad + the last decoder layer's LayerNorm-3 backward (rows 1..T; row 0 of dh stays 0)
             o.gemm_nt_ln_bwd(self.dlogits, st.t("decoder.output_layer.weight"), self.bd_l[last].dh, M=B * T, N=Dd, K=ldv,
                              c_remap=(T, Sd, 1),
-                             **self._out_ln_bwd("decoder", last, self.dec[last], Dd, cfg.d_dropout, site_d + 3 * last, self.bd_l[last], B * T))
+                             **self._out_ln_bwd("decoder", last, self.dec[last], cfg.d_dropout, site_d + 3 * last, self.bd_l[last], B * T))
         else:
             o.gemm_nt(self.dlogits, st.t("decoder.output_layer.weight"), self.d_dec_out, M=B * T, N=Dd, K=ldv, c_remap=(T, Sd, 1))
         self._wgrads.append(o.wgrad_problem(self.dlogits, self.dec_out, st.grad("decoder.output_layer.weight"),
                                             st.grad("decoder.output_layer.bias"), M=B * T, N=cfg.out_dim, K=Dd, b_remap=(T, Sd, 1)))
-        dy, tgt, nxt = self.d_dec_out, self.bd_l[0].dx_a, self.bd_l[0].dx_b
-        self._bwd_rider = self._bwd_dx0 = None
-        for i in reversed(range(cfg.d_layers)):
+        dy, pingpong, handed = self.d_dec_out, (self.bd_l[0].dx_a, self.bd_l[0].dx_b), None
+        for n, i in enumerate(reversed(range(cfg.d_layers))):
             x_in = self.dec[i - 1].x2 if i > 0 else self.x0_d
-            below = (self._out_ln_bwd("decoder", i - 1, self.dec[i - 1], Dd, cfg.d_dropout, site_d + 3 * (i - 1), self.bd_l[i - 1], self.Md),
-                     self.bd_l[i - 1]) if (fuse_d and i > 0) else None
-            self._layer_bwd("decoder", i, self.dec[i], x_in, dy, tgt, self.keymask_d, Dd, cfg.d_heads, Sd, cfg.d_dropout,
-                            site_d + 3 * i, self.bd_l[i], dy_done=fuse_d, next_ln=below)
-            dy, tgt, nxt = tgt, nxt, tgt
+            handed = self._layer_bwd("decoder", i, self.dec[i], x_in, dy, pingpong[n % 2], self.keymask_d, Dd, cfg.d_heads, Sd,
+                                     cfg.d_dropout, site_d + 3 * i, self.bd_l[i], dy_done=F.ln_bwd_d,
+                                     next_ln=self._below("decoder", i, F.ln_bwd_d), ride=F.riders and i == 0)
+            dy = pingpong[n % 2]
         d_x0_d = dy  # gradient w.r.t. the decoder input [B, Sd, Dd]
+        rider, dx0 = handed or (None, None)
         # ---- decoder input: rows 1..T -> embedding, row 0 -> latent block
         if cfg.kind == "token":
             o.embed_bwd(self.tokens, st.grad("decoder.embedding.weight"), d_x0_d.view(B, Sd, -1), 1, sq_d)
@@ -1275,32 +1295,29 @@ class StepPlan:
         o.latent_bwd_vec(st.p("encoder.latent_proj.weight"), self.eps, st.p("decoder.latent2hid.weight"), self.classes, self.mu,
                          self.sigma, d_x0_d.view(B, Sd, -1), sq_d, self.kl_weight, self.gscale_enc,
                          st.grad("decoder.class2hid.weight"), d_enc.view(B, Se, -1), self.lat_scratch,
-                         enc_scale=self.gscale_enc / self.gscale, proj=self._bwd_dx0)
+                         enc_scale=self.gscale_enc / self.gscale, proj=dx0)
         self._outers += o.latent_outer_jobs(self.lat_scratch, self.enc_out.view(B, Se, -1), self.z,
                                             st.grad("encoder.latent_proj.weight"), st.grad("encoder.latent_proj.bias"),
                                             st.grad("decoder.latent2hid.weight"), st.grad("decoder.latent2hid.bias"))
         top = cfg.e_layers - 1
         x_in = self.enc[top - 1].x2 if top > 0 else self.x0_e
-        below = (self._out_ln_bwd("encoder", top - 1, self.enc[top - 1], De, cfg.e_dropout, self._site_e(top - 1), self.be_l[top - 1], self.Me),
-                 self.be_l[top - 1]) if (fuse_e and top > 0) else None
-        self._top_encoder_layer_bwd(top, self.enc[top], x_in, self.be_l[0].dx_a, self.be_l[top], next_ln=below)
+        self._top_encoder_layer_bwd(top, self.enc[top], x_in, self.be_l[0].dx_a, next_ln=self._below("encoder", top, F.ln_bwd_e),
+                                    rider=rider)
         if flush and cfg.e_layers >= 2:
             self._flush_grads()
 
     def backward_late(self):
         """The encoder layers below the top one, the encoder input, and the (remaining) weight gradients."""
-        cfg, st, B, T = self.cfg, self.store, self.B, self.T
+        cfg, st, B, T, F = self.cfg, self.store, self.B, self.T, self.forms
         De, Se = cfg.e_model, T
         sq_e = math.sqrt(float(De))
-        dy, tgt, nxt = self.be_l[0].dx_a, self.be_l[0].dx_b, self.be_l[0].dx_a  # the top layer wrote dx_a
-        fuse_e = o.ln_bwd_fusion_pays(De)  # then every layer's leading LayerNorm backward already ran in the GEMM above it
-        for i in reversed(range(cfg.e_layers - 1)):
+        dy, pingpong = self.be_l[0].dx_a, (self.be_l[0].dx_b, self.be_l[0].dx_a)  # the top layer wrote dx_a
+        # (F.ln_bwd_e: every layer's leading LayerNorm backward already ran in the GEMM above it)
+        for n, i in enumerate(reversed(range(cfg.e_layers - 1))):
             x_in = self.enc[i - 1].x2 if i > 0 else self.x0_e
-            below = (self._out_ln_bwd("encoder", i - 1, self.enc[i - 1], De, cfg.e_dropout, self._site_e(i - 1), self.be_l[i - 1], self.Me),
-                     self.be_l[i - 1]) if (fuse_e and i > 0) else None
-            self._layer_bwd("encoder", i, self.enc[i], x_in, dy, tgt, self.keymask_e, De, cfg.e_heads, Se, cfg.e_dropout,
-                            self._site_e(i), self.be_l[i], dy_done=fuse_e, next_ln=below)
-            dy, tgt, nxt = tgt, nxt, tgt
+            self._layer_bwd("encoder", i, self.enc[i], x_in, dy, pingpong[n % 2], self.keymask_e, De, cfg.e_heads, Se, cfg.e_dropout,
+                            self._site_e(i), self.be_l[i], dy_done=F.ln_bwd_e, next_ln=self._below("encoder", i, F.ln_bwd_e))
+            dy = pingpong[n % 2]
         d_x0_e = dy
         if cfg.kind == "token":
             o.embed_bwd(self.tokens, st.grad("encoder.embedding.weight"), d_x0_e.view(B, Se, -1), 0, sq_e,
@@ -1308,8 +1325,8 @@ class StepPlan:
         else:
             # with cls_fold, rows in_dim.. of this problem are the class table's gradient (model.py:89: one class row per frame)
             self._wgrads.append(o.wgrad_problem(self.roll_cls, d_x0_e, st.grad("encoder.embedding.weight"), M=B * T,
-                                                N=cfg.in_dim + (cfg.num_classes if self.cls_fold else 0), K=De, scale=sq_e))
-            if not self.cls_fold:
+                                                N=cfg.in_dim + (cfg.num_classes if F.cls_fold else 0), K=De, scale=sq_e))
+            if not F.cls_fold:
                 o.group_colsum(d_x0_e.view(B, Se, -1), T, De, 0, self.classes, st.grad("encoder.class2hid.weight"), sq_e)
         # every (remaining) Dense weight / bias gradient in ONE launch — all 15 problems of the step at configs[1] on a
         # single GPU: one resident round of workgroups with the smallest possible M-split instead of six launches
@@ -1317,11 +1334,12 @@ class StepPlan:
 
     def optimizer(self):
         st = self.store
+        deferred = self.forms.shadows != "own"
         clip = self.clip if self.clip is not None else -1.0
         # end-of-step bookkeeping (total loss, running metric sums) on the first Adam launch: losses(combine=False)
         guard = self._guard()
         mt = dict(recon=self.recon, kl=self.kl, kl_weight=self.kl_weight, total=self.total, metric=self.metric_acc, **guard)
-        emb = (lambda base: dict(base=base, specs=st.emb_specs, wt16=st.wt16)) if st.shadows_deferred else (lambda base: None)
+        emb = (lambda base: dict(base=base, specs=st.emb_specs, wt16=st.wt16)) if deferred else (lambda base: None)
         if self.gscale == self.gscale_enc:
             o.adam_flat(st.w, st.g, st.m, st.v, st.w16, st.step_state, lr=self.lr,
                         rescale=1.0 / (self.global_batch * self.gscale), clip=clip, advance_step=False, metrics=mt, emb=emb(0), **self.opt)
@@ -1334,7 +1352,7 @@ class StepPlan:
                 o.adam_flat(st.w[a:b], st.g[a:b], st.m[a:b], st.v[a:b], st.w16[a:b], st.step_state, lr=self.lr,
                             rescale=1.0 / (self.global_batch * gs), clip=clip, advance_step=adv,
                             metrics=mt if a == 0 else (guard or None), emb=emb(a), **self.opt)
-        if not st.shadows_deferred:  # (deferred: the next step's first launch rebuilds them, forward())
+        if not deferred:  # (deferred: the next step's first launch rebuilds them, forward())
             o.transpose_shadows(st.w, st.wt16, st.t_desc, st.t_prefix, len(st.t_specs), st.t_tiles)
 
     # ------------------------------------------------------------------------------ step

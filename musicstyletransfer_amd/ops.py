@@ -106,6 +106,12 @@ def can_row_tail(B, D):
     return D in (128, 256) and 0 < B <= 64
 
 
+def row_tail_barriers(D):
+    """(forward, backward) value of the tails' barrier counter (sync[0]) after a complete launch: G = D / 16 workgroups pass three
+    barriers forward, two backward"""
+    return 3 * (D // 16), 2 * (D // 16)
+
+
 def row_tail_fwd(att, resid, Wp, bp, g1, be1, W1, b1, W2, b2, g2, be2, h1, x1, a, h2, x2, mean1, rstd1, mean2, rstd2, sync, stat_stride,
                  phys_stride, eps=1e-5, dropout_p=0.0, dropout_seed_ptr=None, site0=0, status=None, rider=None, queue=None, shadows=None):
     """att / resid / h1 / x1 / a / h2 / x2: [B, width] row views (stride(0) = the row stride in elements) of the layer's

@@ -60,7 +60,7 @@ def test_config1_full_size_step_with_riders(gpu, causal):
     activation rounding shows; the attention kernels themselves are checked in both types in test_attention_causal_gpu.py, and
     bench.py's bf16 configs[1] step runs causal in test_thirty_steps_train_and_identical_runs_agree_bit_for_bit."""
     plan = _step(gpu, causal, "pianoroll", CFG1, B=64, T=256, seed=1234, steps=1, lr=3e-4, dtype=torch.float16)
-    assert plan._ride_fwd  # decoder layer 0's projection came from the forward tail's riders
+    assert plan.forms.riders  # decoder layer 0's projection came from the forward tail's riders
 
 
 def test_config4_shape_fp16_step(gpu, causal):

@@ -712,7 +712,7 @@ def test_shadow_refresh_on_the_forward_tail_matches_the_first_launch(gpu):
         for _ in range(3):
             plan.step_kernels(True)
         torch.cuda.synchronize()
-        assert (plan._tail_shadows is not None) == mode
+        assert (plan.forms.shadows == "tail") == mode
         assert int(store.step_status.cpu()[0]) == 0
         emb = ["encoder.embedding.weight", "decoder.embedding.weight"]
         late = [n for n in store.t_specs if n not in emb]
@@ -743,7 +743,7 @@ def test_identical_runs_agree_on_full_length_batches(gpu):
         for _ in range(3):
             plan.step_kernels(True)
         torch.cuda.synchronize()
-        assert plan._ride_fwd and plan._tail_shadows is not None and int(store.step_status.cpu()[0]) == 0
+        assert plan.forms.riders and plan.forms.shadows == "tail" and int(store.step_status.cpu()[0]) == 0
         ws.append(store.w.cpu().numpy().copy())
     for w in ws[1:]:
         d = np.abs(w - ws[0])

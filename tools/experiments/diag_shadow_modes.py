@@ -25,7 +25,7 @@ for rep in range(int(sys.argv[2]) if len(sys.argv) > 2 else 3):
             torch.cuda.synchronize()
             ws.append(store.w.cpu().numpy().copy())
         res[(name, rep)] = ws
-        print(name, rep, "status", store.step_status.cpu().tolist()[:4], "tail shadows", plan._tail_shadows is not None, flush=True)
+        print(name, rep, "status", store.step_status.cpu().tolist()[:4], "shadow refresh", plan.forms.shadows, flush=True)
 ref = res[(order[0], 0)]
 for key, ws in res.items():
     print(key, " ".join(f"step{i + 1}: {(np.abs(w - r) > 2e-5).mean():.4f}" for i, (w, r) in enumerate(zip(ws, ref))))

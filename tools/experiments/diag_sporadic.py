@@ -23,7 +23,7 @@ for rep in range(reps):
         plan.step_kernels(True)
     torch.cuda.synchronize()
     ws.append(store.w.cpu().numpy().copy())
-    ride = (plan.ride, plan._ride_fwd, plan._ride_bwd, plan._tail_shadows is not None)
+    ride = (plan.ride, plan.forms.riders, plan.forms.shadows)
     del plan, store
 d = np.array([[(np.abs(a - b) > 2e-5).mean() for b in ws] for a in ws])
 med = np.median(d, axis=1)
