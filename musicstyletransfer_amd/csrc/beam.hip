@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(int64_t N, int64_t V, 
       if (acc >= target) { tok = w; break; }
     }
   }
-  // exactly one lane owns the draw (rounding at a chunk boundary could leave none: the last token with mass then takes it)
+  // exactly one lane owns the draw (rounding at a chunk boundary could leave none: token V - 1 then takes it, whatever its mass)
   const unsigned long long owners = __ballot(mine && tok >= 0);
   int chosen = tok;
   if (owners == 0ull) chosen = (int)V - 1;
