@@ -43,8 +43,6 @@ enum mst_act { MST_ACT_NONE = 0, MST_ACT_RELU = 1 };
 
 int mst_version(void);
 const char* mst_last_error(void);
-/* number of HIP devices visible, or negative status (used by the loader to fail loudly) */
-int mst_device_count(void);
 
 /* ---- stream-capture helpers (hipGraph instead of a tracing compiler) ---- */
 int mst_graph_begin(mst_stream_t stream);
@@ -254,21 +252,6 @@ typedef struct mst_wgrad_args {
                  * the way into LDS; lda % 8 == 0 */
 } mst_wgrad_args;
 
-int mst_gemm_wgrad(const mst_wgrad_args* args, mst_stream_t stream);
-/* up to 16 problems (host array) in ONE launch — the engine hands over every weight gradient of the backward pass at
- * once: one resident round of workgroups, the M-split (and with it the fp32-atomic traffic) as small as it gets */
-int mst_gemm_wgrad_batch(const mst_wgrad_args* list, int n, mst_stream_t stream);
-/* The same with a caller-owned fp32 scratch buffer (16-byte aligned). When the batch is large enough for 256x256 tiles
- * and the buffer holds tiles * split * 256 KiB, the M-slabs' partial tiles are written there with plain stores and
- * summed in slab order by a second launch: no fp32 atomics on dW (deterministic gradients, and 62 MB of atomic traffic
- * less at configs[1]). Otherwise identical to mst_gemm_wgrad_batch. 64 MiB covers configs[1]. */
-int mst_gemm_wgrad_batch_ws(const mst_wgrad_args* list, int n, float* scratch, int64_t scratch_bytes, mst_stream_t stream);
-/* The same plus up to 20 column-sum jobs (mst_partial_sum below: the LayerNorm-backward launches' per-workgroup dgamma /
- * dbeta rows): they are executed by extra workgroups of the reduction pass when there is one, else by one
- * mst_partial_sums launch after the weight gradients — either way the flush of a backward pass is one call. */
-int mst_gemm_wgrad_batch_sums(const mst_wgrad_args* list, int n, float* scratch, int64_t scratch_bytes,
-                              const mst_partial_sum* sums, int n_sums, mst_stream_t stream);
-
 /* Deferred batch outer products: out[j, i] += sum_b L[b, j] * R[b, i] (out fp32 [J, I] contiguous, accumulated into) and, with
  * obias, obias[j] += sum_b L[b, j]. L fp32 [B, J] contiguous; R [B, >= I] of r_dtype (MST_F32 / MST_BF16 / MST_F16) with row stride
  * r_stride elements. The parameter gradients of a layer that sees one row per sample — the latent block's latent_proj and
@@ -280,8 +263,17 @@ typedef struct mst_outer_job {
   float* out; float* obias;
 } mst_outer_job;
 int mst_outer_jobs(const mst_outer_job* jobs, int n, mst_stream_t stream);
-/* mst_gemm_wgrad_batch_sums plus up to 2 outer-product jobs: extra workgroups of the reduction pass when there is one, else one
- * mst_outer_jobs launch after the weight gradients. */
+/* The weight gradients of a backward pass in ONE call: up to 16 problems (host array) in one launch — one resident round of
+ * workgroups, the M-split (and with it the fp32-atomic traffic) as small as it gets.
+ *   scratch (optional, NULL / 0: none): a caller-owned fp32 buffer (16-byte aligned). When the batch is large enough for 256x256
+ *     tiles and the buffer holds tiles * split * 256 KiB, the M-slabs' partial tiles are written there with plain stores and summed
+ *     in slab order by a second launch: no fp32 atomics on dW (deterministic gradients, and 62 MB of atomic traffic less at
+ *     configs[1]). 64 MiB covers configs[1].
+ *   sums (optional, NULL / 0: none): up to 20 column-sum jobs (mst_partial_sum above: the LayerNorm-backward launches'
+ *     per-workgroup dgamma / dbeta rows), executed by extra workgroups of the reduction pass when there is one, else by one
+ *     mst_partial_sums launch after the weight gradients.
+ *   outers (optional, NULL / 0: none): up to 2 outer-product jobs: extra workgroups of the reduction pass when there is one, else
+ *     one mst_outer_jobs launch after the weight gradients. */
 int mst_gemm_wgrad_batch_flush(const mst_wgrad_args* list, int n, float* scratch, int64_t scratch_bytes,
                                const mst_partial_sum* sums, int n_sums, const mst_outer_job* outers, int n_outers,
                                mst_stream_t stream);
@@ -752,12 +744,6 @@ int mst_rng_advance(uint64_t* state, mst_stream_t stream);
  * skip that part. rng_state is the uint64[4] state of mst_rng_advance.
  * eps_index0 (even): eps_out[i] is draw number eps_index0 + i of the step's stream, so a data-parallel rank that
  * passes its first global sample index times Z draws exactly what a single process draws for those samples. */
-int mst_step_begin(uint64_t* rng_state, int32_t* adam_state, double lr, double beta1, double beta2,
-                   float* eps_out, int64_t n_eps, uint32_t eps_site, int64_t eps_index0,
-                   const int32_t* lens, int64_t B, uint8_t* mask_e, int64_t Se, int32_t add_e,
-                   uint8_t* mask_d, int64_t Sd, int32_t add_d,
-                   void* zero_a, int64_t zero_a_bytes, void* zero_b, int64_t zero_b_bytes, mst_stream_t stream);
-/* the same, arguments in a struct */
 typedef struct mst_step_begin_args {
   uint64_t* rng_state; int32_t* adam_state; double lr, beta1, beta2;
   float* eps_out; int64_t n_eps; uint32_t eps_site; int64_t eps_index0;
@@ -769,10 +755,10 @@ typedef struct mst_step_begin_args {
    * piano-roll embedding tables of mst_gemm_nt_pair_begin) must not be listed: mst_adam_flat_emb keeps those current. */
   int32_t sh_dtype; const float* sh_w; void* sh_wt16; const int64_t* sh_desc; const int64_t* sh_prefix; int64_t sh_n_mat, sh_tiles;
 } mst_step_begin_args;
-int mst_step_begin_v(const mst_step_begin_args* args, mst_stream_t stream);
+int mst_step_begin(const mst_step_begin_args* args, mst_stream_t stream);
 /* mst_step_begin and mst_gemm_nt_pair in ONE launch: nothing in the piano-roll ends' embedding GEMMs (the first arithmetic of the
  * step) reads what the bookkeeping writes, so its workgroups ride in front of the tiles of that launch. Where mst_gemm_nt_pair
- * would fall back to two launches this is exactly mst_step_begin_v(begin) followed by mst_gemm_nt_pair(args0, args1). */
+ * would fall back to two launches this is exactly mst_step_begin(begin) followed by mst_gemm_nt_pair(args0, args1). */
 int mst_gemm_nt_pair_begin(const mst_gemm_args* args0, const mst_gemm_args* args1, const mst_step_begin_args* begin,
                            mst_stream_t stream);
 /* eps ~ N(0,1) (replaces mx.nd.random_normal, model.py:292): Box-Muller over the counter hash;

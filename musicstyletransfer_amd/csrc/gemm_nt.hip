@@ -1368,7 +1368,7 @@ extern "C" int mst_gemm_nt_pair_begin(const mst_gemm_args* args0, const mst_gemm
            (!a.grpadd || a.grp_index) && gemm_fast_form<64, 64>(a) && a.K % 64 == 0 && cdiv(a.M, 64) * cdiv(a.N, 64) < (1 << 20);
   };
   if (a0.dtype != a1.dtype || !plain(a0) || !plain(a1) || (begin && begin->sh_w && begin->sh_dtype != a0.dtype)) {
-    int rc = begin ? mst_step_begin_v(begin, stream) : MST_OK;  // (runs the shadow refresh as a launch of its own)
+    int rc = begin ? mst_step_begin(begin, stream) : MST_OK;  // (runs the shadow refresh as a launch of its own)
     if (rc == MST_OK) rc = mst_gemm_nt(args0, stream);
     return rc != MST_OK ? rc : mst_gemm_nt(args1, stream);
   }

@@ -609,39 +609,29 @@ static int check_wgrad(const mst_wgrad_args& a) {
 
 using namespace mst;
 
-extern "C" int mst_gemm_wgrad_batch_ws(const mst_wgrad_args* list, int n, float* scratch, int64_t scratch_bytes,
-                                       mst_stream_t stream) {
-  return mst_gemm_wgrad_batch_sums(list, n, scratch, scratch_bytes, nullptr, 0, stream);
-}
-
-extern "C" int mst_gemm_wgrad_batch_sums(const mst_wgrad_args* list, int n, float* scratch, int64_t scratch_bytes,
-                                         const mst_partial_sum* sums, int n_sums, mst_stream_t stream) {
-  return mst_gemm_wgrad_batch_flush(list, n, scratch, scratch_bytes, sums, n_sums, nullptr, 0, stream);
-}
-
 extern "C" int mst_gemm_wgrad_batch_flush(const mst_wgrad_args* list, int n, float* scratch, int64_t scratch_bytes,
                                           const mst_partial_sum* sums, int n_sums, const mst_outer_job* outers, int n_outers,
                                           mst_stream_t stream) {
-  MST_CHECK_ARG(list != nullptr && n >= 1 && n <= WG_MAXP, "mst_gemm_wgrad_batch: need 1..%d problems", WG_MAXP);
+  MST_CHECK_ARG(list != nullptr && n >= 1 && n <= WG_MAXP, "mst_gemm_wgrad_batch_flush: need 1..%d problems", WG_MAXP);
   OuterBatch ob;
   {
     int rc = pack_outer_jobs(outers, n_outers, ob);
     if (rc) return rc;
   }
-  MST_CHECK_ARG(n_sums >= 0 && (n_sums == 0 || sums != nullptr), "mst_gemm_wgrad_batch_sums: bad column-sum job list");
+  MST_CHECK_ARG(n_sums >= 0 && (n_sums == 0 || sums != nullptr), "mst_gemm_wgrad_batch_flush: bad column-sum job list");
   PartialSumBatch ps;
   if (n_sums > 0) {
     int rc = pack_partial_sums(sums, n_sums, ps);
     if (rc) return rc;
   }
-  MST_CHECK_ARG(!scratch || ((uintptr_t)scratch % 16 == 0 && scratch_bytes > 0), "mst_gemm_wgrad_batch_ws: bad scratch buffer");
+  MST_CHECK_ARG(!scratch || ((uintptr_t)scratch % 16 == 0 && scratch_bytes > 0), "mst_gemm_wgrad_batch_flush: bad scratch buffer");
   WgradBatch b;
   b.n = n;
   int64_t out_elems = 0, maxM = 0;
   for (int i = 0; i < n; ++i) {
     int rc = check_wgrad(list[i]);
     if (rc) return rc;
-    MST_CHECK_ARG(list[i].dtype == list[0].dtype, "mst_gemm_wgrad_batch: mixed dtypes");
+    MST_CHECK_ARG(list[i].dtype == list[0].dtype, "mst_gemm_wgrad_batch_flush: mixed dtypes");
     b.p[i] = list[i];
     out_elems += list[i].N * list[i].K;
     if (list[i].M > maxM) maxM = list[i].M;
@@ -717,15 +707,6 @@ extern "C" int mst_gemm_wgrad_batch_flush(const mst_wgrad_args* list, int n, flo
   if (rc == MST_OK && n_sums > 0 && !ps_done) rc = mst_partial_sums(sums, n_sums, stream);  // no reduction pass: own launch
   if (rc == MST_OK && n_outers > 0 && !ps_done) rc = mst_outer_jobs(outers, n_outers, stream);
   return rc;
-}
-
-extern "C" int mst_gemm_wgrad_batch(const mst_wgrad_args* list, int n, mst_stream_t stream) {
-  return mst_gemm_wgrad_batch_ws(list, n, nullptr, 0, stream);
-}
-
-extern "C" int mst_gemm_wgrad(const mst_wgrad_args* args, mst_stream_t stream) {
-  MST_CHECK_ARG(args != nullptr, "mst_gemm_wgrad: null args");
-  return mst_gemm_wgrad_batch(args, 1, stream);
 }
 
 #ifdef MST_WGRAD_STAMPS

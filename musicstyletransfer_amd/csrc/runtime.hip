@@ -16,18 +16,8 @@ void set_error(const char* fmt, ...) {
 
 using namespace mst;
 
-extern "C" int mst_version(void) { return 100; }
+extern "C" int mst_version(void) { return 101; }
 extern "C" const char* mst_last_error(void) { return g_err; }
-
-extern "C" int mst_device_count(void) {
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess) {
-    set_error("hipGetDeviceCount: %s", hipGetErrorString(e));
-    return MST_ERR_LAUNCH;
-  }
-  return n;
-}
 
 #define HIP_TRY(expr)                                             \
   do {                                                            \

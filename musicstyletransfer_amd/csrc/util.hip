@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void partial_sums_kernel(PartialSumBatch b) {
 
 using namespace mst;
 
-extern "C" int mst_step_begin_v(const mst_step_begin_args* args, mst_stream_t stream) {
+extern "C" int mst_step_begin(const mst_step_begin_args* args, mst_stream_t stream) {
   MST_CHECK_ARG(args != nullptr, "mst_step_begin: null args");
   StepBegin q;
   int64_t grid = 0;
@@ -62,15 +62,6 @@ extern "C" int mst_step_begin_v(const mst_step_begin_args* args, mst_stream_t st
   if (args->sh_w)
     return mst_transpose_shadows(args->sh_dtype, args->sh_w, args->sh_wt16, args->sh_desc, args->sh_prefix, args->sh_n_mat, args->sh_tiles, stream);
   return MST_OK;
-}
-
-extern "C" int mst_step_begin(uint64_t* rng_state, int32_t* adam_state, double lr, double beta1, double beta2, float* eps_out,
-                              int64_t n_eps, uint32_t eps_site, int64_t eps_index0, const int32_t* lens, int64_t B, uint8_t* mask_e, int64_t Se,
-                              int32_t add_e, uint8_t* mask_d, int64_t Sd, int32_t add_d, void* zero_a, int64_t zero_a_bytes,
-                              void* zero_b, int64_t zero_b_bytes, mst_stream_t stream) {
-  const mst_step_begin_args a = {rng_state, adam_state, lr, beta1, beta2, eps_out, n_eps, eps_site, eps_index0, lens, B, mask_e, Se,
-                                 add_e, mask_d, Sd, add_d, zero_a, zero_a_bytes, zero_b, zero_b_bytes, 0, nullptr, nullptr, nullptr, nullptr, 0, 0};
-  return mst_step_begin_v(&a, stream);
 }
 
 extern "C" int mst_partial_sums(const mst_partial_sum* jobs, int n, mst_stream_t stream) {

@@ -324,7 +324,7 @@ class ParamStore:
     def wgrad_scratch(self, n_floats=16 * 1024 * 1024 + 256 * 256):
         """fp32 work buffer of the wgrad launch's two-pass reduction: one full resident round of 256 x 256 slab tiles
         (256 work items x 256 KiB = 64 MiB) plus each item's 256 bias column sums (256 KiB) is all
-        mst_gemm_wgrad_batch_sums ever asks for. Buffers are never freed:
+        mst_gemm_wgrad_batch_flush ever asks for. Buffers are never freed:
         captured graphs keep the pointer they were recorded with."""
         for t in self._wgrad_scratch:
             if t.numel() >= n_floats:

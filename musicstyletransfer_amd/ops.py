@@ -418,24 +418,20 @@ def outer_jobs(jobs):
 
 
 def gemm_wgrad_batch(problems, scratch=None, sums=None, outers=None):
-    """dW_i[N,K] += A_i^T @ B_i for a list of problems, 16 per launch. scratch: optional fp32 work buffer for the
-    atomic-free two-pass reduction of big batches (mst_gemm_wgrad_batch_ws). sums: column-sum jobs (partial_sum_job),
-    outers: batch outer products (outer_job), to execute along with the weight gradients (mst_gemm_wgrad_batch_flush)."""
+    """dW_i[N,K] += A_i^T @ B_i for a list of problems, 16 per launch (mst_gemm_wgrad_batch_flush). scratch: optional fp32 work
+    buffer for the atomic-free two-pass reduction of big batches. sums: column-sum jobs (partial_sum_job), outers: batch outer
+    products (outer_job), to execute along with the weight gradients."""
     sums, outers = list(sums or []), list(outers or [])
     for i in range(0, len(problems), WGRAD_MAX_PROBLEMS):
         chunk = problems[i:i + WGRAD_MAX_PROBLEMS]
-        arr = (WgradArgs * len(chunk))(*chunk)
-        if (sums or outers) and i + WGRAD_MAX_PROBLEMS >= len(problems):  # the last launch takes (the first 20 of) the sums along
+        take, tko = [], []
+        if i + WGRAD_MAX_PROBLEMS >= len(problems):  # the last launch takes (the first 20 of) the sums along
             take, sums = sums[:PARTIAL_SUM_MAX_JOBS], sums[PARTIAL_SUM_MAX_JOBS:]
             tko, outers = outers[:OUTER_MAX_JOBS], outers[OUTER_MAX_JOBS:]
-            call("mst_gemm_wgrad_batch_flush", arr, len(chunk), ptr(scratch),
-                 (scratch.numel() * scratch.element_size() if scratch is not None else 0),
-                 (PartialSum * len(take))(*take) if take else None, len(take),
-                 (OuterJob * len(tko))(*tko) if tko else None, len(tko), stream())
-        elif scratch is None:
-            call("mst_gemm_wgrad_batch", arr, len(chunk), stream())
-        else:
-            call("mst_gemm_wgrad_batch_ws", arr, len(chunk), ptr(scratch), scratch.numel() * scratch.element_size(), stream())
+        call("mst_gemm_wgrad_batch_flush", (WgradArgs * len(chunk))(*chunk), len(chunk), ptr(scratch),
+             (scratch.numel() * scratch.element_size() if scratch is not None else 0),
+             (PartialSum * len(take))(*take) if take else None, len(take),
+             (OuterJob * len(tko))(*tko) if tko else None, len(tko), stream())
     if sums:
         partial_sums(sums)
     if outers:
@@ -772,7 +768,7 @@ def _step_begin_args(rng_state=None, adam_state=None, lr=0.0, beta1=0.9, beta2=0
 
 def step_begin(**kw):
     """mst_step_begin (keyword arguments: _step_begin_args)"""
-    call("mst_step_begin_v", C.byref(_step_begin_args(**kw)), stream())
+    call("mst_step_begin", C.byref(_step_begin_args(**kw)), stream())
 
 
 def selftest():
