@@ -25,13 +25,9 @@
 
 namespace mst {
 
-// rows staged in LDS per step: the whole key (or query) range of a 256-long sequence in ONE stage, so a workgroup
-// pays one exposed global-load latency and two barriers instead of four of each (the kernels are latency-bound:
-// 60 % of wave cycles were waits with 64-row stages)
-#ifndef MST_ATT_STAGE
-#define MST_ATT_STAGE 64
-#endif
-template <int DH> struct Stage { static constexpr int ROWS = MST_ATT_STAGE; };
+// rows staged in LDS per step by the streaming kernels (128 and 256 change nothing forward and cost 20 % backward, in
+// registers: docs/kernel_notes.md)
+constexpr int ATT_STAGE = 64;
 // LDS row stride of the staged tiles: +8 elements (16 bytes). With rows of exactly DH*2 = 32/64/128 bytes the
 // 16-byte row-fragment reads of 16 different rows fall on 4 bank groups (4-way conflict, measured 57 % of LDS cycles
 // in attn_bwd_kv); 80-byte rows put them on 16 distinct ones and leave the transposed reads at most 2-way.
@@ -91,7 +87,7 @@ __device__ __forceinline__ i16x4 att_tr_read(const void* p) {
 // round trips per workgroup).
 template <typename T, int DH> struct StageRegs {
   static constexpr int CPR = DH / 8;
-  static constexpr int N = (Stage<DH>::ROWS * CPR + 255) / 256;
+  static constexpr int N = (ATT_STAGE * CPR + 255) / 256;
   u32x4 v[N];
 };
 template <typename T, int DH>
@@ -101,7 +97,7 @@ __device__ __forceinline__ void stage_load(StageRegs<T, DH>& r, const T* __restr
   for (int i = 0; i < StageRegs<T, DH>::N; ++i) {
     const int c = tid + i * 256, row = c / CPR, ch = c % CPR;
     u32x4 v = {0u, 0u, 0u, 0u};
-    if (c < Stage<DH>::ROWS * CPR && row0 + row < S) v = *reinterpret_cast<const u32x4*>(g + (row0 + row) * ld + ch * 8);
+    if (c < ATT_STAGE * CPR && row0 + row < S) v = *reinterpret_cast<const u32x4*>(g + (row0 + row) * ld + ch * 8);
     r.v[i] = v;
   }
 }
@@ -111,7 +107,7 @@ __device__ __forceinline__ void stage_store(T* lds, const StageRegs<T, DH>& r, i
 #pragma unroll
   for (int i = 0; i < StageRegs<T, DH>::N; ++i) {
     const int c = tid + i * 256, row = c / CPR, ch = c % CPR;
-    if (c < Stage<DH>::ROWS * CPR) *reinterpret_cast<u32x4*>(lds + row * LdsLd<DH>::V + ch * 8) = r.v[i];
+    if (c < ATT_STAGE * CPR) *reinterpret_cast<u32x4*>(lds + row * LdsLd<DH>::V + ch * 8) = r.v[i];
   }
 }
 
@@ -344,7 +340,6 @@ __device__ __forceinline__ void stats_sweep(const T* sQ, int n_tiles, int64_t q0
 // ------------------------------------------------------------------------------------ fwd_stats
 template <typename T, int DH>
 __global__ __launch_bounds__(256) void attn_fwd_stats_kernel(AttnArgs a) {
-  constexpr int ATT_STAGE = Stage<DH>::ROWS;
   constexpr int KS = DH / 16;
   __shared__ __attribute__((aligned(16))) T sQ[ATT_STAGE * LdsLd<DH>::V];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -560,7 +555,6 @@ __device__ __forceinline__ void bwd_kv_tile(const T* sQ, const T* sdO, int qt, f
 // ------------------------------------------------------------------------------------ fwd_out
 template <typename T, int DH>
 __global__ __launch_bounds__(256) void attn_fwd_out_kernel(AttnArgs a) {
-  constexpr int ATT_STAGE = Stage<DH>::ROWS;
   constexpr int KS = DH / 16, DB = (DH + 31) / 32;
   __shared__ __attribute__((aligned(16))) T sK[ATT_STAGE * LdsLd<DH>::V];
   __shared__ __attribute__((aligned(16))) T sV[ATT_STAGE * LdsLd<DH>::V];
@@ -623,7 +617,6 @@ __global__ __launch_bounds__(256) void attn_fwd_out_kernel(AttnArgs a) {
 // ------------------------------------------------------------------------------------ bwd_kv
 template <typename T, int DH, bool SPARSE = false>
 __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(AttnArgs a) {
-  constexpr int ATT_STAGE = Stage<DH>::ROWS;
   constexpr int KS = DH / 16, DB = (DH + 31) / 32;
   __shared__ __attribute__((aligned(16))) T sQ[ATT_STAGE * LdsLd<DH>::V];
   __shared__ __attribute__((aligned(16))) T sdO[ATT_STAGE * LdsLd<DH>::V];
@@ -715,7 +708,6 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(AttnArgs a) {
 // ------------------------------------------------------------------------------------ bwd_q
 template <typename T, int DH>
 __global__ __launch_bounds__(256) void attn_bwd_q_kernel(AttnArgs a) {
-  constexpr int ATT_STAGE = Stage<DH>::ROWS;
   constexpr int KS = DH / 16, DB = (DH + 31) / 32;
   __shared__ __attribute__((aligned(16))) T sK[ATT_STAGE * LdsLd<DH>::V];
   __shared__ __attribute__((aligned(16))) T sV[ATT_STAGE * LdsLd<DH>::V];
@@ -867,12 +859,7 @@ constexpr int LONE_RED = 16 * 32;  // floats of cross-wave reduction scratch beh
 __host__ __device__ inline bool lone_row_shape(int64_t S, int dh) { return dh <= 16 && S > 32 && (S & 31) == 1; }  // (head size 32: the three fp32 rows spill the dense kernel)
 
 // waves per SIMD the head-size-16 resident kernels are compiled for (5 = 96 VGPRs, two 9-wave workgroups per CU, measured no faster forward and spills backward: the kernels are VALU-bound, not occupancy-bound)
-#ifndef MST_ATT16_WAVES_FWD
-#define MST_ATT16_WAVES_FWD 4
-#endif
-#ifndef MST_ATT16_WAVES_BWD
-#define MST_ATT16_WAVES_BWD 4
-#endif
+constexpr int ATT16_WAVES = 4;
 // Waves per workgroup the resident kernels are compiled for. Head size 64 carries twice the fragments and accumulators per
 // wave: under 1024-thread bounds (128 registers per lane) its kernels spilled 46-162 registers; eight waves (256 registers,
 // two per SIMD) hold everything, and three 64-wide tiles of a sequence leave room for one workgroup per CU anyway.
@@ -882,17 +869,10 @@ template <int DH> constexpr int RES_MAX_WAVES = DH == 64 ? 8 : 16;
 template <int DH, bool HEAVY> constexpr int FWD_MAX_WAVES = HEAVY ? RES_MAX_WAVES<DH> : 16;
 
 // (batch*head) of a 1-D grid; batch elements are dealt to the XCDs so that the heads of one element share an L2
-#ifndef MST_XCD_ROWS
-#define MST_XCD_ROWS 1
-#endif
 __device__ __forceinline__ int64_t res_wg_bh(int64_t B, int64_t H) {
-  const int64_t lin = blockIdx.x;
   // (batch, head) pairs in XCD-contiguous eighths: the samples whose K | Q | V rows the projection GEMM's tiles left in
   // this XCD's L2 (common.hpp xcd_chunk; the heads of a sample stay together)
-  if (MST_XCD_ROWS) return xcd_chunk(lin, B * H);
-  if (B % 8 != 0) return lin;
-  const int64_t xcd = lin % 8, j = lin / 8;
-  return (xcd + 8 * (j / H)) * H + j % H;
+  return xcd_chunk(blockIdx.x, B * H);
 }
 
 // ---- the K | Q | V projection of ONE (batch, head) inside the attention launch (head size 32). The Dense layers' GEMM
@@ -1043,7 +1023,7 @@ __device__ __forceinline__ void qkv_prologue(const AttnArgs& a, T* sQ, T* sK, T*
 // the output phase stages K and V in C chunks of SP / C keys over the Q tile and every wave carries the accumulators of its (at most
 // two) owned query blocks across the chunks. A separate instantiation: the two accumulator sets are registers the other forms do not pay.
 template <typename T, int DH, bool QKV = false, bool CHUNKED = false>
-__global__ __launch_bounds__((FWD_MAX_WAVES<DH, QKV || CHUNKED> * 64)) __attribute__((amdgpu_waves_per_eu((DH == 16 ? MST_ATT16_WAVES_FWD : (FWD_MAX_WAVES<DH, QKV || CHUNKED> == 8 ? 2 : 4))))) void attn_fwd_res_kernel(AttnArgs a) {
+__global__ __launch_bounds__((FWD_MAX_WAVES<DH, QKV || CHUNKED> * 64)) __attribute__((amdgpu_waves_per_eu((DH == 16 ? ATT16_WAVES : (FWD_MAX_WAVES<DH, QKV || CHUNKED> == 8 ? 2 : 4))))) void attn_fwd_res_kernel(AttnArgs a) {
   constexpr int KS = DH / 16, DB = (DH + 31) / 32, LD = LdsLd<DH>::V;
   extern __shared__ __attribute__((aligned(16))) unsigned char att_smem[];
   const int64_t S = a.S;
@@ -1251,7 +1231,7 @@ __global__ __launch_bounds__((FWD_MAX_WAVES<DH, QKV || CHUNKED> * 64)) __attribu
 }
 
 template <typename T, int DH, bool SPARSE>
-__global__ __launch_bounds__(RES_MAX_WAVES<DH> * 64) __attribute__((amdgpu_waves_per_eu(DH == 16 ? MST_ATT16_WAVES_BWD : (DH == 64 ? 2 : 4)))) void attn_bwd_res_kernel(AttnArgs a) {
+__global__ __launch_bounds__(RES_MAX_WAVES<DH> * 64) __attribute__((amdgpu_waves_per_eu(DH == 16 ? ATT16_WAVES : (DH == 64 ? 2 : 4)))) void attn_bwd_res_kernel(AttnArgs a) {
   constexpr int KS = DH / 16, DB = (DH + 31) / 32, LD = LdsLd<DH>::V;
   extern __shared__ __attribute__((aligned(16))) unsigned char att_smem[];
   const int64_t S = a.S;
@@ -1651,7 +1631,7 @@ static int launch_fwd(const AttnArgs& a_in, hipStream_t s) {
   AttnArgs a = a_in;
   size_t lds = res_lds_fwd<DH>(a.S);
   const bool lone_f = lone_row_shape(a.S, DH) && a.q_limit >= a.S;
-  const int waves_cu = DH == 16 ? 4 * MST_ATT16_WAVES_FWD : 16;
+  const int waves_cu = DH == 16 ? 4 * ATT16_WAVES : 16;
   int nw = choose_resident(a.S, a.B * a.H, lds, waves_cu, lone_f);
   if (!nw) {  // Q | K | V do not fit together: two tiles, K and V staged over Q between the phases (configs[4]'s decoder: S 1025, dh 16)
     const size_t lds2 = res_lds_fwd<DH>(a.S, 2);
@@ -1702,7 +1682,7 @@ template <typename T, int DH>
 static int launch_bwd(const AttnArgs& a, hipStream_t s) {
   const size_t lds = res_lds_bwd<DH>(a.S);
   const bool sparse_shape = a.q_limit > 0 && a.q_limit <= 32;
-  if (const int nw = choose_resident(a.S, a.B * a.H, lds, DH == 16 ? 4 * MST_ATT16_WAVES_BWD : RES_MAX_WAVES<DH>, lone_row_shape(a.S, DH) && !sparse_shape, RES_MAX_WAVES<DH>)) {
+  if (const int nw = choose_resident(a.S, a.B * a.H, lds, DH == 16 ? 4 * ATT16_WAVES : RES_MAX_WAVES<DH>, lone_row_shape(a.S, DH) && !sparse_shape, RES_MAX_WAVES<DH>)) {
     const bool sparse = sparse_shape;
     static size_t attr_lds[2] = {64 * 1024, 64 * 1024};  // dynamic LDS above 64 KB has to be opted into, per kernel
     if (lds > attr_lds[sparse]) {

@@ -524,11 +524,8 @@ __global__ __launch_bounds__(WGM * WGN * 64) void ffn_ln_kernel(mst_gemm_args g1
   float* sPar = sBias1 + g1.N;   // [2][3 BN]: bias | gamma | beta of the final epilogue, then of the head's (EXTRA forward)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WGN, wn = wave % WGN, frow = lane & 15, fq = lane >> 4;
-#ifndef MST_XCD_ROWS
-#define MST_XCD_ROWS 1
-#endif
   // (row tiles in XCD-contiguous eighths, like the GEMMs' tiles and the attention workgroups: common.hpp xcd_chunk)
-  int64_t m0 = (MST_XCD_ROWS ? xcd_chunk(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x) * BM;
+  int64_t m0 = xcd_chunk(blockIdx.x, gridDim.x) * BM;
   // Row groups (g1's A remap, the only remap the block takes): the block's M rows are rows [offset, offset + rows_per_group) of
   // every group of `stride` physical rows — the last decoder layer skips each sample's position-0 row, whose output is dropped
   // before the loss (model.py:253): 64 x 256 rows are 256 tiles, one resident round, where 64 x 257 were 257. Groups are whole
@@ -562,22 +559,10 @@ __global__ __launch_bounds__(WGM * WGN * 64) void ffn_ln_kernel(mst_gemm_args g1
   // Chunk order rotated per workgroup: every workgroup streams BOTH weight matrices in full, and 256 of them walking the
   // same lines in lockstep hit the same L2 channels at the same time. Workgroup i of an XCD starts at hidden chunk
   // i mod n_chunks; the second GEMM's sum over the chunks then runs in rotated order (fp32, a different rounding order
-  // than the three-launch form; `a` itself is unchanged).
-#ifndef MST_FFN_ROT
-#define MST_FFN_ROT 1
-#endif
-#ifndef MST_FFN_EARLY_STORE
-#define MST_FFN_EARLY_STORE 0  /* measured 43.9 vs 42.6 us at width 256: slower, kept as a switch */
-#endif
-  const int rot = MST_FFN_ROT ? (int)((blockIdx.x / 8) % (unsigned)n_chunks) : 0;
+  // than the three-launch form; `a` itself is unchanged). The K order inside a GEMM is not rotated, so `a` stays
+  // bit-identical to the three-launch form.
+  const int rot = (int)((blockIdx.x / 8) % (unsigned)n_chunks);
   auto phys = [&](int c) { const int pc = c + rot; return pc >= n_chunks ? pc - n_chunks : pc; };
-  // ... and the K stages inside each GEMM of a chunk start at a per-workgroup offset too (KST is a power of two)
-#ifndef MST_FFN_ROTK
-#define MST_FFN_ROTK 0  /* measured: no effect (43.9 vs 43.6 us); off keeps `a` bit-identical to the three-launch form */
-#endif
-  static_assert((KST & (KST - 1)) == 0, "stage rotation masks with KST - 1");
-  const int rotk = MST_FFN_ROTK ? (int)((blockIdx.x / 8 / (unsigned)n_chunks) & (KST - 1)) : 0;
-  auto kstage = [&](int s) { return (s + rotk) & (KST - 1); };  // stage s of a GEMM reads K slice kstage(s)
   const T* __restrict__ W1 = reinterpret_cast<const T*>(g1.B);
   const T* __restrict__ W2 = reinterpret_cast<const T*>(g2.B);
   const T* __restrict__ WX = reinterpret_cast<const T*>(gx.B);  // EXTRA: chunk -1 (head) / chunk n_chunks (tail) of the stream
@@ -604,15 +589,15 @@ __global__ __launch_bounds__(WGM * WGN * 64) void ffn_ln_kernel(mst_gemm_args g1
   u32x4 ring[RING][B_CH];
   auto load_stage = [&](int c, int s, u32x4 (&rb)[B_CH]) {  // (c, s) uniform
     if (HEAD && c < 0) {  // the extra GEMM's K stage s
-      const T* base = WX + kstage(s) * BK;
+      const T* base = WX + s * BK;
 #pragma unroll
       for (int i = 0; i < B_CH; ++i) rb[i] = *reinterpret_cast<const u32x4*>(base + offx[i]);
     } else if (s < KST) {
-      const T* base = W1 + (int64_t)phys(c) * BN * g1.ldb + kstage(s) * BK;
+      const T* base = W1 + (int64_t)phys(c) * BN * g1.ldb + s * BK;
 #pragma unroll
       for (int i = 0; i < B_CH; ++i) rb[i] = *reinterpret_cast<const u32x4*>(base + off1[i]);
     } else {
-      const T* base = W2 + (int64_t)phys(c) * BN + kstage(s - KST) * BK;
+      const T* base = W2 + (int64_t)phys(c) * BN + (s - KST) * BK;
 #pragma unroll
       for (int i = 0; i < B_CH; ++i) rb[i] = *reinterpret_cast<const u32x4*>(base + off2[i]);
     }
@@ -621,9 +606,9 @@ __global__ __launch_bounds__(WGM * WGN * 64) void ffn_ln_kernel(mst_gemm_args g1
     constexpr int i = decltype(ic)::value;
     const T* base;
     uint32_t off;
-    if (HEAD && c < 0) { base = WX + kstage(s) * BK; off = offx[i]; }
-    else if (s < KST) { base = W1 + (int64_t)phys(c) * BN * g1.ldb + kstage(s) * BK; off = off1[i]; }
-    else { base = W2 + (int64_t)phys(c) * BN + kstage(s - KST) * BK; off = off2[i]; }
+    if (HEAD && c < 0) { base = WX + s * BK; off = offx[i]; }
+    else if (s < KST) { base = W1 + (int64_t)phys(c) * BN * g1.ldb + s * BK; off = off1[i]; }
+    else { base = W2 + (int64_t)phys(c) * BN + (s - KST) * BK; off = off2[i]; }
     rb[i] = *reinterpret_cast<const u32x4*>(base + off);
   };
   auto store_stage = [&](int buf, const u32x4 (&rb)[B_CH]) {
@@ -741,10 +726,10 @@ __global__ __launch_bounds__(WGM * WGN * 64) void ffn_ln_kernel(mst_gemm_args g1
       *reinterpret_cast<u32x4*>(sX + row * LDA + ch * 8) = v;
     }
   }
-  // one 64-deep K stage: acc += A[64, 64] (LDS tile `sA`, columns k0..) x stage `buf`
+  // one 64-deep K stage: acc += A[64, 64] (`sA`: the stage's first column in an LDS tile of row stride LDA) x stage `buf`
   // hook(k), k < 2 * TN: called behind the k-th row of MFMAs of the stage — the staged form hangs the weight staging
-  // there (MST_FFN_IL), piece by piece, instead of issuing it in front of / behind the whole stage
-  auto mma_stage = [&](f32x4 (&acc)[TN][TM], const T* sA, int k0, int buf, const u32x4 (&rb)[B_CH], auto&& hook) {
+  // there (IL below), piece by piece, instead of issuing it in front of / behind the whole stage
+  auto mma_stage = [&](f32x4 (&acc)[TN][TM], const T* sA, int buf, const u32x4 (&rb)[B_CH], auto&& hook) {
     const u32x4* cB = sB + buf * BN * CHUNKS;
 #pragma unroll
     for (int ks = 0; ks < BK / 32; ++ks) {
@@ -752,7 +737,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void ffn_ln_kernel(mst_gemm_args g1
       const int kc = ks * 4 + fq;
 #pragma unroll
       for (int i = 0; i < TM; ++i)
-        xf[i] = __builtin_bit_cast(vec8, *reinterpret_cast<const u32x4*>(sA + (wm * WTM + i * 16 + frow) * LDA + k0 + kc * 8));
+        xf[i] = __builtin_bit_cast(vec8, *reinterpret_cast<const u32x4*>(sA + (wm * WTM + i * 16 + frow) * LDA + kc * 8));
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
         const int row = wn * WTN + j * 16 + frow;
@@ -806,7 +791,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void ffn_ln_kernel(mst_gemm_args g1
         constexpr int t = s + AHEAD;
         if constexpr (t < KST) load_stage(cx, t, ring[t % RING]);
         else if constexpr (HEAD) load_stage(0, t - KST, ring[t % RING]);  // the first chunk's stages follow (KST % RING == 0)
-        mma_stage(acc1, sX, kstage(s) * BK, s & 1, ring[s % RING], no_hook);
+        mma_stage(acc1, sX + s * BK, s & 1, ring[s % RING], no_hook);
         if constexpr (s + 1 < KST) store_stage((s + 1) & 1, ring[(s + 1) % RING]);
         __syncthreads();
       }
@@ -845,22 +830,13 @@ __global__ __launch_bounds__(WGM * WGN * 64) void ffn_ln_kernel(mst_gemm_args g1
     auto stage = [&](auto sc) {
       constexpr int s = decltype(sc)::value;      // stage within the chunk: ring slot s % RING, LDS buffer s % 2
       if constexpr (s < SPC) {
-#ifndef MST_FFN_IL
-#define MST_FFN_IL 1
-#endif
-        constexpr bool IL = MST_FFN_IL && BN >= 256 && !MST_FFN_EARLY_STORE && B_CH <= 2 * TN;  // (width 128, two workgroups per CU: measured 1 us slower)
+        constexpr bool IL = BN >= 256 && B_CH <= 2 * TN;  // (width 128, two workgroups per CU: measured 1 us slower)
         // request stage s + AHEAD of the stream (it may belong to the next chunk)
         constexpr int t = s + AHEAD;
         // (unconditional: past the last chunk the clamped load fetches a stage nobody stores)
         const int tc = t < SPC ? c : (c + 1 < n_chunks ? c + 1 : c);
         const bool more = s + 1 < SPC || c + 1 < n_chunks;  // a next stage exists: its weights go to the other LDS buffer
         // interleaved form: piece k of { load of stage s + AHEAD, LDS store of stage s + 1 } behind the k-th row of MFMAs
-#ifndef MST_FFN_COPY_IL
-#define MST_FFN_COPY_IL 0  /* measured: -1 us on the isolated launch, +1..2 us at step level (in-call A/B): off */
-#endif
-        // (experiment) forward: the finished chunk's copy to `a` rides behind the last MFMA rows of the second GEMM's first
-        // stage, a 16-byte piece of a row at a time, instead of standing between the barrier and that stage
-        constexpr bool COPY_IL = MST_FFN_COPY_IL && MODE == 1 && OUT_CH <= 2 * TN;
         auto piece = [&](auto kc) {
           constexpr int k = decltype(kc)::value;
           if constexpr (IL && k < B_CH) {
@@ -869,25 +845,11 @@ __global__ __launch_bounds__(WGM * WGN * 64) void ffn_ln_kernel(mst_gemm_args g1
             if (more) sB[((s + 1) & 1) * BN * CHUNKS + b_lds[k]] = ring[(s + 1) % RING][k];
             __builtin_amdgcn_sched_barrier(0);
           }
-          if constexpr (COPY_IL && s == KST && k >= 2 * TN - OUT_CH) {
-            constexpr int i = k - (2 * TN - OUT_CH), CPRc = BN / 8;
-            const int cc = tid + i * NT, row = cc / CPRc, ch = cc % CPRc;
-            __builtin_amdgcn_sched_barrier(0);
-            const u32x4 v = *reinterpret_cast<const u32x4*>(sH + row * LDA + ch * 8);
-            if (m0 + row < Mg) *reinterpret_cast<u32x4*>(Aout + (m0 + row) * g1.ldc + (int64_t)pc * BN + ch * 8) = v;
-            __builtin_amdgcn_sched_barrier(0);
-          }
         };
         if constexpr (!IL) load_stage(tc, t % SPC, ring[t % RING]);
         FFN_STAMP(8 + (c * SPC + s) * 4);
-        if (MST_FFN_EARLY_STORE) {
-          // Experiment (off): the next stage's weights go to the OTHER LDS buffer ahead of this stage's MFMAs (legal: that
-          // buffer was last read in the previous stage, which ended with a barrier) instead of after them.
-          if (s + 1 < SPC || c + 1 < n_chunks) store_stage((s + 1) & 1, ring[(s + 1) % RING]);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        if constexpr (s < KST) mma_stage(acc1, sX, kstage(s) * BK, s & 1, ring[s % RING], piece);
-        else mma_stage(acc2, sH, kstage(s - KST) * BK, s & 1, ring[s % RING], piece);
+        if constexpr (s < KST) mma_stage(acc1, sX + s * BK, s & 1, ring[s % RING], piece);
+        else mma_stage(acc2, sH + (s - KST) * BK, s & 1, ring[s % RING], piece);
         FFN_STAMP(8 + (c * SPC + s) * 4 + 1);
         if constexpr (s == KST - 1) {
           // ---- chunk epilogue of GEMM 1, in registers: bias, ReLU, dropout, rounding (the order of gemm_epilogue) -> sH.
@@ -932,11 +894,11 @@ __global__ __launch_bounds__(WGM * WGN * 64) void ffn_ln_kernel(mst_gemm_args g1
           if (step_form1) chunk_epilogue(std::true_type()); else chunk_epilogue(std::false_type());
         }
         // the next stage of the stream (requested AHEAD iterations ago) -> the other LDS buffer
-        if (!IL && !MST_FFN_EARLY_STORE && more) store_stage((s + 1) & 1, ring[(s + 1) % RING]);
+        if (!IL && more) store_stage((s + 1) & 1, ring[(s + 1) % RING]);
         FFN_STAMP(8 + (c * SPC + s) * 4 + 2);
         __syncthreads();
         FFN_STAMP(8 + (c * SPC + s) * 4 + 3);
-        if constexpr (s == KST - 1 && !COPY_IL) {
+        if constexpr (s == KST - 1) {
           // the finished chunk goes out to `a` (the backward pass needs it) as whole 16-byte pieces of rows, while the
           // second GEMM's stages run
           constexpr int CPR = BN / 8;

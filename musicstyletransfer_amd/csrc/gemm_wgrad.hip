@@ -253,11 +253,8 @@ __device__ __forceinline__ void wgrad_body(const WgradBatch& b, unsigned char* s
   // registers since the previous stage), reload the register with chunk p of stage t+2 } — placed between the 8 MFMA groups
   // of stage t: a stalled load issue of one wave overlaps the other wave's MFMAs, the loads get a whole stage to arrive, and
   // nothing but the barrier separates the last MFMA of a stage from the first of the next.
-#ifndef MST_WGRAD_IL
-#define MST_WGRAD_IL 1
-#endif
   bool done_il = false;
-  if constexpr (MST_WGRAD_IL && A_CH + B_CH <= TN * (BMR / 32)) {
+  if constexpr (A_CH + B_CH <= TN * (BMR / 32)) {
     if ((m_end - m_begin) % BMR == 0 && !div_a && !div_b) {
       done_il = true;
       // every load is unconditional: a chunk beyond N / K reads the tile's first column instead and is zeroed when it is
@@ -668,11 +665,8 @@ extern "C" int mst_gemm_wgrad_batch_flush(const mst_wgrad_args* list, int n, flo
   const int64_t slots = big >= 2 ? 256 : (big ? 512 : 1024);
   auto split_of = [&](int i, int64_t S) -> int64_t {
     const int64_t cap = cdiv(list[i].M, 2 * BMR);
-#ifndef MST_WGRAD_NARROW_SPLIT
-#define MST_WGRAD_NARROW_SPLIT 1
-#endif
     // (per-workgroup stamps, tools/bench_wgrad_wgs.py: a narrow tile's stage costs ~0.93 us, a wide one's ~2.0)
-    int64_t sp = (bk_p[i] < bk) ? (MST_WGRAD_NARROW_SPLIT == 0 ? S : MST_WGRAD_NARROW_SPLIT == 1 ? (S * 5 + 4) / 8 : S / 2) : S;
+    int64_t sp = (bk_p[i] < bk) ? (S * 5 + 4) / 8 : S;
     if (sp < 1) sp = 1;
     return sp < cap ? sp : cap;
   };

@@ -160,10 +160,7 @@ __device__ uint32_t g_tail_stamps[32];
 // claimed XCD would leave the bounded barrier spin and fail the step's parity, not hang). The barrier counter itself stays
 // agent-scope.
 // sync: [0] barrier counter, [1] claimed XCD + 1, [2] roles handed out (all zero at launch).
-#ifndef MST_TAIL_OVERSUBSCRIBE
-#define MST_TAIL_OVERSUBSCRIBE 12  /* 8 is exact under round-robin dispatch; measured 8 / 10 / 12 / 16: 0.7245 / 0.7234 / 0.7256 / 0.7256 ms per step */
-#endif
-constexpr int TAIL_OVERSUBSCRIBE = MST_TAIL_OVERSUBSCRIBE;
+constexpr int TAIL_OVERSUBSCRIBE = 12;  // 8 is exact under round-robin dispatch; measured 8 / 10 / 12 / 16: 0.7245 / 0.7234 / 0.7256 / 0.7256 ms per step
 __device__ __forceinline__ int tail_join(uint32_t* sync, int G) {
   __shared__ int role;
   if (threadIdx.x == 0) {

@@ -1,5 +1,5 @@
 """Per-stage timeline of ONE workgroup of the whole-step weight-gradient launch shape.
-Build with MST_EXTRA_FLAGS="gemm_wgrad.hip=-DMST_WGRAD_STAMPS [-DMST_WGRAD_GLDS=0]" (GPU box)."""
+Build with MST_EXTRA_FLAGS="gemm_wgrad.hip=-DMST_WGRAD_STAMPS" (GPU box)."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

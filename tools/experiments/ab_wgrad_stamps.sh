@@ -1,8 +1,6 @@
-for v in "-DMST_WGRAD_IL=0" "-DMST_WGRAD_IL=1"; do
-  export MST_EXTRA_FLAGS="gemm_wgrad.hip=-DMST_WGRAD_STAMPS $v"
-  python -m musicstyletransfer_amd.csrc.build --force > /dev/null 2>&1 || { echo build failed; exit 1; }
-  echo "== $v"; python tools/bench_wgrad_stamps.py | tail -4
-done
+export MST_EXTRA_FLAGS="gemm_wgrad.hip=-DMST_WGRAD_STAMPS"
+python -m musicstyletransfer_amd.csrc.build --force > /dev/null 2>&1 || { echo build failed; exit 1; }
+python tools/bench_wgrad_stamps.py | tail -4
 unset MST_EXTRA_FLAGS
 python -m musicstyletransfer_amd.csrc.build --force > /dev/null 2>&1
 python -m pytest tests/test_kernels_gpu.py -x -q -m gpu -k "wgrad" 2>&1 | tail -2
