@@ -609,6 +609,25 @@ int mst_sample_step(int64_t N, int64_t V, int64_t i, int64_t L, const float* pro
 int mst_frame_step(int dtype, int64_t N, int64_t P, int64_t i, int64_t L, const void* logits, int64_t ldl, float tau, int mode, float thr,
                    const uint64_t* seed_ptr, uint8_t* frames, int64_t ldf, uint8_t* roll, int64_t ldr, float* scores, float* probs_out,
                    mst_stream_t stream);
+/* The token ends' draw with a temperature, a top-k and a nucleus (top-p) cut, from the position's LOGITS (act dtype, [N, ldl >= V]:
+ * DecodePlan.logits) — mst_frame_step's counterpart, one launch per position, capturable: the seed is a device word. Per sequence,
+ * over columns 0..V-1:
+ *   x_j = logit_j / tau (fp32); s = softmax(x) is the sampling distribution, p = softmax(logit) the model's own. x is non-decreasing
+ *   in the stored 16-bit logit, so every cut is a cut on the stored value (as an order-preserving 16-bit integer key):
+ *   top-k : c_k = the k-th largest stored logit with multiplicity; logit_j >= c_k survives (tie groups at the cut survive whole: the
+ *           kept set is a function of the values, never of the column order); top_k = 0 or >= V keeps everything;
+ *   top-p : among the survivors, mass measured by s: c_p = the largest stored value c with mass{logit_j >= c} >= top_p *
+ *           mass{survivors}; logit_j >= c_p is kept — the smallest set of most likely tokens, in whole tie groups, that reaches
+ *           top_p (the arg-max group always); top_p = 1 is off;
+ *   draw  : inverse CDF over the kept tokens in column order, u = ((counter hash of (*seed_ptr, i, n) >> 8) + 1) * 2^-24 times the
+ *           kept mass (mst_sample_step's rule); if rounding leaves no owner the LAST KEPT token takes the draw, never one outside.
+ * Bookkeeping is mst_sample_step's: a finished sequence (seqs[n, i-1] EOS, or PAD from position 2 on) gets PAD at no cost; otherwise
+ * seqs[n, i] = word[n] = token and scores[n] += -log max(p_token, 1e-30) — the MODEL's probability, unfiltered at temperature 1, so
+ * the scores of every decoder are the same quantity; active[i] (optional) += running sequences; kept_out[n] (optional, int32 [N]) =
+ * the number of kept tokens (finished sequences too). tau > 0 finite; top_k >= 0; 0 < top_p <= 1; 1 <= i < L; all launch constants. */
+int mst_token_step(int dtype, int64_t N, int64_t V, int64_t i, int64_t L, const void* logits, int64_t ldl, float tau, int32_t top_k,
+                   float top_p, const uint64_t* seed_ptr, int32_t* seqs, float* scores, int32_t* word, int32_t* active,
+                   int32_t* kept_out, int32_t eos, int32_t pad, mst_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * K12/K13: softmax over V + SoftmaxCrossEntropy (model.py:256; loss.py:15-23).

@@ -259,6 +259,23 @@ class Model:
         self._frame_plans[key] = fs
         return fs
 
+    def token_sampling_plan(self, N, L, attention=None, keep_logits=False):
+        """decode.TokenSampling of this shape (token ends: caches, token rows, one captured graph per position and filter setting), kept
+        across batches"""
+        from .. import decode
+        attention = resolve_attention(self.engine_config, attention)
+        if not hasattr(self, "_token_plans") or getattr(self, "_token_store", None) is not self.store:
+            self._token_plans, self._token_store = OrderedDict(), self.store
+        key = (N, L, attention, bool(keep_logits))
+        ts = self._token_plans.pop(key, None)
+        if ts is None:
+            ts = decode.TokenSampling(self.store, N, L, attention=attention, keep_logits=keep_logits)
+            while len(self._token_plans) >= self.DECODE_PLAN_MAX:
+                torch.cuda.synchronize(self.store.device)
+                self._token_plans.popitem(last=False)
+        self._token_plans[key] = ts
+        return ts
+
     def on_plan_evicted(self, callback):
         """callback(plan) when the cache drops a plan (holders of per-plan state — graphs, input rings — forget it)"""
         self._evict_hooks.append(callback)

@@ -80,11 +80,17 @@ class Sampling(SamplerBase):
     """ancestral sampling (sampler.py:155-190): draw the next token from the decoder's distribution until every sequence
     has ended or twice the input length is reached. Piano-roll ends: every pitch of the next frame is a Bernoulli draw."""
 
-    def __init__(self, *args, frames_on_device=False, **kw):
+    def __init__(self, *args, frames_on_device=False, temperature=1.0, top_k=0, top_p=1.0, **kw):
         """frames_on_device: the piano-roll ends' draw as a device kernel inside every position's captured graph
-        (decode.FrameSampling) instead of the host loop below and its numpy random stream (the default, unchanged)"""
+        (decode.FrameSampling) instead of the host loop below and its numpy random stream (the default, unchanged).
+        temperature, top_k, top_p: the draw's temperature (logits are divided by it) and, for the token ends, its top-k (0: off) and
+        nucleus (1: off) cuts — decode.TokenSampling, the whole position on the device; at their defaults the paths below are taken
+        unchanged. The host loops have neither; the piano-roll ends take a temperature with frames_on_device only."""
         super().__init__(*args, **kw)
         self.frames_on_device = bool(frames_on_device)
+        self.temperature, self.top_k, self.top_p = float(temperature), int(top_k), float(top_p)
+        if not 0.0 < self.temperature < float("inf") or self.top_k < 0 or not 0.0 < self.top_p <= 1.0:
+            raise ValueError("temperature > 0, top_k >= 0 and 0 < top_p <= 1 wanted, got {}, {}, {}".format(temperature, top_k, top_p))
 
     def sample(self, batch):
         tokens, seq_lens, classes = batch.data
@@ -94,6 +100,19 @@ class Sampling(SamplerBase):
         dec = self.model.decoder
         kind = self.model.engine_config.kind
         self.scores = np.zeros(B)
+        cuts = self.top_k != 0 or self.top_p != 1.0
+        if kind == "token" and (cuts or self.temperature != 1.0):
+            # temperature and cuts are the device draw's (mst_token_step): one captured graph per position
+            self._dev = self.model.token_sampling_plan(B, i_max, self.attention)
+            self._dev_key = None
+            seqs, scores = self._dev.run(dec.initial_rows(tokens, seq_lens, classes), tau=self.temperature, top_k=self.top_k,
+                                         top_p=self.top_p, seed=int(self.rng.integers(1 << 62)))
+            self.scores = scores.astype(np.float64)
+            return seqs.astype(np.int64)
+        if kind != "token" and cuts:
+            raise ValueError("top_k and top_p rank tokens; a piano-roll frame is one Bernoulli draw per pitch (temperature applies)")
+        if kind != "token" and self.temperature != 1.0 and not self.frames_on_device:
+            raise ValueError("the piano-roll host loop has no temperature: Sampling(frames_on_device=True, temperature=...)")
         if kind == "token" and os.environ.get("MST_SAMPLE_DEVICE", "1") != "0":
             # the draw on the device (decode.AncestralSampling): no distribution crosses to the host
             from ..decode import AncestralSampling
@@ -105,7 +124,7 @@ class Sampling(SamplerBase):
             return seqs.astype(np.int64)
         if kind != "token" and self.frames_on_device:
             fs = self.model.frame_sampling_plan(B, i_max, self.attention)
-            roll, scores = fs.run(dec.initial_rows(tokens, seq_lens, classes), seed=int(self.rng.integers(1 << 62)))
+            roll, scores = fs.run(dec.initial_rows(tokens, seq_lens, classes), tau=self.temperature, seed=int(self.rng.integers(1 << 62)))
             self.scores = scores.astype(np.float64)
             return roll
         state = dec.get_initial_state(tokens, seq_lens, classes, t_max=i_max + 1, attention=self.attention)
@@ -229,9 +248,11 @@ class ReconstructionSampler(SamplerBase):
 class _GeneratorSampler(SamplerBase):
     """samplers over generate.LatentGenerator: one encode of the batch, every requested row decoded together"""
 
-    def __init__(self, *args, decoder="sampling", beam_size=4, temperature=1.0, steps=8, **kw):
+    def __init__(self, *args, decoder="sampling", beam_size=4, temperature=1.0, steps=8, sample_temperature=1.0, top_k=0, top_p=1.0, **kw):
+        """temperature: the latent noise's scale; sample_temperature, top_k, top_p: the draw's (LatentGenerator)"""
         super().__init__(*args, **kw)
         self.decoder, self.beam_size, self.temperature, self.steps = decoder, beam_size, temperature, steps
+        self.sample_temperature, self.top_k, self.top_p = sample_temperature, top_k, top_p
         self._gen = None
 
     @property
@@ -239,7 +260,8 @@ class _GeneratorSampler(SamplerBase):
         from ..generate import LatentGenerator
         if self._gen is None or self._gen.model is not self.model:
             self._gen = LatentGenerator(self.model, attention=self._attention, seed=int(self.rng.integers(1 << 62)),
-                                        temperature=self.temperature, decoder=self.decoder, beam_size=self.beam_size)
+                                        temperature=self.temperature, decoder=self.decoder, beam_size=self.beam_size,
+                                        sample_temperature=self.sample_temperature, top_k=self.top_k, top_p=self.top_p)
         return self._gen
 
 
@@ -302,8 +324,10 @@ def get_sampler(type, model_folder, context, checkpoint, args):
     """sampler.py:41-53, plus 'reconstruction' (what the trainer's periodic hook uses by default here) and the latent-space
     generators 'prior', 'interpolation', 'transfer' (generate.LatentGenerator)"""
     verbose = bool(getattr(args, "verbose", False))
+    # (the draw's settings, where the caller's arguments carry them; the reference's flag table has none)
+    tau, top_k, top_p = (getattr(args, "sample_temperature", None) or 1.0, getattr(args, "top_k", None) or 0, getattr(args, "top_p", None) or 1.0)
     if type == "sampling":
-        return Sampling(model_folder, context, checkpoint, verbose=verbose)
+        return Sampling(model_folder, context, checkpoint, verbose=verbose, temperature=tau, top_k=top_k, top_p=top_p)
     if type == "beam-search":
         return BeamSearchSampler(model_folder, context, checkpoint, beam_size=int(getattr(args, "beam_size", 4) or 4), verbose=verbose)
     if type == "reconstruction":
@@ -311,5 +335,5 @@ def get_sampler(type, model_folder, context, checkpoint, args):
     generators = {"prior": PriorSampler, "interpolation": InterpolationSampler, "transfer": TransferSampler}
     if type in generators:
         return generators[type](model_folder, context, checkpoint, verbose=verbose, decoder=getattr(args, "decoder", "sampling") or "sampling",
-                                beam_size=int(getattr(args, "beam_size", 4) or 4))
+                                beam_size=int(getattr(args, "beam_size", 4) or 4), sample_temperature=tau, top_k=top_k, top_p=top_p)
     raise ValueError("Sampler {} is not implemented".format(type))

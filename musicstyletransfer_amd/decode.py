@@ -380,3 +380,87 @@ class FrameSampling:
         p._leave()
         self.positions = length - 1
         return roll, scores
+
+
+class TokenSampling:
+    """Sampling for the token ends with a temperature, a top-k and a nucleus cut, the whole position on the device: the decode step of
+    position i up to its logits and mst_token_step — which cuts, draws, writes the token where the next position's embedding reads it
+    and keeps the sampler's books (finished sequences, scores, the `active` counter) — are ONE captured graph per position. The draw's
+    seed is a device word the host rewrites before a run, so the graphs captured by one run replay for every later one. (The draw forms
+    both softmaxes itself: these graphs have no softmax_ce launch.) tau, top_k and top_p are launch constants of mst_token_step: a
+    graph is kept per (position, tau, top_k, top_p)."""
+
+    def __init__(self, store, N, L, attention="query", keep_logits=False):
+        """L positions: the start row + up to L - 1 tokens. keep_logits: every position's logits stay in self.logits (fp32 [N, L, V],
+        row i = what position i's draw read; tests and diagnostics)"""
+        from .MIDIUtil.defaults import EOS_ID, PAD_ID, SOS_ID
+        cfg = store.cfg
+        if cfg.kind != "token":
+            raise ValueError("TokenSampling draws tokens; the piano-roll ends have FrameSampling")
+        if L < 2:
+            raise ValueError("TokenSampling needs at least two positions")
+        self.N, self.L, self.V = N, L, cfg.out_dim
+        self.eos, self.pad, self.sos = EOS_ID, PAD_ID, SOS_ID
+        self.plan = DecodePlan(store, N, L, attention=attention)
+        dev = store.device
+        self.seqs = torch.zeros(N, L, dtype=torch.int32, device=dev)
+        self.scores = torch.zeros(N, dtype=torch.float32, device=dev)
+        self.active = torch.zeros(L + 1, dtype=torch.int32, device=dev)
+        self.logits = torch.zeros(N, L, self.V, dtype=torch.float32, device=dev) if keep_logits else None
+        self.seed_word = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._seed_host = torch.zeros(1, dtype=torch.int64).pin_memory()
+        self._graphs, self._warm = {}, False
+        self.positions = 0
+
+    def _position(self, i, tau, top_k, top_p):
+        p = self.plan
+        p._position(i, probs=False)
+        if self.logits is not None:
+            self.logits[:, i].copy_(p.logits[:, : self.V])  # (a device copy: part of the position's graph)
+        o.token_step(p.logits, self.V, i, self.seed_word, self.seqs, self.scores, p.tokens, self.eos, self.pad, tau=tau, top_k=top_k,
+                     top_p=top_p, active=self.active)
+
+    def run(self, row0, length=None, tau=1.0, top_k=0, top_p=1.0, seed=0, check_every=8):
+        """row0: [N, >= D] initial decoder rows. Decodes positions 1 .. length - 1 (default: all L - 1), stopping early once every
+        sequence has ended (looked at every check_every positions), and returns (token rows [N, n] int32, scores [N]) as host arrays."""
+        p = self.plan
+        length = self.L if length is None else int(length)
+        if not 2 <= length <= self.L:
+            raise ValueError(f"length {length} outside [2, {self.L}]")
+        tau, top_k, top_p = float(tau), int(top_k), float(top_p)
+        if not (0.0 < tau < float("inf")) or top_k < 0 or not 0.0 < top_p <= 1.0:
+            raise ValueError(f"tau > 0 finite, top_k >= 0 and 0 < top_p <= 1 wanted, got {tau}, {top_k}, {top_p}")
+        p.reset()
+        seed &= 0xFFFFFFFFFFFFFFFF
+        self._seed_host[0] = seed - (1 << 64) if seed >= (1 << 63) else seed
+        with p._enter():
+            self.seed_word.copy_(self._seed_host, non_blocking=True)
+            p.x.copy_(row0[:, : p.x.shape[1]])
+            p._run_position(0)
+            p.t = 0
+            self.seqs.fill_(self.pad)
+            self.seqs[:, 0] = self.sos
+            o.zero(self.scores)
+            o.zero(self.active)
+            p.tokens.fill_(self.sos)
+            last = 0
+            for i in range(1, length):
+                key = (i, tau, top_k, top_p)
+                g = self._graphs.get(key) if p.use_graphs else None
+                if g is None and p.use_graphs and self._warm:
+                    g = self._graphs[key] = o.Graph().capture(lambda: self._position(i, tau, top_k, top_p))
+                if g is not None:
+                    g.launch()
+                else:
+                    self._position(i, tau, top_k, top_p)  # (the first position ever runs eagerly: lazy HIP module loads ...
+                    self._warm = True
+                    if p.use_graphs:                      # ... and is captured behind that, so the next run replays it too)
+                        self._graphs[key] = o.Graph().capture(lambda: self._position(i, tau, top_k, top_p))
+                p.t = last = i
+                if i % check_every == 0 and int(self.active[i].item()) == 0:
+                    break
+            seqs = self.seqs[:, : last + 1].cpu().numpy()
+            scores = self.scores.cpu().numpy()
+        p._leave()
+        self.positions = last
+        return seqs, scores

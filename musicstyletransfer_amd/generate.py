@@ -4,8 +4,8 @@ style transfer from ONE encode, and blends of two class embeddings.
 A request is a RECIPE — per output row which source vectors to mix (a, b, w), how much noise to add (tau, optionally scaled by the
 encoder's sigma) and which class embeddings to mix (ca, cb, cw) — built on the host by the functions below (pure numpy: they are what
 the CPU tests check), turned into latent vectors and decoder start rows by ONE launch per chunk (ops.latent_rows: mst_latent_rows),
-and decoded by what the samplers use: decode.AncestralSampling / decode.BeamSearch for the token ends, decode.FrameSampling for the
-piano-roll ends. The reference stops at `latent_vector = means` (sampler.py:146-148); nothing here has a counterpart there.
+and decoded by what the samplers use: decode.AncestralSampling / decode.BeamSearch for the token ends (decode.TokenSampling when the
+draw has a temperature, a top-k or a nucleus cut), decode.FrameSampling for the piano-roll ends. The reference stops at `latent_vector = means` (sampler.py:146-148); nothing here has a counterpart there.
 
     python -m music_style_transfer.VarAutoEncoder.generate --model-output DIR --mode transfer --data MIDI_DIR --out OUT_DIR
 """
@@ -177,18 +177,33 @@ class Generated:
 
 class LatentGenerator:
     """model: an initialised VarAutoEncoder.model.Model. decoder: 'sampling' (ancestral draws), 'greedy' (the most likely token /
-    every pitch above one half) or 'beam' (token ends only). temperature: the scale of the latent noise (prior and posterior draws);
-    frame_temperature: the piano-roll draw's own (logits are divided by it). More than max_rows rows are decoded in chunks."""
+    every pitch above one half) or 'beam' (token ends only). temperature: the scale of the latent noise (prior and posterior draws).
+    sample_temperature, top_k, top_p: the DRAW's own settings (decoder 'sampling'): logits are divided by sample_temperature; the token
+    ends keep the top_k most likely tokens (0: all) and of those the smallest set reaching top_p (1: all) — decode.TokenSampling; with
+    all three at their defaults the token ends draw from the raw softmax (decode.AncestralSampling). frame_temperature: the piano-roll
+    ends' earlier name of sample_temperature. More than max_rows rows are decoded in chunks."""
 
     def __init__(self, model, attention=None, seed=0, temperature=1.0, decoder="sampling", beam_size=4, max_rows=256,
-                 frame_temperature=1.0, keep_probs=False):
+                 frame_temperature=1.0, keep_probs=False, sample_temperature=1.0, top_k=0, top_p=1.0):
         if decoder not in DECODERS:
             raise ValueError("decoder must be one of {}, got {!r}".format(DECODERS, decoder))
         if max_rows <= 0:
             raise ValueError("max_rows must be positive")
+        sample_temperature, top_k, top_p = float(sample_temperature), int(top_k), float(top_p)
+        if not 0.0 < sample_temperature < float("inf") or top_k < 0 or not 0.0 < top_p <= 1.0:
+            raise ValueError("sample_temperature > 0, top_k >= 0 and 0 < top_p <= 1 wanted, got {}, {}, {}".format(sample_temperature, top_k, top_p))
+        if (top_k != 0 or top_p != 1.0) and decoder != "sampling":
+            raise ValueError("top_k and top_p cut the distribution that decoder 'sampling' draws from; decoder {!r} draws nothing".format(decoder))
+        if (top_k != 0 or top_p != 1.0) and model is not None and model.engine_config.kind != "token":
+            raise ValueError("top_k and top_p rank tokens; a piano-roll frame is one Bernoulli draw per pitch (sample_temperature applies)")
+        if sample_temperature != 1.0 and float(frame_temperature) != 1.0 and sample_temperature != float(frame_temperature):
+            raise ValueError("frame_temperature is the earlier name of sample_temperature: give one of them")
+        self.sample_temperature, self.top_k, self.top_p = sample_temperature, top_k, top_p
+        self.last_sampler = None  # the decode.* object of the latest chunk
         self.model, self._attention, self.seed = model, attention, int(seed)
         self.temperature, self.decoder, self.beam_size, self.max_rows = float(temperature), decoder, int(beam_size), int(max_rows)
-        self.frame_temperature, self.keep_probs = float(frame_temperature), bool(keep_probs)
+        self.frame_temperature = sample_temperature if sample_temperature != 1.0 else float(frame_temperature)
+        self.keep_probs = bool(keep_probs)
         self.calls = 0
         self._samplers, self._pos0 = {}, None
         if model is not None and decoder == "beam" and model.engine_config.kind != "token":
@@ -236,11 +251,19 @@ class LatentGenerator:
         m, n = self.model, row0.shape[0]
         attention = resolve_attention(m.engine_config, self._attention)
         if m.engine_config.kind != "token":
-            fs = m.frame_sampling_plan(n, length, attention, keep_probs=self.keep_probs)
+            if self.top_k != 0 or self.top_p != 1.0:
+                raise ValueError("top_k and top_p rank tokens; a piano-roll frame is one Bernoulli draw per pitch")
+            fs = self.last_sampler = m.frame_sampling_plan(n, length, attention, keep_probs=self.keep_probs)
             roll, scores = fs.run(row0, length, tau=self.frame_temperature, mode="draw" if self.decoder == "sampling" else "threshold",
                                   thr=0.5, seed=seed)
             return roll, scores, (fs.probs[:, : length - 1].cpu().numpy() if self.keep_probs else None)
         from .MIDIUtil.defaults import PAD_ID
+        if self.decoder == "sampling" and (self.sample_temperature != 1.0 or self.top_k != 0 or self.top_p != 1.0):
+            ts = self.last_sampler = m.token_sampling_plan(n, length, attention)
+            got, scores = ts.run(row0, length, tau=self.sample_temperature, top_k=self.top_k, top_p=self.top_p, seed=seed)
+            seqs = np.full((n, length), PAD_ID, np.int64)
+            seqs[:, : got.shape[1]] = got
+            return seqs, scores, None
         if self.decoder == "sampling":
             key = (n, length, attention, id(m.store))
             smp = self._samplers.get(key)
@@ -248,12 +271,13 @@ class LatentGenerator:
                 if len(self._samplers) >= 4:
                     self._samplers.pop(next(iter(self._samplers)))
                 smp = self._samplers[key] = decode.AncestralSampling(m.store, n, length, attention, seed=seed)
+            self.last_sampler = smp
             got, scores = smp.run(row0)
             seqs = np.full((n, length), PAD_ID, np.int64)
             seqs[:, : got.shape[1]] = got
             return seqs, scores, None
         K = self.beam_size if self.decoder == "beam" else 1  # (one beam is greedy decoding)
-        bs = m.beam_search_plan(n, K, length, attention)
+        bs = self.last_sampler = m.beam_search_plan(n, K, length, attention)
         seqs, scores = bs.run(row0.repeat_interleave(K, dim=0).contiguous() if K > 1 else row0)
         return seqs.astype(np.int64).reshape(n, K, -1)[:, 0], scores.reshape(n, K)[:, 0], None
 
@@ -315,6 +339,9 @@ def build_parser():
     p.add_argument("--interpolation", default="slerp", choices=("slerp", "lerp"))
     p.add_argument("--temperature", type=float, default=1.0)
     p.add_argument("--decoder", default="sampling", choices=DECODERS)
+    p.add_argument("--sample-temperature", type=float, default=1.0, help="--decoder sampling: the draw's temperature (logits are divided by it)")
+    p.add_argument("--top-k", type=int, default=0, help="--decoder sampling, token models: draw among the k most likely tokens (0: all)")
+    p.add_argument("--top-p", type=float, default=1.0, help="--decoder sampling, token models: ... and of those the smallest set reaching this mass (1: all)")
     p.add_argument("--beam-size", type=int, default=4)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--length", type=int, default=None, help="positions to decode (default: twice the input length; prior: 2 * --max-seq-len)")
@@ -348,7 +375,7 @@ def main(argv=None):
     model = load_inference_model(args.model_output, gpu(args.device), args.checkpoint)
     cfg = model.engine_config
     gen = LatentGenerator(model, seed=args.seed, temperature=args.temperature, decoder=args.decoder, beam_size=args.beam_size,
-                          max_rows=args.max_rows)
+                          max_rows=args.max_rows, sample_temperature=args.sample_temperature, top_k=args.top_k, top_p=args.top_p)
     if args.mode == "prior":
         classes = args.classes if args.classes else np.arange(args.n) % cfg.num_classes
         out = gen.prior(args.n, classes, args.length or 2 * args.max_seq_len)

@@ -506,6 +506,15 @@ def frame_step(logits, P, i, seed_ptr, frames, roll, scores, tau=1.0, mode="draw
          ptr(roll), roll.stride(1), ptr(scores), ptr(probs_out), stream())
 
 
+def token_step(logits, V, i, seed_ptr, seqs, scores, word, eos, pad, tau=1.0, top_k=0, top_p=1.0, active=None, kept_out=None):
+    """the token of position i for every sequence, drawn from the position's logits behind a temperature, a top-k and a nucleus cut
+    (mst_token_step): logits [N, >= V] 16-bit; seqs int32 [N, L]; word int32 [N(, 1)]; kept_out int32 [N] or None; seed_ptr: a
+    device int64 / uint64 word"""
+    assert seqs.is_contiguous()
+    call("mst_token_step", dt(logits), seqs.shape[0], V, i, seqs.shape[1], ptr(logits), ld(logits), tau, top_k, top_p, ptr(seed_ptr), ptr(seqs),
+         ptr(scores), ptr(word), ptr(active), ptr(kept_out), eos, pad, stream())
+
+
 def beam_gather(cache_in, cache_out, src, n_rows, skip_cols=None):
     """cache_out[j, :n_rows] = cache_in[src[j], :n_rows] for [N, t_max, width] caches (mst_beam_gather);
     skip_cols = (first, count): those columns of every row are left alone (mst_beam_gather_cols)"""

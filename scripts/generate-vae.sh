@@ -1,7 +1,8 @@
 #!/bin/bash
 # Generate .mid files from the latent space of a model trained by scripts/train-vae.sh: every melody of the first batch in every
 # class, from one encode. Other modes: --mode prior|posterior|interpolate|blend (python -m ...generate --help); whatever the caller
-# passes in "$@" is appended (e.g. --mode interpolate --pair 0 3 --steps 9 --decoder greedy).
+# passes in "$@" is appended (e.g. --mode interpolate --pair 0 3 --steps 9 --decoder greedy). The draw of --decoder sampling is the raw
+# softmax as set below; flags in "$@" come later and win, e.g. scripts/generate-vae.sh --sample-temperature 0.9 --top-k 40 --top-p 0.9.
 cd "$(dirname "$0")/.." || exit 1
 
 python -m music_style_transfer.VarAutoEncoder.generate \
@@ -14,5 +15,8 @@ python -m music_style_transfer.VarAutoEncoder.generate \
 --batch-size 8 \
 --temperature 1.0 \
 --decoder sampling \
+--sample-temperature 1.0 \
+--top-k 0 \
+--top-p 1.0 \
 --seed 0 \
 --out /tmp/out/generated "$@"

@@ -6,7 +6,12 @@
   2. the restyle of one batch to both classes: what Sampling.process_batch runs in front of its decode loops (one full inference
      forward per class) against what LatentGenerator.transfer runs (one encode + one mst_latent_rows launch for all rows).
 
-    python tools/bench_generate.py [--reps 3] [--out FILE]
+  3. (--case token) the token ends' draw on a token model of the scripts/train-vae.sh shape (V 293, encoder 256 x 2 x 8, decoder
+     128 x 1 x 8, latent 256, B 64, 129 decoded positions): decode.AncestralSampling (eager launches: the decode step, a softmax and
+     mst_sample_step per position) against decode.TokenSampling (one graph replay per position: the decode step and mst_token_step)
+     with the filters off and with top_k 40, top_p 0.9 — per decoded position, row 0 given.
+
+    python tools/bench_generate.py [--case all|pianoroll|token] [--reps 3] [--out FILE]
 
 Every timed window ends in a device synchronise; the two forms of each pair alternate inside the process; the first pass of
 every shape (lazy module loads, plan construction, graph capture) is outside the timed windows. Prints one JSON line."""
@@ -23,15 +28,79 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
+def token_case(args):
+    """-> dict of the token ends' timings (medians over max(reps, 7) windows per form, the forms alternating)"""
+    import torch
+    from musicstyletransfer_amd import decode
+    from musicstyletransfer_amd.MIDIUtil.defaults import NUM_EVENTS
+    from musicstyletransfer_amd.VarAutoEncoder import model
+    from musicstyletransfer_amd.VarAutoEncoder.transformer import TransformerConfig
+    from musicstyletransfer_amd.VarAutoEncoder.utils import gpu
+
+    B, T, V, Z = args.batch, 65, NUM_EVENTS, 256
+    cfg = model.ModelConfig(model.EncoderConfig(TransformerConfig(256, 0.2, 2, 8, V), Z, 2, V),
+                            model.DecoderConfig(TransformerConfig(128, 0.2, 1, 8, V), Z, 2, V))
+    m = model.Model(cfg).initialize(gpu(0), seed=1234)
+    rng = np.random.default_rng(0)
+    tokens = rng.integers(3, V, (B, T))
+    tokens[:, 0] = 1
+    row0 = m.decoder.initial_rows(tokens, np.full(B, T, np.int64), rng.integers(0, 2, B))
+    i_max = 2 * T  # sampler.py:163: 129 decoded positions
+    anc = decode.AncestralSampling(m.store, B, i_max, seed=1)
+    tok = decode.TokenSampling(m.store, B, i_max)
+    forms = {"ancestral": lambda: anc.run(row0),
+             "token_sampling_filters_off": lambda: tok.run(row0, seed=3),
+             "token_sampling_top_k40_top_p0.9": lambda: tok.run(row0, top_k=40, top_p=0.9, seed=3)}
+    who = {"ancestral": anc, "token_sampling_filters_off": tok, "token_sampling_top_k40_top_p0.9": tok}
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    for fn in forms.values():  # module loads, graph capture, then one replay
+        fn()
+        fn()
+    per = {k: [] for k in forms}
+    for _ in range(max(args.reps, 7)):
+        for k, fn in forms.items():
+            t = timed(fn)
+            per[k].append(t / max(1, who[k].positions) * 1e6)
+    res = dict(token_B=B, token_V=V, token_positions=i_max - 1, token_graphs_captured=len(tok._graphs))
+    for k, v in per.items():
+        res["token_" + k + "_us_per_position"] = float(np.median(v))
+        res["token_" + k + "_all_us"] = v
+    return res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--case", default="all", choices=("all", "pianoroll", "token"))
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--frames", type=int, default=256)
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     import torch
     assert torch.cuda.is_available(), "bench_generate needs a GPU"
+    res = dict(bench="generate", reps=args.reps)
+    if args.case in ("all", "pianoroll"):
+        res.update(pianoroll_case(args))
+    if args.case in ("all", "token"):
+        res.update(token_case(args))
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    return res
+
+
+def pianoroll_case(args):
+    import torch
     from musicstyletransfer_amd import generate as G
     from musicstyletransfer_amd.VarAutoEncoder import model, sampler as S
     from musicstyletransfer_amd.VarAutoEncoder.data import Batch
@@ -94,19 +163,13 @@ def main(argv=None):
         t_one.append(timed(one_encode))
 
     med = lambda v: float(np.median(v))
-    res = dict(bench="generate", B=B, T=T, P=P, positions=positions, reps=args.reps,
+    res = dict(B=B, T=T, P=P, positions=positions,
                host_loop_us_per_position=med(t_host) / positions * 1e6, host_loop_s=t_host,
                frame_sampling_us_per_position=med(t_dev) / positions * 1e6, frame_sampling_s=t_dev,
                frame_sampling_loop_only_us_per_position=med(t_loop) / positions * 1e6,
                restyle_two_forwards_ms=med(t_two) * 1e3, restyle_two_forwards_all_ms=[t * 1e3 for t in t_two],
                restyle_one_encode_ms=med(t_one) * 1e3, restyle_one_encode_all_ms=[t * 1e3 for t in t_one],
                graphs_captured=len(fs._graphs))
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
     return res
 
 
