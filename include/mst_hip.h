@@ -111,6 +111,21 @@ typedef struct mst_gemm_args {
 } mst_gemm_args;
 
 int mst_gemm_nt(const mst_gemm_args* args, mst_stream_t stream);
+/* Which kernel mst_gemm_nt(args) launches, decided on the host from the arguments alone (no HIP call, no device needed; the
+ * pointers are looked at for NULL and alignment only). The launch code calls the same decision and nothing else.
+ * Returns tile * 16 + variant:
+ *   tile    0  64 x 64 tiles, 64-deep K stages
+ *           1  64 x 64 tiles, 256-deep K stages (M <= 64, K >= 512, K % 256 == 0: the decoder's skinny GEMMs)
+ *           2  128 x 128 tiles, 64-deep K stages
+ *           3  128 x 128 tiles at three workgroups per CU, 32-deep K stages (513..768 tiles; variant is 0)
+ *   variant 0  fast epilogue (whole tiles, whole K stages, 16-byte friendly operands), 16-bit C
+ *           1  fast epilogue with dropout / self_resid
+ *           2  general (guarded) epilogue, 16-bit C
+ *           3  general epilogue, fp32 C
+ *           4..7  the same four with row ops (rowadd / grpadd / an A or C row remap)
+ *           8, 9  uint8 A with row ops, fast / general
+ * Invalid arguments: what mst_gemm_nt returns for them (MST_ERR_INVALID, or MST_ERR_UNSUPPORTED for the dtype), same message. */
+int mst_gemm_nt_form(const mst_gemm_args* args);
 
 /* Two mst_gemm_nt problems in ONE launch: the piano-roll ends' two embedding GEMMs (model.py:81-91 encoder input and
  * model.py:241-245 decoder input, transformer.py:237,270: the same uint8 frames against two tables), whose outputs and epilogues

@@ -990,16 +990,18 @@ static int launch_gemm_ln(const mst_gemm_args& a, const mst_ln_args& l, hipStrea
 
 // 128 x 128 tiles at THREE or four workgroups per CU: 32-deep K stages (32 KB) and the accumulators staged one 64-row block at
 // a time (34 KB) instead of 64 KB + 68 KB. For launches of 513..768 tiles (the K | Q | V projections: 768) that is one
-// resident round instead of a full one and a half-empty one at two per CU. Eligibility as launch_gemm's fast form without
-// dropout / row ops; returns 1 when the launch is not eligible (caller falls back).
+// resident round instead of a full one and a half-empty one at two per CU. Eligibility (gemm_3cu_form) as launch_gemm's fast
+// form without dropout / row ops.
+static bool gemm_3cu_form(const mst_gemm_args& a) {
+  constexpr int BM = 128, BN = 128, BK = 32;
+  const bool rowops = a.rowadd || a.grpadd || a.a_rows_per_group > 0 || a.c_rows_per_group > 0;
+  return !a.c_f32 && !a.a_u8 && !rowops && a.dropout_p == 0.f && !a.self_resid && a.M % BM == 0 && a.N % BN == 0 && a.K % BK == 0 &&
+         a.ldc % 8 == 0 && (uint64_t)a.M * (uint64_t)a.N < (1ull << 32) &&
+         (!a.resid || (a.ldr % 8 == 0 && (uintptr_t)a.resid % 16 == 0)) && (!a.gate || (a.ldg % 8 == 0 && (uintptr_t)a.gate % 16 == 0));
+}
 template <typename T>
 static int launch_gemm_3cu(const mst_gemm_args& a, hipStream_t s) {
   constexpr int BM = 128, BN = 128, BK = 32;
-  const bool rowops = a.rowadd || a.grpadd || a.a_rows_per_group > 0 || a.c_rows_per_group > 0;
-  const bool ok = !a.c_f32 && !a.a_u8 && !rowops && a.dropout_p == 0.f && !a.self_resid && a.M % BM == 0 && a.N % BN == 0 && a.K % BK == 0 &&
-                  a.ldc % 8 == 0 && (uint64_t)a.M * (uint64_t)a.N < (1ull << 32) &&
-                  (!a.resid || (a.ldr % 8 == 0 && (uintptr_t)a.resid % 16 == 0)) && (!a.gate || (a.ldg % 8 == 0 && (uintptr_t)a.gate % 16 == 0));
-  if (!ok) return 1;
   const size_t lds_loop = (size_t)2 * (BM + BN) * BK * 2, lds_epi = (size_t)(BM / 2) * (BN + 4) * 4;
   const size_t lds = lds_loop > lds_epi ? lds_loop : lds_epi;
   hipLaunchKernelGGL((gemm_nt_kernel<T, BM, BN, 2, 2, false, BK, false, 4, false>), dim3((unsigned)((a.M / BM) * (a.N / BN))), dim3(256), lds, s, a);
@@ -1021,19 +1023,48 @@ static bool gemm_fast_form(const mst_gemm_args& a) {
                       (!a.grpadd || (a.ldga % 4 == 0 && (uintptr_t)a.grpadd % 16 == 0))));
 }
 
+// The epilogue variant of a launch with BM x BN tiles and BK-deep stages:
+// [row-ops][fast without dropout | fast with dropout | general 16-bit | general fp32], then [8], [9]: uint8 A, fast / general
+// ("row ops" in the kernel choice: row-indexed adds or a row remap of A or C)
+// (an epilogue finished in accumulator layout — 8-byte accesses, no LDS round trip — measured +4 us per step and was removed)
+template <int BM, int BN, int BK>
+static int gemm_variant(const mst_gemm_args& a) {
+  const bool rowops = a.rowadd || a.grpadd || a.a_rows_per_group > 0 || a.c_rows_per_group > 0;
+  const bool fast = gemm_fast_form<BM, BN>(a) && a.K % BK == 0;  // (the fast kernels' K loop is unguarded too)
+  const bool drop = a.dropout_p > 0.f || a.self_resid;
+  return a.a_u8 ? (fast ? 8 : 9) : (a.c_f32 ? 3 : (fast ? (drop ? 1 : 0) : 2)) + (rowops ? 4 : 0);
+}
+
+// THE choice of kernel for a valid mst_gemm_nt problem, from the arguments alone (no HIP call): tile * 16 + variant, the
+// codes of mst_gemm_nt_form (include/mst_hip.h). mst_gemm_nt launches what this returns and decides nothing itself.
+static int gemm_nt_form(const mst_gemm_args& a) {
+  const int64_t big_tiles = cdiv(a.M, 128) * cdiv(a.N, 128);
+  // Tile shape is second-order here: 64x64, 128x64, 64x128 and 128x128 tiles measured within 5 % of each other on
+  // every GEMM of the step (time = 4.7 us fixed + 1.7 us per 8.4 MB of output + 4.2 us per 2.1 GFLOP: with K <= 1024
+  // a tile's main loop is 2-16 stages of one exposed L2 round trip each, at 12 TB/s of L2->LDS traffic for the
+  // K = 1024 shapes). 128x128 is used where it still leaves >= 1.5 workgroups per CU.
+  // Two 128x128 workgroups fit a CU (LDS), 512 on the chip: a launch of 516 (the decoder's M = 64 x 257 rows: 129 row
+  // tiles x 4) runs a second resident round for four workgroups — 21 us against 13 us with 64x64 tiles.
+  const int64_t last_round = big_tiles % 512;
+  const bool stub_round = big_tiles > 512 && last_round > 0 && last_round < 128;
+  // (a launch whose rows are whole 64-row tiles but not whole 128-row tiles — the decoder's 64 x 257 — keeps the
+  // fast-epilogue kernel with 64x64 tiles)
+  const bool ragged128 = a.M % 128 != 0 && a.M % 64 == 0 && a.N % 128 == 0 && !a.c_f32;
+  if (big_tiles > 512 && big_tiles <= 768 && a.N >= 128 && !ragged128 && gemm_3cu_form(a)) return 3 * 16;
+  if (big_tiles >= 384 && a.N >= 128 && !stub_round && !ragged128) return 2 * 16 + gemm_variant<128, 128, 64>(a);
+  if (a.M <= 64 && a.K >= 512 && a.K % 256 == 0) return 1 * 16 + gemm_variant<64, 64, 256>(a);
+  // (32-deep K stages for launches of 1281..2048 64 x 64 tiles — eight workgroups per CU, one resident round for the decoder's
+  // 257 x 6 projection tiles — measured no faster: +2 us per step)
+  return gemm_variant<64, 64, 64>(a);
+}
+
 template <typename T, int BM, int BN, int WGM, int WGN, int BK = 64>
-static int launch_gemm(const mst_gemm_args& a, hipStream_t s) {
+static int launch_gemm(const mst_gemm_args& a, int variant, hipStream_t s) {
   const int64_t tiles = cdiv(a.M, BM) * cdiv(a.N, BN);
   const size_t lds_loop = (size_t)2 * (BM + BN) * BK * 2, lds_epi = (size_t)BM * (BN + 4) * 4;
   const size_t lds = lds_loop > lds_epi ? lds_loop : lds_epi;
   dim3 grid((unsigned)tiles), block(WGM * WGN * 64);
-  // ("row ops" in the kernel choice: row-indexed adds or a row remap of A or C)
-  const bool rowops = a.rowadd || a.grpadd || a.a_rows_per_group > 0 || a.c_rows_per_group > 0;
-  const bool fast = gemm_fast_form<BM, BN>(a) && a.K % BK == 0;  // (the fast kernels' K loop is unguarded too)
-  const bool drop = a.dropout_p > 0.f || a.self_resid;
-  // kernels: [row-ops][fast without dropout | fast with dropout | general 16-bit | general fp32]
-  // (an epilogue finished in accumulator layout — 8-byte accesses, no LDS round trip — measured +4 us per step and was removed)
-  const int variant = a.a_u8 ? (fast ? 8 : 9) : (a.c_f32 ? 3 : (fast ? (drop ? 1 : 0) : 2)) + (rowops ? 4 : 0);
+  // kernels: [row-ops][fast without dropout | fast with dropout | general 16-bit | general fp32] (gemm_variant)
   typedef void (*kern_t)(mst_gemm_args);
   // [8], [9]: uint8 A operand (the piano-roll embedding GEMMs: row ops, 16-bit C, no dropout), fast / general
   const kern_t fns[10] = {&gemm_nt_kernel<T, BM, BN, WGM, WGN, false, BK, false, 1, false>, &gemm_nt_kernel<T, BM, BN, WGM, WGN, false, BK, false, 1, true>,
@@ -1266,7 +1297,7 @@ extern "C" int mst_gemm_sigmoid_bce_dgrad_ln(const mst_gemm_args* args, const ms
   });
 }
 
-extern "C" int mst_gemm_nt(const mst_gemm_args* args, mst_stream_t stream) {
+static int check_gemm_nt(const mst_gemm_args* args) {
   MST_CHECK_ARG(args != nullptr, "mst_gemm_nt: null args");
   const mst_gemm_args& a = *args;
   MST_CHECK_ARG(a.M > 0 && a.N > 0 && a.K > 0, "mst_gemm_nt: M,N,K must be positive (got %lld,%lld,%lld)",
@@ -1286,30 +1317,29 @@ extern "C" int mst_gemm_nt(const mst_gemm_args* args, mst_stream_t stream) {
                 "mst_gemm_nt: operands must be 16-byte aligned");
   MST_CHECK_ARG(!a.a_u8 || (!a.c_f32 && a.dropout_p == 0.f && !a.self_resid),
                 "mst_gemm_nt: a uint8 A operand comes with a 16-bit C and without dropout / self_resid");
+  if (a.dtype != MST_BF16 && a.dtype != MST_F16) return dispatch_act(a.dtype, [](auto) { return 0; });  // (its message and status)
+  return MST_OK;
+}
+
+extern "C" int mst_gemm_nt_form(const mst_gemm_args* args) {
+  const int rc = check_gemm_nt(args);
+  return rc != MST_OK ? rc : gemm_nt_form(*args);
+}
+
+extern "C" int mst_gemm_nt(const mst_gemm_args* args, mst_stream_t stream) {
+  const int rc = check_gemm_nt(args);
+  if (rc != MST_OK) return rc;
+  const mst_gemm_args& a = *args;
+  const int form = gemm_nt_form(a), variant = form & 15;
   hipStream_t s = (hipStream_t)stream;
   return dispatch_act(a.dtype, [&](auto tag) -> int {
     typedef decltype(tag) T;
-    const int64_t big_tiles = cdiv(a.M, 128) * cdiv(a.N, 128);
-    // Tile shape is second-order here: 64x64, 128x64, 64x128 and 128x128 tiles measured within 5 % of each other on
-    // every GEMM of the step (time = 4.7 us fixed + 1.7 us per 8.4 MB of output + 4.2 us per 2.1 GFLOP: with K <= 1024
-    // a tile's main loop is 2-16 stages of one exposed L2 round trip each, at 12 TB/s of L2->LDS traffic for the
-    // K = 1024 shapes). 128x128 is used where it still leaves >= 1.5 workgroups per CU.
-    // Two 128x128 workgroups fit a CU (LDS), 512 on the chip: a launch of 516 (the decoder's M = 64 x 257 rows: 129 row
-    // tiles x 4) runs a second resident round for four workgroups — 21 us against 13 us with 64x64 tiles.
-    const int64_t last_round = big_tiles % 512;
-    const bool stub_round = big_tiles > 512 && last_round > 0 && last_round < 128;
-    // (a launch whose rows are whole 64-row tiles but not whole 128-row tiles — the decoder's 64 x 257 — keeps the
-    // fast-epilogue kernel with 64x64 tiles)
-    const bool ragged128 = a.M % 128 != 0 && a.M % 64 == 0 && a.N % 128 == 0 && !a.c_f32;
-    if (big_tiles > 512 && big_tiles <= 768 && a.N >= 128 && !ragged128) {
-      const int rc = launch_gemm_3cu<T>(a, s);
-      if (rc <= 0) return rc;
+    switch (form >> 4) {  // (the tile forms of gemm_nt_form)
+      case 3: return launch_gemm_3cu<T>(a, s);
+      case 2: return launch_gemm<T, 128, 128, 2, 2>(a, variant, s);
+      case 1: return launch_gemm<T, 64, 64, 2, 2, 256>(a, variant, s);
+      default: return launch_gemm<T, 64, 64, 2, 2>(a, variant, s);
     }
-    if (big_tiles >= 384 && a.N >= 128 && !stub_round && !ragged128) return launch_gemm<T, 128, 128, 2, 2>(a, s);
-    if (a.M <= 64 && a.K >= 512 && a.K % 256 == 0) return launch_gemm<T, 64, 64, 2, 2, 256>(a, s);
-    // (32-deep K stages for launches of 1281..2048 64 x 64 tiles — eight workgroups per CU, one resident round for the decoder's
-    // 257 x 6 projection tiles — measured no faster: +2 us per step)
-    return launch_gemm<T, 64, 64, 2, 2>(a, s);
   });
 }
 

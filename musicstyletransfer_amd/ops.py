@@ -85,6 +85,14 @@ def gemm_nt(A, B, C_out, **kw):
     call("mst_gemm_nt", C.byref(_gemm_args(A, B, C_out, **kw)), stream())
 
 
+def gemm_nt_form(A, B, C_out, **kw):
+    """the kernel gemm_nt(A, B, C_out, **kw) launches, as tile * 16 + variant (mst_gemm_nt_form in include/mst_hip.h); no launch"""
+    rc = _lib.load().mst_gemm_nt_form(C.byref(_gemm_args(A, B, C_out, **kw)))
+    if rc < 0:
+        _lib.check(rc, "mst_gemm_nt_form")
+    return rc
+
+
 def gemm_nt_pair(first, second, begin=None):
     """two gemm_nt problems, each a dict(A=, B=, C_out=, **kw), in one launch where their form allows (mst_gemm_nt_pair);
     begin: keyword arguments of step_begin — the step's bookkeeping rides on the same launch (mst_gemm_nt_pair_begin)"""
