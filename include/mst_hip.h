@@ -292,6 +292,22 @@ int mst_outer_jobs(const mst_outer_job* jobs, int n, mst_stream_t stream);
 int mst_gemm_wgrad_batch_flush(const mst_wgrad_args* list, int n, float* scratch, int64_t scratch_bytes,
                                const mst_partial_sum* sums, int n_sums, const mst_outer_job* outers, int n_outers,
                                mst_stream_t stream);
+/* What mst_gemm_wgrad_batch_flush(list, n, scratch, scratch_bytes, ...) launches, decided on the host from the arguments alone (no
+ * HIP call, no device needed; the pointers are looked at for NULL and alignment only, and a scratch buffer is present when
+ * scratch_bytes > 0). The flush calls the same decision and nothing else. plan is a host array of 4 + 16 entries:
+ *   plan[0]      tile form of the launch, by the batch's total output size (sum of N * K):
+ *                0  64 x 64 tiles       (fewer than 393,216 outputs)
+ *                1  128 x 128 tiles     (fewer than 1,179,648)
+ *                2  256 x 128 tiles     (fewer than 1,572,864)
+ *                3  256 x 256 tiles
+ *   plan[1]      narrow mask: bit p set when problem p (K <= 128) runs the 256 x 128 body inside form 3
+ *   plan[2]      work items (tiles x M slabs over all problems) of the main launch
+ *   plan[3]      bit 0: the tiles go through the scratch buffer and the reduction pass (form 3, scratch_bytes >= items * 256 KiB);
+ *                bit 1: the bias rows too (1 KiB more per item); 0: fp32 atomics
+ *   plan[4 + p]  M split of problem p: its rows go to that many slabs of roundup64(ceil(M / split)) rows (0 for p >= n)
+ * Returns 0. Invalid arguments: what the flush returns for them (MST_ERR_INVALID, or MST_ERR_UNSUPPORTED for the dtype), same
+ * message. */
+int mst_gemm_wgrad_plan(const mst_wgrad_args* list, int n, int64_t scratch_bytes, int64_t* plan);
 
 /* ------------------------------------------------------------------------
  * K1/K2: token path input. out[b, s_off + t, :] = alpha*(table[tok[b,t]] + cls[classes[b]]) + pos[s_off+t]

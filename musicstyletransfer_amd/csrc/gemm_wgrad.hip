@@ -602,27 +602,18 @@ static int check_wgrad(const mst_wgrad_args& a) {
   return MST_OK;
 }
 
-}  // namespace mst
+// What a valid batch launches, besides the WgradBatch the kernels read: the codes of mst_gemm_wgrad_plan (include/mst_hip.h).
+struct WgradPlan {
+  int form;      // 0: 64 x 64, 1: 128 x 128, 2: 256 x 128, 3: 256 x 256 tiles
+  int two_pass;  // bit 0: the tiles go through the scratch reduction; bit 1: the bias rows too
+};
 
-using namespace mst;
-
-extern "C" int mst_gemm_wgrad_batch_flush(const mst_wgrad_args* list, int n, float* scratch, int64_t scratch_bytes,
-                                          const mst_partial_sum* sums, int n_sums, const mst_outer_job* outers, int n_outers,
-                                          mst_stream_t stream) {
+// THE plan of a weight-gradient batch, from the arguments alone (no HIP call; the pointers are looked at for NULL and alignment
+// only): validation, tile form, narrow problems, M splits, work items, and whether a scratch buffer of scratch_bytes takes the
+// two-pass reduction. mst_gemm_wgrad_batch_flush launches what this leaves in b and pl and decides nothing itself;
+// mst_gemm_wgrad_plan reports it.
+static int wgrad_plan(const mst_wgrad_args* list, int n, bool have_scratch, int64_t scratch_bytes, WgradBatch& b, WgradPlan& pl) {
   MST_CHECK_ARG(list != nullptr && n >= 1 && n <= WG_MAXP, "mst_gemm_wgrad_batch_flush: need 1..%d problems", WG_MAXP);
-  OuterBatch ob;
-  {
-    int rc = pack_outer_jobs(outers, n_outers, ob);
-    if (rc) return rc;
-  }
-  MST_CHECK_ARG(n_sums >= 0 && (n_sums == 0 || sums != nullptr), "mst_gemm_wgrad_batch_flush: bad column-sum job list");
-  PartialSumBatch ps;
-  if (n_sums > 0) {
-    int rc = pack_partial_sums(sums, n_sums, ps);
-    if (rc) return rc;
-  }
-  MST_CHECK_ARG(!scratch || ((uintptr_t)scratch % 16 == 0 && scratch_bytes > 0), "mst_gemm_wgrad_batch_flush: bad scratch buffer");
-  WgradBatch b;
   b.n = n;
   int64_t out_elems = 0, maxM = 0;
   for (int i = 0; i < n; ++i) {
@@ -633,6 +624,7 @@ extern "C" int mst_gemm_wgrad_batch_flush(const mst_wgrad_args* list, int n, flo
     out_elems += list[i].N * list[i].K;
     if (list[i].M > maxM) maxM = list[i].M;
   }
+  if (list[0].dtype != MST_BF16 && list[0].dtype != MST_F16) return dispatch_act(list[0].dtype, [](auto) { return 0; });  // (its message and status)
   // tile size: 128x128 when that still leaves enough tiles to fill the chip at a modest split
   // Tile shape by total output size (enough tiles for one resident round at a split of a few): the kernel is bound
   // by operand traffic into the CUs, so bytes per FLOP decide: 64x64 tiles (4 waves, up to 5 workgroups per CU),
@@ -687,20 +679,66 @@ extern "C" int mst_gemm_wgrad_batch_flush(const mst_wgrad_args* list, int n, flo
   // 4 N K split bytes of atomics are tens of microseconds)
   // The bias rows behind the tiles need n_items * 1 KiB more: a buffer that holds the tiles only keeps the two-pass tiles and adds
   // the bias atomically, as before the rows existed (ParamStore.wgrad_scratch is sized for both).
-  b.partial = b.partial_bias = nullptr;
-  if (scratch && big == 3 && n_items * (int64_t)(256 * 256) * 4 <= scratch_bytes) {
-    b.partial = scratch;
-    if (n_items * (int64_t)(256 * 256 + 256) * 4 <= scratch_bytes) b.partial_bias = scratch + n_items * (int64_t)(256 * 256);  // (BN = 256)
+  b.partial = b.partial_bias = nullptr;  // (the flush points them into its scratch buffer, as pl.two_pass says)
+  pl.form = big;
+  pl.two_pass = 0;
+  if (have_scratch && big == 3 && n_items * (int64_t)(256 * 256) * 4 <= scratch_bytes) {
+    pl.two_pass = 1;
+    if (n_items * (int64_t)(256 * 256 + 256) * 4 <= scratch_bytes) pl.two_pass = 3;  // (BN = 256)
   }
+  return MST_OK;
+}
+
+}  // namespace mst
+
+using namespace mst;
+
+extern "C" int mst_gemm_wgrad_batch_flush(const mst_wgrad_args* list, int n, float* scratch, int64_t scratch_bytes,
+                                          const mst_partial_sum* sums, int n_sums, const mst_outer_job* outers, int n_outers,
+                                          mst_stream_t stream) {
+  OuterBatch ob;
+  {
+    int rc = pack_outer_jobs(outers, n_outers, ob);
+    if (rc) return rc;
+  }
+  MST_CHECK_ARG(n_sums >= 0 && (n_sums == 0 || sums != nullptr), "mst_gemm_wgrad_batch_flush: bad column-sum job list");
+  PartialSumBatch ps;
+  if (n_sums > 0) {
+    int rc = pack_partial_sums(sums, n_sums, ps);
+    if (rc) return rc;
+  }
+  MST_CHECK_ARG(!scratch || ((uintptr_t)scratch % 16 == 0 && scratch_bytes > 0), "mst_gemm_wgrad_batch_flush: bad scratch buffer");
+  WgradBatch b;
+  WgradPlan pl;
+  {
+    int rc = wgrad_plan(list, n, scratch != nullptr, scratch_bytes, b, pl);
+    if (rc) return rc;
+  }
+  if (pl.two_pass & 1) b.partial = scratch;
+  if (pl.two_pass & 2) b.partial_bias = scratch + b.item_prefix[n] * (int64_t)(256 * 256);  // behind the tiles (BN = 256)
   hipStream_t s = (hipStream_t)stream;
   bool ps_done = false;
   int rc = dispatch_act(list[0].dtype, [&](auto tag) -> int {
     typedef decltype(tag) T;
-    return launch_wgrad<T>(b, big, n_sums > 0 ? &ps : nullptr, &ps_done, s, ob);
+    return launch_wgrad<T>(b, pl.form, n_sums > 0 ? &ps : nullptr, &ps_done, s, ob);
   });
   if (rc == MST_OK && n_sums > 0 && !ps_done) rc = mst_partial_sums(sums, n_sums, stream);  // no reduction pass: own launch
   if (rc == MST_OK && n_outers > 0 && !ps_done) rc = mst_outer_jobs(outers, n_outers, stream);
   return rc;
+}
+
+extern "C" int mst_gemm_wgrad_plan(const mst_wgrad_args* list, int n, int64_t scratch_bytes, int64_t* plan) {
+  MST_CHECK_ARG(plan != nullptr, "mst_gemm_wgrad_plan: null plan");
+  WgradBatch b;
+  WgradPlan pl;
+  const int rc = wgrad_plan(list, n, scratch_bytes > 0, scratch_bytes, b, pl);
+  if (rc) return rc;
+  plan[0] = pl.form;
+  plan[1] = b.narrow;
+  plan[2] = b.item_prefix[n];
+  plan[3] = pl.two_pass;
+  for (int i = 0; i < WG_MAXP; ++i) plan[4 + i] = i < n ? b.split_p[i] : 0;
+  return MST_OK;
 }
 
 #ifdef MST_WGRAD_STAMPS

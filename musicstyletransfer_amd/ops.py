@@ -446,6 +446,15 @@ def gemm_wgrad_batch(problems, scratch=None, sums=None, outers=None):
         outer_jobs(outers)
 
 
+def gemm_wgrad_plan(problems, scratch_bytes=0):
+    """what gemm_wgrad_batch(problems, scratch) with a scratch buffer of scratch_bytes launches (mst_gemm_wgrad_plan in
+    include/mst_hip.h); no launch, no device. -> dict(form, narrow, items, two_pass, splits): tile form 0..3, the mask of problems on
+    the narrow body, work items, bit 0 tiles / bit 1 bias rows through the reduction pass, and every problem's M split"""
+    plan = (C.c_int64 * (4 + WGRAD_MAX_PROBLEMS))()
+    call("mst_gemm_wgrad_plan", (WgradArgs * len(problems))(*problems), len(problems), scratch_bytes, plan)
+    return dict(form=plan[0], narrow=plan[1], items=plan[2], two_pass=plan[3], splits=list(plan[4:4 + len(problems)]))
+
+
 def gemm_wgrad(A, B, dW, db=None, **kw):
     gemm_wgrad_batch([wgrad_problem(A, B, dW, db, **kw)])
 
