@@ -47,6 +47,9 @@ const char* mst_last_error(void);
 /* ---- stream-capture helpers (hipGraph instead of a tracing compiler) ---- */
 int mst_graph_begin(mst_stream_t stream);
 int mst_graph_end(mst_stream_t stream, void** graph_exec_out);
+/* mst_graph_end that also reports what was captured: the graph's node count and how many of them are kernel launches
+ * (either pointer may be NULL). Host-side queries of the captured graph only; the executable graph is the same. */
+int mst_graph_end_counted(mst_stream_t stream, void** graph_exec_out, int32_t* nodes_out, int32_t* kernel_nodes_out);
 int mst_graph_launch(void* graph_exec, mst_stream_t stream);
 int mst_graph_destroy(void* graph_exec);
 
@@ -507,6 +510,23 @@ int mst_latent_bwd_vec_proj(int dtype, int64_t B, int64_t De, int64_t Z, int64_t
                             float alpha_d, float kl_weight, float gscale, float enc_scale, float* dcls_d, int64_t ld_cls,
                             void* d_enc_out, int64_t denc_sample_stride, float* scratch, mst_stream_t stream);
 
+/* The scheduled forms of the two launches above: the scalar kl_weight is replaced by the device schedule block of mst_step_begin
+ * (sched[0] = beta_t, sched[1] = tau, the per-sample KL allowance in nats: "free bits") and the forward pass's per-sample kl [B]:
+ * the KL part of d mu / d sigma of sample b is multiplied by beta_t where kl[b] > tau (strictly) and by exactly 0.f otherwise; the
+ * loss these are the gradients of is recon_b + beta_t * max(kl_b - tau, 0). The test is per SAMPLE, so a data-parallel shard computes
+ * what the whole batch computes. Everything else — and, for a sample above the allowance, every bit of the result — as the
+ * unscheduled launch called with kl_weight = beta_t. */
+int mst_latent_bwd_vec_sched(int dtype, int64_t B, int64_t De, int64_t Z, int64_t Dd, const float* Wl, const float* eps, const float* Wh,
+                             const int32_t* classes, const float* mu, const float* sigma, const void* d_dec_in, int64_t dec_sample_stride,
+                             float alpha_d, const float* sched, const float* kl, float gscale, float enc_scale, float* dcls_d,
+                             int64_t ld_cls, void* d_enc_out, int64_t denc_sample_stride, float* scratch, mst_stream_t stream);
+int mst_latent_bwd_vec_proj_sched(int dtype, int64_t B, int64_t De, int64_t Z, int64_t Dd, const float* Wl, const float* eps,
+                                  const float* Wh, const int32_t* classes, const float* mu, const float* sigma,
+                                  const void* dq0, int64_t dq_sample_stride, const void* Wt, int64_t ld_wt, int64_t nq,
+                                  const void* resid0, int64_t resid_sample_stride,
+                                  float alpha_d, const float* sched, const float* kl, float gscale, float enc_scale, float* dcls_d,
+                                  int64_t ld_cls, void* d_enc_out, int64_t denc_sample_stride, float* scratch, mst_stream_t stream);
+
 /* standalone reparameterisation + KL (loss.VariationalKLLoss, loss.py:4-12; model.py:292) */
 int mst_reparam_kl_fwd(int64_t B, int64_t Z, const float* mu, const float* sigma, const float* eps,
                        float* z, float* kl, mst_stream_t stream);
@@ -764,6 +784,21 @@ int mst_adam_flat_emb(int dtype, int64_t n, float* w, const float* grad, float* 
                       double beta2, float eps, float wd, float rescale, float clip, int32_t* step_state,
                       const mst_step_metrics* metrics, int64_t base, const int64_t* emb, int64_t n_emb, void* wt16, mst_stream_t stream);
 
+/* The scheduled forms of mst_adam_flat (with advance_step = 0: the schedule block exists only behind an mst_step_begin of the same
+ * step) and of mst_adam_flat_emb. The end-of-step bookkeeping reads the device schedule block `sched` of mst_step_begin instead of
+ * metrics->kl_weight, which is ignored:  total[b] = recon[b] + sched[0] * max(kl[b] - sched[1], 0)   (the KL charged beyond the
+ * free bits, at this step's weight); metric[0] += sum_b kl[b] — the RAW KL, comparable across schedules —, metric[1] += sum_b total,
+ * metric[2] += B. The step guard and the non-finite guard (on the raw per-sample losses) are those of the unscheduled launches; a
+ * step they skip takes the step count back, and the schedule — a function of that count alone — with it. lr_t is read from
+ * step_state as always: the learning-rate warm-up is already in it. */
+int mst_adam_flat_sched(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
+                        double beta2, float eps, float wd, float rescale, float clip, int32_t* step_state,
+                        const mst_step_metrics* metrics, const float* sched, mst_stream_t stream);
+int mst_adam_flat_emb_sched(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
+                            double beta2, float eps, float wd, float rescale, float clip, int32_t* step_state,
+                            const mst_step_metrics* metrics, const float* sched, int64_t base, const int64_t* emb, int64_t n_emb,
+                            void* wt16, mst_stream_t stream);
+
 /* 16-bit shadow + transposed shadow refresh for a list of matrices.
  * desc: int64 [n_mat, 4] on device = {src_offset, dst_offset, rows, cols}; dst is [cols, ld_t] with
  * ld_t = roundup8(rows), pad columns zeroed. tiles: int64 prefix sums [n_mat+1] of 32x32 tile counts. */
@@ -804,6 +839,17 @@ typedef struct mst_step_begin_args {
    * of the next step instead of in a launch of their own behind the optimizer. Matrices the launch itself reads (the
    * piano-roll embedding tables of mst_gemm_nt_pair_begin) must not be listed: mst_adam_flat_emb keeps those current. */
   int32_t sh_dtype; const float* sh_w; void* sh_wt16; const int64_t* sh_desc; const int64_t* sh_prefix; int64_t sh_n_mat, sh_tiles;
+  /* Optional training schedules (sched == NULL: none, the launch is exactly the one without these fields; needs adam_state). With t =
+   * adam_state[0] AFTER this launch's increment (1-based) and all arithmetic in double:
+   *   f_lr   = sched_lr_warmup > 0 ? min(1, t / sched_lr_warmup) : 1;      lr_t = (float)((lr * f_lr) * sqrt(1-b2^t) / (1-b1^t))
+   *   u      = sched_kl_cycle > 0 ? ((t - 1) mod sched_kl_cycle) + 1 : t;  ramp = sched_kl_warmup > 0 ? min(1, u / sched_kl_warmup) : 1
+   *   beta_t = (float)((double)sched_kl_weight * ramp)
+   * and the thread that advances Adam's step count writes the fp32 schedule block sched[0..3] = {beta_t, sched_kl_free_bits, f_lr, t},
+   * which the scheduled launches of the same step read (mst_latent_bwd_vec_sched, mst_adam_flat_sched). A pure function of the step
+   * count: it replays inside a captured graph, resumes with the optimizer state and is the same on every data-parallel rank; a
+   * step the optimizer's guards take back (mst_step_metrics) takes the schedule back with the count.
+   * Lengths and free bits must be >= 0; a cycle needs 0 < sched_kl_warmup <= sched_kl_cycle. */
+  float* sched; float sched_kl_weight, sched_kl_free_bits; int32_t sched_kl_warmup, sched_kl_cycle, sched_lr_warmup;
 } mst_step_begin_args;
 int mst_step_begin(const mst_step_begin_args* args, mst_stream_t stream);
 /* mst_step_begin and mst_gemm_nt_pair in ONE launch: nothing in the piano-roll ends' embedding GEMMs (the first arithmetic of the

@@ -2,8 +2,8 @@
 
 The flag set is the reference's, name for name and default for default (config.py:19-70), because
 scripts/train-vae.sh passes them; unknown flags are ignored as there (parse_known_args, :73-75). The flags
-are declared as a table. Two additions, both off by default: --pianoroll (attach the piano-roll ends) and
---dtype."""
+are declared as a table. The additions (group MI355X) are all off by default: --pianoroll (attach the piano-roll ends), --dtype,
+--d-causal and the training schedules."""
 import argparse
 import copy
 import inspect
@@ -61,6 +61,13 @@ _FLAGS = [
     ("MI355X", ("--max-steps",), dict(type=int, default=0)),
     # a causal decoder (softmax over the keys): a model the incremental samplers decode as trained. Off: the reference's decoder
     ("MI355X", ("--d-causal",), dict(action="store_true")),
+    # training schedules, evaluated on the device from Adam's step count (engine.schedule_values); 0: off. The KL weight ramps from
+    # kl-loss / W to kl-loss over W steps, restarting every --kl-cycle-steps; --kl-free-bits nats of KL per sample are not charged;
+    # the learning rate ramps up over --lr-warmup-steps.
+    ("MI355X", ("--kl-warmup-steps",), dict(type=int, default=0)),
+    ("MI355X", ("--kl-cycle-steps",), dict(type=int, default=0)),
+    ("MI355X", ("--kl-free-bits",), dict(type=float, default=0.0)),
+    ("MI355X", ("--lr-warmup-steps",), dict(type=int, default=0)),
 ]
 
 

@@ -24,12 +24,12 @@ def create_toy_model_config(data):
                                            output_dim=data.num_tokens()))
 
 
-def create_toy_train_config(max_steps=0):
-    """main.py:41-55"""
+def create_toy_train_config(max_steps=0, **schedule):
+    """main.py:41-55; schedule: the training-schedule fields of TrainConfig (the --kl-warmup-steps ... flags)"""
     return trainer.TrainConfig(batch_size=1, sampling_frequency=500, checkpoint_frequency=1000, num_checkpoints_not_improved=-1,
                                kl_loss=1.0, optimizer=trainer.OptimizerConfig(learning_rate=1e-3, optimizer="adam",
                                                                               optimizer_params="clip_gradient:1.0"),
-                               label_smoothing=0.0, negative_label_downscaling=True, verbose=False, max_steps=max_steps)
+                               label_smoothing=0.0, negative_label_downscaling=True, verbose=False, max_steps=max_steps, **schedule)
 
 
 def main_toy(context, args):
@@ -39,7 +39,8 @@ def main_toy(context, args):
     model_folder = os.path.join(args.model_output if args.model_output != "models" else "/tmp/music-style-transfer/toy", "model")
     create_directory_if_not_present(model_folder)
     config.save(os.path.join(model_folder, "config"))
-    t = trainer.Trainer(config=create_toy_train_config(args.max_steps), context=context, model=m, sampler=None)
+    schedule = {k: getattr(args, k) for k in ("kl_warmup_steps", "kl_cycle_steps", "kl_free_bits", "lr_warmup_steps")}
+    t = trainer.Trainer(config=create_toy_train_config(args.max_steps, **schedule), context=context, model=m, sampler=None)
     t.fit(dataset=dataset, validation_dataset=dataset, model_folder=model_folder, epochs=20000 if not args.max_steps else args.max_steps)
     return t
 
@@ -52,7 +53,9 @@ def create_train_config(args):
                                optimizer=trainer.OptimizerConfig(learning_rate=args.learning_rate, optimizer=args.optimizer,
                                                                  optimizer_params=args.optimizer_params),
                                label_smoothing=args.label_smoothing, negative_label_downscaling=args.negative_label_downscaling,
-                               verbose=args.verbose, dtype=args.dtype, max_steps=args.max_steps)
+                               verbose=args.verbose, dtype=args.dtype, max_steps=args.max_steps,
+                               kl_warmup_steps=args.kl_warmup_steps, kl_cycle_steps=args.kl_cycle_steps,
+                               kl_free_bits=args.kl_free_bits, lr_warmup_steps=args.lr_warmup_steps)
 
 
 def create_model_config(args, dataset):

@@ -15,12 +15,15 @@ import numpy as np
 import torch
 
 from . import utils
+from .config import Config
 from .. import parallel
+from ..engine import check_schedule
 from ..pianoroll import PinnedBatchPipeline
 
 
-class OptimizerConfig:
+class OptimizerConfig(Config):
     def __init__(self, optimizer: str, optimizer_params: str, learning_rate: float):
+        super().__init__()
         self.optimizer, self.optimizer_params, self.learning_rate = optimizer, optimizer_params, learning_rate
 
     def params_to_dict(self):
@@ -33,10 +36,18 @@ class OptimizerConfig:
         return out
 
 
-class TrainConfig:
+class TrainConfig(Config):
+    """kl_warmup_steps / kl_cycle_steps / kl_free_bits / lr_warmup_steps: the training schedules (engine.schedule_values), all off at
+    their defaults. YAML-serialisable (Config): a file written before a field existed loads with that field's default."""
+
     def __init__(self, batch_size: int, sampling_frequency: int, checkpoint_frequency: int, num_checkpoints_not_improved: int,
                  optimizer: OptimizerConfig, kl_loss: float, label_smoothing: float, negative_label_downscaling: bool,
-                 verbose: bool, dtype: str = "bf16", max_steps: int = 0):
+                 verbose: bool, dtype: str = "bf16", max_steps: int = 0, kl_warmup_steps: int = 0, kl_cycle_steps: int = 0,
+                 kl_free_bits: float = 0.0, lr_warmup_steps: int = 0):
+        super().__init__()
+        check_schedule(kl_warmup_steps, kl_cycle_steps, kl_free_bits, lr_warmup_steps)
+        self.kl_warmup_steps, self.kl_cycle_steps = kl_warmup_steps, kl_cycle_steps
+        self.kl_free_bits, self.lr_warmup_steps = kl_free_bits, lr_warmup_steps
         self.batch_size = batch_size
         self.sampling_frequency = sampling_frequency
         self.checkpoint_frequency = checkpoint_frequency
@@ -110,6 +121,12 @@ class Trainer:
         self.hyper = dict(lr=self.config.optimizer.learning_rate, clip_gradient=extra.get("clip_gradient", None),
                           kl_weight=self.config.kl_loss_weight, label_smoothing=self.config.label_smoothing,
                           negative_label_downscaling=self.config.negative_label_downscaling, internal_eps=True)
+        # the training schedules join the plan's hyper-parameters (and with them the plan cache's key) only when one is on
+        sched = {k: getattr(self.config, k, 0) for k in ("kl_warmup_steps", "kl_cycle_steps", "kl_free_bits", "lr_warmup_steps")}
+        check_schedule(**sched)
+        self.scheduled = any(sched.values())
+        if self.scheduled:
+            self.hyper.update(sched)
         self.opt_extra = {k: v for k, v in extra.items() if k in ("beta1", "beta2", "epsilon", "wd")}
 
     # ------------------------------------------------------------------ the hot loop
@@ -227,7 +244,9 @@ class Trainer:
     def collect_metrics(self, reset=True):
         """the reference's five metrics over every step since the last reset (trainer.py:107-120,181-186): kl_loss /
         total_loss batch means and, for the token ends, masked ppl / acc / topk — all accumulated on the device by the
-        steps themselves and read here with one synchronisation"""
+        steps themselves and read here with one synchronisation. kl_weight / lr_scale: the KL weight and the learning-rate factor
+        of the last training step, from the device schedule block in the same read (the configured constants without schedules;
+        computed per rank from the same step count, so there is nothing to reduce)"""
         failure = None
         with torch.cuda.stream(self.stream):  # ordered behind every step launched so far
             try:
@@ -237,6 +256,8 @@ class Trainer:
                     raise
                 failure = e
                 m = self.model.store.read_metrics(reset)
+        kl_weight, lr_scale = ((m.get("kl_weight", self.config.kl_loss_weight), m.get("lr_scale", 1.0)) if self.scheduled
+                               else (self.config.kl_loss_weight, 1.0))
         keys = [k for k in ("kl_sum", "total_sum", "count", "nll_sum", "acc_hits", "topk_hits", "n_tokens") if k in m]
         if self.dist is not None:
             with torch.cuda.stream(self.stream):
@@ -258,6 +279,7 @@ class Trainer:
         n = max(m["count"], 1.0)
         out["kl_loss"] = m["kl_sum"] / n
         out["total_loss"] = m["total_sum"] / n
+        out["kl_weight"], out["lr_scale"] = kl_weight, lr_scale
         return out
 
     def _metric_to_string_output(self, n_batches):

@@ -14,6 +14,7 @@
 // they are kept in fp32 because the KL term's log(sigma^2) is the most precision-sensitive
 // quantity in the ELBO.
 #include <math.h>
+#include <type_traits>
 #include "common.hpp"
 #include "outer_jobs.hpp"
 #include "latent_fwd.hpp"
@@ -142,7 +143,11 @@ struct LatentDx0 {  // (optional) what latent_bwd_vec_kernel computes d(dec_in[b
   const void* dq; int64_t dq_stride; const void* Wq; int64_t ld_wq; int nq; const void* resid; int64_t resid_stride;
 };
 
-template <typename T, bool PRE>
+// SCHED (mst_latent_bwd_vec*_sched): the weight on the KL terms is this step's, from the device schedule block {beta_t, tau, ...} of
+// step_begin.hpp, and only for a sample whose KL exceeds the allowance tau (free bits) — sched[0] * (kl[b] > sched[1]) in place of the
+// launch constant kl_weight. Three uniform (scalar) loads per workgroup; a switch of the template so that the unscheduled
+// instantiations stay what they were (this kernel has no register to spare: docs/kernel_notes.md).
+template <typename T, bool PRE, bool SCHED>
 __global__ __launch_bounds__(LAT_THREADS) void latent_bwd_vec_kernel(int De, int Z, int Dd, const float* __restrict__ Wl,
                                                                      const float* __restrict__ eps,
                                                                      const float* __restrict__ Wh,
@@ -153,13 +158,18 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_bwd_vec_kernel(int De, int
                                                                      float enc_scale, float* __restrict__ tvec,
                                                                      float* __restrict__ dlat, T* __restrict__ d_enc_out,
                                                                      int64_t denc_stride, const int32_t* __restrict__ classes,
-                                                                     float* __restrict__ dcls, int64_t ld_cls, LatentDx0 x0) {
+                                                                     float* __restrict__ dcls, int64_t ld_cls, LatentDx0 x0,
+                                                                     const float* __restrict__ sched, const float* __restrict__ kl) {
   extern __shared__ float sm[];
   float* t = sm;             // [Dd]
   float* dl = sm + Dd;       // [2Z]
   float* part = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(dl + 2 * Z) + 15) & ~(uintptr_t)15);  // [LAT_THREADS] partial sums (general form: float4 each)
   const int64_t b = blockIdx.x;
   const int tid = threadIdx.x;
+  // (SCHED: resolved here, ahead of everything, so that the code below sees one uniform value either way — the same contractions
+  // and the same bits as the unscheduled form at kl_weight = beta_t, which tests/test_schedule_gpu.py compares)
+  float klw = kl_weight;
+  if constexpr (SCHED) klw = kl[b] > sched[1] ? sched[0] : 0.f;
   // Fast path (one round per product, few rows per thread): the weight elements a thread will contract, and mu / sigma
   // / eps, are loaded before the first barrier — their addresses depend on nothing computed here, and in the step they
   // are cold lines (three dependent round trips otherwise).
@@ -241,8 +251,8 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_bwd_vec_kernel(int De, int
         const float m = pre ? m_r : mu[b * Z + ii], s2 = pre ? s_r : sigma[b * Z + ii], ee = pre ? e_r : eps[b * Z + ii];
         // gscale: loss scale of everything upstream of here (the encoder); enc_scale = gscale / (loss scale the
         // incoming decoder-side gradient carries). Both are 1 unless fp16 loss scaling is on.
-        const float dm = kl_weight * gscale * m + enc_scale * a;
-        const float ds = kl_weight * gscale * (s2 - 1.f / s2) + enc_scale * ee * a;
+        const float dm = klw * gscale * m + enc_scale * a;
+        const float ds = klw * gscale * (s2 - 1.f / s2) + enc_scale * ee * a;
         dl[ii] = dm;
         dl[Z + ii] = ds;
         dlat[b * 2 * Z + ii] = dm;
@@ -409,8 +419,9 @@ static int latent_bwd_vec_impl(int dtype, int64_t B, int64_t De, int64_t Z, int6
                                const float* Wh, const int32_t* classes, const float* mu, const float* sigma,
                                const void* d_dec_in, int64_t dec_sample_stride, float alpha_d, float kl_weight, float gscale,
                                float enc_scale, float* dcls_d, int64_t ld_cls, void* d_enc_out, int64_t denc_sample_stride,
-                               float* scratch, const LatentDx0& x0, mst_stream_t stream) {
+                               float* scratch, const LatentDx0& x0, const float* sched, const float* kl, mst_stream_t stream) {
   MST_CHECK_ARG(B > 0 && De > 0 && Z > 0 && Dd > 0, "mst_latent_bwd_vec: sizes must be positive");
+  MST_CHECK_ARG(!sched == !kl, "mst_latent_bwd_vec_sched: the schedule block and the per-sample KL go together");
   MST_CHECK_ARG(Wl && eps && Wh && classes && mu && sigma && (d_dec_in || x0.dq) && dcls_d && d_enc_out && scratch, "mst_latent_bwd_vec: null pointer");
   MST_CHECK_ARG(Z <= LAT_THREADS, "mst_latent_bwd_vec: latent size above %d", LAT_THREADS);
   MST_CHECK_ARG(!x0.dq || (x0.Wq && (x0.nq == 384 || x0.nq == 768) && x0.ld_wq >= x0.nq && x0.ld_wq % 2 == 0 && ((uintptr_t)x0.Wq % 4) == 0),
@@ -418,14 +429,17 @@ static int latent_bwd_vec_impl(int dtype, int64_t B, int64_t De, int64_t Z, int6
   const size_t lds = sizeof(float) * (Dd + 2 * Z + (latent_bwd_pre_shape(De, Z, Dd) ? 1 : 4) * LAT_THREADS + 4);  // (+ 4: the float4 view's alignment)
   return dispatch_act(dtype, [&](auto tag) -> int {
     typedef decltype(tag) T;
-    if (latent_bwd_pre_shape(De, Z, Dd))
-      hipLaunchKernelGGL((latent_bwd_vec_kernel<T, true>), dim3((unsigned)B), dim3(LAT_THREADS), lds, (hipStream_t)stream, (int)De, (int)Z,
-                         (int)Dd, Wl, eps, Wh, mu, sigma, (const T*)d_dec_in, dec_sample_stride, alpha_d, kl_weight, gscale, enc_scale,
-                         scratch, scratch + B * Dd, (T*)d_enc_out, denc_sample_stride, classes, (float*)nullptr, ld_cls, x0);
-    else
-      hipLaunchKernelGGL((latent_bwd_vec_kernel<T, false>), dim3((unsigned)B), dim3(LAT_THREADS), lds, (hipStream_t)stream, (int)De, (int)Z,
-                         (int)Dd, Wl, eps, Wh, mu, sigma, (const T*)d_dec_in, dec_sample_stride, alpha_d, kl_weight, gscale, enc_scale,
-                         scratch, scratch + B * Dd, (T*)d_enc_out, denc_sample_stride, classes, (float*)nullptr, ld_cls, x0);
+    auto launch = [&](auto pre, auto scheduled) {
+      hipLaunchKernelGGL((latent_bwd_vec_kernel<T, decltype(pre)::value, decltype(scheduled)::value>), dim3((unsigned)B), dim3(LAT_THREADS), lds,
+                         (hipStream_t)stream, (int)De, (int)Z, (int)Dd, Wl, eps, Wh, mu, sigma, (const T*)d_dec_in, dec_sample_stride, alpha_d,
+                         kl_weight, gscale, enc_scale, scratch, scratch + B * Dd, (T*)d_enc_out, denc_sample_stride, classes, (float*)nullptr,
+                         ld_cls, x0, sched, kl);
+    };
+    const bool pre = latent_bwd_pre_shape(De, Z, Dd);
+    if (pre && sched) launch(std::true_type{}, std::true_type{});
+    else if (pre) launch(std::true_type{}, std::false_type{});
+    else if (sched) launch(std::false_type{}, std::true_type{});
+    else launch(std::false_type{}, std::false_type{});
     MST_CHECK_LAUNCH("latent_bwd_vec_kernel");
     // the class table's gradient from the rows the kernel left in scratch (tvec), in batch order
     hipLaunchKernelGGL(class_table_grad_kernel, dim3((unsigned)cdiv(Dd, 64)), dim3(256), 0, (hipStream_t)stream, B, (int)Dd,
@@ -441,7 +455,16 @@ extern "C" int mst_latent_bwd_vec(int dtype, int64_t B, int64_t De, int64_t Z, i
                                   float* scratch, mst_stream_t stream) {
   MST_CHECK_ARG(d_dec_in != nullptr, "mst_latent_bwd_vec: null pointer");
   return latent_bwd_vec_impl(dtype, B, De, Z, Dd, Wl, eps, Wh, classes, mu, sigma, d_dec_in, dec_sample_stride, alpha_d, kl_weight, gscale, enc_scale,
-                             dcls_d, ld_cls, d_enc_out, denc_sample_stride, scratch, LatentDx0{}, stream);
+                             dcls_d, ld_cls, d_enc_out, denc_sample_stride, scratch, LatentDx0{}, nullptr, nullptr, stream);
+}
+extern "C" int mst_latent_bwd_vec_sched(int dtype, int64_t B, int64_t De, int64_t Z, int64_t Dd, const float* Wl, const float* eps,
+                                        const float* Wh, const int32_t* classes, const float* mu, const float* sigma,
+                                        const void* d_dec_in, int64_t dec_sample_stride, float alpha_d, const float* sched, const float* kl,
+                                        float gscale, float enc_scale, float* dcls_d, int64_t ld_cls, void* d_enc_out,
+                                        int64_t denc_sample_stride, float* scratch, mst_stream_t stream) {
+  MST_CHECK_ARG(d_dec_in != nullptr && sched != nullptr && kl != nullptr, "mst_latent_bwd_vec_sched: null pointer");
+  return latent_bwd_vec_impl(dtype, B, De, Z, Dd, Wl, eps, Wh, classes, mu, sigma, d_dec_in, dec_sample_stride, alpha_d, 0.f, gscale, enc_scale,
+                             dcls_d, ld_cls, d_enc_out, denc_sample_stride, scratch, LatentDx0{}, sched, kl, stream);
 }
 extern "C" int mst_latent_bwd_vec_proj(int dtype, int64_t B, int64_t De, int64_t Z, int64_t Dd, const float* Wl, const float* eps,
                                        const float* Wh, const int32_t* classes, const float* mu, const float* sigma,
@@ -452,7 +475,18 @@ extern "C" int mst_latent_bwd_vec_proj(int dtype, int64_t B, int64_t De, int64_t
   MST_CHECK_ARG(dq0 != nullptr && Wq != nullptr, "mst_latent_bwd_vec_proj: null pointer");
   LatentDx0 x0 = {dq0, dq_sample_stride, Wq, ld_wq, (int)nq, resid0, resid_sample_stride};
   return latent_bwd_vec_impl(dtype, B, De, Z, Dd, Wl, eps, Wh, classes, mu, sigma, nullptr, 0, alpha_d, kl_weight, gscale, enc_scale, dcls_d, ld_cls,
-                             d_enc_out, denc_sample_stride, scratch, x0, stream);
+                             d_enc_out, denc_sample_stride, scratch, x0, nullptr, nullptr, stream);
+}
+extern "C" int mst_latent_bwd_vec_proj_sched(int dtype, int64_t B, int64_t De, int64_t Z, int64_t Dd, const float* Wl, const float* eps,
+                                             const float* Wh, const int32_t* classes, const float* mu, const float* sigma,
+                                             const void* dq0, int64_t dq_sample_stride, const void* Wq, int64_t ld_wq, int64_t nq,
+                                             const void* resid0, int64_t resid_sample_stride, float alpha_d, const float* sched,
+                                             const float* kl, float gscale, float enc_scale, float* dcls_d, int64_t ld_cls, void* d_enc_out,
+                                             int64_t denc_sample_stride, float* scratch, mst_stream_t stream) {
+  MST_CHECK_ARG(dq0 != nullptr && Wq != nullptr && sched != nullptr && kl != nullptr, "mst_latent_bwd_vec_proj_sched: null pointer");
+  LatentDx0 x0 = {dq0, dq_sample_stride, Wq, ld_wq, (int)nq, resid0, resid_sample_stride};
+  return latent_bwd_vec_impl(dtype, B, De, Z, Dd, Wl, eps, Wh, classes, mu, sigma, nullptr, 0, alpha_d, 0.f, gscale, enc_scale, dcls_d, ld_cls,
+                             d_enc_out, denc_sample_stride, scratch, x0, sched, kl, stream);
 }
 
 namespace mst {

@@ -6,13 +6,15 @@
 
 namespace mst {
 
-// one 256-thread workgroup; red: 8 floats of LDS
-__device__ __forceinline__ void loss_combine_wg(int64_t B, const float* __restrict__ recon, const float* __restrict__ kl,
-                                                float kl_weight, float* __restrict__ total, float* __restrict__ metric,
-                                                float (*red)[4]) {
+// one 256-thread workgroup; red: 8 floats of LDS. FREE_BITS (the scheduled form, loss_combine_sched_wg): the KL charged is what
+// exceeds the per-sample allowance tau, max(kl - tau, 0); the running KL sum stays the raw one, comparable across schedules.
+template <bool FREE_BITS>
+__device__ __forceinline__ void loss_combine_body(int64_t B, const float* __restrict__ recon, const float* __restrict__ kl,
+                                                  float kl_weight, float tau, float* __restrict__ total, float* __restrict__ metric,
+                                                  float (*red)[4]) {
   float skl = 0.f, stot = 0.f;
   for (int64_t b = threadIdx.x; b < B; b += 256) {
-    const float t = recon[b] + kl_weight * kl[b];
+    const float t = recon[b] + kl_weight * (FREE_BITS ? fmaxf(kl[b] - tau, 0.f) : kl[b]);
     if (total) total[b] = t;
     skl += kl[b];
     stot += t;
@@ -26,6 +28,18 @@ __device__ __forceinline__ void loss_combine_wg(int64_t B, const float* __restri
     metric[1] += red[1][0] + red[1][1] + red[1][2] + red[1][3];
     metric[2] += (float)B;
   }
+}
+
+__device__ __forceinline__ void loss_combine_wg(int64_t B, const float* __restrict__ recon, const float* __restrict__ kl,
+                                                float kl_weight, float* __restrict__ total, float* __restrict__ metric,
+                                                float (*red)[4]) {
+  loss_combine_body<false>(B, recon, kl, kl_weight, 0.f, total, metric, red);
+}
+// ... with this step's KL weight and the free bits from the device schedule block {beta_t, tau, ...} (step_begin.hpp)
+__device__ __forceinline__ void loss_combine_sched_wg(int64_t B, const float* __restrict__ recon, const float* __restrict__ kl,
+                                                      const float* __restrict__ sched, float* __restrict__ total,
+                                                      float* __restrict__ metric, float (*red)[4]) {
+  loss_combine_body<true>(B, recon, kl, sched[0], sched[1], total, metric, red);
 }
 
 // the step guard of mst_step_metrics: true when this step must not count (uniform over the launch: every workgroup reads the

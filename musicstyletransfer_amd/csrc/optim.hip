@@ -45,12 +45,14 @@ __device__ __forceinline__ void adam_emb_store(const AdamEmb& e, int64_t i, floa
     }
 }
 
-template <typename T>
+// SCHED (mst_adam_flat_sched): the bookkeeping takes the KL weight and the free bits from the device schedule block
+template <typename T, bool SCHED>
 __global__ __launch_bounds__(256) void adam_flat_kernel(int64_t n, float* __restrict__ w, const float* __restrict__ grad,
                                                         float* __restrict__ m, float* __restrict__ v,
                                                         T* __restrict__ w16, const int32_t* __restrict__ state,
                                                         float beta1, float beta2, float eps, float wd, float rescale,
-                                                        float clip, mst_step_metrics mt, int32_t* state_rw, AdamEmb emb) {
+                                                        float clip, mst_step_metrics mt, int32_t* state_rw, AdamEmb emb,
+                                                        const float* __restrict__ sched) {
   __shared__ float red[2][4];
   bool incomplete;
   if (step_is_bad(mt, incomplete)) {
@@ -69,7 +71,10 @@ __global__ __launch_bounds__(256) void adam_flat_kernel(int64_t n, float* __rest
     }
     return;
   }
-  if (blockIdx.x == 0 && mt.recon) loss_combine_wg(mt.B, mt.recon, mt.kl, mt.kl_weight, mt.total, mt.metric, red);  // (uniform branch)
+  if (blockIdx.x == 0 && mt.recon) {  // (uniform branch)
+    if constexpr (SCHED) loss_combine_sched_wg(mt.B, mt.recon, mt.kl, sched, mt.total, mt.metric, red);
+    else loss_combine_wg(mt.B, mt.recon, mt.kl, mt.kl_weight, mt.total, mt.metric, red);
+  }
   const float lr_t = reinterpret_cast<const float*>(state)[1];
   const int64_t nvec = n / 4;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
@@ -153,7 +158,8 @@ static unsigned grid_for(int64_t n, int per_thread) {
 
 static int adam_flat_impl(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr,
                           double beta1, double beta2, float eps, float wd, float rescale, float clip,
-                          int32_t* step_state, int advance_step, const mst_step_metrics* metrics, const AdamEmb& emb, mst_stream_t stream) {
+                          int32_t* step_state, int advance_step, const mst_step_metrics* metrics, const AdamEmb& emb, const float* sched,
+                          mst_stream_t stream) {
   MST_CHECK_ARG(n > 0 && w && grad && m && v && step_state, "mst_adam_flat: bad argument");
   mst_step_metrics mt = {};
   if (metrics) {
@@ -170,8 +176,12 @@ static int adam_flat_impl(int dtype, int64_t n, float* w, const float* grad, flo
   }
   return dispatch_act(dtype, [&](auto tag) -> int {
     typedef decltype(tag) T;
-    hipLaunchKernelGGL((adam_flat_kernel<T>), dim3(grid_for(n, 4)), dim3(256), 0, s, n, w, grad, m, v, (T*)w16, step_state,
-                       (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb);
+    if (sched)
+      hipLaunchKernelGGL((adam_flat_kernel<T, true>), dim3(grid_for(n, 4)), dim3(256), 0, s, n, w, grad, m, v, (T*)w16, step_state,
+                         (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, sched);
+    else
+      hipLaunchKernelGGL((adam_flat_kernel<T, false>), dim3(grid_for(n, 4)), dim3(256), 0, s, n, w, grad, m, v, (T*)w16, step_state,
+                         (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, (const float*)nullptr);
     MST_CHECK_LAUNCH("adam_flat_kernel");
     return MST_OK;
   });
@@ -181,13 +191,22 @@ extern "C" int mst_adam_flat(int dtype, int64_t n, float* w, const float* grad, 
                              double beta1, double beta2, float eps, float wd, float rescale, float clip,
                              int32_t* step_state, int advance_step, const mst_step_metrics* metrics, mst_stream_t stream) {
   AdamEmb none = {};
-  return adam_flat_impl(dtype, n, w, grad, m, v, w16, lr, beta1, beta2, eps, wd, rescale, clip, step_state, advance_step, metrics, none, stream);
+  return adam_flat_impl(dtype, n, w, grad, m, v, w16, lr, beta1, beta2, eps, wd, rescale, clip, step_state, advance_step, metrics, none, nullptr,
+                        stream);
 }
 
-extern "C" int mst_adam_flat_emb(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
-                                 double beta2, float eps, float wd, float rescale, float clip, int32_t* step_state,
-                                 const mst_step_metrics* metrics, int64_t base, const int64_t* emb, int64_t n_emb, void* wt16,
-                                 mst_stream_t stream) {
+extern "C" int mst_adam_flat_sched(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
+                                   double beta2, float eps, float wd, float rescale, float clip, int32_t* step_state,
+                                   const mst_step_metrics* metrics, const float* sched, mst_stream_t stream) {
+  MST_CHECK_ARG(sched != nullptr, "mst_adam_flat_sched: null schedule block");
+  AdamEmb none = {};
+  return adam_flat_impl(dtype, n, w, grad, m, v, w16, lr, beta1, beta2, eps, wd, rescale, clip, step_state, 0, metrics, none, sched, stream);
+}
+
+static int adam_flat_emb_impl(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
+                              double beta2, float eps, float wd, float rescale, float clip, int32_t* step_state,
+                              const mst_step_metrics* metrics, const float* sched, int64_t base, const int64_t* emb, int64_t n_emb,
+                              void* wt16, mst_stream_t stream) {
   MST_CHECK_ARG(n_emb >= 0 && n_emb <= 2 && (n_emb == 0 || (emb && wt16)) && base >= 0, "mst_adam_flat_emb: up to two matrices, with their table and wt16");
   AdamEmb e = {};
   for (int j = 0; j < (int)n_emb; ++j) {
@@ -198,7 +217,24 @@ extern "C" int mst_adam_flat_emb(int dtype, int64_t n, float* w, const float* gr
     ++e.n;
   }
   e.wt16 = wt16;
-  return adam_flat_impl(dtype, n, w, grad, m, v, w16, lr, beta1, beta2, eps, wd, rescale, clip, step_state, 0, metrics, e, stream);
+  return adam_flat_impl(dtype, n, w, grad, m, v, w16, lr, beta1, beta2, eps, wd, rescale, clip, step_state, 0, metrics, e, sched, stream);
+}
+
+extern "C" int mst_adam_flat_emb(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
+                                 double beta2, float eps, float wd, float rescale, float clip, int32_t* step_state,
+                                 const mst_step_metrics* metrics, int64_t base, const int64_t* emb, int64_t n_emb, void* wt16,
+                                 mst_stream_t stream) {
+  return adam_flat_emb_impl(dtype, n, w, grad, m, v, w16, lr, beta1, beta2, eps, wd, rescale, clip, step_state, metrics, nullptr, base, emb, n_emb,
+                            wt16, stream);
+}
+
+extern "C" int mst_adam_flat_emb_sched(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
+                                       double beta2, float eps, float wd, float rescale, float clip, int32_t* step_state,
+                                       const mst_step_metrics* metrics, const float* sched, int64_t base, const int64_t* emb, int64_t n_emb,
+                                       void* wt16, mst_stream_t stream) {
+  MST_CHECK_ARG(sched != nullptr, "mst_adam_flat_emb_sched: null schedule block");
+  return adam_flat_emb_impl(dtype, n, w, grad, m, v, w16, lr, beta1, beta2, eps, wd, rescale, clip, step_state, metrics, sched, base, emb, n_emb,
+                            wt16, stream);
 }
 
 extern "C" int mst_transpose_shadows(int dtype, const float* w, void* wt16, const int64_t* desc,

@@ -16,7 +16,7 @@ void set_error(const char* fmt, ...) {
 
 using namespace mst;
 
-extern "C" int mst_version(void) { return 104; }
+extern "C" int mst_version(void) { return 105; }
 extern "C" const char* mst_last_error(void) { return g_err; }
 
 #define HIP_TRY(expr)                                             \
@@ -32,10 +32,41 @@ extern "C" int mst_graph_begin(mst_stream_t stream) {
   HIP_TRY(hipStreamBeginCapture((hipStream_t)stream, hipStreamCaptureModeThreadLocal));
   return MST_OK;
 }
+// node count of a captured graph and how many of the nodes are kernel launches
+static hipError_t count_nodes(hipGraph_t g, int32_t* nodes_out, int32_t* kernel_nodes_out) {
+  size_t n = 0;
+  hipError_t e = hipGraphGetNodes(g, nullptr, &n);
+  if (e != hipSuccess) return e;
+  int32_t kernels = 0;
+  if (n > 0 && kernel_nodes_out) {
+    hipGraphNode_t* nodes = new hipGraphNode_t[n];
+    e = hipGraphGetNodes(g, nodes, &n);
+    for (size_t i = 0; e == hipSuccess && i < n; ++i) {
+      hipGraphNodeType t;
+      e = hipGraphNodeGetType(nodes[i], &t);
+      kernels += (e == hipSuccess && t == hipGraphNodeTypeKernel);
+    }
+    delete[] nodes;
+    if (e != hipSuccess) return e;
+  }
+  if (nodes_out) *nodes_out = (int32_t)n;
+  if (kernel_nodes_out) *kernel_nodes_out = kernels;
+  return hipSuccess;
+}
+
 extern "C" int mst_graph_end(mst_stream_t stream, void** graph_exec_out) {
+  return mst_graph_end_counted(stream, graph_exec_out, nullptr, nullptr);
+}
+extern "C" int mst_graph_end_counted(mst_stream_t stream, void** graph_exec_out, int32_t* nodes_out, int32_t* kernel_nodes_out) {
   MST_CHECK_ARG(graph_exec_out != nullptr, "mst_graph_end: null output");
   hipGraph_t g = nullptr;
   HIP_TRY(hipStreamEndCapture((hipStream_t)stream, &g));
+  hipError_t ec = (nodes_out || kernel_nodes_out) ? count_nodes(g, nodes_out, kernel_nodes_out) : hipSuccess;
+  if (ec != hipSuccess) {
+    (void)hipGraphDestroy(g);
+    set_error("hipGraphGetNodes: %s", hipGetErrorString(ec));
+    return MST_ERR_LAUNCH;
+  }
   hipGraphExec_t ge = nullptr;
   hipError_t e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
   (void)hipGraphDestroy(g);

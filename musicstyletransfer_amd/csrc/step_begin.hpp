@@ -1,5 +1,5 @@
 // step_begin.hpp — the bookkeeping at the top of every training step (mst_step_begin): advances the RNG state, advances Adam's step
-// counter and bias-corrected learning rate, draws eps, writes the two padding masks from the sequence lengths (SequenceMask,
+// counter and bias-corrected learning rate (and, asked to, the step's training-schedule block: KL weight, free bits, lr factor), draws eps, writes the two padding masks from the sequence lengths (SequenceMask,
 // model.py:246-247; the encoder's for the piano-roll ends) and clears the loss sums and the gradient bucket. A launch of its own
 // (util.hip) or extra workgroups of the step's first GEMM launch (mst_gemm_nt_pair_begin, gemm_nt.hip): every kernel in the captured
 // graph costs ~4.7 us however small, and nothing in the embedding GEMMs depends on this.
@@ -25,7 +25,19 @@ struct StepBegin {  // mst_step_begin_args with the zero lists in 16-byte units 
   u32x4* zero_a; int64_t n16_a; u32x4* zero_b; int64_t n16_b; int n_state;
   // optional transposed-shadow refresh hosted by the same launch (mst_step_begin_args.sh_*; sh_w == nullptr: none)
   const float* sh_w; void* sh_wt16; const int64_t* sh_desc; const int64_t* sh_prefix; int sh_n_mat; int64_t sh_tiles;
+  // optional training schedules (mst_step_begin_args.sched*; sched == nullptr: none)
+  float* sched; float kl_weight, kl_free_bits; int32_t kl_warmup, kl_cycle, lr_warmup;
 };
+
+// The training schedules, pure functions of Adam's step count t (1-based), in double: the learning-rate warm-up factor f_lr and the
+// (cyclical) KL warm-up ramp. W = 0 switches a warm-up off; C > 0 restarts the KL ramp every C steps.
+__host__ __device__ inline double sched_lr_factor(int t, int W_lr) {
+  return W_lr > 0 ? fmin(1.0, (double)t / (double)W_lr) : 1.0;
+}
+__host__ __device__ inline double sched_kl_ramp(int t, int W_b, int C) {
+  const int u = C > 0 ? (t - 1) % C + 1 : t;
+  return W_b > 0 ? fmin(1.0, (double)u / (double)W_b) : 1.0;
+}
 
 // Workgroup `wg` of `nwg` (NT threads each). Every workgroup derives the new seed itself from (base seed, step counter + 1); the
 // state is written back by the workgroup that ARRIVES LAST at rng_state[3], i.e. after every other workgroup has read the old
@@ -50,7 +62,18 @@ __device__ __forceinline__ void step_begin_wg(const StepBegin& q, int wg, int nw
     const int t = q.adam_state[0] + 1;
     q.adam_state[0] = t;
     const double c1 = 1.0 - pow(q.beta1, (double)t), c2 = 1.0 - pow(q.beta2, (double)t);  // double, like the reference
-    reinterpret_cast<float*>(q.adam_state)[1] = (float)(q.lr * sqrt(c2) / c1);
+    double lr = q.lr;
+    if (q.sched) {
+      // the schedule block {beta_t, tau, f_lr, t} of this step: the latent block's backward launch and the step-closing bookkeeping
+      // read it in place of their kl_weight constant (a captured graph replays with the weight of ITS step)
+      const double f_lr = sched_lr_factor(t, q.lr_warmup);
+      lr = q.lr * f_lr;
+      q.sched[0] = (float)((double)q.kl_weight * sched_kl_ramp(t, q.kl_warmup, q.kl_cycle));
+      q.sched[1] = q.kl_free_bits;
+      q.sched[2] = (float)f_lr;
+      q.sched[3] = (float)t;
+    }
+    reinterpret_cast<float*>(q.adam_state)[1] = (float)(lr * sqrt(c2) / c1);
   }
   if (q.eps_out) {
     for (int64_t i = gid; i < (q.n_eps + 1) / 2; i += gsz) {
@@ -119,7 +142,16 @@ static inline int pack_step_begin(const mst_step_begin_args& a, StepBegin& q, in
   *grid = g;
   q = StepBegin{a.rng_state, a.adam_state, a.lr, a.beta1, a.beta2, a.eps_out, a.n_eps, a.eps_site, a.eps_index0, a.lens, a.B,
                 a.mask_e, a.Se, a.add_e, a.mask_d, a.Sd, a.add_d, (u32x4*)a.zero_a, n16_a, (u32x4*)a.zero_b, n16_b, (int)n_state,
-                nullptr, nullptr, nullptr, nullptr, 0, 0};
+                nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 0.f, 0.f, 0, 0, 0};
+  if (a.sched) {
+    MST_CHECK_ARG(a.adam_state, "mst_step_begin: the schedule block is a function of Adam's step count (adam_state)");
+    MST_CHECK_ARG(a.sched_kl_warmup >= 0 && a.sched_kl_cycle >= 0 && a.sched_lr_warmup >= 0 && a.sched_kl_free_bits >= 0.f,
+                  "mst_step_begin: schedule lengths and the free bits must not be negative");
+    MST_CHECK_ARG(a.sched_kl_cycle == 0 || (a.sched_kl_warmup > 0 && a.sched_kl_warmup <= a.sched_kl_cycle),
+                  "mst_step_begin: a KL cycle needs a warm-up no longer than the cycle");
+    q.sched = a.sched; q.kl_weight = a.sched_kl_weight; q.kl_free_bits = a.sched_kl_free_bits;
+    q.kl_warmup = a.sched_kl_warmup; q.kl_cycle = a.sched_kl_cycle; q.lr_warmup = a.sched_lr_warmup;
+  }
   if (a.sh_w) {
     MST_CHECK_ARG(a.sh_wt16 && a.sh_desc && a.sh_prefix && a.sh_n_mat > 0 && a.sh_tiles > 0 && a.sh_tiles < (1ll << 30),
                   "mst_step_begin: the shadow refresh needs w, wt16, the matrix table and its tile prefix sums");

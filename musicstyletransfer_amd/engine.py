@@ -208,9 +208,12 @@ class ParamStore:
         # step_status = three int32 words of the step guard (mst_step_metrics), read with the metrics (same device->host copy):
         # {flags, skipped steps} — sticky, set on the device when a one-launch position-0 tail (mst_row_tail_*) could not finish —
         # and the number of steps the optimizer skipped because a loss was not finite (not sticky: the next batch is tried again)
-        self._metric_buf = torch.zeros(8, **f32)
+        # sched = the fp32 schedule block {beta_t, tau, f_lr, t} the step's first launch writes for a plan with training schedules
+        # (schedule_values; mst_step_begin_args.sched*), read by that step's scheduled launches — and here, with the metrics
+        self._metric_buf = torch.zeros(12, **f32)
         self.metric_acc = self._metric_buf[:3]
         self.step_status = self._metric_buf[4:7].view(torch.int32)
+        self.sched = self._metric_buf[8:12]
         self.nonfinite_steps = 0      # steps skipped for a non-finite loss since the store was made (read_metrics adds them up)
         self.tail_fused = os.environ.get("MST_ROW_TAIL", "1") != "0"  # False: the five-launch form of the position-0 tails
         self.tail_checked = False     # row_tail_selfcheck() ran for this store
@@ -298,7 +301,10 @@ class ParamStore:
     def read_metrics(self, reset=True):
         """one device->host read of the running sums: {'kl_sum', 'total_sum', 'count'} and, for the token ends,
         {'nll_sum', 'acc_hits', 'topk_hits', 'n_tokens'} (the caller orders this after the steps it wants included).
-        The step-status words travel in the same copy: a set flag is handled here (handle_step_status)."""
+        The step-status words travel in the same copy: a set flag is handled here (handle_step_status). So does the schedule
+        block: once a plan with training schedules has run, 'kl_weight' (beta_t) and 'lr_scale' (f_lr) of the last such step.
+        (The last step that RAN: after a step the guards skipped, whose step count was taken back, the block still holds that
+        step's values until the next step's first launch writes it again from the count — training is unaffected.)"""
         buf = self._metric_buf.cpu()
         acc = buf[:3].tolist()
         flags, skipped, nonfinite = buf[4:7].view(torch.int32).tolist()
@@ -312,6 +318,9 @@ class ParamStore:
         if flags or skipped:
             self.handle_step_status(flags, skipped)
         out = {"kl_sum": acc[0], "total_sum": acc[1], "count": acc[2], "skipped_steps": skipped, "nonfinite_steps": int(nonfinite)}
+        beta_t, _, f_lr, sched_t = buf[8:12].tolist()
+        if sched_t > 0:  # (a scheduled step wrote the block)
+            out.update(kl_weight=beta_t, lr_scale=f_lr)
         if self.tok_parts is not None:
             t = self.tok_parts.cpu().double().sum(0).tolist()
             out.update(nll_sum=t[0], acc_hits=t[1], topk_hits=t[2], n_tokens=t[3])
@@ -646,7 +655,33 @@ def row_tail_selfcheck(store, B=64, S=2):
 
 # The launch forms of one issued kernel sequence (StepPlan._resolve_forms): tails — the position-0 tails as one launch; riders — GEMMs
 # riding on them; shadows — where the transposed-shadow refresh goes ('own' / 'begin' / 'tail'); the rest as named there.
-Forms = namedtuple("Forms", "tails riders shadows fuse_bce bce_dgrad skip_row0 cls_fold ffn_e ffn_d ln_bwd_e ln_bwd_d")
+# sched — the latent block's backward launch and the step-closing bookkeeping in their scheduled forms (training schedules on).
+Forms = namedtuple("Forms", "tails riders shadows fuse_bce bce_dgrad skip_row0 cls_fold ffn_e ffn_d ln_bwd_e ln_bwd_d sched")
+
+
+def check_schedule(kl_warmup_steps=0, kl_cycle_steps=0, kl_free_bits=0.0, lr_warmup_steps=0):
+    """the combinations of training-schedule settings that mean something; raises ValueError otherwise"""
+    for name, val in (("kl_warmup_steps", kl_warmup_steps), ("kl_cycle_steps", kl_cycle_steps), ("lr_warmup_steps", lr_warmup_steps)):
+        if int(val) != val or val < 0:
+            raise ValueError(f"{name} must be a non-negative integer, not {val!r}")
+    if not kl_free_bits >= 0:
+        raise ValueError(f"kl_free_bits must be >= 0 nats per sample, not {kl_free_bits!r}")
+    if kl_cycle_steps > 0 and kl_warmup_steps == 0:
+        raise ValueError("kl_cycle_steps restarts the KL warm-up: it needs kl_warmup_steps > 0")
+    if kl_cycle_steps > 0 and kl_warmup_steps > kl_cycle_steps:
+        raise ValueError(f"kl_warmup_steps ({kl_warmup_steps}) must not exceed kl_cycle_steps ({kl_cycle_steps})")
+
+
+def schedule_values(t, kl_weight=1.0, kl_warmup_steps=0, kl_cycle_steps=0, lr_warmup_steps=0):
+    """(beta_t, f_lr) of training step t (Adam's step count after the step's increment, 1-based) — the formulas the device evaluates
+    (step_begin.hpp), stated once for the host. Double arithmetic; beta_t is rounded once, to fp32, and returned as that value:
+        f_lr   = min(1, t / W_lr) if W_lr > 0 else 1                 the step runs at lr * f_lr
+        u      = ((t - 1) mod C) + 1 if C > 0 else t                 position in the current KL cycle
+        beta_t = fp32(fp32(kl_weight) * (min(1, u / W_b) if W_b > 0 else 1))"""
+    f_lr = min(1.0, t / lr_warmup_steps) if lr_warmup_steps > 0 else 1.0
+    u = (t - 1) % kl_cycle_steps + 1 if kl_cycle_steps > 0 else t
+    ramp = min(1.0, u / kl_warmup_steps) if kl_warmup_steps > 0 else 1.0
+    return float(np.float32(float(np.float32(kl_weight)) * ramp)), f_lr
 
 
 class StepPlan:
@@ -654,8 +689,11 @@ class StepPlan:
 
     def __init__(self, store, B, T, lr=3e-4, clip_gradient=1.0, kl_weight=1.0, label_smoothing=0.0,
                  negative_label_downscaling=False, global_batch=None, gscale=None, want_probs=False, seed=0,
-                 internal_eps=False, optimizer_params=None, sample_offset=0, site_base=0):
-        """sample_offset: index of this plan's first sample in the global batch (data parallel: rank * B) — the in-graph eps
+                 internal_eps=False, optimizer_params=None, sample_offset=0, site_base=0,
+                 kl_warmup_steps=0, kl_cycle_steps=0, kl_free_bits=0.0, lr_warmup_steps=0):
+        """kl_warmup_steps / kl_cycle_steps / kl_free_bits / lr_warmup_steps: the training schedules (schedule_values),
+        evaluated on the device from Adam's step count. All zero (the default): the plain launches with their constants.
+        sample_offset: index of this plan's first sample in the global batch (data parallel: rank * B) — the in-graph eps
         is drawn per GLOBAL sample index, so the result does not depend on the sharding.
         site_base: added to every dropout site id (data parallel: a different value per rank gives every rank its own
         masks under the common step seed)."""
@@ -663,6 +701,10 @@ class StepPlan:
         self.store, self.cfg, self.B, self.T = store, cfg, B, T
         self.dev, self.adt = store.device, store.act_dtype
         self.lr, self.clip, self.kl_weight = lr, clip_gradient, kl_weight
+        check_schedule(kl_warmup_steps, kl_cycle_steps, kl_free_bits, lr_warmup_steps)
+        self.schedule = dict(kl_warmup_steps=int(kl_warmup_steps), kl_cycle_steps=int(kl_cycle_steps), kl_free_bits=float(kl_free_bits),
+                             lr_warmup_steps=int(lr_warmup_steps))
+        self.scheduled = any(self.schedule.values())  # resolved once: the scheduled launches, or the plain ones
         self.ls, self.nld = label_smoothing, negative_label_downscaling
         self.global_batch = global_batch or B
         self.sample_offset, self.site_base = int(sample_offset), int(site_base)
@@ -860,7 +902,10 @@ class StepPlan:
                       st.offsets["encoder.class2hid.weight"] == st.offsets["encoder.embedding.weight"] + cfg.in_dim * De),
             # the row-wise block of a layer as one launch forward / backward (row_block_fwd / _bwd 'fused'), and Dense dgrad +
             # LayerNorm backward in one launch (row_block_bwd 'ln_fused', the chain of leading LayerNorm backwards: _out_ln_bwd)
-            ffn_e=o.ffn_fusion_pays(De, 4 * De), ffn_d=ffn_d, ln_bwd_e=o.ln_bwd_fusion_pays(De), ln_bwd_d=ln_bwd_d)
+            ffn_e=o.ffn_fusion_pays(De, 4 * De), ffn_d=ffn_d, ln_bwd_e=o.ln_bwd_fusion_pays(De), ln_bwd_d=ln_bwd_d,
+            # training schedules: KL weight, free bits and lr warm-up from the device schedule block (training steps only — a
+            # validation step keeps the constants: its objective must not move with the schedule)
+            sched=self.scheduled)
 
     def _guard(self):
         """step guard of the launches that close a step (optimizer / loss_combine): the barrier counters of the one-launch
@@ -1065,6 +1110,8 @@ class StepPlan:
                      zero_a=self._recon_buf, zero_b=st.g if tick else None)
         if F.shadows == "begin":
             begin["shadows"] = self._late_shadows()
+        if F.sched and tick:  # the thread that ticks Adam writes this step's schedule block
+            begin["schedule"] = dict(block=st.sched, kl_weight=self.kl_weight, **self.schedule)
         # (piano-roll ends: nothing in the embedding GEMMs reads what the bookkeeping writes — it rides on their launch)
         ride = cfg.kind != "token"
         if not ride:
@@ -1295,7 +1342,7 @@ class StepPlan:
         o.latent_bwd_vec(st.p("encoder.latent_proj.weight"), self.eps, st.p("decoder.latent2hid.weight"), self.classes, self.mu,
                          self.sigma, d_x0_d.view(B, Sd, -1), sq_d, self.kl_weight, self.gscale_enc,
                          st.grad("decoder.class2hid.weight"), d_enc.view(B, Se, -1), self.lat_scratch,
-                         enc_scale=self.gscale_enc / self.gscale, proj=dx0)
+                         enc_scale=self.gscale_enc / self.gscale, proj=dx0, sched=(st.sched, self.kl) if F.sched else None)
         self._outers += o.latent_outer_jobs(self.lat_scratch, self.enc_out.view(B, Se, -1), self.z,
                                             st.grad("encoder.latent_proj.weight"), st.grad("encoder.latent_proj.bias"),
                                             st.grad("decoder.latent2hid.weight"), st.grad("decoder.latent2hid.bias"))
@@ -1335,6 +1382,7 @@ class StepPlan:
     def optimizer(self):
         st = self.store
         deferred = self.forms.shadows != "own"
+        sched = st.sched if self.forms.sched else None  # (the launch that carries the bookkeeping reads it)
         clip = self.clip if self.clip is not None else -1.0
         # end-of-step bookkeeping (total loss, running metric sums) on the first Adam launch: losses(combine=False)
         guard = self._guard()
@@ -1342,7 +1390,8 @@ class StepPlan:
         emb = (lambda base: dict(base=base, specs=st.emb_specs, wt16=st.wt16)) if deferred else (lambda base: None)
         if self.gscale == self.gscale_enc:
             o.adam_flat(st.w, st.g, st.m, st.v, st.w16, st.step_state, lr=self.lr,
-                        rescale=1.0 / (self.global_batch * self.gscale), clip=clip, advance_step=False, metrics=mt, emb=emb(0), **self.opt)
+                        rescale=1.0 / (self.global_batch * self.gscale), clip=clip, advance_step=False, metrics=mt, emb=emb(0),
+                        sched=sched, **self.opt)
         else:
             # encoder.* tensors come first in the flat buffers; everything from decoder.latent2hid on is decoder-side.
             # NOTE the latent_proj gradients are produced by latent_bwd_vec at the encoder-side scale.
@@ -1351,7 +1400,7 @@ class StepPlan:
             for a, b, gs, adv in rng:
                 o.adam_flat(st.w[a:b], st.g[a:b], st.m[a:b], st.v[a:b], st.w16[a:b], st.step_state, lr=self.lr,
                             rescale=1.0 / (self.global_batch * gs), clip=clip, advance_step=adv,
-                            metrics=mt if a == 0 else (guard or None), emb=emb(a), **self.opt)
+                            metrics=mt if a == 0 else (guard or None), emb=emb(a), sched=sched if a == 0 else None, **self.opt)
         if not deferred:  # (deferred: the next step's first launch rebuilds them, forward())
             o.transpose_shadows(st.w, st.wt16, st.t_desc, st.t_prefix, len(st.t_specs), st.t_tiles)
 
@@ -1396,6 +1445,11 @@ class StepPlan:
             self.graph_opt = None
         return self
 
+    def graph_nodes(self):
+        """(nodes, kernel launches among them) of the captured step, summed over its graphs"""
+        gs = [g for g in (self.graph, self.graph_late, self.graph_opt) if g is not None]
+        return sum(g.nodes for g in gs), sum(g.kernel_nodes for g in gs)
+
     def run(self, reduce_fn=None, reducer=None, stamps=None):
         """Replay the captured step. reduce_fn(flat): blocking-in-stream-order all-reduce of the whole bucket between the
         two graphs. reducer (parallel.GradReducer): asynchronous per-range all-reduce, used with capture(overlap=True).
@@ -1434,4 +1488,6 @@ class StepPlan:
         """(kl_loss, total_loss) batch means accumulated on the device (trainer.py:115-116,185-186); one sync."""
         m = self.store.read_metrics(reset)
         n = max(m["count"], 1.0)
-        return {"kl_loss": m["kl_sum"] / n, "total_loss": m["total_sum"] / n, "count": m["count"], "nonfinite_steps": m["nonfinite_steps"]}
+        return {"kl_loss": m["kl_sum"] / n, "total_loss": m["total_sum"] / n, "count": m["count"], "nonfinite_steps": m["nonfinite_steps"],
+                "kl_weight": m.get("kl_weight", self.kl_weight) if self.scheduled else self.kl_weight,
+                "lr_scale": m.get("lr_scale", 1.0) if self.scheduled else 1.0}

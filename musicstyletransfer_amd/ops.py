@@ -627,20 +627,26 @@ def latent_rows(zsrc, ssrc, a, b, w, ca, cb, cw, Wh, bh, cls_d, pos_d, alpha_d, 
 
 
 def latent_bwd_vec(Wl, eps, Wh, classes, mu, sigma, d_dec_in3, alpha_d, kl_weight, gscale, dcls_d, d_enc_out3, scratch, enc_scale=1.0,
-                   proj=None):
+                   proj=None, sched=None):
     """the latent block's backward pass with the decoder class table's gradient folded in (mst_latent_bwd_vec); the other parameter
     gradients are latent_outer_jobs(...) of the caller's weight-gradient flush.
     proj = (dqkv3 [B, S, >= nq], Wt [Dd, nq] the transposed 16-bit weight, resid3 [B, S, Dd] or None): d(dec_in[:, 0, :]) is computed
-    here from the projection's gradient at position 0 instead of being read from d_dec_in3 (mst_latent_bwd_vec_proj)"""
+    here from the projection's gradient at position 0 instead of being read from d_dec_in3 (mst_latent_bwd_vec_proj).
+    sched = (block, kl): the scheduled forms (mst_latent_bwd_vec*_sched) — the device schedule block of step_begin {beta_t, tau, ...}
+    and the forward pass's per-sample kl [B] replace kl_weight, which is then ignored: beta_t where kl[b] > tau, else 0"""
     B, De, Z, Dd = d_dec_in3.shape[0], Wl.shape[1], Wh.shape[1], Wh.shape[0]
+    if sched is not None:
+        assert sched[0].dtype == sched[1].dtype == torch.float32 and sched[0].numel() >= 4 and sched[1].numel() == B
+    weight = (kl_weight,) if sched is None else (ptr(sched[0]), ptr(sched[1]))
+    suffix = "" if sched is None else "_sched"
     if proj is not None:
         dq3, Wt, r3 = proj
-        call("mst_latent_bwd_vec_proj", dt(dq3), B, De, Z, Dd, ptr(Wl), ptr(eps), ptr(Wh), ptr(classes), ptr(mu), ptr(sigma),
-             ptr(dq3), dq3.stride(0), ptr(Wt), ld(Wt), 3 * Dd, ptr(r3), (r3.stride(0) if r3 is not None else 0), alpha_d, kl_weight,
+        call("mst_latent_bwd_vec_proj" + suffix, dt(dq3), B, De, Z, Dd, ptr(Wl), ptr(eps), ptr(Wh), ptr(classes), ptr(mu), ptr(sigma),
+             ptr(dq3), dq3.stride(0), ptr(Wt), ld(Wt), 3 * Dd, ptr(r3), (r3.stride(0) if r3 is not None else 0), alpha_d, *weight,
              gscale, enc_scale, ptr(dcls_d), dcls_d.stride(0), ptr(d_enc_out3), d_enc_out3.stride(0), ptr(scratch), stream())
         return
-    call("mst_latent_bwd_vec", dt(d_dec_in3), B, De, Z, Dd, ptr(Wl), ptr(eps), ptr(Wh), ptr(classes), ptr(mu), ptr(sigma),
-         ptr(d_dec_in3), d_dec_in3.stride(0), alpha_d, kl_weight, gscale, enc_scale, ptr(dcls_d), dcls_d.stride(0), ptr(d_enc_out3),
+    call("mst_latent_bwd_vec" + suffix, dt(d_dec_in3), B, De, Z, Dd, ptr(Wl), ptr(eps), ptr(Wh), ptr(classes), ptr(mu), ptr(sigma),
+         ptr(d_dec_in3), d_dec_in3.stride(0), alpha_d, *weight, gscale, enc_scale, ptr(dcls_d), dcls_d.stride(0), ptr(d_enc_out3),
          d_enc_out3.stride(0), ptr(scratch), stream())
 
 
@@ -726,16 +732,25 @@ def loss_combine(recon, kl, kl_weight, total=None, metric_acc=None, guard=None):
 
 # --------------------------------------------------------------------------- optimizer / shadows
 def adam_flat(w, grad, m, v, w16, step_state, lr, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.0, rescale=1.0, clip=-1.0,
-              advance_step=True, metrics=None, emb=None):
+              advance_step=True, metrics=None, emb=None, sched=None):
     """metrics: dict(recon, kl, kl_weight, total, metric) -> loss_combine's bookkeeping runs in this launch;
-    + status / expect: the step guard (_step_metrics)"""
+    + status / expect: the step guard (_step_metrics).
+    sched: the device schedule block of step_begin {beta_t, tau, ...} — the bookkeeping charges total = recon + beta_t * max(kl - tau, 0)
+    instead of recon + kl_weight * kl (mst_adam_flat_sched / mst_adam_flat_emb_sched; the step count is step_begin's: no advance_step)"""
     mt = _step_metrics(metrics) if metrics is not None else None
+    if sched is not None:
+        assert not advance_step and sched.dtype == torch.float32 and sched.numel() >= 4
+    block = () if sched is None else (ptr(sched),)
     if emb is not None:  # (the optimizer keeps the transposed shadows of these matrices current: mst_adam_flat_emb)
         assert not advance_step
         flat = [int(x) for spec in emb["specs"] for x in spec]
-        call("mst_adam_flat_emb", dt(w16), w.numel(), ptr(w), ptr(grad), ptr(m), ptr(v), ptr(w16), lr, beta1, beta2, eps, wd, rescale, clip,
-             ptr(step_state), C.byref(mt) if mt is not None else None, emb.get("base", 0), (_lib.c_i64 * len(flat))(*flat), len(emb["specs"]),
-             ptr(emb["wt16"]), stream())
+        call("mst_adam_flat_emb" + ("_sched" if sched is not None else ""), dt(w16), w.numel(), ptr(w), ptr(grad), ptr(m), ptr(v), ptr(w16),
+             lr, beta1, beta2, eps, wd, rescale, clip, ptr(step_state), C.byref(mt) if mt is not None else None, *block, emb.get("base", 0),
+             (_lib.c_i64 * len(flat))(*flat), len(emb["specs"]), ptr(emb["wt16"]), stream())
+        return
+    if sched is not None:
+        call("mst_adam_flat_sched", dt(w16), w.numel(), ptr(w), ptr(grad), ptr(m), ptr(v), ptr(w16), lr, beta1, beta2, eps, wd,
+             rescale, clip, ptr(step_state), C.byref(mt) if mt is not None else None, *block, stream())
         return
     call("mst_adam_flat", dt(w16), w.numel(), ptr(w), ptr(grad), ptr(m), ptr(v), ptr(w16), lr, beta1, beta2, eps, wd,
          rescale, clip, ptr(step_state), 1 if advance_step else 0, C.byref(mt) if mt is not None else None, stream())
@@ -775,9 +790,11 @@ def randn(out, seed=0, seed_ptr=None, site=0):
 
 
 def _step_begin_args(rng_state=None, adam_state=None, lr=0.0, beta1=0.9, beta2=0.999, eps_out=None, eps_site=0x7FFF0000, eps_index0=0,
-                     lens=None, mask_e=None, add_e=0, mask_d=None, add_d=1, zero_a=None, zero_b=None, shadows=None):
+                     lens=None, mask_e=None, add_e=0, mask_d=None, add_d=1, zero_a=None, zero_b=None, shadows=None, schedule=None):
     """shadows: dict(w, wt16, desc, prefix, n_mat, tiles) — a transposed-shadow refresh (transpose_shadows' arguments) hosted by the
-    launch that carries the bookkeeping"""
+    launch that carries the bookkeeping.
+    schedule: dict(block, kl_weight, kl_warmup_steps, kl_cycle_steps, kl_free_bits, lr_warmup_steps) — the thread that advances Adam's
+    step count also writes the fp32 schedule block {beta_t, tau, f_lr, t} and puts the warm-up factor into lr_t (mst_step_begin_args.sched*)"""
     q = StepBeginArgs()
     nbytes = lambda t: t.numel() * t.element_size() if t is not None else 0
     q.rng_state, q.adam_state, q.lr, q.beta1, q.beta2 = ptr(rng_state), ptr(adam_state), lr, beta1, beta2
@@ -789,6 +806,12 @@ def _step_begin_args(rng_state=None, adam_state=None, lr=0.0, beta1=0.9, beta2=0
     if shadows:
         q.sh_dtype, q.sh_w, q.sh_wt16 = dt(shadows["wt16"]), ptr(shadows["w"]), ptr(shadows["wt16"])
         q.sh_desc, q.sh_prefix, q.sh_n_mat, q.sh_tiles = ptr(shadows["desc"]), ptr(shadows["prefix"]), shadows["n_mat"], shadows["tiles"]
+    if schedule:
+        block = schedule["block"]
+        assert block.dtype == torch.float32 and block.numel() >= 4
+        q.sched, q.sched_kl_weight, q.sched_kl_free_bits = ptr(block), schedule["kl_weight"], schedule.get("kl_free_bits", 0.0)
+        q.sched_kl_warmup, q.sched_kl_cycle = int(schedule.get("kl_warmup_steps", 0)), int(schedule.get("kl_cycle_steps", 0))
+        q.sched_lr_warmup = int(schedule.get("lr_warmup_steps", 0))
     return q
 
 
@@ -810,14 +833,17 @@ class Graph:
 
     def __init__(self):
         self.exec = C.c_void_p()
+        self.nodes = self.kernel_nodes = None  # of the captured graph: every node / the kernel launches among them
 
     def capture(self, fn):
         st = stream()
+        n, k = C.c_int32(), C.c_int32()
         call("mst_graph_begin", st)
         try:
             fn()
         finally:
-            call("mst_graph_end", st, C.byref(self.exec))
+            call("mst_graph_end_counted", st, C.byref(self.exec), C.byref(n), C.byref(k))
+        self.nodes, self.kernel_nodes = n.value, k.value
         return self
 
     def launch(self):
