@@ -233,6 +233,19 @@ int mst_ffn_ln_bwd_lead(const mst_ln_bwd_in* lead, const mst_gemm_args* ff2_dgra
  * The projection is width x width (N = K = the model width) on the same M rows. Same results as the separate launches. */
 int mst_proj_ffn_ln_fwd(const mst_gemm_args* proj, const mst_ln_args* ln1, const mst_gemm_args* ff1, const mst_gemm_args* ff2,
                         const mst_ln_args* ln2, mst_stream_t stream);
+/* The last decoder layer's row-wise block, the loss and their backward in ONE launch — three consecutive launches of a training
+ * step whose 64-row tiles coincide, as consecutive phases of one workgroup:
+ *     mst_proj_ffn_ln_fwd(proj, ln1, ff1, ff2, ln3)
+ *     mst_gemm_sigmoid_bce_dgrad_ln(out, bce, out_dgrad, ln3_bwd)
+ *     mst_ffn_ln_bwd(ff2_dgrad, ff1_dgrad, ln1_bwd)
+ * with bit-identical results in every tensor they store (the per-sample loss sums are atomics, as there). Each phase hands its tile
+ * to the next on chip. Accepted: model width 128, hidden width 512, 128 pitches, T % 64 == 0, whole 64-row tiles, row groups
+ * (T, T + 1, 1) on all three parts, ln3_bwd->mask_mode 2, out->A == ln3->out, out_dgrad->A == out->C, ff2_dgrad->A == out_dgrad->C.
+ * Anything else is an error (MST_ERR_INVALID before any HIP call): the caller issues the three launches. */
+int mst_dec_tail_step(const mst_gemm_args* proj, const mst_ln_args* ln1, const mst_gemm_args* ff1, const mst_gemm_args* ff2,
+                      const mst_ln_args* ln3, const mst_gemm_args* out, const mst_bce_args* bce, const mst_gemm_args* out_dgrad,
+                      const mst_ln_args* ln3_bwd, const mst_gemm_args* ff2_dgrad, const mst_gemm_args* ff1_dgrad,
+                      const mst_ln_args* ln1_bwd, mst_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Deferred column sums: dst[0..len) += scale * sum_{p < n_parts} src[p*stride + 0..len), parts added in index order

@@ -311,16 +311,14 @@ __global__ __launch_bounds__(WGM * WGN * 64) void gemm_nt_ln_kernel(mst_gemm_arg
 // form reads back. A tile holds rows of ONE sample (the host requires T % 64 == 0): one atomic per workgroup.
 // keepA (KEEP): the logit-gradient tile ALSO goes to LDS as the A operand of a GEMM that follows in the same launch, in
 // gemm_mainloop's stage layout (BK = 64: columns [64 s, 64 s + 64) in stage buffer s, 16-byte chunks XOR-swizzled by the row)
-template <typename T, int BN, bool KEEP>
-__device__ __forceinline__ void gemm_bce_tile(const mst_gemm_args& a, const mst_bce_args& q, unsigned char* smem, float* red, u32x4* keepA) {
+// bce_tile_finish: the tile's epilogue, from the fp32 accumulators of the 64 x BN logit tile at (m0, n0). KEEP 1: the stage layout
+// above; KEEP 2: the kept tile is row-major with a row stride of BN + 8 elements (ffn_ln_body's x tile: dec_tail_kernel).
+template <typename T, int BN, int KEEP>
+__device__ __forceinline__ void bce_tile_finish(const mst_gemm_args& a, const mst_bce_args& q, unsigned char* smem, float* red, u32x4* keepA,
+                                                f32x4 (&acc)[(BN / 4) / 16][(64 / 2) / 16], int64_t m0, int64_t n0, const float (&bias8)[8]) {
   constexpr int BM = 64, WGM = 2, WGN = 4, NT = 512;
   constexpr int WTM = BM / WGM, WTN = BN / WGN, TM = WTM / 16, TN = WTN / 16;
   constexpr int LDS_F = BN + 4, CPR = BN / 8, RSTEP = NT / CPR, ITERS = BM / RSTEP;
-  f32x4 acc[TN][TM];
-  int64_t m0, n0;
-  float bias8[8];
-  gemm_bias_preload<BM, BN>(a, bias8);
-  gemm_mainloop<T, BM, BN, WGM, WGN, 64>(a, smem, acc, m0, n0);
   const int64_t P = a.N;                       // pitches per frame (a multiple of BN: this tile holds columns [n0, n0 + BN))
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WGN, wn = wave % WGN, frow = lane & 15, fq = lane >> 4;
@@ -390,7 +388,8 @@ __device__ __forceinline__ void gemm_bce_tile(const mst_gemm_args& a, const mst_
       }
       if (!live) continue;
       if (a.C) *reinterpret_cast<u32x4*>(reinterpret_cast<T*>(a.C) + m * a.ldc + gc) = gb.u;
-      if constexpr (KEEP) keepA[(ch >> 3) * (BM * 8) + row * 8 + ((ch & 7) ^ (row & 7))] = gb.u;  // (KEEP: P == BN)
+      if constexpr (KEEP == 1) keepA[(ch >> 3) * (BM * 8) + row * 8 + ((ch & 7) ^ (row & 7))] = gb.u;  // (KEEP: P == BN)
+      if constexpr (KEEP == 2) *reinterpret_cast<u32x4*>(reinterpret_cast<T*>(keepA) + row * (BN + 8) + nc) = gb.u;
       if (q.probs) *reinterpret_cast<u32x4*>(reinterpret_cast<T*>(q.probs) + m * q.ldp + gc) = pb.u;
       if (q.logits) *reinterpret_cast<u32x4*>(reinterpret_cast<T*>(q.logits) + m * q.ldl + gc) = xb.u;
     }
@@ -405,6 +404,17 @@ __device__ __forceinline__ void gemm_bce_tile(const mst_gemm_args& a, const mst_
     for (int i = 0; i < NT / 64; ++i) tot += red[i];
     atomicAdd(q.loss + b, tot * inv_n);
   }
+}
+
+template <typename T, int BN, bool KEEP>
+__device__ __forceinline__ void gemm_bce_tile(const mst_gemm_args& a, const mst_bce_args& q, unsigned char* smem, float* red, u32x4* keepA) {
+  constexpr int BM = 64, WGM = 2, WGN = 4;
+  f32x4 acc[(BN / WGN) / 16][(BM / WGM) / 16];
+  int64_t m0, n0;
+  float bias8[8];
+  gemm_bias_preload<BM, BN>(a, bias8);
+  gemm_mainloop<T, BM, BN, WGM, WGN, 64>(a, smem, acc, m0, n0);
+  bce_tile_finish<T, BN, KEEP ? 1 : 0>(a, q, smem, red, keepA, acc, m0, n0, bias8);
 }
 
 template <typename T, int BN>
@@ -501,10 +511,19 @@ static int launch_gemm_bce(const mst_gemm_args& a, const mst_bce_args& q, hipStr
 // (gx, lnx) into the x tile (and stored, with h1 and the statistics, for the backward pass). (The mirror image — the projection's
 // dgrad behind the backward block — and a form with every wave loading its own weight fragments straight into MFMA operand
 // registers were built, measured slower / not worth a third shadow layout, and removed: docs/kernel_notes.md.)
-template <typename T, int BN, int WGM, int WGN, int MODE, bool LEAD, bool FULL, bool EXTRA = false>
-__global__ __launch_bounds__(WGM * WGN * 64) void ffn_ln_kernel(mst_gemm_args g1, mst_gemm_args g2, mst_ln_args ln, mst_ln_bwd_in lead,
-                                                                mst_gemm_args gx, mst_ln_args lnx) {
+// The block is a device function (ffn_ln_body) so that a launch can run it as one of several phases of a workgroup (dec_tail_kernel):
+//   X_IN_LDS   the input tile already sits in the x tile (the previous phase's epilogue left it there): it is not loaded
+//   KEEP_OUT   the last epilogue's result rows ALSO stay in the x tile (gemm_epilogue_ln's lds_out), for the phase that follows
+//   PAR_READY  the first GEMM's bias and bias | gamma | beta of the last epilogue already wait at `par` ([F][3 BN] floats)
+//   before_epilogue()  called in front of the last epilogue (the next phase's first loads, whose latency then runs under it)
+// The argument structs come by value: the row-group form rewrites their M, and the compiler sees private copies, as in a kernel.
+template <typename T, int BN, int WGM, int WGN, int MODE, bool LEAD, bool FULL, bool EXTRA, bool X_IN_LDS = false, bool KEEP_OUT = false,
+          bool PAR_READY = false, typename Hook>
+__device__ __forceinline__ void ffn_ln_body(unsigned char* smem, mst_gemm_args g1, mst_gemm_args g2, const mst_ln_args ln,
+                                            const mst_ln_bwd_in lead, mst_gemm_args gx, const mst_ln_args lnx, float* par,
+                                            Hook&& before_epilogue) {
   constexpr bool HEAD = EXTRA;
+  static_assert(!(X_IN_LDS && (LEAD || EXTRA)), "a tile left in LDS is the block's own input");
   static_assert(!EXTRA || MODE == 1, "the extra GEMM is the forward form's head");
   constexpr int BM = 64, BK = 64, CHUNKS = BK / 8;
   constexpr int NT = WGM * WGN * 64;
@@ -514,13 +533,12 @@ __global__ __launch_bounds__(WGM * WGN * 64) void ffn_ln_kernel(mst_gemm_args g1
   constexpr int KST = BN / BK;                 // K stages of one GEMM of a chunk (K = BN for both)
   static_assert(BN * CHUNKS % NT == 0 && (BM * BN / 8) % NT == 0, "tile/threads mismatch");
   typedef typename Act<T>::vec8 vec8;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // [weight stages 2 x BN x 64][hidden chunk 64 x LDA][x tile 64 x LDA]; the LayerNorm epilogue's fp32 staging tile reuses
   // the first two regions (both dead by then)
   u32x4* sB = reinterpret_cast<u32x4*>(smem);
   T* sH = reinterpret_cast<T*>(smem + (size_t)2 * BN * BK * 2);
   T* sX = sH + BM * LDA;
-  float* sBias1 = reinterpret_cast<float*>(sX + BM * LDA);  // [F] the first GEMM's bias (zeros without one)
+  float* sBias1 = PAR_READY ? par : reinterpret_cast<float*>(sX + BM * LDA);  // [F] the first GEMM's bias (zeros without one)
   float* sPar = sBias1 + g1.N;   // [2][3 BN]: bias | gamma | beta of the final epilogue, then of the head's (EXTRA forward)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WGN, wn = wave % WGN, frow = lane & 15, fq = lane >> 4;
@@ -540,11 +558,13 @@ __global__ __launch_bounds__(WGM * WGN * 64) void ffn_ln_kernel(mst_gemm_args g1
   const int64_t F = g1.N;
   FFN_STAMP(0); FFN_RT(190);
   const int64_t Mg = FULL ? (int64_t)1 << 62 : g1.M;  // row guards compare against this (FULL: always true, folded away)
+  if constexpr (!PAR_READY)
   for (int i = tid * 4; i < (int)F; i += NT * 4)
     *reinterpret_cast<f32x4*>(sBias1 + i) = g1.bias ? *reinterpret_cast<const f32x4*>(g1.bias + i) : f32x4{0.f, 0.f, 0.f, 0.f};
   // (the step's dropout seed words too: a scalar load at an epilogue's start is one more exposed round trip)
   const uint64_t seed2 = g2.dropout_seed ^ ((g2.dropout_p > 0.f && g2.dropout_seed_ptr) ? g2.dropout_seed_ptr[0] : 0ull);
   const uint64_t seedx = EXTRA ? gx.dropout_seed ^ ((gx.dropout_p > 0.f && gx.dropout_seed_ptr) ? gx.dropout_seed_ptr[0] : 0ull) : 0ull;
+  if constexpr (!PAR_READY)
   for (int i = tid; i < BN; i += NT) {
     sPar[i] = g2.bias ? g2.bias[i] : 0.f;
     sPar[BN + i] = ln.gamma[i];
@@ -711,7 +731,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void ffn_ln_kernel(mst_gemm_args g1
       else atomicAdd((which ? lead.dbeta : lead.dgamma) + col, sm);
     }
     __syncthreads();  // the scratch becomes the first weight stage
-  } else
+  } else if constexpr (!X_IN_LDS)
   // ---- the x tile (rows past M read as zero)
   {
     // (HEAD: the attention output tile, the extra GEMM's A operand; the block's own input is computed from it below)
@@ -931,8 +951,18 @@ __global__ __launch_bounds__(WGM * WGN * 64) void ffn_ln_kernel(mst_gemm_args g1
   // (a residual that IS the block's input — the encoder's x1 + dropout(ff) — is taken from the x tile in LDS)
   const bool resid_is_x = g2.resid == g1.A && g2.ldr == g1.lda;
   FFN_STAMP(2);
-  gemm_epilogue_ln<T, BM, BN, WGM, WGN, MODE>(g2, ln, smem, acc2, m0, resid_is_x ? sX : nullptr, LDA, nullptr, 0, sPar, &seed2);
+  before_epilogue();
+  // (KEEP_OUT with the residual in the x tile: a thread reads its own residual pieces before it writes the same pieces back)
+  gemm_epilogue_ln<T, BM, BN, WGM, WGN, MODE>(g2, ln, smem, acc2, m0, resid_is_x ? sX : nullptr, LDA, KEEP_OUT ? sX : nullptr, KEEP_OUT ? LDA : 0,
+                                              sPar, &seed2);
   FFN_STAMP(3); FFN_RT(191);
+}
+
+template <typename T, int BN, int WGM, int WGN, int MODE, bool LEAD, bool FULL, bool EXTRA = false>
+__global__ __launch_bounds__(WGM * WGN * 64) void ffn_ln_kernel(mst_gemm_args g1, mst_gemm_args g2, mst_ln_args ln, mst_ln_bwd_in lead,
+                                                                mst_gemm_args gx, mst_ln_args lnx) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  ffn_ln_body<T, BN, WGM, WGN, MODE, LEAD, FULL, EXTRA>(smem, g1, g2, ln, lead, gx, lnx, nullptr, [] {});
 }
 
 template <typename T, int BN>
@@ -963,6 +993,148 @@ static int launch_ffn_ln(const mst_gemm_args& g1, const mst_gemm_args& g2, const
   hipLaunchKernelGGL(fns[mi], dim3((unsigned)cdiv(g1.M, BM)), dim3(512), lds, s, g1, g2, ln, lead ? *lead : none,
                      gx ? *gx : no_gemm, lnx ? *lnx : no_ln);
   MST_CHECK_LAUNCH("ffn_ln_kernel");
+  return MST_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The last decoder layer's row-wise block, the loss and their backward in ONE launch (mst_dec_tail_step): width 128, 128 pitches,
+// whole 64-row tiles. A workgroup runs on its tile what were three consecutive launches of identical grids:
+//   1  mst_proj_ffn_ln_fwd            ffn_ln_body, forward with the projection head; x2 = LayerNorm-3's output stays in the x tile
+//   2  mst_gemm_sigmoid_bce           logits = x2 W_out^T from that tile, bce_tile_finish; the logit gradient stays in the x tile
+//   3  ... _dgrad_ln                  dh = LayerNorm-3 backward(dlogits W_out) (gemm_epilogue_ln mode 2); dh stays in the x tile
+//   4  mst_ffn_ln_bwd                 ffn_ln_body, backward, its input tile in LDS
+// Every tensor the separate launches store is stored here too (the weight-gradient launch and the layers below read them), and what a
+// later phase reads back from global memory (h2 and its statistics, a, h1) was written by the SAME workgroup: a barrier orders it.
+// Same tile per workgroup (xcd_chunk), same chunk rotation, same K order, same epilogues: bit-identical results. Two launch floors,
+// two cold prologues and two chip-wide drains go. No data crosses between workgroups.
+// The two middle GEMMs (K = 128: two 64-deep stages) take their A operand from the x tile with mma_stage's arithmetic, both weight
+// stages loaded to registers while the previous phase's epilogue runs.
+template <typename T>
+__device__ __forceinline__ void tile128_load_w(const mst_gemm_args& g, u32x4 (&rw)[2][2]) {
+  const T* __restrict__ W = reinterpret_cast<const T*>(g.B);
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int c = threadIdx.x + i * 512, row = c / 8, ch = c % 8;
+      rw[s][i] = *reinterpret_cast<const u32x4*>(W + (int64_t)row * g.ldb + s * 64 + ch * 8);
+    }
+}
+// acc = A[64, 128] (x tile `sA`, row stride 136) x W[128, 128]^T (`rw`); the caller's barrier has freed the first 32 KB of smem and
+// completed the tile; on return every wave has passed the last barrier
+template <typename T>
+__device__ __forceinline__ void tile128_gemm(unsigned char* smem, const T* sA, const u32x4 (&rw)[2][2], f32x4 (&acc)[2][2]) {
+  constexpr int BN = 128, LDA = BN + 8, CHUNKS = 8, WTM = 32, WTN = 32, TM = 2, TN = 2, WGN = 4;
+  typedef typename Act<T>::vec8 vec8;
+  u32x4* sB = reinterpret_cast<u32x4*>(smem);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave / WGN, wn = wave % WGN, frow = lane & 15, fq = lane >> 4;
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int c = tid + i * 512, row = c / CHUNKS, ch = c % CHUNKS;
+      sB[s * BN * CHUNKS + row * CHUNKS + (ch ^ (row & 7))] = rw[s][i];
+    }
+#pragma unroll
+  for (int j = 0; j < TN; ++j)
+#pragma unroll
+    for (int i = 0; i < TM; ++i) acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  __syncthreads();
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    const u32x4* cB = sB + s * BN * CHUNKS;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      vec8 xf[TM], wf[TN];
+      const int kc = ks * 4 + fq;
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+        xf[i] = __builtin_bit_cast(vec8, *reinterpret_cast<const u32x4*>(sA + (wm * WTM + i * 16 + frow) * LDA + s * 64 + kc * 8));
+#pragma unroll
+      for (int j = 0; j < TN; ++j) {
+        const int row = wn * WTN + j * 16 + frow;
+        wf[j] = __builtin_bit_cast(vec8, cB[row * CHUNKS + (kc ^ (row & 7))]);
+      }
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int i = 0; i < TM; ++i) acc[j][i] = Act<T>::mfma16(wf[j], xf[i], acc[j][i]);
+    }
+  }
+  __syncthreads();
+}
+
+constexpr size_t DEC_TAIL_F = 512;  // hidden width the launch is built for (host check)
+constexpr size_t DEC_TAIL_BODY_LDS = (size_t)2 * 128 * 64 * 2 + (size_t)2 * 64 * (128 + 8) * 2 + DEC_TAIL_F * 4 + (size_t)6 * 128 * 4;
+constexpr size_t DEC_TAIL_LDS = DEC_TAIL_BODY_LDS + ((size_t)128 + 3 * 128 + DEC_TAIL_F + 3 * 128) * 4;
+static_assert(DEC_TAIL_LDS <= (size_t)48 * 1024 + (size_t)2 * (64 + 128) * 64 * 2 + (size_t)3 * 128 * 4, "no more LDS than the loss launch takes");
+
+template <typename T>
+__global__ __launch_bounds__(512) void dec_tail_kernel(mst_gemm_args proj, mst_ln_args ln1, mst_gemm_args ff1, mst_gemm_args ff2, mst_ln_args ln3,
+                                                       mst_gemm_args out, mst_bce_args bce, mst_gemm_args odg, mst_ln_args ln3b,
+                                                       mst_gemm_args f2d, mst_gemm_args f1d, mst_ln_args ln1b) {
+  constexpr int BM = 64, BN = 128, WGM = 2, WGN = 4, LDA = BN + 8, F = (int)DEC_TAIL_F;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ float red[512 / 64];
+  T* sX = reinterpret_cast<T*>(smem + (size_t)2 * BN * 64 * 2 + (size_t)BM * LDA * 2);  // ffn_ln_body's x tile
+  // behind the forward block's own LDS: the parameters of the three later phases — cold lines after every optimizer step, requested now
+  float* sBiasO = reinterpret_cast<float*>(smem + DEC_TAIL_BODY_LDS);  // [BN] the output layer's bias
+  float* sPar3 = sBiasO + BN;                                           // [3 BN] bias | gamma | 0 of LayerNorm-3 backward
+  float* sPar4 = sPar3 + 3 * BN;                                        // [F][3 BN] the backward block's (ffn_ln_body's `par`)
+  const int tid = threadIdx.x;
+  for (int i = tid; i < BN; i += 512) {
+    sBiasO[i] = out.bias ? out.bias[i] : 0.f;
+    sPar3[i] = odg.bias ? odg.bias[i] : 0.f;
+    sPar3[BN + i] = ln3b.gamma[i];
+    sPar3[2 * BN + i] = 0.f;
+    sPar4[F + i] = f1d.bias ? f1d.bias[i] : 0.f;
+    sPar4[F + BN + i] = ln1b.gamma[i];
+    sPar4[F + 2 * BN + i] = 0.f;
+  }
+  for (int i = tid; i < F; i += 512) sPar4[i] = f2d.bias ? f2d.bias[i] : 0.f;
+  const int64_t m0 = xcd_chunk(blockIdx.x, gridDim.x) * BM;  // the tile's first LOGICAL row (the loss phases' index: b T + t)
+  const mst_ln_bwd_in no_lead = {};
+  u32x4 rw[2][2];
+  f32x4 acc[2][2];
+  // ---- 1: projection + LayerNorm-1, feed-forward, LayerNorm-3; x2 also lands in the x tile
+  ffn_ln_body<T, BN, WGM, WGN, 1, false, true, true, false, true, false>(smem, ff1, ff2, ln3, no_lead, proj, ln1, nullptr,
+                                                                         [&] { tile128_load_w<T>(out, rw); });
+  __syncthreads();  // the x tile is complete, the staging tile dead
+  // ---- 2: output layer + sigmoid + BCE; the logit gradient also lands in the x tile
+  tile128_gemm<T>(smem, sX, rw, acc);
+  tile128_load_w<T>(odg, rw);  // (the dgrad's weights: requested in front of the loss arithmetic)
+  {
+    float bias8[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) bias8[e] = sBiasO[(tid % (BN / 8)) * 8 + e];
+    bce_tile_finish<T, BN, 2>(out, bce, smem, red, reinterpret_cast<u32x4*>(sX), acc, m0, 0, bias8);
+  }
+  __syncthreads();  // the logit-gradient tile is complete, the staging tile dead
+  // ---- 3: the output layer's input gradient + LayerNorm-3 backward; dh also lands in the x tile
+  tile128_gemm<T>(smem, sX, rw, acc);
+  gemm_epilogue_ln<T, BM, BN, WGM, WGN, 2>(odg, ln3b, smem, acc, m0, nullptr, 0, sX, LDA, sPar3);
+  __syncthreads();  // dh is complete, the column-sum scratch dead
+  // ---- 4: both feed-forward dgrads + LayerNorm-1 backward on the tile in LDS
+  mst_gemm_args no_gemm = {};
+  const mst_ln_args no_ln = {};
+  ffn_ln_body<T, BN, WGM, WGN, 2, false, true, false, true, false, true>(smem, f2d, f1d, ln1b, no_lead, no_gemm, no_ln, sPar4, [] {});
+}
+
+template <typename T>
+static int launch_dec_tail(const mst_gemm_args& proj, const mst_ln_args& ln1, const mst_gemm_args& ff1, const mst_gemm_args& ff2,
+                           const mst_ln_args& ln3, const mst_gemm_args& out, const mst_bce_args& bce, const mst_gemm_args& odg,
+                           const mst_ln_args& ln3b, const mst_gemm_args& f2d, const mst_gemm_args& f1d, const mst_ln_args& ln1b, hipStream_t s) {
+  static bool opted = false;
+  if (!opted) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_tail_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)DEC_TAIL_LDS);
+    if (e != hipSuccess) { set_error("dec_tail_kernel: LDS opt-in of %zu bytes: %s", DEC_TAIL_LDS, hipGetErrorString(e)); return MST_ERR_LAUNCH; }
+    opted = true;
+  }
+  hipLaunchKernelGGL((dec_tail_kernel<T>), dim3((unsigned)(out.M / 64)), dim3(512), DEC_TAIL_LDS, s, proj, ln1, ff1, ff2, ln3, out, bce, odg,
+                     ln3b, f2d, f1d, ln1b);
+  MST_CHECK_LAUNCH("dec_tail_kernel");
   return MST_OK;
 }
 
@@ -1104,9 +1276,9 @@ static int check_gemm_common(const mst_gemm_args& a) {
 
 extern "C" int64_t mst_gemm_nt_ln_parts(int64_t M) { return M > 0 ? cdiv(M, 64) : 0; }  // launch_gemm_ln's 64-row tiles
 
-static int ffn_ln_impl(const char* who, const mst_gemm_args* first, const mst_gemm_args* second, const mst_ln_args* ln, int mode,
-                       mst_stream_t stream, const mst_ln_bwd_in* lead = nullptr, const mst_gemm_args* extra = nullptr,
-                       const mst_ln_args* extra_ln = nullptr) {
+// the argument checks of the feed-forward block's launches (no HIP call)
+static int check_ffn_ln(const char* who, const mst_gemm_args* first, const mst_gemm_args* second, const mst_ln_args* ln, int mode,
+                        const mst_ln_bwd_in* lead = nullptr, const mst_gemm_args* extra = nullptr, const mst_ln_args* extra_ln = nullptr) {
   MST_CHECK_ARG(first != nullptr && second != nullptr && ln != nullptr, "%s: null args", who);
   const mst_gemm_args& a = *first;
   const mst_gemm_args& b = *second;
@@ -1175,6 +1347,16 @@ static int ffn_ln_impl(const char* who, const mst_gemm_args* first, const mst_ge
                   "%s: the leading LayerNorm's output must be the first GEMM's A operand", who);
     MST_CHECK_ARG(!x.resid || (x.ldr % 8 == 0 && x.ldr >= x.N && (uintptr_t)x.resid % 16 == 0), "%s: bad residual layout", who);
   }
+  return MST_OK;
+}
+
+static int ffn_ln_impl(const char* who, const mst_gemm_args* first, const mst_gemm_args* second, const mst_ln_args* ln, int mode,
+                       mst_stream_t stream, const mst_ln_bwd_in* lead = nullptr, const mst_gemm_args* extra = nullptr,
+                       const mst_ln_args* extra_ln = nullptr) {
+  const int rc = check_ffn_ln(who, first, second, ln, mode, lead, extra, extra_ln);
+  if (rc) return rc;
+  const mst_gemm_args &a = *first, &b = *second;
+  const mst_ln_args& l = *ln;
   hipStream_t s = (hipStream_t)stream;
   return dispatch_act(a.dtype, [&](auto tag) -> int {
     typedef decltype(tag) T;
@@ -1294,6 +1476,46 @@ extern "C" int mst_gemm_sigmoid_bce_dgrad_ln(const mst_gemm_args* args, const ms
   return dispatch_act(a.dtype, [&](auto tag) -> int {
     typedef decltype(tag) T;
     return launch_gemm_bce_dgrad_ln<T>(a, q, g2, l, s);
+  });
+}
+
+extern "C" int mst_dec_tail_step(const mst_gemm_args* proj, const mst_ln_args* ln1, const mst_gemm_args* ff1, const mst_gemm_args* ff2,
+                                 const mst_ln_args* ln3, const mst_gemm_args* out, const mst_bce_args* bce, const mst_gemm_args* out_dgrad,
+                                 const mst_ln_args* ln3_bwd, const mst_gemm_args* ff2_dgrad, const mst_gemm_args* ff1_dgrad,
+                                 const mst_ln_args* ln1_bwd, mst_stream_t stream) {
+  const char* who = "mst_dec_tail_step";
+  MST_CHECK_ARG(proj && ln1 && ff1 && ff2 && ln3 && out && bce && out_dgrad && ln3_bwd && ff2_dgrad && ff1_dgrad && ln1_bwd, "%s: null args", who);
+  const mst_gemm_args &o = *out, &g = *out_dgrad, &d2 = *ff2_dgrad;
+  const int64_t T = bce->T;
+  // the ONE shape the launch is built for; anything else is the caller's three launches (no fallback here)
+  MST_CHECK_ARG(ff2->N == 128 && ff1->K == 128 && proj->N == 128 && g.N == 128 && ff1_dgrad->N == 128,
+                "%s: the model width must be 128 (got %lld)", who, (long long)ff2->N);
+  MST_CHECK_ARG(ff1->N == 512 && d2.N == 512, "%s: the hidden width must be 512 (got %lld)", who, (long long)ff1->N);
+  MST_CHECK_ARG(o.N == 128 && o.K == 128 && g.K == 128, "%s: the output layer must have 128 pitches (got %lld)", who, (long long)o.N);
+  MST_CHECK_ARG(T > 0 && T % 64 == 0, "%s: T must be a multiple of 64 (got %lld)", who, (long long)T);
+  MST_CHECK_ARG(o.M > 0 && o.M % 64 == 0 && o.M % T == 0 && ff1->M == o.M && ff2->M == o.M && proj->M == o.M && g.M == o.M && d2.M == o.M &&
+                ff1_dgrad->M == o.M, "%s: every part works on the same whole 64-row tiles (M %lld)", who, (long long)o.M);
+  auto groups = [&](int64_t rpg, int64_t stride, int64_t off) { return rpg == T && stride == T + 1 && off == 1; };
+  MST_CHECK_ARG(groups(ff1->a_rows_per_group, ff1->a_group_stride, ff1->a_group_offset) &&
+                groups(o.a_rows_per_group, o.a_group_stride, o.a_group_offset) &&
+                groups(g.c_rows_per_group, g.c_group_stride, g.c_group_offset) &&
+                groups(d2.a_rows_per_group, d2.a_group_stride, d2.a_group_offset) && g.a_rows_per_group <= 0,
+                "%s: row groups must be (T, T + 1, 1) on all three parts", who);
+  MST_CHECK_ARG(ln3_bwd->mode == 2 && ln3_bwd->mask_mode == 2, "%s: the LayerNorm-3 backward takes mask mode 2 (got %d)", who, (int)ln3_bwd->mask_mode);
+  MST_CHECK_ARG(o.A == ln3->out && o.lda == ln3->ld_out, "%s: the output layer's A operand must be LayerNorm-3's output", who);
+  MST_CHECK_ARG(o.C && g.A == o.C && g.lda == o.ldc, "%s: the output dgrad's A operand must be the logit gradient", who);
+  MST_CHECK_ARG(d2.A == g.C && d2.lda == g.ldc, "%s: the A operand of the FF2 dgrad must be the output dgrad's dX_out", who);
+  MST_CHECK_ARG(proj->dtype == o.dtype && g.dtype == o.dtype && d2.dtype == o.dtype && ff1->dtype == o.dtype && !g.a_u8,
+                "%s: every part must share one activation dtype", who);
+  int rc = check_ffn_ln(who, ff1, ff2, ln3, 1, nullptr, proj, ln1);
+  if (rc == MST_OK) rc = check_gemm_bce(o, *bce);
+  if (rc == MST_OK) rc = check_gemm_ln(g, *ln3_bwd);
+  if (rc == MST_OK) rc = check_ffn_ln(who, ff2_dgrad, ff1_dgrad, ln1_bwd, 2);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  return dispatch_act(o.dtype, [&](auto tag) -> int {
+    typedef decltype(tag) T_;
+    return launch_dec_tail<T_>(*proj, *ln1, *ff1, *ff2, *ln3, o, *bce, g, *ln3_bwd, d2, *ff1_dgrad, *ln1_bwd, s);
   });
 }
 

@@ -468,13 +468,14 @@ class Dropout(namedtuple("Dropout", "p seed_ptr site0")):
 NO_DROPOUT = Dropout(0.0, None, 0)
 
 
-def row_block_fwd(P, L, x_in, rows, drop, form, row_groups=None, tail=None):
+def row_block_fwd(P, L, x_in, rows, drop, form, row_groups=None, tail=None, launch=True):
     """The row-wise block of a transformer layer behind the attention mix: W_proj + residual -> LayerNorm-1 -> FF1 + ReLU -> FF2 +
     residual -> LayerNorm-2/3, on `rows` of the layer's buffers L (att in; h1, x1, a, h2, x2, mean1/2, rstd1/2 out). form:
       'launches'  the five launches (any rows: the recovery path of the position-0 tail, and every width without a fused kernel)
       'fused'     one launch, mst_proj_ffn_ln_fwd (all rows; row_groups: ops.ffn_ln_fwd's, the last decoder layer without position 0)
       'tail'      one launch, mst_row_tail_fwd (position-0 rows; tail: its sync / stat_stride / phys_stride / status / rider / queue /
-                  shadows keywords)"""
+                  shadows keywords)
+    launch=False ('fused' only): nothing is launched; returns ops.ffn_ln_fwd's keyword arguments (StepPlan.losses: ops.dec_tail_step)"""
     D, v = P.proj.w.shape[0], rows.view
     if form == "tail":
         o.row_tail_fwd(v(L.att), v(x_in), P.proj.w, P.proj.b, P.ln1.gamma, P.ln1.beta, P.ff1.w, P.ff1.b, P.ff2.w, P.ff2.b, P.ln2.gamma,
@@ -488,8 +489,11 @@ def row_block_fwd(P, L, x_in, rows, drop, form, row_groups=None, tail=None):
     if form == "fused":  # (same results as the five launches, bit for bit in a / h2. The projection's dgrad behind the backward block
         # measured +14 us and was removed.)
         head = dict(att=L.att, W=P.proj.w, h1=L.h1, gamma=P.ln1.gamma, beta=P.ln1.beta, mean=L.mean1, rstd=L.rstd1, **proj)
-        o.ffn_ln_fwd(L.x1, P.ff1.w, L.a, P.ff2.w, L.h2, P.ln2.gamma, P.ln2.beta, L.x2, L.mean2, L.rstd2, ff1=ff1, ff2=ff2, proj=head,
-                     row_groups=row_groups)
+        kw = dict(x=L.x1, W1=P.ff1.w, a_out=L.a, W2=P.ff2.w, h_out=L.h2, gamma=P.ln2.gamma, beta=P.ln2.beta, y_out=L.x2, mean=L.mean2,
+                  rstd=L.rstd2, ff1=ff1, ff2=ff2, proj=head, row_groups=row_groups)
+        if not launch:
+            return kw
+        o.ffn_ln_fwd(**kw)
         return L.x2
     # (Dense + LayerNorm in one launch, ops.gemm_nt_ln_fwd, does not pay in the forward pass: graph-replay timings at
     # M = 16384 are 17.8 vs 19.9 us for N 256 K 256 but 30.3 vs 30.2 for K 1024 and 16.6 vs 13.0 / 21.3 vs 16.5 for
@@ -515,7 +519,23 @@ def no_partials(norm, parts):
     return None
 
 
-def row_block_bwd(P, L, t, dy, rows, drop, form, partials, dy_done=False, row_groups=None, tail=None):
+def ffn_bwd_parts(L, row_groups=None):
+    """workgroups (rows of LayerNorm-1 partials) of a layer's one-launch backward block"""
+    M = L.h1.shape[0]
+    return o.gemm_nt_ln_parts(M if row_groups is None else M // row_groups[1] * row_groups[0])
+
+
+def ffn_bwd_kw(P, L, t, drop, partials_buf, row_groups=None):
+    """ops.ffn_ln_bwd's keyword arguments (all but lead=) for a layer's one-launch backward block: row_block_bwd 'fused', and
+    StepPlan.losses where the block is a phase of ops.dec_tail_step. partials_buf: LayerNorm-1's partials buffer, or None (atomics)."""
+    dff = t.dhm if (drop.p > 0 and not P.self_resid) else t.dh
+    ln1 = dict(dx_masked=t.dh1m, mask_mode=1, **drop.at(0)) if drop.p > 0 else {}
+    return dict(dff=dff, W2t=P.ff2.t, dpre_out=t.dpre, gate=L.a, W1t=P.ff1.t, dx_out=t.dh1, x=L.h1, gamma=P.ln1.gamma, mean=L.mean1,
+                rstd=L.rstd1, dgamma=P.ln1.dgamma, dbeta=P.ln1.dbeta, alpha=1.0 / (1.0 - drop.p) if drop.p > 0 else 1.0,
+                resid=None if P.self_resid else t.dh, partials=partials_buf, row_groups=row_groups, **ln1)
+
+
+def row_block_bwd(P, L, t, dy, rows, drop, form, partials, dy_done=False, row_groups=None, tail=None, launch=True):
     """Backward of row_block_fwd on the same rows: LayerNorm-2/3 backward of dy, both FFN dgrads, LayerNorm-1 backward, the W_proj
     dgrad. t: the layer's backward buffers — dh, dhm, dx1, dh1m, dpre indexed by the block's own rows, dh1 and datt by the layer's
     (written through `rows`). partials(norm, n_workgroups) -> the partials buffer of one LayerNorm-backward launch, or None
@@ -525,7 +545,9 @@ def row_block_bwd(P, L, t, dy, rows, drop, form, partials, dy_done=False, row_gr
       'fused'     both dgrads + LayerNorm-1 backward in one launch (mst_ffn_ln_bwd); an encoder layer's LayerNorm-2 backward rides in
                   its prologue (mst_ffn_ln_bwd_lead; the prologue has no mask_mode 2). row_groups as in row_block_fwd
       'tail'      one launch, mst_row_tail_bwd (position-0 rows; tail: its keywords)
-    dy_done: the producer of dy already ran the leading LayerNorm backward (t.dh / t.dhm are filled; not with 'tail')."""
+    dy_done: the producer of dy already ran the leading LayerNorm backward (t.dh / t.dhm are filled; not with 'tail').
+    launch=False ('fused' with dy_done only): the one-launch block itself is not issued — it ran as a phase of ops.dec_tail_step, from
+    ffn_bwd_kw's arguments —; the partial-sum job is registered and the W_proj dgrad issued as always."""
     D, v = P.proj.w.shape[0], rows.view
     if form == "tail":
         o.row_tail_bwd(v(dy), v(L.h2), v(L.h1), v(L.a), L.mean1, L.rstd1, L.mean2, L.rstd2, P.ln1.gamma, P.ln2.gamma, P.ff2.t, P.ff1.t,
@@ -550,10 +572,11 @@ def row_block_bwd(P, L, t, dy, rows, drop, form, partials, dy_done=False, row_gr
     inv_keep = 1.0 / (1.0 - drop.p) if drop.p > 0 else 1.0
     ln1 = dict(dx_masked=t.dh1m, mask_mode=1, **drop.at(0)) if drop.p > 0 else {}
     if form == "fused":
-        n = M if row_groups is None else M // row_groups[1] * row_groups[0]
-        o.ffn_ln_bwd(dff, P.ff2.t, t.dpre, L.a, P.ff1.t, t.dh1, L.h1, P.ln1.gamma, L.mean1, L.rstd1, P.ln1.dgamma, P.ln1.dbeta,
-                     alpha=inv_keep, resid=resid_ff, partials=partials(P.ln1, o.gemm_nt_ln_parts(n)), lead=lead, row_groups=row_groups,
-                     **ln1)
+        buf = partials(P.ln1, ffn_bwd_parts(L, row_groups))
+        if launch:
+            o.ffn_ln_bwd(lead=lead, **ffn_bwd_kw(P, L, t, drop, buf, row_groups))
+        elif lead is not None:
+            raise ValueError("row_block_bwd(launch=False) needs dy_done: the block that ran elsewhere has no leading LayerNorm backward")
     else:
         o.gemm_nt(dff, P.ff2.t, t.dpre, N=4 * D, K=D, gate=v(L.a), alpha=inv_keep)
         if form == "ln_fused":
@@ -656,7 +679,8 @@ def row_tail_selfcheck(store, B=64, S=2):
 # The launch forms of one issued kernel sequence (StepPlan._resolve_forms): tails — the position-0 tails as one launch; riders — GEMMs
 # riding on them; shadows — where the transposed-shadow refresh goes ('own' / 'begin' / 'tail'); the rest as named there.
 # sched — the latent block's backward launch and the step-closing bookkeeping in their scheduled forms (training schedules on).
-Forms = namedtuple("Forms", "tails riders shadows fuse_bce bce_dgrad skip_row0 cls_fold ffn_e ffn_d ln_bwd_e ln_bwd_d sched")
+# dec_tail — the last decoder layer's row-wise block, the loss launch and the block's backward as ONE launch (a training step with gradient).
+Forms = namedtuple("Forms", "tails riders shadows fuse_bce bce_dgrad skip_row0 cls_fold ffn_e ffn_d ln_bwd_e ln_bwd_d sched dec_tail")
 
 
 def check_schedule(kl_warmup_steps=0, kl_cycle_steps=0, kl_free_bits=0.0, lr_warmup_steps=0):
@@ -741,6 +765,10 @@ class StepPlan:
         # the deferred shadow refresh (ParamStore.shadows_deferred) behind the forward tail's riders where that launch has them;
         # False: behind the tiles of the step's first launch
         self.shadows_on_tail = True
+        # the last decoder layer's row-wise block, the loss and the block's backward in one launch where the shape has that form
+        # (ops.dec_tail_pays) and the step is a training step; False: the three launches (diagnostics, tests)
+        self.dec_tail = True
+        self.n_cu = torch.cuda.get_device_properties(self.dev).multi_processor_count if self.dev.type == "cuda" else 0
         # the launch forms of the sequence issued last (resolved again by every forward(); here: the buffers below follow from them)
         self.forms = self._resolve_forms()
         # ---- inputs: ONE static device blob (so a batch arrives with a single copy) viewed as typed tensors
@@ -867,10 +895,11 @@ class StepPlan:
     def d_p(self):
         return 0.0 if self._infer else self.cfg.d_dropout
 
-    def _resolve_forms(self):
-        """Which form every launch of the sequence about to be issued takes: from the shape, and from the four attributes diagnostics
+    def _resolve_forms(self, with_grad=False):
+        """Which form every launch of the sequence about to be issued takes: from the shape, and from the five attributes diagnostics
         set before the first forward() / capture() (store.tail_fused — which a failed tail also clears —, store.shadows_deferred,
-        plan.ride, plan.shadows_on_tail). forward() resolves them; every phase of the step reads this record and nothing else."""
+        plan.ride, plan.shadows_on_tail, plan.dec_tail). forward() resolves them; every phase of the step reads this record and nothing
+        else. with_grad: the forward pass of a training step whose caller issues losses(with_grad=True) next (fwd_bwd_kernels)."""
         cfg, st, B, T = self.cfg, self.store, self.B, self.T
         De, Dd = cfg.e_model, cfg.d_model
         roll = cfg.kind == "pianoroll"
@@ -884,16 +913,23 @@ class StepPlan:
         # output layer + BCE in one launch when a tile can hold whole rows of pitches of one sample (configs[1]: P 128, T 256)
         fuse_bce = roll and o.can_fuse_bce(cfg.out_dim, T, self.nld) and o.bce_fusion_pays(cfg.out_dim)
         ffn_d, ln_bwd_d = o.ffn_fusion_pays(Dd, 4 * Dd), o.ln_bwd_fusion_pays(Dd)
+        bce_dgrad = fuse_bce and ln_bwd_d
+        skip_row0 = cfg.d_layers > 0 and T % 64 == 0 and ffn_d
         return Forms(
             tails=tails, riders=riders, shadows=shadows, fuse_bce=fuse_bce,
             # ... and the output layer's input gradient + the last decoder layer's LayerNorm-3 backward in the same workgroups
-            bce_dgrad=fuse_bce and ln_bwd_d,
+            bce_dgrad=bce_dgrad,
             # The LAST decoder layer's row-wise part (W_proj, LayerNorm-1, feed-forward, LayerNorm-3 and their backward) skips every
             # sample's position-0 row: its output is dropped before the loss (model.py:253), so nothing it computes there is ever
             # read and every gradient there is zero — the buffers' position-0 rows simply stay at the zeros they were allocated with.
             # B x T rows are B T / 64 tiles of the one-workgroup-per-CU feed-forward launches: ONE resident round at configs[1]
             # (256 tiles) where B (T + 1) rows were 257 (measured: forward 22.8 -> 18.9 us, backward 24.6 -> 20.3).
-            skip_row0=cfg.d_layers > 0 and T % 64 == 0 and ffn_d,
+            skip_row0=skip_row0,
+            # ... and that block, the loss launch and the block's backward — three consecutive launches on the same 64-row tiles — as
+            # consecutive phases of ONE launch's workgroups (mst_dec_tail_step). Only in a training step with gradient: forward()
+            # then leaves the block to losses(with_grad=True); every other path keeps the three launches.
+            dec_tail=bool(with_grad and not self._infer and self.dec_tail and bce_dgrad and ffn_d and skip_row0 and
+                          o.dec_tail_pays(Dd, 4 * Dd, cfg.out_dim, T, B * T // 64, self.n_cu)),
             # The class-embedding gradient is a column sum of d(x0) per class = onehot(class)^T d(x0): with the one-hot class id
             # of a frame in C extra columns behind its pitches, and the class table behind the embedding table in the flat
             # buffers, it is rows in_dim.. of the encoder embedding's weight-gradient problem — whose 256-row tile has the
@@ -1070,6 +1106,8 @@ class StepPlan:
         else:
             o.attn_qkv_fwd(x_in, P.kqv.w, P.kqv.b, L.qkv, keymask, L.lse, L.att, self.B, S, H, dh, 0, D, 2 * D)
         fused = F.ffn_e if side == "encoder" else F.ffn_d
+        if F.dec_tail and side == "decoder" and i == self.cfg.d_layers - 1:
+            return L.x2  # (the block runs inside the loss launch: losses())
         return row_block_fwd(P, L, x_in, ALL_ROWS, self._dropout(p, site0), "fused" if fused else "launches",
                              row_groups=self._row0_groups(side, i))
 
@@ -1080,19 +1118,23 @@ class StepPlan:
             return (self.T, self.T + 1, 1)
         return None
 
-    def forward(self, inference=False, upto=None):
+    def forward(self, inference=False, upto=None, with_grad=False):
         """inference=True: the forward pass as the reference runs it OUTSIDE autograd.record() (Model(...) called directly, the
         samplers: sampler.py:146-148) — every Dropout is the identity and the training RNG stream is left alone (an eps the
         caller did not supply is drawn from the store's inference stream).
         upto="latent" (inference only): stop behind the latent launch — mu, sigma, z and decoder row 0 are there, no decoder layer,
-        output layer or loss launch is issued (Model.encode)."""
+        output layer or loss launch is issued (Model.encode).
+        with_grad=True (fwd_bwd_kernels, a training step): the caller issues losses(with_grad=True) next — where Forms.dec_tail holds,
+        the last decoder layer's row-wise block is left to that launch and dec_out is filled by it, not by forward()."""
+        if with_grad and (inference or upto):
+            raise ValueError("forward(with_grad=True) is the forward pass of a training step")
         if upto not in (None, "latent") or (upto and not inference):
             raise ValueError("forward(upto=...) takes 'latent', in inference mode only")
         cfg, st, B, T = self.cfg, self.store, self.B, self.T
         self._infer = bool(inference)
         # (every forward: handle_step_status() may have cleared store.tail_fused since the last one. losses(), the backward phases and
         # optimizer() — also when captured as graphs of their own — read the record this forward leaves.)
-        F = self.forms = self._resolve_forms()
+        F = self.forms = self._resolve_forms(with_grad)
         self._tail_used = dict(fwd=False, bwd=False)
         De, Dd = cfg.e_model, cfg.d_model
         Se, Sd = T, T + 1
@@ -1169,6 +1211,8 @@ class StepPlan:
                          tok_parts=self.store.tok_parts if self.track_token_metrics else None)
         elif F.fuse_bce:
             dgrad = None
+            if F.dec_tail and not with_grad:
+                raise RuntimeError("forward(with_grad=True) left the last decoder layer to losses(with_grad=True)")
             if with_grad and F.bce_dgrad:
                 # the first launch of the backward pass — the output layer's input gradient + the last decoder layer's LayerNorm-3
                 # backward (backward_early) — consumes exactly the logit-gradient tile this launch produces: same workgroup
@@ -1177,9 +1221,19 @@ class StepPlan:
                              K=self.dlogits.shape[1], c_remap=(T, Sd, 1),
                              **self._out_ln_bwd("decoder", last, self.dec[last], cfg.d_dropout, self._site_d(0) + 3 * last,
                                                 self.bd_l[last], B * T))
-            o.gemm_sigmoid_bce(self.dec_out, self.store.h("decoder.output_layer.weight"), self.labels, self.recon, T, dgrad=dgrad,
-                               dlogits=dl, probs=self.probs, label_smoothing=self.ls, downweight=self.nld, gscale=self.gscale, M=B * T,
-                               K=cfg.d_model, bias=self.store.p("decoder.output_layer.bias"), a_remap=(T, T + 1, 1))
+            loss = dict(A=self.dec_out, B=self.store.h("decoder.output_layer.weight"), labels=self.labels, loss=self.recon, T=T,
+                        dlogits=dl, probs=self.probs, label_smoothing=self.ls, downweight=self.nld, gscale=self.gscale, M=B * T,
+                        K=cfg.d_model, bias=self.store.p("decoder.output_layer.bias"), a_remap=(T, T + 1, 1))
+            if F.dec_tail:
+                # ... and around it, in the same workgroups again, the last decoder layer's row-wise block (forward() left it out) and
+                # that block's backward (backward_early skips its launch, and registers its partial sums and weight gradients as ever)
+                L, t, P = self.dec[last], self.bd_l[last], self.store.layer("decoder", last)
+                drop, groups = self._dropout(self.d_p, self._site_d(0) + 3 * last), self._row0_groups("decoder", last)
+                x_in = self.dec[last - 1].x2 if last > 0 else self.x0_d
+                o.dec_tail_step(row_block_fwd(P, L, x_in, ALL_ROWS, drop, "fused", row_groups=groups, launch=False), loss, dgrad,
+                                ffn_bwd_kw(P, L, t, drop, self._ln_partials_buf(P.ln1, ffn_bwd_parts(L, groups)), groups))
+            else:
+                o.gemm_sigmoid_bce(dgrad=dgrad, **loss)
         else:
             o.sigmoid_bce(self.logits, self.labels, self.recon, B, T, cfg.out_dim, label_smoothing=self.ls,
                           downweight=self.nld, npos=self.npos, probs=self.probs, dlogits=dl, gscale=self.gscale,
@@ -1190,12 +1244,16 @@ class StepPlan:
     # ------------------------------------------------------------------------------ backward
     LN_PARTIALS_MIN = 32  # fewer workgroups than this: their atomics are cheaper than a row of partials each
 
+    def _ln_partials_buf(self, norm, parts):
+        """the buffer _ln_partials hands out, without registering anything"""
+        return self._ln_part[norm.site] if parts >= self.LN_PARTIALS_MIN else None
+
     def _ln_partials(self, norm, parts):
         """partials buffer of one LayerNorm-backward launch of `parts` workgroups (None: few workgroups, keep the atomics); registers
         the deferred column sums into dgamma / dbeta, executed by _flush_grads()"""
-        if parts < self.LN_PARTIALS_MIN:
+        buf, dg, db = self._ln_partials_buf(norm, parts), norm.dgamma, norm.dbeta
+        if buf is None:
             return None
-        buf, dg, db = self._ln_part[norm.site], norm.dgamma, norm.dbeta
         D = dg.numel()
         if db.data_ptr() == dg.data_ptr() + 4 * D:  # adjacent in the flat bucket: one job
             self._psums.append(o.partial_sum_job(buf, parts, dg, length=2 * D))
@@ -1227,8 +1285,10 @@ class StepPlan:
         latent_bwd_vec's proj= triple) for backward_early to hand them on. Else returns None."""
         F, P = self.forms, self.store.layer(side, i)
         ffn, ln = (F.ffn_e, F.ln_bwd_e) if side == "encoder" else (F.ffn_d, F.ln_bwd_d)
+        # (Forms.dec_tail: the last decoder layer's one-launch block already ran inside the loss launch, losses())
+        in_loss = F.dec_tail and side == "decoder" and i == self.cfg.d_layers - 1
         dff, dproj = row_block_bwd(P, L, t, dy, ALL_ROWS, self._dropout(p, site0), "fused" if ffn else ("ln_fused" if ln else "launches"),
-                                   self._ln_partials, dy_done=dy_done, row_groups=self._row0_groups(side, i))
+                                   self._ln_partials, dy_done=dy_done, row_groups=self._row0_groups(side, i), launch=not in_loss)
         if side == "decoder" and self.cfg.d_causal:
             o.attn_causal_bwd(L.qkv, keymask, L.lse, t.datt, t.dqkv, t.delta, self.B, S, H, D // H, 0, D, 2 * D)
         else:
@@ -1407,7 +1467,7 @@ class StepPlan:
     # ------------------------------------------------------------------------------ step
     def fwd_bwd_kernels(self, is_train=True):
         self._tick_adam = is_train  # the step counter / lr_t are advanced by forward()'s step_begin launch
-        self.forward()
+        self.forward(with_grad=is_train)
         self.losses(with_grad=is_train, combine=not is_train)
         if is_train:
             self.backward()
@@ -1431,7 +1491,7 @@ class StepPlan:
         if is_train and split_optimizer and overlap and self.grad_cut() > 0:
             def early():
                 self._tick_adam = True
-                self.forward()
+                self.forward(with_grad=True)
                 self.losses(with_grad=True, combine=False)
                 self.backward_early(flush=True)
             self.graph = o.Graph().capture(early)

@@ -265,6 +265,15 @@ def ffn_ln_fwd(x, W1, a_out, W2, h_out, gamma, beta, y_out, mean, rstd, eps=1e-5
     an OUTPUT as well as the block's input)
     row_groups = (rows_per_group, stride, offset): the launch works on those rows of every operand only (the last decoder
     layer without each sample's position-0 row); the other rows are neither read nor written"""
+    g0, l0, g1, g2, l = _ffn_ln_fwd_args(x, W1, a_out, W2, h_out, gamma, beta, y_out, mean, rstd, eps, ff1, ff2, proj, row_groups)
+    if proj is None:
+        call("mst_ffn_ln_fwd", C.byref(g1), C.byref(g2), C.byref(l), stream())
+    else:
+        call("mst_proj_ffn_ln_fwd", C.byref(g0), C.byref(l0), C.byref(g1), C.byref(g2), C.byref(l), stream())
+
+
+def _ffn_ln_fwd_args(x, W1, a_out, W2, h_out, gamma, beta, y_out, mean, rstd, eps=1e-5, ff1=None, ff2=None, proj=None, row_groups=None):
+    """ffn_ln_fwd's structs (proj, ln1, ff1, ff2, ln): mst_proj_ffn_ln_fwd's five, the first two None without a projection head"""
     ff1, ff2 = dict(ff1 or {}), dict(ff2 or {})
     if row_groups is not None:
         M, remap = _row_groups(x.shape[0], row_groups)
@@ -279,24 +288,19 @@ def ffn_ln_fwd(x, W1, a_out, W2, h_out, gamma, beta, y_out, mean, rstd, eps=1e-5
     l.out, l.ld_out = ptr(y_out), ld(y_out)
     l.mean, l.rstd = ptr(mean), ptr(rstd)
     if proj is None:
-        call("mst_ffn_ln_fwd", C.byref(g1), C.byref(g2), C.byref(l), stream())
-        return
+        return None, None, g1, g2, l
     kw = {k: v for k, v in proj.items() if k not in ("att", "W", "h1", "gamma", "beta", "mean", "rstd")}
     g0 = _gemm_args(proj["att"], proj["W"], proj["h1"], **kw)
     l0 = LnArgs()
     l0.mode, l0.gamma, l0.beta, l0.eps = 1, ptr(proj["gamma"]), ptr(proj["beta"]), eps
     l0.out, l0.ld_out = ptr(x), ld(x)
     l0.mean, l0.rstd = ptr(proj["mean"]), ptr(proj["rstd"])
-    call("mst_proj_ffn_ln_fwd", C.byref(g0), C.byref(l0), C.byref(g1), C.byref(g2), C.byref(l), stream())
+    return g0, l0, g1, g2, l
 
 
-def ffn_ln_bwd(dff, W2t, dpre_out, gate, W1t, dx_out, x, gamma, mean, rstd, dgamma, dbeta, alpha=1.0, dx_masked=None, mask_mode=0,
-               partials=None, lead=None, row_groups=None, **kw):
-    """dpre_out = ((dff @ W2t^T) * alpha) gated by gate > 0; dx_out = LayerNorm-backward(dpre_out @ W1t^T + resid; x, mean, rstd,
-    gamma) in one launch (mst_ffn_ln_bwd). W2t / W1t: the transposed 16-bit weights ([F, D] and [D, F]); **kw: resid and the
-    dropout fields of the LayerNorm-backward mask, as for gemm_nt_ln_bwd.
-    lead: dict(dy, x, gamma, mean, rstd, dx, [dx_masked, dropout_*], [dgamma, dbeta | partials]) -> the layer's leading
-    LayerNorm backward runs in the prologue (mst_ffn_ln_bwd_lead); dff must then be lead's dx_masked (or dx)."""
+def _ffn_ln_bwd_args(dff, W2t, dpre_out, gate, W1t, dx_out, x, gamma, mean, rstd, dgamma, dbeta, alpha=1.0, dx_masked=None, mask_mode=0,
+                     partials=None, row_groups=None, **kw):
+    """ffn_ln_bwd's structs (ff2_dgrad, ff1_dgrad, ln): mst_ffn_ln_bwd's three"""
     rg = {}
     if row_groups is not None:  # (as in ffn_ln_fwd: the same rows of every operand)
         M, remap = _row_groups(dff.shape[0], row_groups)
@@ -313,6 +317,48 @@ def ffn_ln_bwd(dff, W2t, dpre_out, gate, W1t, dx_out, x, gamma, mean, rstd, dgam
     l.partials = ptr(partials)
     if partials is not None:
         assert partials.shape[0] >= gemm_nt_ln_parts(g1.M) and partials.shape[1] == 2 * g2.N and partials.is_contiguous()
+    return g1, g2, l
+
+
+def can_dec_tail(D, F, P, T):
+    """shapes the one-launch decoder tail exists for (mst_dec_tail_step)"""
+    return D == 128 and F == 512 and P == 128 and T > 0 and T % 64 == 0
+
+
+def dec_tail_pays(D, F, P, T, tiles, n_cu=256):
+    """Where the engine runs the last decoder layer's row-wise block, the loss launch and the block's backward as ONE launch
+    (dec_tail_step) instead of three. tiles: B T / 64, the grid of each of the three; n_cu: compute units of the device.
+    The one launch keeps a workgroup's LDS for all four phases, so it runs one workgroup per compute unit where the two
+    feed-forward launches co-reside two: above one resident round (configs[4]: 512 tiles on 256 compute units) the separate
+    launches stay. The token path and 2048 pitches (configs[2]) have no fused loss launch to join.
+    Measured on one MI355X (bench.py medians, us per step, parent commit against this form; profiles/r07_dectail_*): configs[1]
+    628.0 -> 616.4 over three alternated pairs (the launch: 60.3 against 27.5 + 23.4 + 21.8 = 72.7), fp16 636.3 -> 627.1. configs[4]
+    with the one launch forced: 1567.9 against 1569.4 with the three launches — no difference beyond the runs' own spread, so
+    above one resident round nothing is gained and the rule stays at tiles <= n_cu."""
+    return can_dec_tail(D, F, P, T) and 0 < tiles <= n_cu
+
+
+def dec_tail_step(fwd, loss, dgrad, bwd):
+    """ffn_ln_fwd(**fwd) (with proj= and row_groups=), gemm_sigmoid_bce(**loss, dgrad=dgrad) and ffn_ln_bwd(**bwd) (row_groups=, no
+    lead=) in one launch, with their results bit for bit (mst_dec_tail_step). Only the shape can_dec_tail() names; anything else
+    raises."""
+    g0, l0, g1, g2, l3 = _ffn_ln_fwd_args(**fwd)
+    go, q = _gemm_bce_args(**loss)
+    gd, l3b = _gemm_ln_bwd_args(**dgrad)
+    b1, b2, l1b = _ffn_ln_bwd_args(**bwd)
+    call("mst_dec_tail_step", C.byref(g0), C.byref(l0), C.byref(g1), C.byref(g2), C.byref(l3), C.byref(go), C.byref(q), C.byref(gd),
+         C.byref(l3b), C.byref(b1), C.byref(b2), C.byref(l1b), stream())
+
+
+def ffn_ln_bwd(dff, W2t, dpre_out, gate, W1t, dx_out, x, gamma, mean, rstd, dgamma, dbeta, alpha=1.0, dx_masked=None, mask_mode=0,
+               partials=None, lead=None, row_groups=None, **kw):
+    """dpre_out = ((dff @ W2t^T) * alpha) gated by gate > 0; dx_out = LayerNorm-backward(dpre_out @ W1t^T + resid; x, mean, rstd,
+    gamma) in one launch (mst_ffn_ln_bwd). W2t / W1t: the transposed 16-bit weights ([F, D] and [D, F]); **kw: resid and the
+    dropout fields of the LayerNorm-backward mask, as for gemm_nt_ln_bwd.
+    lead: dict(dy, x, gamma, mean, rstd, dx, [dx_masked, dropout_*], [dgamma, dbeta | partials]) -> the layer's leading
+    LayerNorm backward runs in the prologue (mst_ffn_ln_bwd_lead); dff must then be lead's dx_masked (or dx)."""
+    g1, g2, l = _ffn_ln_bwd_args(dff, W2t, dpre_out, gate, W1t, dx_out, x, gamma, mean, rstd, dgamma, dbeta, alpha, dx_masked, mask_mode,
+                                 partials, row_groups, **kw)
     if lead is None:
         call("mst_ffn_ln_bwd", C.byref(g1), C.byref(g2), C.byref(l), stream())
         return
