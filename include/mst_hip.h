@@ -396,6 +396,37 @@ int mst_attn_keysoftmax_bwd(int dtype, int64_t B, int64_t S, int64_t H, int64_t 
                                                streaming kernels read dout in full, so the rows must really be zero */,
                             mst_stream_t stream);
 
+/* What mst_attn_keysoftmax_fwd (fused = 0) or mst_attn_qkv_fwd (fused = 1; ld_x and ld_w are looked at then only) launches for these
+ * arguments, and what mst_attn_keysoftmax_bwd launches: decided on the host from the shape alone (and the MST_ATTN_PATH=stream
+ * override), no HIP call, no device needed. The launches call the same decision and nothing else. The arguments are validated as
+ * the launch validates them, pointers apart (same status, same message). form is a host array of 8 entries.
+ * mst_attn_fwd_form:
+ *   form[0]  path: 0  resident, Q | K | V tiles together in LDS            (one launch, one workgroup per (batch, head))
+ *                  1  resident, two tiles: K and V staged over Q between the phases
+ *                  2  resident, one tile: the output phase over two chunks of keys (head sizes 32 and 64, an even number of blocks)
+ *                  3  resident with the K | Q | V projection inside the launch (fused = 1, head size 32, 6..16 row blocks)
+ *                  4  streaming: the statistics launch, then the output launch (fused = 1 and path != 3: mst_gemm_nt comes first)
+ *   form[1]  waves per workgroup (streaming: 4)
+ *   form[2]  dynamic LDS bytes (streaming: 0)
+ *   form[3]  1 when the last row of a 32 n + 1 sequence is handled apart (head size 16, every query produced; resident paths)
+ *   form[4]  grid.x of the streaming statistics launch, ceil(S / 128) (resident: 0)
+ *   form[5]  grid.x of the streaming output launch, ceil(min(q_limit, S) / 128) (resident: 0)
+ * mst_attn_bwd_form:
+ *   form[0]  path: 0  resident (one launch)
+ *                  1  streaming dV / dK launch, then dQ by one workgroup per (batch, head) with the keys in form[5] chunks
+ *                  2  streaming dV / dK launch, then the streaming dQ launch
+ *   form[1]  waves per workgroup of the first launch (streaming: 4)
+ *   form[2]  dynamic LDS bytes: of the resident launch (path 0), of the chunked dQ launch (path 1), else 0
+ *   form[3]  1: the sparse kernels (0 < q_limit <= 32: only those rows of dout are read), 0: dense
+ *   form[4]  1 when the last row of a 32 n + 1 sequence is handled apart (head size 16, dense, resident)
+ *   form[5]  key chunks of the chunked dQ launch (path 1: 1, 2 or 4; else 0)
+ *   form[6]  waves per workgroup of the chunked dQ launch (path 1: 8; else 0)
+ * Entries not listed are 0. Returns 0; invalid arguments: MST_ERR_INVALID, or MST_ERR_UNSUPPORTED for the dtype. */
+int mst_attn_fwd_form(int dtype, int64_t B, int64_t S, int64_t H, int64_t dh, int64_t ld_qkv, int64_t k_off, int64_t q_off,
+                      int64_t v_off, int64_t ld_out, int64_t q_limit, int fused, int64_t ld_x, int64_t ld_w, int64_t* form);
+int mst_attn_bwd_form(int dtype, int64_t B, int64_t S, int64_t H, int64_t dh, int64_t ld_qkv, int64_t k_off, int64_t q_off,
+                      int64_t v_off, int64_t ld_dout, int64_t ld_dqkv, int64_t q_limit, int64_t* form);
+
 /* ------------------------------------------------------------------------
  * Causal self-attention with a conventional softmax over the KEY axis (the decoder's opt-in causal mode; the
  * model mst_attn_decode mode 1 samples from). Per (batch b, head h), with keymask[b,k] the decoder's mask:

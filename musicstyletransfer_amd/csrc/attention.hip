@@ -1592,8 +1592,10 @@ static int choose_resident(int64_t S, int64_t n_wg, size_t lds_bytes, int waves_
   }
   return best;
 }
-template <int DH> static size_t res_lds_fwd(int64_t S, int tiles = 3) { const size_t SP = (size_t)cdiv(S, 32) * 32; return (size_t)tiles * SP * LdsLd<DH>::V * 2 + 5 * SP * 4 + LONE_RED * 4; }
-template <int DH> static size_t res_lds_bwd(int64_t S) { const size_t SP = (size_t)cdiv(S, 32) * 32; return 2 * SP * LdsLd<DH>::V * 2 + 6 * SP * 4 + LONE_RED * 4; }
+// dynamic LDS of the resident kernels: the staged tiles ([SP][dh + 8] 16-bit each, LdsLd), the per-key fp32 arrays, the lone row's scratch
+static size_t res_lds_fwd(int dh, int64_t S, int tiles) { const size_t SP = (size_t)cdiv(S, 32) * 32; return (size_t)tiles * SP * (dh + 8) * 2 + 5 * SP * 4 + LONE_RED * 4; }
+static size_t res_lds_bwd(int dh, int64_t S) { const size_t SP = (size_t)cdiv(S, 32) * 32; return 2 * SP * (dh + 8) * 2 + 6 * SP * 4 + LONE_RED * 4; }
+static int res_max_waves(int dh) { return dh == 64 ? RES_MAX_WAVES<64> : RES_MAX_WAVES<32>; }
 
 static int attn_check(int64_t B, int64_t S, int64_t H, int64_t dh, int64_t ld, int64_t k_off, int64_t q_off, int64_t v_off) {
   MST_CHECK_ARG(B > 0 && S > 0 && H > 0, "attention: B,S,H must be positive");
@@ -1602,128 +1604,198 @@ static int attn_check(int64_t B, int64_t S, int64_t H, int64_t dh, int64_t ld, i
   MST_CHECK_ARG(B * H <= 65535, "attention: B*H too large for grid.y");
   return MST_OK;
 }
+// the checks of each entry point that do not look at a pointer (the form queries make the same ones)
+static int attn_check_fwd(int64_t B, int64_t S, int64_t H, int64_t dh, int64_t ld_qkv, int64_t k_off, int64_t q_off, int64_t v_off, int64_t ld_out) {
+  const int rc = attn_check(B, S, H, dh, ld_qkv, k_off, q_off, v_off);
+  if (rc) return rc;
+  MST_CHECK_ARG(ld_out >= H * dh, "mst_attn_keysoftmax_fwd: ld_out < H*dh");
+  return MST_OK;
+}
+static int attn_check_qkv(int64_t B, int64_t S, int64_t H, int64_t dh, int64_t ld_x, int64_t ld_w, int64_t ld_qkv, int64_t k_off, int64_t q_off,
+                          int64_t v_off, int64_t ld_out) {
+  const int rc = attn_check(B, S, H, dh, ld_qkv, k_off, q_off, v_off);
+  if (rc) return rc;
+  const int64_t Dm = H * dh;
+  MST_CHECK_ARG(ld_x % 8 == 0 && ld_x >= Dm && ld_w % 8 == 0 && ld_w >= Dm && ld_qkv >= 3 * Dm && ld_out >= Dm,
+                "mst_attn_qkv_fwd: leading dimensions must be multiples of 8 and cover the model width");
+  MST_CHECK_ARG(k_off + Dm <= 3 * Dm && q_off + Dm <= 3 * Dm && v_off + Dm <= 3 * Dm, "mst_attn_qkv_fwd: section offsets beyond the 3 D weight rows");
+  return MST_OK;
+}
+static int attn_check_bwd(int64_t B, int64_t S, int64_t H, int64_t dh, int64_t ld_qkv, int64_t k_off, int64_t q_off, int64_t v_off, int64_t ld_dout,
+                          int64_t ld_dqkv) {
+  const int rc = attn_check(B, S, H, dh, ld_qkv, k_off, q_off, v_off);
+  if (rc) return rc;
+  MST_CHECK_ARG(ld_dout % 8 == 0 && ld_dout >= H * dh && ld_dqkv % 8 == 0, "mst_attn_keysoftmax_bwd: bad leading dims");
+  return MST_OK;
+}
+static int check_act_dtype(int dtype) { return dispatch_act(dtype, [](auto) -> int { return MST_OK; }); }
+// the q_limit the kernels see: forward, queries [0, q_limit) are produced; backward, 0 = dense dO
+static int64_t fwd_q_limit(int64_t q_limit, int64_t S) { return (q_limit > 0 && q_limit < S) ? q_limit : S; }
+static int64_t bwd_q_limit(int64_t q_limit, int64_t S) { return (q_limit > 0 && q_limit < S) ? q_limit : 0; }
 
-// the fused-projection launch: 1 when it ran, 0 when this shape does not take it (the caller then runs the projection GEMM and the
-// plain launch), negative on error
-template <typename T>
-static int launch_fwd_qkv(const AttnArgs& a, hipStream_t s) {
-  constexpr int DH = 32;
-  const size_t lds = res_lds_fwd<DH>(a.S);  // (the projection's slices borrow the Q / K / V tiles)
-  const int NB = (int)cdiv(a.S, 32);
-  const int nw = choose_resident(a.S, a.B * a.H, lds, 16, false);
-  // every owner block needs its own wave (one pass over the weight slices); the staging pattern is laid out for 512 threads
-  // (four x pieces and two weight pieces per thread; the weight slice must fit the V tile: NB >= 6)
-  if (nw < NB || nw < 6 || a.Dm % QKV_KC != 0 || a.Dm != a.H * DH) return 0;
-  static size_t attr_lds = 64 * 1024;
-  if (lds > attr_lds) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_res_kernel<T, DH, true>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { set_error("attn_fwd_res_kernel (fused projection): LDS opt-in of %zu bytes: %s", lds, hipGetErrorString(e)); return MST_ERR_LAUNCH; }
-    attr_lds = lds;
+// ---- What a valid call launches: the codes of mst_attn_fwd_form / mst_attn_bwd_form (include/mst_hip.h). Every decision between
+// kernels is made HERE, from the shape (and the MST_ATTN_PATH override inside choose_resident) alone; the launchers below switch
+// on the result and decide nothing themselves, and the form queries report it.
+enum { ATT_FWD_RES3 = 0, ATT_FWD_RES2 = 1, ATT_FWD_CHUNKED = 2, ATT_FWD_FUSED = 3, ATT_FWD_STREAM = 4 };
+enum { ATT_BWD_RES = 0, ATT_BWD_STREAM_CHUNKQ = 1, ATT_BWD_STREAM = 2 };
+struct AttnFwdForm { int path, waves; size_t lds; int lone, restage; int64_t grid_stats, grid_out; };
+struct AttnBwdForm { int path, waves; size_t lds; int sparse, lone, dq_chunks, dq_waves; };
+constexpr int ATT_DQ_OBM = 4, ATT_DQ_NW = 8;  // chunked dQ: owner blocks per wave, waves per workgroup
+
+// q_limit: fwd_q_limit's. fused_call: mst_attn_qkv_fwd (the projection inside the launch where the shape takes it, else the
+// GEMM and one of the plain forms)
+static AttnFwdForm attn_fwd_form(int dh, int64_t S, int64_t H, int64_t n_wg, int64_t q_limit, bool fused_call) {
+  AttnFwdForm f = {};
+  const int NB = (int)cdiv(S, 32);
+  if (fused_call && dh == 32) {
+    const int64_t Dm = H * dh;
+    const size_t lds = res_lds_fwd(32, S, 3);  // (the projection's slices borrow the Q / K / V tiles)
+    const int nw = choose_resident(S, n_wg, lds, 16, false);
+    // every owner block needs its own wave (one pass over the weight slices); the staging pattern is laid out for 512 threads
+    // (four x pieces and two weight pieces per thread; the weight slice must fit the V tile: NB >= 6)
+    if (nw >= NB && nw >= 6 && Dm % QKV_KC == 0) { f.path = ATT_FWD_FUSED; f.waves = nw; f.lds = lds; return f; }
   }
-  hipLaunchKernelGGL((attn_fwd_res_kernel<T, DH, true>), dim3((unsigned)(a.B * a.H)), dim3(nw * 64), lds, s, a);
-  MST_CHECK_LAUNCH("attn_fwd_res_kernel (fused projection)");
-  return 1;
+  const bool lone = lone_row_shape(S, dh) && q_limit >= S;
+  const int waves_cu = dh == 16 ? 4 * ATT16_WAVES : 16;
+  f.lone = lone;
+  for (int tiles = 3; tiles >= 2; --tiles) {
+    // three tiles: Q | K | V together. Two (restage = 1): they do not fit, K and V are staged over Q between the phases (configs[4]'s
+    // decoder: S 1025, dh 16)
+    const size_t lds = res_lds_fwd(dh, S, tiles);
+    if (const int nw = choose_resident(S, n_wg, lds, waves_cu, lone)) {
+      f.path = tiles == 3 ? ATT_FWD_RES3 : ATT_FWD_RES2; f.waves = nw; f.lds = lds; f.restage = tiles == 3 ? 0 : 1;
+      return f;
+    }
+  }
+  if (!lone && dh >= 32 && NB % 2 == 0) {
+    // ... nor K | V alone: one tile (restage = 2), the output phase in two chunks of keys (configs[4]'s encoder: S 1024, head size 32)
+    const size_t lds = res_lds_fwd(dh, S, 1);
+    const int maxw = res_max_waves(dh);  // (the chunked instantiation's launch bounds)
+    const int nw = choose_resident(S, n_wg, lds, maxw, false, maxw);
+    if (nw && NB <= 2 * nw) { f.path = ATT_FWD_CHUNKED; f.waves = nw; f.lds = lds; f.restage = 2; return f; }
+  }
+  f.path = ATT_FWD_STREAM; f.waves = 4; f.lone = 0;
+  f.grid_stats = cdiv(S, ATT_WG_ROWS); f.grid_out = cdiv(q_limit, ATT_WG_ROWS);
+  return f;
+}
+// q_limit: bwd_q_limit's
+static AttnBwdForm attn_bwd_form(int dh, int64_t S, int64_t n_wg, int64_t q_limit) {
+  AttnBwdForm f = {};
+  f.sparse = q_limit > 0 && q_limit <= 32;
+  const bool lone = lone_row_shape(S, dh) && !f.sparse;
+  const size_t lds = res_lds_bwd(dh, S);
+  if (const int nw = choose_resident(S, n_wg, lds, dh == 16 ? 4 * ATT16_WAVES : res_max_waves(dh), lone, res_max_waves(dh))) {
+    f.path = ATT_BWD_RES; f.waves = nw; f.lds = lds; f.lone = lone;
+    return f;
+  }
+  f.path = ATT_BWD_STREAM; f.waves = 4;
+  // dQ: one workgroup per (batch, head) with the keys staged in chunks where the constants and two chunk tiles fit LDS
+  // (head size 32: at 64 four blocks' accumulators and fragments do not fit 256 registers)
+  const int NB = (int)cdiv(S, 32);
+  if (dh == 32 && NB <= ATT_DQ_OBM * ATT_DQ_NW) {
+    for (int nc = 1; nc <= 4; nc *= 2) {
+      if (NB % nc != 0) break;
+      const size_t lds_q = (size_t)2 * (NB * 32 / nc) * (dh + 8) * 2 + (size_t)6 * NB * 32 * 4;
+      if (lds_q > 150 * 1024) continue;
+      f.path = ATT_BWD_STREAM_CHUNKQ; f.lds = lds_q; f.dq_chunks = nc; f.dq_waves = ATT_DQ_NW;
+      break;
+    }
+  }
+  return f;
+}
+
+// dynamic LDS above 64 KB has to be opted into, per kernel (*granted: what the kernel has been granted so far)
+static int lds_opt_in(const void* fn, size_t lds, size_t* granted, const char* what) {
+  if (lds <= *granted) return MST_OK;
+  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) { set_error("%s: LDS opt-in of %zu bytes: %s", what, lds, hipGetErrorString(e)); return MST_ERR_LAUNCH; }
+  *granted = lds;
+  return MST_OK;
 }
 
 template <typename T, int DH>
-static int launch_fwd(const AttnArgs& a_in, hipStream_t s) {
+static int launch_fwd(const AttnArgs& a_in, const AttnFwdForm& f, hipStream_t s) {
   AttnArgs a = a_in;
-  size_t lds = res_lds_fwd<DH>(a.S);
-  const bool lone_f = lone_row_shape(a.S, DH) && a.q_limit >= a.S;
-  const int waves_cu = DH == 16 ? 4 * ATT16_WAVES : 16;
-  int nw = choose_resident(a.S, a.B * a.H, lds, waves_cu, lone_f);
-  if (!nw) {  // Q | K | V do not fit together: two tiles, K and V staged over Q between the phases (configs[4]'s decoder: S 1025, dh 16)
-    const size_t lds2 = res_lds_fwd<DH>(a.S, 2);
-    const int nw2 = choose_resident(a.S, a.B * a.H, lds2, waves_cu, lone_f);
-    if (nw2) { nw = nw2; lds = lds2; a.restage = 1; }
-    else if (!lone_f && DH >= 32) {
-      // ... nor K | V alone: one tile, the output phase in two chunks of keys (configs[4]'s encoder: S 1024, head size 32)
-      const int NB = (int)cdiv(a.S, 32);
-      const size_t lds1 = res_lds_fwd<DH>(a.S, 1);
-      constexpr int MAXW = FWD_MAX_WAVES<DH, true>;  // (the chunked instantiation's launch bounds)
-      const int nw1 = NB % 2 == 0 ? choose_resident(a.S, a.B * a.H, lds1, DH == 16 ? waves_cu : MAXW, false, MAXW) : 0;
-      if (nw1 && NB <= 2 * nw1) {
-        a.restage = 2;
-        static size_t attr_lds1 = 64 * 1024;
-        if (lds1 > attr_lds1) {
-          const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_res_kernel<T, DH, false, true>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
-          if (e != hipSuccess) { set_error("attn_fwd_res_kernel (chunked): LDS opt-in of %zu bytes: %s", lds1, hipGetErrorString(e)); return MST_ERR_LAUNCH; }
-          attr_lds1 = lds1;
-        }
-        hipLaunchKernelGGL((attn_fwd_res_kernel<T, DH, false, true>), dim3((unsigned)(a.B * a.H)), dim3(nw1 * 64), lds1, s, a);
+  a.restage = f.restage;
+  const dim3 grid_res((unsigned)(a.B * a.H)), block_res(f.waves * 64);
+  switch (f.path) {
+    case ATT_FWD_FUSED: {
+      if constexpr (DH == 32) {
+        static size_t granted = 64 * 1024;
+        if (const int rc = lds_opt_in(reinterpret_cast<const void*>(&attn_fwd_res_kernel<T, DH, true>), f.lds, &granted, "attn_fwd_res_kernel (fused projection)")) return rc;
+        hipLaunchKernelGGL((attn_fwd_res_kernel<T, DH, true>), grid_res, block_res, f.lds, s, a);
+        MST_CHECK_LAUNCH("attn_fwd_res_kernel (fused projection)");
+        return MST_OK;
+      }
+      break;
+    }
+    case ATT_FWD_CHUNKED: {
+      if (DH >= 32) {  // (a run-time test on purpose: every head size keeps its instantiation, the code object is the one it was)
+        static size_t granted = 64 * 1024;
+        if (const int rc = lds_opt_in(reinterpret_cast<const void*>(&attn_fwd_res_kernel<T, DH, false, true>), f.lds, &granted, "attn_fwd_res_kernel (chunked)")) return rc;
+        hipLaunchKernelGGL((attn_fwd_res_kernel<T, DH, false, true>), grid_res, block_res, f.lds, s, a);
         MST_CHECK_LAUNCH("attn_fwd_res_kernel (chunked)");
         return MST_OK;
       }
+      break;
+    }
+    case ATT_FWD_RES3:
+    case ATT_FWD_RES2: {
+      static size_t granted = 64 * 1024;
+      if (const int rc = lds_opt_in(reinterpret_cast<const void*>(&attn_fwd_res_kernel<T, DH>), f.lds, &granted, "attn_fwd_res_kernel")) return rc;
+      hipLaunchKernelGGL((attn_fwd_res_kernel<T, DH>), grid_res, block_res, f.lds, s, a);
+      MST_CHECK_LAUNCH("attn_fwd_res_kernel");
+      return MST_OK;
+    }
+    case ATT_FWD_STREAM: {
+      const dim3 grid((unsigned)f.grid_stats, (unsigned)(a.B * a.H));
+      hipLaunchKernelGGL((attn_fwd_stats_kernel<T, DH>), grid, dim3(256), 0, s, a);
+      MST_CHECK_LAUNCH("attn_fwd_stats_kernel");
+      const dim3 grid_o((unsigned)f.grid_out, (unsigned)(a.B * a.H));
+      hipLaunchKernelGGL((attn_fwd_out_kernel<T, DH>), grid_o, dim3(256), 0, s, a);
+      MST_CHECK_LAUNCH("attn_fwd_out_kernel");
+      return MST_OK;
     }
   }
-  if (nw) {
-    static size_t attr_lds = 64 * 1024;  // dynamic LDS above 64 KB has to be opted into
-    if (lds > attr_lds) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_res_kernel<T, DH>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) { set_error("attn_fwd_res_kernel: LDS opt-in of %zu bytes: %s", lds, hipGetErrorString(e)); return MST_ERR_LAUNCH; }
-      attr_lds = lds;
-    }
-    hipLaunchKernelGGL((attn_fwd_res_kernel<T, DH>), dim3((unsigned)(a.B * a.H)), dim3(nw * 64), lds, s, a);
-    MST_CHECK_LAUNCH("attn_fwd_res_kernel");
-    return MST_OK;
-  }
-  dim3 grid((unsigned)cdiv(a.S, ATT_WG_ROWS), (unsigned)(a.B * a.H));
-  hipLaunchKernelGGL((attn_fwd_stats_kernel<T, DH>), grid, dim3(256), 0, s, a);
-  MST_CHECK_LAUNCH("attn_fwd_stats_kernel");
-  dim3 grid_o((unsigned)cdiv(a.q_limit, ATT_WG_ROWS), (unsigned)(a.B * a.H));
-  hipLaunchKernelGGL((attn_fwd_out_kernel<T, DH>), grid_o, dim3(256), 0, s, a);
-  MST_CHECK_LAUNCH("attn_fwd_out_kernel");
-  return MST_OK;
+  set_error("attention forward: form %d has no kernel at head size %d", f.path, DH);
+  return MST_ERR_INVALID;
 }
 template <typename T, int DH>
-static int launch_bwd(const AttnArgs& a, hipStream_t s) {
-  const size_t lds = res_lds_bwd<DH>(a.S);
-  const bool sparse_shape = a.q_limit > 0 && a.q_limit <= 32;
-  if (const int nw = choose_resident(a.S, a.B * a.H, lds, DH == 16 ? 4 * ATT16_WAVES : RES_MAX_WAVES<DH>, lone_row_shape(a.S, DH) && !sparse_shape, RES_MAX_WAVES<DH>)) {
-    const bool sparse = sparse_shape;
-    static size_t attr_lds[2] = {64 * 1024, 64 * 1024};  // dynamic LDS above 64 KB has to be opted into, per kernel
-    if (lds > attr_lds[sparse]) {
-      const void* fn = sparse ? reinterpret_cast<const void*>(&attn_bwd_res_kernel<T, DH, true>)
+static int launch_bwd(const AttnArgs& a, const AttnBwdForm& f, hipStream_t s) {
+  if (f.path == ATT_BWD_RES) {
+    static size_t granted[2] = {64 * 1024, 64 * 1024};
+    const void* fn = f.sparse ? reinterpret_cast<const void*>(&attn_bwd_res_kernel<T, DH, true>)
                               : reinterpret_cast<const void*>(&attn_bwd_res_kernel<T, DH, false>);
-      const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) { set_error("attn_bwd_res_kernel: LDS opt-in of %zu bytes: %s", lds, hipGetErrorString(e)); return MST_ERR_LAUNCH; }
-      attr_lds[sparse] = lds;
-    }
-    if (sparse) hipLaunchKernelGGL((attn_bwd_res_kernel<T, DH, true>), dim3((unsigned)(a.B * a.H)), dim3(nw * 64), lds, s, a);
-    else hipLaunchKernelGGL((attn_bwd_res_kernel<T, DH, false>), dim3((unsigned)(a.B * a.H)), dim3(nw * 64), lds, s, a);
+    if (const int rc = lds_opt_in(fn, f.lds, &granted[f.sparse], "attn_bwd_res_kernel")) return rc;
+    if (f.sparse) hipLaunchKernelGGL((attn_bwd_res_kernel<T, DH, true>), dim3((unsigned)(a.B * a.H)), dim3(f.waves * 64), f.lds, s, a);
+    else hipLaunchKernelGGL((attn_bwd_res_kernel<T, DH, false>), dim3((unsigned)(a.B * a.H)), dim3(f.waves * 64), f.lds, s, a);
     MST_CHECK_LAUNCH("attn_bwd_res_kernel");
     return MST_OK;
   }
-  dim3 grid((unsigned)cdiv(a.S, ATT_WG_ROWS), (unsigned)(a.B * a.H));
-  if (sparse_shape) hipLaunchKernelGGL((attn_bwd_kv_kernel<T, DH, true>), grid, dim3(256), 0, s, a);
+  const dim3 grid((unsigned)cdiv(a.S, ATT_WG_ROWS), (unsigned)(a.B * a.H));
+  if (f.sparse) hipLaunchKernelGGL((attn_bwd_kv_kernel<T, DH, true>), grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL((attn_bwd_kv_kernel<T, DH, false>), grid, dim3(256), 0, s, a);
   MST_CHECK_LAUNCH("attn_bwd_kv_kernel");
-  {  // dQ: one workgroup per (batch, head) with the keys staged in chunks where the constants and two chunk tiles fit LDS
-    constexpr int OBM = 4, NWQ = 8;
-    const int NB = (int)cdiv(a.S, 32);
-    if (DH == 32 && NB <= OBM * NWQ) {  // (head size 32: at 64 four blocks' accumulators and fragments do not fit 256 registers)
-      for (int nc = 1; nc <= 4; nc *= 2) {
-        if (NB % nc != 0) break;
-        const size_t lds = (size_t)2 * (NB * 32 / nc) * LdsLd<DH>::V * 2 + (size_t)6 * NB * 32 * 4;
-        if (lds > 150 * 1024) continue;
-        static size_t attr_lds = 64 * 1024;
-        if (lds > attr_lds) {
-          const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_q_chunk_kernel<T, DH, OBM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-          if (e != hipSuccess) { set_error("attn_bwd_q_chunk_kernel: LDS opt-in of %zu bytes: %s", lds, hipGetErrorString(e)); return MST_ERR_LAUNCH; }
-          attr_lds = lds;
-        }
-        hipLaunchKernelGGL((attn_bwd_q_chunk_kernel<T, DH, OBM>), dim3((unsigned)(a.B * a.H)), dim3(NWQ * 64), lds, s, a, nc);
-        MST_CHECK_LAUNCH("attn_bwd_q_chunk_kernel");
-        return MST_OK;
-      }
+  if (f.path == ATT_BWD_STREAM_CHUNKQ) {
+    if (DH == 32) {  // (run-time, as above)
+      static size_t granted = 64 * 1024;
+      if (const int rc = lds_opt_in(reinterpret_cast<const void*>(&attn_bwd_q_chunk_kernel<T, DH, ATT_DQ_OBM>), f.lds, &granted, "attn_bwd_q_chunk_kernel")) return rc;
+      hipLaunchKernelGGL((attn_bwd_q_chunk_kernel<T, DH, ATT_DQ_OBM>), dim3((unsigned)(a.B * a.H)), dim3(f.dq_waves * 64), f.lds, s, a, f.dq_chunks);
+      MST_CHECK_LAUNCH("attn_bwd_q_chunk_kernel");
+      return MST_OK;
     }
+    set_error("attention backward: chunked dQ has no kernel at head size %d", DH);
+    return MST_ERR_INVALID;
   }
   hipLaunchKernelGGL((attn_bwd_q_kernel<T, DH>), grid, dim3(256), 0, s, a);
   MST_CHECK_LAUNCH("attn_bwd_q_kernel");
   return MST_OK;
+}
+template <typename T>
+static int launch_fwd_dh(int64_t dh, const AttnArgs& a, const AttnFwdForm& f, hipStream_t s) {
+  if (dh == 16) return launch_fwd<T, 16>(a, f, s);
+  if (dh == 32) return launch_fwd<T, 32>(a, f, s);
+  return launch_fwd<T, 64>(a, f, s);
 }
 
 
@@ -1791,19 +1863,43 @@ extern "C" int mst_attn_keysoftmax_fwd(int dtype, int64_t B, int64_t S, int64_t 
   int rc = attn_check(B, S, H, dh, ld_qkv, k_off, q_off, v_off);
   if (rc) return rc;
   MST_CHECK_ARG(qkv && keymask && lse && out, "mst_attn_keysoftmax_fwd: null pointer");
-  MST_CHECK_ARG(ld_out >= H * dh, "mst_attn_keysoftmax_fwd: ld_out < H*dh");
+  rc = attn_check_fwd(B, S, H, dh, ld_qkv, k_off, q_off, v_off, ld_out);
+  if (rc) return rc;
   AttnArgs a = {};
   a.B = B; a.S = S; a.H = H; a.qkv = qkv; a.ld_qkv = ld_qkv; a.k_off = k_off; a.q_off = q_off; a.v_off = v_off;
   a.keymask = keymask; a.lse = lse; a.out = out; a.ld_out = ld_out;
-  a.q_limit = (q_limit > 0 && q_limit < S) ? q_limit : S;
+  a.q_limit = fwd_q_limit(q_limit, S);
   a.scale = 1.f / sqrtf((float)dh);
   hipStream_t s = (hipStream_t)stream;
   return dispatch_act(dtype, [&](auto tag) -> int {
-    typedef decltype(tag) T;
-    if (dh == 16) return launch_fwd<T, 16>(a, s);
-    if (dh == 32) return launch_fwd<T, 32>(a, s);
-    return launch_fwd<T, 64>(a, s);
+    return launch_fwd_dh<decltype(tag)>(dh, a, attn_fwd_form((int)dh, S, H, B * H, a.q_limit, false), s);
   });
+}
+
+static void put_fwd_form(const AttnFwdForm& f, int64_t* form) {
+  const int64_t v[8] = {f.path, f.waves, (int64_t)f.lds, f.lone, f.grid_stats, f.grid_out, 0, 0};
+  for (int i = 0; i < 8; ++i) form[i] = v[i];
+}
+extern "C" int mst_attn_fwd_form(int dtype, int64_t B, int64_t S, int64_t H, int64_t dh, int64_t ld_qkv, int64_t k_off, int64_t q_off,
+                                 int64_t v_off, int64_t ld_out, int64_t q_limit, int fused, int64_t ld_x, int64_t ld_w, int64_t* form) {
+  MST_CHECK_ARG(form != nullptr, "mst_attn_fwd_form: null form");
+  int rc = fused ? attn_check_qkv(B, S, H, dh, ld_x, ld_w, ld_qkv, k_off, q_off, v_off, ld_out)
+                 : attn_check_fwd(B, S, H, dh, ld_qkv, k_off, q_off, v_off, ld_out);
+  if (rc == MST_OK) rc = check_act_dtype(dtype);
+  if (rc) return rc;
+  put_fwd_form(attn_fwd_form((int)dh, S, H, B * H, fwd_q_limit(q_limit, S), fused != 0), form);
+  return MST_OK;
+}
+extern "C" int mst_attn_bwd_form(int dtype, int64_t B, int64_t S, int64_t H, int64_t dh, int64_t ld_qkv, int64_t k_off, int64_t q_off,
+                                 int64_t v_off, int64_t ld_dout, int64_t ld_dqkv, int64_t q_limit, int64_t* form) {
+  MST_CHECK_ARG(form != nullptr, "mst_attn_bwd_form: null form");
+  int rc = attn_check_bwd(B, S, H, dh, ld_qkv, k_off, q_off, v_off, ld_dout, ld_dqkv);
+  if (rc == MST_OK) rc = check_act_dtype(dtype);
+  if (rc) return rc;
+  const AttnBwdForm f = attn_bwd_form((int)dh, S, B * H, bwd_q_limit(q_limit, S));
+  const int64_t v[8] = {f.path, f.waves, (int64_t)f.lds, f.sparse, f.lone, f.dq_chunks, f.dq_waves, 0};
+  for (int i = 0; i < 8; ++i) form[i] = v[i];
+  return MST_OK;
 }
 
 #ifdef MST_ATT_STAMPS
@@ -1818,33 +1914,32 @@ extern "C" int mst_debug_att_stamps(uint64_t* host_out) {  // diagnostic builds 
 extern "C" int mst_attn_qkv_fwd(int dtype, int64_t B, int64_t S, int64_t H, int64_t dh, const void* x, int64_t ld_x, const void* w,
                                 int64_t ld_w, const float* bias, void* qkv, int64_t ld_qkv, int64_t k_off, int64_t q_off, int64_t v_off,
                                 const uint8_t* keymask, float* lse, void* out, int64_t ld_out, int64_t q_limit, mst_stream_t stream) {
-  int rc = attn_check(B, S, H, dh, ld_qkv, k_off, q_off, v_off);
+  int rc = attn_check_qkv(B, S, H, dh, ld_x, ld_w, ld_qkv, k_off, q_off, v_off, ld_out);
   if (rc) return rc;
   const int64_t Dm = H * dh;
   MST_CHECK_ARG(x && w && bias && qkv && keymask && lse && out, "mst_attn_qkv_fwd: null pointer");
-  MST_CHECK_ARG(ld_x % 8 == 0 && ld_x >= Dm && ld_w % 8 == 0 && ld_w >= Dm && ld_qkv >= 3 * Dm && ld_out >= Dm,
-                "mst_attn_qkv_fwd: leading dimensions must be multiples of 8 and cover the model width");
   MST_CHECK_ARG(((uintptr_t)x % 16 == 0) && ((uintptr_t)w % 16 == 0) && ((uintptr_t)bias % 16 == 0) && ((uintptr_t)qkv % 16 == 0),
                 "mst_attn_qkv_fwd: operands must be 16-byte aligned");
-  MST_CHECK_ARG(k_off + Dm <= 3 * Dm && q_off + Dm <= 3 * Dm && v_off + Dm <= 3 * Dm, "mst_attn_qkv_fwd: section offsets beyond the 3 D weight rows");
-  hipStream_t s = (hipStream_t)stream;
-  if (dh == 32) {
-    AttnArgs a = {};
-    a.B = B; a.S = S; a.H = H; a.qkv = qkv; a.ld_qkv = ld_qkv; a.k_off = k_off; a.q_off = q_off; a.v_off = v_off;
-    a.keymask = keymask; a.lse = lse; a.out = out; a.ld_out = ld_out;
-    a.q_limit = (q_limit > 0 && q_limit < S) ? q_limit : S;
-    a.scale = 1.f / sqrtf((float)dh);
-    a.x = x; a.ld_x = ld_x; a.w = w; a.ld_w = ld_w; a.bias = bias; a.Dm = Dm;
-    rc = dispatch_act(dtype, [&](auto tag) -> int { return launch_fwd_qkv<decltype(tag)>(a, s); });
-    if (rc != 0) return rc < 0 ? rc : MST_OK;
-  }
-  // shapes the fused form does not take: the projection as the GEMM it is, then the plain attention launch
-  mst_gemm_args g = {};
-  g.dtype = dtype; g.M = B * S; g.N = 3 * Dm; g.K = Dm;
-  g.A = x; g.lda = ld_x; g.B = w; g.ldb = ld_w; g.C = qkv; g.ldc = ld_qkv; g.bias = bias; g.alpha = 1.f;
-  rc = mst_gemm_nt(&g, stream);
+  rc = check_act_dtype(dtype);
   if (rc) return rc;
-  return mst_attn_keysoftmax_fwd(dtype, B, S, H, dh, qkv, ld_qkv, k_off, q_off, v_off, keymask, lse, out, ld_out, q_limit, stream);
+  AttnArgs a = {};
+  a.B = B; a.S = S; a.H = H; a.qkv = qkv; a.ld_qkv = ld_qkv; a.k_off = k_off; a.q_off = q_off; a.v_off = v_off;
+  a.keymask = keymask; a.lse = lse; a.out = out; a.ld_out = ld_out;
+  a.q_limit = fwd_q_limit(q_limit, S);
+  a.scale = 1.f / sqrtf((float)dh);
+  const AttnFwdForm f = attn_fwd_form((int)dh, S, H, B * H, a.q_limit, true);
+  if (f.path == ATT_FWD_FUSED) {
+    a.x = x; a.ld_x = ld_x; a.w = w; a.ld_w = ld_w; a.bias = bias; a.Dm = Dm;
+  } else {
+    // shapes the fused form does not take: the projection as the GEMM it is, then the plain attention launch
+    mst_gemm_args g = {};
+    g.dtype = dtype; g.M = B * S; g.N = 3 * Dm; g.K = Dm;
+    g.A = x; g.lda = ld_x; g.B = w; g.ldb = ld_w; g.C = qkv; g.ldc = ld_qkv; g.bias = bias; g.alpha = 1.f;
+    rc = mst_gemm_nt(&g, stream);
+    if (rc) return rc;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  return dispatch_act(dtype, [&](auto tag) -> int { return launch_fwd_dh<decltype(tag)>(dh, a, f, s); });
 }
 
 extern "C" int mst_attn_keysoftmax_bwd(int dtype, int64_t B, int64_t S, int64_t H, int64_t dh, const void* qkv,
@@ -1854,19 +1949,21 @@ extern "C" int mst_attn_keysoftmax_bwd(int dtype, int64_t B, int64_t S, int64_t 
   int rc = attn_check(B, S, H, dh, ld_qkv, k_off, q_off, v_off);
   if (rc) return rc;
   MST_CHECK_ARG(qkv && keymask && lse && dout && dqkv && delta, "mst_attn_keysoftmax_bwd: null pointer");
-  MST_CHECK_ARG(ld_dout % 8 == 0 && ld_dout >= H * dh && ld_dqkv % 8 == 0, "mst_attn_keysoftmax_bwd: bad leading dims");
+  rc = attn_check_bwd(B, S, H, dh, ld_qkv, k_off, q_off, v_off, ld_dout, ld_dqkv);
+  if (rc) return rc;
   AttnArgs a = {};
   a.B = B; a.S = S; a.H = H; a.qkv = qkv; a.ld_qkv = ld_qkv; a.k_off = k_off; a.q_off = q_off; a.v_off = v_off;
   a.keymask = keymask; a.lse = const_cast<float*>(lse); a.dout = dout; a.ld_dout = ld_dout; a.dqkv = dqkv;
   a.ld_dqkv = ld_dqkv; a.delta = delta;
-  a.q_limit = (q_limit > 0 && q_limit < S) ? q_limit : 0;  // 0: dense dO
+  a.q_limit = bwd_q_limit(q_limit, S);
   a.scale = 1.f / sqrtf((float)dh);
   hipStream_t s = (hipStream_t)stream;
   return dispatch_act(dtype, [&](auto tag) -> int {
     typedef decltype(tag) T;
-    if (dh == 16) return launch_bwd<T, 16>(a, s);
-    if (dh == 32) return launch_bwd<T, 32>(a, s);
-    return launch_bwd<T, 64>(a, s);
+    const AttnBwdForm f = attn_bwd_form((int)dh, S, B * H, a.q_limit);
+    if (dh == 16) return launch_bwd<T, 16>(a, f, s);
+    if (dh == 32) return launch_bwd<T, 32>(a, f, s);
+    return launch_bwd<T, 64>(a, f, s);
   });
 }
 

@@ -524,6 +524,27 @@ def attn_bwd(qkv, keymask, lse, dout, dqkv, delta, B, S, H, dh, k_off, q_off, v_
          ptr(lse), ptr(dout), ld(dout), ptr(dqkv), ld(dqkv), ptr(delta), q_limit, stream())
 
 
+ATTN_FWD_PATHS = ("resident-3", "resident-2", "chunked", "fused", "stream")
+ATTN_BWD_PATHS = ("resident", "stream+chunked-dq", "stream")
+
+
+def attn_fwd_form(dtype, B, S, H, dh, k_off, q_off, v_off, ld_qkv, ld_out, q_limit=0, fused=False, ld_x=0, ld_w=0):
+    """what attn_fwd (fused: attn_qkv_fwd) launches for these arguments (mst_attn_fwd_form in include/mst_hip.h); no launch, no device.
+    -> dict(path (one of ATTN_FWD_PATHS), waves, lds, lone, grid_stats, grid_out)"""
+    form = (C.c_int64 * 8)()
+    call("mst_attn_fwd_form", dt(dtype), B, S, H, dh, ld_qkv, k_off, q_off, v_off, ld_out, q_limit, 1 if fused else 0, ld_x, ld_w, form)
+    return dict(path=ATTN_FWD_PATHS[form[0]], waves=form[1], lds=form[2], lone=form[3], grid_stats=form[4], grid_out=form[5])
+
+
+def attn_bwd_form(dtype, B, S, H, dh, k_off, q_off, v_off, ld_qkv, ld_dout, ld_dqkv, q_limit=0):
+    """what attn_bwd launches for these arguments (mst_attn_bwd_form); no launch, no device.
+    -> dict(path (one of ATTN_BWD_PATHS), waves, lds, sparse, lone, dq_chunks, dq_waves)"""
+    form = (C.c_int64 * 8)()
+    call("mst_attn_bwd_form", dt(dtype), B, S, H, dh, ld_qkv, k_off, q_off, v_off, ld_dout, ld_dqkv, q_limit, form)
+    return dict(path=ATTN_BWD_PATHS[form[0]], waves=form[1], lds=form[2], sparse=form[3], lone=form[4], dq_chunks=form[5],
+                dq_waves=form[6])
+
+
 def attn_causal_fwd(qkv, keymask, lse, out, B, S, H, dh, k_off, q_off, v_off):
     """causal attention with the softmax over the keys (mst_attn_causal_fwd): lse gets per-query statistics"""
     call("mst_attn_causal_fwd", dt(qkv), B, S, H, dh, ptr(qkv), ld(qkv), k_off, q_off, v_off, ptr(keymask), ptr(lse), ptr(out),

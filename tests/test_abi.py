@@ -104,6 +104,8 @@ def test_parser_known_answers():
                                    vp, i64, vp, vp, ci, f32, u64, u32, vp, i64, vp, vp]),
         "mst_gemm_wgrad_batch_flush": (ci, [P(_lib.WgradArgs), ci, vp, i64, P(_lib.PartialSum), ci, P(_lib.OuterJob), ci, vp]),
         "mst_gemm_wgrad_plan": (ci, [P(_lib.WgradArgs), ci, i64, vp]),
+        "mst_attn_fwd_form": (ci, [ci, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, ci, i64, i64, vp]),
+        "mst_attn_bwd_form": (ci, [ci, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, vp]),
         "mst_step_begin": (ci, [P(_lib.StepBeginArgs), vp]),
         "mst_mask_from_lengths": (ci, [i64, i64, vp, i32, vp, vp]),
     }
