@@ -571,6 +571,18 @@ int mst_latent_bwd_vec_proj_sched(int dtype, int64_t B, int64_t De, int64_t Z, i
                                   float alpha_d, const float* sched, const float* kl, float gscale, float enc_scale, float* dcls_d,
                                   int64_t ld_cls, void* d_enc_out, int64_t denc_sample_stride, float* scratch, mst_stream_t stream);
 
+/* What the latent block's launches above take for a shape, from the two host functions the launches themselves decide with; no HIP
+ * call, and Wl is looked at for its alignment only (never followed). nq: outputs of the fused projection (mst_latent_fwd_proj's nq,
+ * mst_latent_bwd_vec_proj's nq), 0 for the plain launches. form: eight entries,
+ *   [0] forward preloaded (1) / general (0)       [1] loader of the h0 . Wl product: 0 registers (preloaded), 1 wave_dots_pre, 2 wave_dots
+ *   [2] the same for z . Wh                        [3] elements per lane of the forward projection (1, 2 or 4; 0: no projection)
+ *   [4] forward dynamic LDS bytes                  [5] backward preloaded (1) / general (0)
+ *   [6] dh0 path: 0 preloaded, 1 four columns per thread, 2 one column per thread                 [7] backward dynamic LDS bytes
+ * The shape is validated as the launches validate it, the forward launch's checks first: same status, same message. [0 .. 4] are
+ * written before the backward launch's checks run, so they are valid for a shape only the backward launch refuses (a forward
+ * projection of a width the backward one does not take: form[5] stays as the caller left it). */
+int mst_latent_form(int64_t De, int64_t Z, int64_t Dd, int64_t nq, const void* Wl, int64_t* form);
+
 /* standalone reparameterisation + KL (loss.VariationalKLLoss, loss.py:4-12; model.py:292) */
 int mst_reparam_kl_fwd(int64_t B, int64_t Z, const float* mu, const float* sigma, const float* eps,
                        float* z, float* kl, mst_stream_t stream);

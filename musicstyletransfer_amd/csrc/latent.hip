@@ -71,6 +71,11 @@ __host__ __device__ inline bool latent_bwd_pre_shape(int64_t De, int64_t Z, int6
   const int64_t np_h = LAT_THREADS / Z, np_l = LAT_THREADS / De;
   return (Dd + np_h - 1) / np_h <= LAT_PRE_H && (2 * Z + np_l - 1) / np_l <= LAT_PRE_L;
 }
+// which dh0 loop the backward kernel runs (entry [6] of mst_latent_form): 0 the preloaded weights, 1 four columns per thread
+// (strided_col_dot4: whole 16-byte pieces of a row of Wl, and no more column quads than threads), 2 one column per thread
+inline int latent_bwd_dh0_path(bool pre, int64_t De, const void* Wl) {
+  return pre ? 0 : (De % 4 == 0 && De / 4 <= LAT_THREADS && ((uintptr_t)Wl & 15) == 0) ? 1 : 2;
+}
 // the same for FOUR consecutive columns (one 16-byte load per row): four times fewer load instructions and four times more row parts
 // per output (latent_bwd_vec's general path at configs[2]: 512 rows x 256 columns — 32 rows per thread in four batches instead of 128 in eight)
 template <int UNR>
@@ -159,7 +164,8 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_bwd_vec_kernel(int De, int
                                                                      float* __restrict__ dlat, T* __restrict__ d_enc_out,
                                                                      int64_t denc_stride, const int32_t* __restrict__ classes,
                                                                      float* __restrict__ dcls, int64_t ld_cls, LatentDx0 x0,
-                                                                     const float* __restrict__ sched, const float* __restrict__ kl) {
+                                                                     const float* __restrict__ sched, const float* __restrict__ kl,
+                                                                     int dh0_path) {
   extern __shared__ float sm[];
   float* t = sm;             // [Dd]
   float* dl = sm + Dd;       // [2Z]
@@ -262,7 +268,7 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_bwd_vec_kernel(int De, int
     }
   }
   // dh0[d] = sum_j dlat[j] * Wl[j,d], same split
-  if (!pre && De % 4 == 0 && De / 4 <= LAT_THREADS && ((uintptr_t)Wl & 15) == 0) {
+  if (!pre && dh0_path == 1) {  // (host: latent_bwd_dh0_path)
     // general path, four columns per thread: `part` holds LAT_THREADS float4 here (the host sizes it for the general form)
     const int dc4 = De / 4, np4 = LAT_THREADS / dc4;
     const int c4 = tid % dc4, pt = tid / dc4;
@@ -369,6 +375,42 @@ __global__ __launch_bounds__(256) void class_table_grad_kernel(int64_t B, int Dd
 
 using namespace mst;
 
+// ---- What a valid call launches: the entries of mst_latent_form (include/mst_hip.h). The launchers below validate a shape and take
+// every decision between kernels, loaders and LDS sizes through these two functions and nothing else; no HIP call in either.
+// f: five entries (form[0 .. 4]); nq: outputs of the row-0 projection, 0 without one
+static int latent_fwd_form(int64_t De, int64_t Z, int64_t Dd, int64_t nq, int64_t* f) {
+  MST_CHECK_ARG(De > 0 && Z > 0 && Dd > 0, "mst_latent_fwd: sizes must be positive");
+  MST_CHECK_ARG(nq == 0 || (nq > 0 && (Dd == 64 || Dd == 128 || Dd == 256)),
+                "mst_latent_fwd_proj: the row-0 projection takes a decoder width of 64, 128 or 256 and an 8-byte aligned weight");
+  const int64_t lds = (int64_t)sizeof(float) * (De + 3 * Z + (nq ? Dd + nq : 0));
+  MST_CHECK_ARG(lds <= 60000, "mst_latent_fwd: De + 3Z too large for one workgroup");
+  const bool pre = latent_fwd_pre_shape(De, Z, Dd);
+  f[0] = pre ? 1 : 0;
+  f[1] = latent_fwd_loader(pre, De);
+  f[2] = latent_fwd_loader(pre, Z);
+  f[3] = nq ? latent_proj_vec(Dd) : 0;
+  f[4] = lds;
+  return MST_OK;
+}
+// f: three entries (form[5 .. 7]); nq: columns of the transposed projection weight, 0 when d(dec_in) is read
+static int latent_bwd_form(int64_t De, int64_t Z, int64_t Dd, int64_t nq, const void* Wl, int64_t* f) {
+  MST_CHECK_ARG(De > 0 && Z > 0 && Dd > 0, "mst_latent_bwd_vec: sizes must be positive");
+  MST_CHECK_ARG(Z <= LAT_THREADS, "mst_latent_bwd_vec: latent size above %d", LAT_THREADS);
+  MST_CHECK_ARG(nq == 0 || nq == 384 || nq == 768,
+                "mst_latent_bwd_vec_proj: the projection must have 384 or 768 outputs (decoder width 128 or 256) and a 4-byte aligned transposed weight");
+  const bool pre = latent_bwd_pre_shape(De, Z, Dd);
+  f[0] = pre ? 1 : 0;
+  f[1] = latent_bwd_dh0_path(pre, De, Wl);
+  f[2] = (int64_t)sizeof(float) * (Dd + 2 * Z + (pre ? 1 : 4) * LAT_THREADS + 4);  // (+ 4: the float4 view's alignment)
+  return MST_OK;
+}
+extern "C" int mst_latent_form(int64_t De, int64_t Z, int64_t Dd, int64_t nq, const void* Wl, int64_t* form) {
+  MST_CHECK_ARG(form != nullptr, "mst_latent_form: null form");
+  int rc = latent_fwd_form(De, Z, Dd, nq, form);
+  if (rc) return rc;
+  return latent_bwd_form(De, Z, Dd, nq, Wl, form + 5);
+}
+
 static int latent_fwd_impl(int dtype, int64_t B, int64_t De, int64_t Z, int64_t Dd, const void* enc_out,
                            int64_t enc_sample_stride, const float* Wl, const float* bl, const float* eps,
                            const float* Wh, const float* bh, const int32_t* classes, const float* cls_d,
@@ -378,10 +420,12 @@ static int latent_fwd_impl(int dtype, int64_t B, int64_t De, int64_t Z, int64_t 
   MST_CHECK_ARG(B > 0 && De > 0 && Z > 0 && Dd > 0, "mst_latent_fwd: sizes must be positive");
   MST_CHECK_ARG(enc_out && Wl && bl && eps && Wh && bh && classes && cls_d && pos_d && mu && sigma && z && kl && dec_in,
                 "mst_latent_fwd: null pointer");
-  MST_CHECK_ARG(!Wq || (qkv0 && nq > 0 && (Dd == 64 || Dd == 128 || Dd == 256) && ld_wq >= Dd && ((uintptr_t)Wq % 8) == 0 && ld_wq % 4 == 0),
+  MST_CHECK_ARG(!Wq || (qkv0 && nq > 0 && ld_wq >= Dd && ((uintptr_t)Wq % 8) == 0 && ld_wq % 4 == 0),
                 "mst_latent_fwd_proj: the row-0 projection takes a decoder width of 64, 128 or 256 and an 8-byte aligned weight");
-  const size_t lds = sizeof(float) * (De + 3 * Z + (Wq ? Dd + nq : 0));
-  MST_CHECK_ARG(lds <= 60000, "mst_latent_fwd: De + 3Z too large for one workgroup");
+  int64_t form[5];
+  int frc = latent_fwd_form(De, Z, Dd, Wq ? nq : 0, form);
+  if (frc) return frc;
+  const size_t lds = (size_t)form[4];
   return dispatch_act(dtype, [&](auto tag) -> int {
     typedef decltype(tag) T;
     LatentFwdArgs la = {};
@@ -390,7 +434,7 @@ static int latent_fwd_impl(int dtype, int64_t B, int64_t De, int64_t Z, int64_t 
     la.pos_d = pos_d; la.alpha_d = alpha_d; la.mu = mu; la.sigma = sigma; la.z = z; la.kl = kl; la.dec_in = dec_in;
     la.dec_stride = dec_sample_stride;
     la.Wq = Wq; la.ld_wq = ld_wq; la.bq = bq; la.qkv0 = qkv0; la.qkv_stride = qkv_sample_stride; la.nq = (int)nq;
-    if (latent_fwd_pre_shape(De, Z, Dd)) hipLaunchKernelGGL((latent_fwd_kernel<T, true>), dim3((unsigned)B), dim3(LAT_THREADS), lds, (hipStream_t)stream, la);
+    if (form[0]) hipLaunchKernelGGL((latent_fwd_kernel<T, true>), dim3((unsigned)B), dim3(LAT_THREADS), lds, (hipStream_t)stream, la);
     else hipLaunchKernelGGL((latent_fwd_kernel<T, false>), dim3((unsigned)B), dim3(LAT_THREADS), lds, (hipStream_t)stream, la);
     MST_CHECK_LAUNCH("latent_fwd_kernel");
     return MST_OK;
@@ -423,19 +467,23 @@ static int latent_bwd_vec_impl(int dtype, int64_t B, int64_t De, int64_t Z, int6
   MST_CHECK_ARG(B > 0 && De > 0 && Z > 0 && Dd > 0, "mst_latent_bwd_vec: sizes must be positive");
   MST_CHECK_ARG(!sched == !kl, "mst_latent_bwd_vec_sched: the schedule block and the per-sample KL go together");
   MST_CHECK_ARG(Wl && eps && Wh && classes && mu && sigma && (d_dec_in || x0.dq) && dcls_d && d_enc_out && scratch, "mst_latent_bwd_vec: null pointer");
-  MST_CHECK_ARG(Z <= LAT_THREADS, "mst_latent_bwd_vec: latent size above %d", LAT_THREADS);
-  MST_CHECK_ARG(!x0.dq || (x0.Wq && (x0.nq == 384 || x0.nq == 768) && x0.ld_wq >= x0.nq && x0.ld_wq % 2 == 0 && ((uintptr_t)x0.Wq % 4) == 0),
+  int64_t form[3];
+  // (a projection of no columns is refused like any other width that is not 384 or 768)
+  int frc = latent_bwd_form(De, Z, Dd, x0.dq ? (x0.nq ? x0.nq : -1) : 0, Wl, form);
+  if (frc) return frc;
+  MST_CHECK_ARG(!x0.dq || (x0.Wq && x0.ld_wq >= x0.nq && x0.ld_wq % 2 == 0 && ((uintptr_t)x0.Wq % 4) == 0),
                 "mst_latent_bwd_vec_proj: the projection must have 384 or 768 outputs (decoder width 128 or 256) and a 4-byte aligned transposed weight");
-  const size_t lds = sizeof(float) * (Dd + 2 * Z + (latent_bwd_pre_shape(De, Z, Dd) ? 1 : 4) * LAT_THREADS + 4);  // (+ 4: the float4 view's alignment)
+  const size_t lds = (size_t)form[2];
+  const int dh0_path = (int)form[1];
   return dispatch_act(dtype, [&](auto tag) -> int {
     typedef decltype(tag) T;
     auto launch = [&](auto pre, auto scheduled) {
       hipLaunchKernelGGL((latent_bwd_vec_kernel<T, decltype(pre)::value, decltype(scheduled)::value>), dim3((unsigned)B), dim3(LAT_THREADS), lds,
                          (hipStream_t)stream, (int)De, (int)Z, (int)Dd, Wl, eps, Wh, mu, sigma, (const T*)d_dec_in, dec_sample_stride, alpha_d,
                          kl_weight, gscale, enc_scale, scratch, scratch + B * Dd, (T*)d_enc_out, denc_sample_stride, classes, (float*)nullptr,
-                         ld_cls, x0, sched, kl);
+                         ld_cls, x0, sched, kl, dh0_path);
     };
-    const bool pre = latent_bwd_pre_shape(De, Z, Dd);
+    const bool pre = form[0] != 0;
     if (pre && sched) launch(std::true_type{}, std::true_type{});
     else if (pre) launch(std::true_type{}, std::false_type{});
     else if (sched) launch(std::false_type{}, std::true_type{});

@@ -103,6 +103,12 @@ __device__ __forceinline__ void wave_dots_pre(const float* x, int n_in, const fl
 __host__ __device__ inline bool latent_fwd_pre_shape(int64_t De, int64_t Z, int64_t Dd) {
   return 2 * Z <= (LAT_THREADS / 64) * OPW && De <= 64 * PRE_C && Dd <= (LAT_THREADS / 64) * OPW && Z <= 64;
 }
+// how the general form fetches the weights of a product with n_in terms per output (entries [1] and [2] of mst_latent_form): 0 the
+// preloaded registers of PRE, 1 wave_dots_pre (the contraction fits PRE_C chunks of 64), 2 wave_dots: the host's statement of the two
+// `<= 64 * PRE_C` branches of latent_fwd_wg's general form below (a uniform branch inside the one general kernel, not a launch decision).
+inline int latent_fwd_loader(bool pre, int64_t n_in) { return pre ? 0 : n_in <= 64 * PRE_C ? 1 : 2; }
+// elements of the contraction a lane owns in the row-0 projection (wave_dots_t's VEC, chosen below from the same three widths)
+inline int latent_proj_vec(int64_t Dd) { return Dd == 64 ? 1 : Dd == 128 ? 2 : 4; }
 struct LatentFwdArgs {
   int De, Z, Dd;
   const void* enc_out; int64_t enc_stride;

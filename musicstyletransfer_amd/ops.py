@@ -674,6 +674,20 @@ def latent_fwd(enc_out3, Wl, bl, eps, Wh, bh, classes, cls_d, pos_d, alpha_d, mu
         call("mst_latent_fwd_proj", *args, ptr(Wq), ld(Wq), ptr(bq), ptr(qkv3), qkv3.stride(0), Wq.shape[0], stream())
 
 
+def latent_form(De, Z, Dd, nq=0, Wl=0, part=None):
+    """what latent_fwd / latent_bwd_vec launch for a shape (mst_latent_form in include/mst_hip.h); no launch, no device. Wl: a device
+    tensor or a plain address, looked at for alignment only. -> dict(fwd_pre, loader_l, loader_h, proj_vec, fwd_lds, bwd_pre, dh0,
+    bwd_lds). part="fwd": the five forward entries alone, also for a shape that only the backward launch refuses"""
+    form = (C.c_int64 * 8)(*([-1] * 8))
+    addr = Wl.data_ptr() if isinstance(Wl, torch.Tensor) else Wl
+    rc = _lib.load().mst_latent_form(De, Z, Dd, nq, addr, form)
+    names = ("fwd_pre", "loader_l", "loader_h", "proj_vec", "fwd_lds", "bwd_pre", "dh0", "bwd_lds")
+    if part == "fwd" and form[0] >= 0:
+        return dict(zip(names[:5], form[:5]))
+    _lib.check(rc, "mst_latent_form")
+    return dict(zip(names[5:], form[5:8])) if part == "bwd" else dict(zip(names, form))
+
+
 LATENT_ROWS_SITE = 0x7FFE0000  # the generator's eps stream (the training step's eps site is 0x7FFF0000)
 INTERP = {"lerp": 0, "slerp": 1}
 

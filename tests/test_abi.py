@@ -106,6 +106,7 @@ def test_parser_known_answers():
         "mst_gemm_wgrad_plan": (ci, [P(_lib.WgradArgs), ci, i64, vp]),
         "mst_attn_fwd_form": (ci, [ci, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, ci, i64, i64, vp]),
         "mst_attn_bwd_form": (ci, [ci, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, vp]),
+        "mst_latent_form": (ci, [i64, i64, i64, i64, vp, vp]),
         "mst_step_begin": (ci, [P(_lib.StepBeginArgs), vp]),
         "mst_mask_from_lengths": (ci, [i64, i64, vp, i32, vp, vp]),
     }
