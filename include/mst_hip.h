@@ -855,6 +855,37 @@ int mst_adam_flat_emb_sched(int dtype, int64_t n, float* w, const float* grad, f
                             const mst_step_metrics* metrics, const float* sched, int64_t base, const int64_t* emb, int64_t n_emb,
                             void* wt16, mst_stream_t stream);
 
+/* Clipping by the global L2 norm (gluon.utils.clip_global_norm's rule), inside the step: two entry points.
+ *
+ * mst_grad_sumsq: ONE launch of mst_grad_sumsq_parts() workgroups (a fixed count, <= 256) over the flat fp32 gradient bucket
+ * grad[0..n) (16-byte aligned). Element i is multiplied by rescale_lo if i < cut, else by rescale_hi (0 <= cut <= n, any residue
+ * mod 4: the two loss-scale ranges of an fp16 step), and squared; workgroup j stores the sum over its elements at parts[j].
+ * Order: per thread an fp32 chain over its grid-stride 4-vectors (the up-to-three tail elements on the last workgroup), a DPP
+ * wave sum, the four waves through LDS in wave order. No atomics: the same data gives the same bits in every launch. A NaN or
+ * inf in the bucket — or an element whose square overflows fp32, |g r| > 1.8e19 — makes a part non-finite.
+ *
+ * mst_adam_flat_gnorm: mst_adam_flat_emb_sched in which `sched` may be NULL and n_emb may be 0 (both are then ignored: one entry
+ * point for the four forms; advance_step = 0 as there), with the gradient clipped by the norm the parts state:
+ *   S    = sum of parts[0..n_parts) in double, formed by every wave alike: lane l adds parts[4l..4l+3] as (p0 + p1) + (p2 + p3),
+ *          then six pairwise levels across the 64 lanes (partners 1 and 2 apart, mirrored within 8 and within 16, 16 and 32
+ *          apart; each level the commutative sum of two lanes' values) — the same instructions on the same words in every wave
+ *          of every launch of the step, so all of them apply the same factor
+ *   norm = sqrtf((float)S);  c = max_norm / (norm + 1e-8f) in fp32, and c = 1 unless c < 1
+ *   g    = grad * fl32(rescale * c) + wd * w, then the per-element clip and the update of mst_adam_flat
+ * The norm is that of the batch-mean, loss-scale-free gradient, before weight decay: pass mst_grad_sumsq the rescales of the
+ * Adam launches. A step whose norm is not finite is SKIPPED by every launch handed these parts: parameters, moments, shadows and
+ * the metric sums stay as they were; the launch with `gstat` (the one that carries the step's bookkeeping; NULL on the others)
+ * takes the step count back and, if metrics->status is given, increments status[2] — once per step, for any number of ranks.
+ * This guard comes after the two of mst_step_metrics, which count their own skips. On a step that counts, that launch writes
+ * gstat[0..6) = {norm, c, running sum of norms, largest norm, steps, steps with c < 1}; the host clears the running fields.
+ * parts non-NULL and 16-byte aligned, n_parts == mst_grad_sumsq_parts() and 0 < max_norm < inf are checked before any HIP call. */
+int64_t mst_grad_sumsq_parts(void);
+int mst_grad_sumsq(int64_t n, const float* grad, int64_t cut, float rescale_lo, float rescale_hi, float* parts, mst_stream_t stream);
+int mst_adam_flat_gnorm(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
+                        double beta2, float eps, float wd, float rescale, float clip, int32_t* step_state,
+                        const mst_step_metrics* metrics, const float* sched, int64_t base, const int64_t* emb, int64_t n_emb,
+                        void* wt16, const float* parts, int64_t n_parts, float max_norm, float* gstat, mst_stream_t stream);
+
 /* 16-bit shadow + transposed shadow refresh for a list of matrices.
  * desc: int64 [n_mat, 4] on device = {src_offset, dst_offset, rows, cols}; dst is [cols, ld_t] with
  * ld_t = roundup8(rows), pad columns zeroed. tiles: int64 prefix sums [n_mat+1] of 32x32 tile counts. */

@@ -25,7 +25,7 @@ def create_toy_model_config(data):
 
 
 def create_toy_train_config(max_steps=0, **schedule):
-    """main.py:41-55; schedule: the training-schedule fields of TrainConfig (the --kl-warmup-steps ... flags)"""
+    """main.py:41-55; schedule: the training-schedule fields of TrainConfig (the --kl-warmup-steps ... flags) and clip_global_norm"""
     return trainer.TrainConfig(batch_size=1, sampling_frequency=500, checkpoint_frequency=1000, num_checkpoints_not_improved=-1,
                                kl_loss=1.0, optimizer=trainer.OptimizerConfig(learning_rate=1e-3, optimizer="adam",
                                                                               optimizer_params="clip_gradient:1.0"),
@@ -39,7 +39,7 @@ def main_toy(context, args):
     model_folder = os.path.join(args.model_output if args.model_output != "models" else "/tmp/music-style-transfer/toy", "model")
     create_directory_if_not_present(model_folder)
     config.save(os.path.join(model_folder, "config"))
-    schedule = {k: getattr(args, k) for k in ("kl_warmup_steps", "kl_cycle_steps", "kl_free_bits", "lr_warmup_steps")}
+    schedule = {k: getattr(args, k) for k in ("kl_warmup_steps", "kl_cycle_steps", "kl_free_bits", "lr_warmup_steps", "clip_global_norm")}
     t = trainer.Trainer(config=create_toy_train_config(args.max_steps, **schedule), context=context, model=m, sampler=None)
     t.fit(dataset=dataset, validation_dataset=dataset, model_folder=model_folder, epochs=20000 if not args.max_steps else args.max_steps)
     return t
@@ -55,7 +55,8 @@ def create_train_config(args):
                                label_smoothing=args.label_smoothing, negative_label_downscaling=args.negative_label_downscaling,
                                verbose=args.verbose, dtype=args.dtype, max_steps=args.max_steps,
                                kl_warmup_steps=args.kl_warmup_steps, kl_cycle_steps=args.kl_cycle_steps,
-                               kl_free_bits=args.kl_free_bits, lr_warmup_steps=args.lr_warmup_steps)
+                               kl_free_bits=args.kl_free_bits, lr_warmup_steps=args.lr_warmup_steps,
+                               clip_global_norm=args.clip_global_norm)
 
 
 def create_model_config(args, dataset):

@@ -17,7 +17,7 @@ import torch
 from . import utils
 from .config import Config
 from .. import parallel
-from ..engine import check_schedule
+from ..engine import check_clip, check_schedule
 from ..pianoroll import PinnedBatchPipeline
 
 
@@ -38,14 +38,17 @@ class OptimizerConfig(Config):
 
 class TrainConfig(Config):
     """kl_warmup_steps / kl_cycle_steps / kl_free_bits / lr_warmup_steps: the training schedules (engine.schedule_values), all off at
-    their defaults. YAML-serialisable (Config): a file written before a field existed loads with that field's default."""
+    their defaults. clip_global_norm: bound on the global L2 norm of the gradient, applied inside the step (engine.clip_scale); 0: off.
+    YAML-serialisable (Config): a file written before a field existed loads with that field's default."""
 
     def __init__(self, batch_size: int, sampling_frequency: int, checkpoint_frequency: int, num_checkpoints_not_improved: int,
                  optimizer: OptimizerConfig, kl_loss: float, label_smoothing: float, negative_label_downscaling: bool,
                  verbose: bool, dtype: str = "bf16", max_steps: int = 0, kl_warmup_steps: int = 0, kl_cycle_steps: int = 0,
-                 kl_free_bits: float = 0.0, lr_warmup_steps: int = 0):
+                 kl_free_bits: float = 0.0, lr_warmup_steps: int = 0, clip_global_norm: float = 0.0):
         super().__init__()
         check_schedule(kl_warmup_steps, kl_cycle_steps, kl_free_bits, lr_warmup_steps)
+        check_clip(clip_global_norm)
+        self.clip_global_norm = clip_global_norm
         self.kl_warmup_steps, self.kl_cycle_steps = kl_warmup_steps, kl_cycle_steps
         self.kl_free_bits, self.lr_warmup_steps = kl_free_bits, lr_warmup_steps
         self.batch_size = batch_size
@@ -127,6 +130,11 @@ class Trainer:
         self.scheduled = any(sched.values())
         if self.scheduled:
             self.hyper.update(sched)
+        # ... and so does clipping by the global gradient norm
+        self.clip_global_norm = float(getattr(self.config, "clip_global_norm", 0.0))
+        check_clip(self.clip_global_norm)
+        if self.clip_global_norm > 0:
+            self.hyper["clip_global_norm"] = self.clip_global_norm
         self.opt_extra = {k: v for k, v in extra.items() if k in ("beta1", "beta2", "epsilon", "wd")}
 
     # ------------------------------------------------------------------ the hot loop
@@ -246,7 +254,9 @@ class Trainer:
         total_loss batch means and, for the token ends, masked ppl / acc / topk — all accumulated on the device by the
         steps themselves and read here with one synchronisation. kl_weight / lr_scale: the KL weight and the learning-rate factor
         of the last training step, from the device schedule block in the same read (the configured constants without schedules;
-        computed per rank from the same step count, so there is nothing to reduce)"""
+        computed per rank from the same step count, so there is nothing to reduce). With clip_global_norm on, also grad_norm (the mean
+        gradient norm before clipping over those steps), grad_norm_max and clip_frac: taken from the all-reduced bucket, the same on
+        every rank, so nothing to reduce either."""
         failure = None
         with torch.cuda.stream(self.stream):  # ordered behind every step launched so far
             try:
@@ -258,6 +268,7 @@ class Trainer:
                 m = self.model.store.read_metrics(reset)
         kl_weight, lr_scale = ((m.get("kl_weight", self.config.kl_loss_weight), m.get("lr_scale", 1.0)) if self.scheduled
                                else (self.config.kl_loss_weight, 1.0))
+        gnorm = {k: m[k] for k in ("grad_norm", "grad_norm_max", "clip_frac") if k in m} if self.clip_global_norm > 0 else {}
         keys = [k for k in ("kl_sum", "total_sum", "count", "nll_sum", "acc_hits", "topk_hits", "n_tokens") if k in m]
         if self.dist is not None:
             with torch.cuda.stream(self.stream):
@@ -280,6 +291,7 @@ class Trainer:
         out["kl_loss"] = m["kl_sum"] / n
         out["total_loss"] = m["total_sum"] / n
         out["kl_weight"], out["lr_scale"] = kl_weight, lr_scale
+        out.update(gnorm)
         return out
 
     def _metric_to_string_output(self, n_batches):

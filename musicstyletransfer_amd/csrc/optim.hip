@@ -45,15 +45,64 @@ __device__ __forceinline__ void adam_emb_store(const AdamEmb& e, int64_t i, floa
     }
 }
 
+// workgroups of mst_grad_sumsq = rows of its `parts` (mst_grad_sumsq_parts): one per compute unit of an MI355X
+constexpr int kGnormParts = 256;
+
+// global-norm clipping (mst_adam_flat_gnorm): the per-workgroup sums of squares of mst_grad_sumsq, the bound, the statistics block
+struct AdamGnorm {
+  const float* parts;
+  float max_norm;
+  float* gstat;
+};
+
+// wave_sum (common.hpp) on doubles: every level adds the values of two lanes, a commutative sum, so both partners — and in the end
+// all 64 lanes — hold the same bits
+template <int CTRL> __device__ __forceinline__ double dpp_mov_f64(double v) {
+  const uint64_t b = __builtin_bit_cast(uint64_t, v);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)b, CTRL, 0xF, 0xF, true);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(b >> 32), CTRL, 0xF, 0xF, true);
+  return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
+  v += dpp_mov_f64<0xB1>(v);   // quad_perm [1,0,3,2]
+  v += dpp_mov_f64<0x4E>(v);   // quad_perm [2,3,0,1]
+  v += dpp_mov_f64<0x141>(v);  // row_half_mirror
+  v += dpp_mov_f64<0x140>(v);  // row_mirror
+  const uint64_t b = __builtin_bit_cast(uint64_t, v);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_swizzle((int)(uint32_t)b, 0x401F);  // swizzle(SWAP, 16)
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_swizzle((int)(uint32_t)(b >> 32), 0x401F);
+  v += __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+  v += __shfl_xor(v, 32, 64);
+  return v;
+}
+
+// S = the sum of parts[0 .. kGnormParts) in double, by every wave alike: lane l takes parts[4l .. 4l + 3] (one 16-byte load, `gp`)
+// as (p0 + p1) + (p2 + p3), then wave_sum_f64's six pairwise levels across the lanes. Every wave of every workgroup of every range
+// of a step runs these instructions on the same words, so all of them hold the same norm and the same factor.
+// norm = sqrtf((float)S); c = max_norm / (norm + 1e-8f), 1 unless below 1 (fp32, correctly rounded division and square root:
+// engine.clip_scale states the same in np.float32).
+static_assert(kGnormParts == 4 * 64, "one f32x4 of parts per lane of a wave");
+__device__ __forceinline__ float gnorm_of_parts(f32x4 gp) {
+  const double s = ((double)gp[0] + (double)gp[1]) + ((double)gp[2] + (double)gp[3]);
+  return sqrtf((float)wave_sum_f64(s));
+}
+__device__ __forceinline__ float gnorm_clip_scale(float norm, float max_norm) {
+  const float c = max_norm / (norm + 1e-8f);
+  return c < 1.f ? c : 1.f;
+}
+
 // SCHED (mst_adam_flat_sched): the bookkeeping takes the KL weight and the free bits from the device schedule block
-template <typename T, bool SCHED>
+// GNORM (mst_adam_flat_gnorm): the gradient is clipped by its global L2 norm, and a step whose norm is not finite is skipped
+template <typename T, bool SCHED, bool GNORM>
 __global__ __launch_bounds__(256) void adam_flat_kernel(int64_t n, float* __restrict__ w, const float* __restrict__ grad,
                                                         float* __restrict__ m, float* __restrict__ v,
                                                         T* __restrict__ w16, const int32_t* __restrict__ state,
                                                         float beta1, float beta2, float eps, float wd, float rescale,
                                                         float clip, mst_step_metrics mt, int32_t* state_rw, AdamEmb emb,
-                                                        const float* __restrict__ sched) {
+                                                        const float* __restrict__ sched, AdamGnorm gn) {
   __shared__ float red[2][4];
+  f32x4 gp;
+  if constexpr (GNORM) gp = reinterpret_cast<const f32x4*>(gn.parts)[threadIdx.x & 63];  // (asked for ahead of the guards' loads)
   bool incomplete;
   if (step_is_bad(mt, incomplete)) {
     // the step's position-0 tail did not finish (mst_step_metrics): no update, no metric sums, the step count taken back —
@@ -70,6 +119,28 @@ __global__ __launch_bounds__(256) void adam_flat_kernel(int64_t n, float* __rest
       state_rw[0] -= 1;
     }
     return;
+  }
+  if constexpr (GNORM) {
+    // (uniform over the launch and over the launches of a step: gnorm_of_parts) — rescale holds r * c from here on, rounded once
+    const float norm = gnorm_of_parts(gp);
+    if (!(norm <= 3.0e38f)) {  // (inf, or NaN: a non-finite gradient somewhere in the bucket) — the launch with gstat keeps the books
+      if (blockIdx.x == 0 && threadIdx.x == 0 && gn.gstat) {
+        if (mt.status) __hip_atomic_fetch_add(mt.status + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        state_rw[0] -= 1;
+      }
+      return;
+    }
+    const float c = gnorm_clip_scale(norm, gn.max_norm);
+    rescale = rescale * c;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && gn.gstat) {
+      float* gs = gn.gstat;  // {norm, c, sum of norms, largest norm, steps, clipped steps}
+      gs[0] = norm;
+      gs[1] = c;
+      gs[2] += norm;
+      gs[3] = fmaxf(gs[3], norm);
+      gs[4] += 1.f;
+      gs[5] += c < 1.f ? 1.f : 0.f;
+    }
   }
   if (blockIdx.x == 0 && mt.recon) {  // (uniform branch)
     if constexpr (SCHED) loss_combine_sched_wg(mt.B, mt.recon, mt.kl, sched, mt.total, mt.metric, red);
@@ -159,7 +230,7 @@ static unsigned grid_for(int64_t n, int per_thread) {
 static int adam_flat_impl(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr,
                           double beta1, double beta2, float eps, float wd, float rescale, float clip,
                           int32_t* step_state, int advance_step, const mst_step_metrics* metrics, const AdamEmb& emb, const float* sched,
-                          mst_stream_t stream) {
+                          mst_stream_t stream, const AdamGnorm* gnorm = nullptr) {
   MST_CHECK_ARG(n > 0 && w && grad && m && v && step_state, "mst_adam_flat: bad argument");
   mst_step_metrics mt = {};
   if (metrics) {
@@ -176,12 +247,19 @@ static int adam_flat_impl(int dtype, int64_t n, float* w, const float* grad, flo
   }
   return dispatch_act(dtype, [&](auto tag) -> int {
     typedef decltype(tag) T;
-    if (sched)
-      hipLaunchKernelGGL((adam_flat_kernel<T, true>), dim3(grid_for(n, 4)), dim3(256), 0, s, n, w, grad, m, v, (T*)w16, step_state,
-                         (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, sched);
+    const AdamGnorm gn = gnorm ? *gnorm : AdamGnorm{};
+    if (gnorm && sched)
+      hipLaunchKernelGGL((adam_flat_kernel<T, true, true>), dim3(grid_for(n, 4)), dim3(256), 0, s, n, w, grad, m, v, (T*)w16, step_state,
+                         (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, sched, gn);
+    else if (gnorm)
+      hipLaunchKernelGGL((adam_flat_kernel<T, false, true>), dim3(grid_for(n, 4)), dim3(256), 0, s, n, w, grad, m, v, (T*)w16, step_state,
+                         (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, (const float*)nullptr, gn);
+    else if (sched)
+      hipLaunchKernelGGL((adam_flat_kernel<T, true, false>), dim3(grid_for(n, 4)), dim3(256), 0, s, n, w, grad, m, v, (T*)w16, step_state,
+                         (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, sched, gn);
     else
-      hipLaunchKernelGGL((adam_flat_kernel<T, false>), dim3(grid_for(n, 4)), dim3(256), 0, s, n, w, grad, m, v, (T*)w16, step_state,
-                         (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, (const float*)nullptr);
+      hipLaunchKernelGGL((adam_flat_kernel<T, false, false>), dim3(grid_for(n, 4)), dim3(256), 0, s, n, w, grad, m, v, (T*)w16, step_state,
+                         (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, (const float*)nullptr, gn);
     MST_CHECK_LAUNCH("adam_flat_kernel");
     return MST_OK;
   });
@@ -206,7 +284,7 @@ extern "C" int mst_adam_flat_sched(int dtype, int64_t n, float* w, const float* 
 static int adam_flat_emb_impl(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
                               double beta2, float eps, float wd, float rescale, float clip, int32_t* step_state,
                               const mst_step_metrics* metrics, const float* sched, int64_t base, const int64_t* emb, int64_t n_emb,
-                              void* wt16, mst_stream_t stream) {
+                              void* wt16, mst_stream_t stream, const AdamGnorm* gnorm = nullptr) {
   MST_CHECK_ARG(n_emb >= 0 && n_emb <= 2 && (n_emb == 0 || (emb && wt16)) && base >= 0, "mst_adam_flat_emb: up to two matrices, with their table and wt16");
   AdamEmb e = {};
   for (int j = 0; j < (int)n_emb; ++j) {
@@ -217,7 +295,7 @@ static int adam_flat_emb_impl(int dtype, int64_t n, float* w, const float* grad,
     ++e.n;
   }
   e.wt16 = wt16;
-  return adam_flat_impl(dtype, n, w, grad, m, v, w16, lr, beta1, beta2, eps, wd, rescale, clip, step_state, 0, metrics, e, sched, stream);
+  return adam_flat_impl(dtype, n, w, grad, m, v, w16, lr, beta1, beta2, eps, wd, rescale, clip, step_state, 0, metrics, e, sched, stream, gnorm);
 }
 
 extern "C" int mst_adam_flat_emb(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
@@ -235,6 +313,66 @@ extern "C" int mst_adam_flat_emb_sched(int dtype, int64_t n, float* w, const flo
   MST_CHECK_ARG(sched != nullptr, "mst_adam_flat_emb_sched: null schedule block");
   return adam_flat_emb_impl(dtype, n, w, grad, m, v, w16, lr, beta1, beta2, eps, wd, rescale, clip, step_state, metrics, sched, base, emb, n_emb,
                             wt16, stream);
+}
+
+extern "C" int mst_adam_flat_gnorm(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
+                                   double beta2, float eps, float wd, float rescale, float clip, int32_t* step_state,
+                                   const mst_step_metrics* metrics, const float* sched, int64_t base, const int64_t* emb, int64_t n_emb,
+                                   void* wt16, const float* parts, int64_t n_parts, float max_norm, float* gstat, mst_stream_t stream) {
+  MST_CHECK_ARG(parts != nullptr, "mst_adam_flat_gnorm: null parts (mst_grad_sumsq writes them)");
+  MST_CHECK_ARG((uintptr_t)parts % 16 == 0, "mst_adam_flat_gnorm: parts must be 16-byte aligned");
+  MST_CHECK_ARG(n_parts == kGnormParts, "mst_adam_flat_gnorm: n_parts must be mst_grad_sumsq_parts() = %d", kGnormParts);
+  MST_CHECK_ARG(max_norm > 0.f && max_norm <= 3.0e38f, "mst_adam_flat_gnorm: max_norm must be positive and finite");
+  const AdamGnorm gn = {parts, max_norm, gstat};
+  return adam_flat_emb_impl(dtype, n, w, grad, m, v, w16, lr, beta1, beta2, eps, wd, rescale, clip, step_state, metrics, sched, base, emb, n_emb,
+                            wt16, stream, &gn);
+}
+
+// sums of squares of the rescaled flat gradient for mst_adam_flat_gnorm: workgroup j leaves parts[j]. Per thread an fp32 chain over
+// its grid-stride elements, then wave_sum (DPP), then the four waves through LDS in wave order: no atomics, a fixed order
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(int64_t n, const float* __restrict__ grad, int64_t cut, float rescale_lo,
+                                                         float rescale_hi, float* __restrict__ parts) {
+  __shared__ float red[4];
+  const int64_t nvec = n / 4, stride = (int64_t)kGnormParts * 256;
+  int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  f32x4 cur = {0.f, 0.f, 0.f, 0.f};
+  if (i < nvec) cur = reinterpret_cast<const f32x4*>(grad)[i];  // the first load is on its way before anything else
+  float acc = 0.f;
+  while (i < nvec) {
+    const int64_t nx = i + stride;
+    f32x4 nxt = {0.f, 0.f, 0.f, 0.f};
+    if (nx < nvec) nxt = reinterpret_cast<const f32x4*>(grad)[nx];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float x = cur[e] * (4 * i + e < cut ? rescale_lo : rescale_hi);
+      acc += x * x;
+    }
+    cur = nxt;
+    i = nx;
+  }
+  // tail (n not a multiple of 4): up to three elements, on the last workgroup
+  if (blockIdx.x == kGnormParts - 1) {
+    const int64_t k = nvec * 4 + threadIdx.x;
+    if (k < n) {
+      const float x = grad[k] * (k < cut ? rescale_lo : rescale_hi);
+      acc += x * x;
+    }
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) parts[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+extern "C" int64_t mst_grad_sumsq_parts(void) { return kGnormParts; }
+
+extern "C" int mst_grad_sumsq(int64_t n, const float* grad, int64_t cut, float rescale_lo, float rescale_hi, float* parts,
+                              mst_stream_t stream) {
+  MST_CHECK_ARG(n > 0 && grad && parts && cut >= 0 && cut <= n, "mst_grad_sumsq: bad argument (n > 0, 0 <= cut <= n, grad and parts given)");
+  MST_CHECK_ARG((uintptr_t)grad % 16 == 0, "mst_grad_sumsq: grad must be 16-byte aligned");
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(kGnormParts), dim3(256), 0, (hipStream_t)stream, n, grad, cut, rescale_lo, rescale_hi, parts);
+  MST_CHECK_LAUNCH("grad_sumsq_kernel");
+  return MST_OK;
 }
 
 extern "C" int mst_transpose_shadows(int dtype, const float* w, void* wt16, const int64_t* desc,

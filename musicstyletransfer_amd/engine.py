@@ -210,10 +210,14 @@ class ParamStore:
         # and the number of steps the optimizer skipped because a loss was not finite (not sticky: the next batch is tried again)
         # sched = the fp32 schedule block {beta_t, tau, f_lr, t} the step's first launch writes for a plan with training schedules
         # (schedule_values; mst_step_begin_args.sched*), read by that step's scheduled launches — and here, with the metrics
-        self._metric_buf = torch.zeros(12, **f32)
+        # gstat = the statistics block of global-norm clipping {norm, c, sum of norms, largest norm, steps, clipped steps}, written by
+        # the bookkeeping thread of every counted step of a plan with clip_global_norm (mst_adam_flat_gnorm), read with the metrics
+        self._metric_buf = torch.zeros(20, **f32)
         self.metric_acc = self._metric_buf[:3]
         self.step_status = self._metric_buf[4:7].view(torch.int32)
         self.sched = self._metric_buf[8:12]
+        self.gstat = self._metric_buf[12:20]
+        self._grad_parts = None
         self.nonfinite_steps = 0      # steps skipped for a non-finite loss since the store was made (read_metrics adds them up)
         self.tail_fused = os.environ.get("MST_ROW_TAIL", "1") != "0"  # False: the five-launch form of the position-0 tails
         self.tail_checked = False     # row_tail_selfcheck() ran for this store
@@ -231,6 +235,14 @@ class ParamStore:
         if self._rng_state is None:
             self._rng_state = torch.tensor([0, 0, seed ^ 0x5DEECE66D, 0], dtype=torch.int64, device=self.device)
         return self._rng_state
+
+    def grad_parts(self):
+        """the per-workgroup sums of squares a step's mst_grad_sumsq launch leaves for its Adam launches (global-norm clipping), made
+        for the first plan that asks — a store without such a plan allocates what it always did — and never freed: captured graphs
+        keep the pointer"""
+        if self._grad_parts is None:
+            self._grad_parts = torch.zeros(o.grad_sumsq_parts(), dtype=torch.float32, device=self.device)
+        return self._grad_parts
 
     def rng_state_inference(self):
         """the RNG state inference-mode forward passes advance (eps of Model.__call__ when none is given): never the
@@ -304,7 +316,10 @@ class ParamStore:
         The step-status words travel in the same copy: a set flag is handled here (handle_step_status). So does the schedule
         block: once a plan with training schedules has run, 'kl_weight' (beta_t) and 'lr_scale' (f_lr) of the last such step.
         (The last step that RAN: after a step the guards skipped, whose step count was taken back, the block still holds that
-        step's values until the next step's first launch writes it again from the count — training is unaffected.)"""
+        step's values until the next step's first launch writes it again from the count — training is unaffected.)
+        And the statistics of global-norm clipping: once a step of a plan with clip_global_norm has counted, 'grad_norm' (the mean
+        norm before clipping over the counted steps since the last reset), 'grad_norm_max' and 'clip_frac' (the share of them that
+        were clipped); reset clears these running fields with the sums."""
         buf = self._metric_buf.cpu()
         acc = buf[:3].tolist()
         flags, skipped, nonfinite = buf[4:7].view(torch.int32).tolist()
@@ -321,11 +336,16 @@ class ParamStore:
         beta_t, _, f_lr, sched_t = buf[8:12].tolist()
         if sched_t > 0:  # (a scheduled step wrote the block)
             out.update(kl_weight=beta_t, lr_scale=f_lr)
+        _, _, norm_sum, norm_max, g_steps, g_clipped = buf[12:18].tolist()
+        if g_steps > 0:  # (a step with global-norm clipping counted)
+            out.update(grad_norm=norm_sum / g_steps, grad_norm_max=norm_max, clip_frac=g_clipped / g_steps)
         if self.tok_parts is not None:
             t = self.tok_parts.cpu().double().sum(0).tolist()
             out.update(nll_sum=t[0], acc_hits=t[1], topk_hits=t[2], n_tokens=t[3])
         if reset:
             o.zero(self.metric_acc)
+            if g_steps > 0:
+                o.zero(self.gstat[2:6])
             if self.tok_parts is not None:
                 o.zero(self.tok_parts)
         return out
@@ -680,7 +700,8 @@ def row_tail_selfcheck(store, B=64, S=2):
 # riding on them; shadows — where the transposed-shadow refresh goes ('own' / 'begin' / 'tail'); the rest as named there.
 # sched — the latent block's backward launch and the step-closing bookkeeping in their scheduled forms (training schedules on).
 # dec_tail — the last decoder layer's row-wise block, the loss launch and the block's backward as ONE launch (a training step with gradient).
-Forms = namedtuple("Forms", "tails riders shadows fuse_bce bce_dgrad skip_row0 cls_fold ffn_e ffn_d ln_bwd_e ln_bwd_d sched dec_tail")
+# gnorm — the optimizer clips by the global gradient norm: one mst_grad_sumsq launch ahead of the Adam launches in their gnorm form.
+Forms = namedtuple("Forms", "tails riders shadows fuse_bce bce_dgrad skip_row0 cls_fold ffn_e ffn_d ln_bwd_e ln_bwd_d sched dec_tail gnorm")
 
 
 def check_schedule(kl_warmup_steps=0, kl_cycle_steps=0, kl_free_bits=0.0, lr_warmup_steps=0):
@@ -694,6 +715,20 @@ def check_schedule(kl_warmup_steps=0, kl_cycle_steps=0, kl_free_bits=0.0, lr_war
         raise ValueError("kl_cycle_steps restarts the KL warm-up: it needs kl_warmup_steps > 0")
     if kl_cycle_steps > 0 and kl_warmup_steps > kl_cycle_steps:
         raise ValueError(f"kl_warmup_steps ({kl_warmup_steps}) must not exceed kl_cycle_steps ({kl_cycle_steps})")
+
+
+def check_clip(clip_global_norm=0.0):
+    """clip_global_norm: 0 (off) or a positive finite bound on the gradient's global L2 norm; raises ValueError otherwise"""
+    if not (0 <= clip_global_norm < float("inf")):
+        raise ValueError(f"clip_global_norm must be 0 (off) or a positive finite norm, not {clip_global_norm!r}")
+
+
+def clip_scale(norm, max_norm):
+    """the factor c global-norm clipping applies to a gradient of L2 norm `norm` — gluon.utils.clip_global_norm's rule as the device
+    evaluates it (mst_adam_flat_gnorm), stated once for the host in np.float32 arithmetic: c = max_norm / (norm + 1e-8), and 1 unless
+    that is below 1"""
+    c = np.float32(max_norm) / (np.float32(norm) + np.float32(1e-8))
+    return c if c < np.float32(1) else np.float32(1)
 
 
 def schedule_values(t, kl_weight=1.0, kl_warmup_steps=0, kl_cycle_steps=0, lr_warmup_steps=0):
@@ -714,9 +749,11 @@ class StepPlan:
     def __init__(self, store, B, T, lr=3e-4, clip_gradient=1.0, kl_weight=1.0, label_smoothing=0.0,
                  negative_label_downscaling=False, global_batch=None, gscale=None, want_probs=False, seed=0,
                  internal_eps=False, optimizer_params=None, sample_offset=0, site_base=0,
-                 kl_warmup_steps=0, kl_cycle_steps=0, kl_free_bits=0.0, lr_warmup_steps=0):
+                 kl_warmup_steps=0, kl_cycle_steps=0, kl_free_bits=0.0, lr_warmup_steps=0, clip_global_norm=0.0):
         """kl_warmup_steps / kl_cycle_steps / kl_free_bits / lr_warmup_steps: the training schedules (schedule_values),
         evaluated on the device from Adam's step count. All zero (the default): the plain launches with their constants.
+        clip_global_norm: bound on the global L2 norm of the batch-mean gradient, applied on the device ahead of Adam (clip_scale;
+        DESIGN §12); a step whose norm is not finite is skipped. 0 (the default): off, the optimizer launches as they were.
         sample_offset: index of this plan's first sample in the global batch (data parallel: rank * B) — the in-graph eps
         is drawn per GLOBAL sample index, so the result does not depend on the sharding.
         site_base: added to every dropout site id (data parallel: a different value per rank gives every rank its own
@@ -729,6 +766,9 @@ class StepPlan:
         self.schedule = dict(kl_warmup_steps=int(kl_warmup_steps), kl_cycle_steps=int(kl_cycle_steps), kl_free_bits=float(kl_free_bits),
                              lr_warmup_steps=int(lr_warmup_steps))
         self.scheduled = any(self.schedule.values())  # resolved once: the scheduled launches, or the plain ones
+        check_clip(clip_global_norm)
+        self.clip_global_norm = float(clip_global_norm)
+        self.grad_parts = store.grad_parts() if self.clip_global_norm > 0 else None  # (allocated here, never inside a capture)
         self.ls, self.nld = label_smoothing, negative_label_downscaling
         self.global_batch = global_batch or B
         self.sample_offset, self.site_base = int(sample_offset), int(site_base)
@@ -941,7 +981,9 @@ class StepPlan:
             ffn_e=o.ffn_fusion_pays(De, 4 * De), ffn_d=ffn_d, ln_bwd_e=o.ln_bwd_fusion_pays(De), ln_bwd_d=ln_bwd_d,
             # training schedules: KL weight, free bits and lr warm-up from the device schedule block (training steps only — a
             # validation step keeps the constants: its objective must not move with the schedule)
-            sched=self.scheduled)
+            sched=self.scheduled,
+            # clipping by the global gradient norm: a sum-of-squares launch ahead of Adam, the Adam launches in their gnorm form
+            gnorm=self.clip_global_norm > 0)
 
     def _guard(self):
         """step guard of the launches that close a step (optimizer / loss_combine): the barrier counters of the one-launch
@@ -1448,19 +1490,29 @@ class StepPlan:
         guard = self._guard()
         mt = dict(recon=self.recon, kl=self.kl, kl_weight=self.kl_weight, total=self.total, metric=self.metric_acc, **guard)
         emb = (lambda base: dict(base=base, specs=st.emb_specs, wt16=st.wt16)) if deferred else (lambda base: None)
+        # clipping by the global norm: every Adam launch of the step reads the same sums of squares — taken here, behind the
+        # all-reduce, from the whole bucket at the launches' own rescales —; the launch with the bookkeeping keeps the statistics.
+        # Off: no extra keyword, the calls as they were
+        gn = ((lambda a: dict(gnorm=dict(parts=self.grad_parts, max_norm=self.clip_global_norm, gstat=st.gstat if a == 0 else None)))
+              if self.forms.gnorm else (lambda a: {}))
         if self.gscale == self.gscale_enc:
+            r = 1.0 / (self.global_batch * self.gscale)
+            if self.forms.gnorm:
+                o.grad_sumsq(st.g, 0, r, r, self.grad_parts)
             o.adam_flat(st.w, st.g, st.m, st.v, st.w16, st.step_state, lr=self.lr,
-                        rescale=1.0 / (self.global_batch * self.gscale), clip=clip, advance_step=False, metrics=mt, emb=emb(0),
-                        sched=sched, **self.opt)
+                        rescale=r, clip=clip, advance_step=False, metrics=mt, emb=emb(0),
+                        sched=sched, **gn(0), **self.opt)
         else:
             # encoder.* tensors come first in the flat buffers; everything from decoder.latent2hid on is decoder-side.
             # NOTE the latent_proj gradients are produced by latent_bwd_vec at the encoder-side scale.
             cut = st.offsets["decoder.latent2hid.weight"]
             rng = [(0, cut, self.gscale_enc, False), (cut, st.n, self.gscale, False)]
+            if self.forms.gnorm:
+                o.grad_sumsq(st.g, cut, 1.0 / (self.global_batch * self.gscale_enc), 1.0 / (self.global_batch * self.gscale), self.grad_parts)
             for a, b, gs, adv in rng:
                 o.adam_flat(st.w[a:b], st.g[a:b], st.m[a:b], st.v[a:b], st.w16[a:b], st.step_state, lr=self.lr,
                             rescale=1.0 / (self.global_batch * gs), clip=clip, advance_step=adv,
-                            metrics=mt if a == 0 else (guard or None), emb=emb(a), sched=sched if a == 0 else None, **self.opt)
+                            metrics=mt if a == 0 else (guard or None), emb=emb(a), sched=sched if a == 0 else None, **gn(a), **self.opt)
         if not deferred:  # (deferred: the next step's first launch rebuilds them, forward())
             o.transpose_shadows(st.w, st.wt16, st.t_desc, st.t_prefix, len(st.t_specs), st.t_tiles)
 
@@ -1550,4 +1602,5 @@ class StepPlan:
         n = max(m["count"], 1.0)
         return {"kl_loss": m["kl_sum"] / n, "total_loss": m["total_sum"] / n, "count": m["count"], "nonfinite_steps": m["nonfinite_steps"],
                 "kl_weight": m.get("kl_weight", self.kl_weight) if self.scheduled else self.kl_weight,
-                "lr_scale": m.get("lr_scale", 1.0) if self.scheduled else 1.0}
+                "lr_scale": m.get("lr_scale", 1.0) if self.scheduled else 1.0,
+                **{k: m[k] for k in ("grad_norm", "grad_norm_max", "clip_frac") if k in m}}
