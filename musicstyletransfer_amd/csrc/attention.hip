@@ -1704,15 +1704,6 @@ static AttnBwdForm attn_bwd_form(int dh, int64_t S, int64_t n_wg, int64_t q_limi
   return f;
 }
 
-// dynamic LDS above 64 KB has to be opted into, per kernel (*granted: what the kernel has been granted so far)
-static int lds_opt_in(const void* fn, size_t lds, size_t* granted, const char* what) {
-  if (lds <= *granted) return MST_OK;
-  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) { set_error("%s: LDS opt-in of %zu bytes: %s", what, lds, hipGetErrorString(e)); return MST_ERR_LAUNCH; }
-  *granted = lds;
-  return MST_OK;
-}
-
 template <typename T, int DH>
 static int launch_fwd(const AttnArgs& a_in, const AttnFwdForm& f, hipStream_t s) {
   AttnArgs a = a_in;

@@ -1,5 +1,5 @@
 // bce_math.hpp — one element of sigmoid + BinaryCrossEntropy (loss.py:27-80) and its logit gradient, shared by
-// sigmoid_bce_kernel (losses.hip) and the output-layer GEMM's epilogue (gemm_nt.hip: gemm_bce_tile), so the two produce
+// sigmoid_bce_kernel (losses.hip) and the output-layer GEMM's epilogue (gemm_bce.hpp: bce_tile_finish), so the two produce
 // the same bits.
 //
 // bce_exact is the reference's operation order in fp32:

@@ -27,6 +27,17 @@ void set_error(const char* fmt, ...);
     }                                                                            \
   } while (0)
 
+// Dynamic LDS above 64 KB has to be opted into, per kernel. *granted is what the kernel `fn` has been granted so far: a function-static
+// size_t of the launch site, one per kernel (per template instantiation), starting at 64 * 1024. The runtime is asked only when a launch
+// needs more than that — for every form of the step during warm-up, before a graph is captured.
+static inline int lds_opt_in(const void* fn, size_t lds, size_t* granted, const char* what) {
+  if (lds <= *granted) return MST_OK;
+  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) { set_error("%s: LDS opt-in of %zu bytes: %s", what, lds, hipGetErrorString(e)); return MST_ERR_LAUNCH; }
+  *granted = lds;
+  return MST_OK;
+}
+
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int64_t roundup(int64_t a, int64_t b) { return cdiv(a, b) * b; }
 

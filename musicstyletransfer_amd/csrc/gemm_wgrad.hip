@@ -537,13 +537,8 @@ static int launch_wgrad(const WgradBatch& b, int big, const PartialSumBatch* ps,
   if (big == 3) {
     constexpr int BN = 256, BKO = 256;
     size_t lds = (size_t)2 * BMR * (BN + BKO + 2 * LDS_PAD) * 2;
-    static bool opted = false;
-    if (!opted) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<T, BN, BKO, 4, 2>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) { set_error("wgrad_kernel: LDS opt-in of %zu bytes: %s", lds, hipGetErrorString(e)); return MST_ERR_LAUNCH; }
-      opted = true;
-    }
+    static size_t granted = 64 * 1024;
+    if (const int rc = lds_opt_in(reinterpret_cast<const void*>(&wgrad_kernel<T, BN, BKO, 4, 2>), lds, &granted, "wgrad_kernel")) return rc;
     hipLaunchKernelGGL((wgrad_kernel<T, BN, BKO, 4, 2>), dim3((unsigned)total), dim3(512), lds, s, b);
     if (b.partial) {
       MST_CHECK_LAUNCH("wgrad_kernel");
@@ -559,24 +554,14 @@ static int launch_wgrad(const WgradBatch& b, int big, const PartialSumBatch* ps,
   } else if (big == 2) {
     constexpr int BN = 256, BKO = 128;
     size_t lds = (size_t)2 * BMR * (BN + BKO + 2 * LDS_PAD) * 2;
-    static bool opted = false;
-    if (!opted) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<T, BN, BKO, 4, 2>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) { set_error("wgrad_kernel: LDS opt-in of %zu bytes: %s", lds, hipGetErrorString(e)); return MST_ERR_LAUNCH; }
-      opted = true;
-    }
+    static size_t granted = 64 * 1024;
+    if (const int rc = lds_opt_in(reinterpret_cast<const void*>(&wgrad_kernel<T, BN, BKO, 4, 2>), lds, &granted, "wgrad_kernel")) return rc;
     hipLaunchKernelGGL((wgrad_kernel<T, BN, BKO, 4, 2>), dim3((unsigned)total), dim3(512), lds, s, b);
   } else if (big) {
     constexpr int BN = 128, BKO = 128;
     size_t lds = (size_t)2 * BMR * (BN + BKO + 2 * LDS_PAD) * 2;
-    static bool opted = false;  // 73.7 KB of dynamic LDS: above the 64 KB default
-    if (!opted) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<T, BN, BKO, 2, 2>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) { set_error("wgrad_kernel: LDS opt-in of %zu bytes: %s", lds, hipGetErrorString(e)); return MST_ERR_LAUNCH; }
-      opted = true;
-    }
+    static size_t granted = 64 * 1024;  // 73.7 KB of dynamic LDS: above the 64 KB default
+    if (const int rc = lds_opt_in(reinterpret_cast<const void*>(&wgrad_kernel<T, BN, BKO, 2, 2>), lds, &granted, "wgrad_kernel")) return rc;
     hipLaunchKernelGGL((wgrad_kernel<T, BN, BKO, 2, 2>), dim3((unsigned)total), dim3(256), lds, s, b);
   } else {
     constexpr int BN = 64, BKO = 64;

@@ -3,7 +3,7 @@
 // Replaces gluon.nn.LayerNorm (eps 1e-5, biased variance, gamma/beta) at
 // VarAutoEncoder/transformer.py:142,147,175,180 as applied at :155,158,197,200. The residual
 // add that precedes every LayerNorm in the reference is fused into the producing GEMM's
-// epilogue (gemm_nt.hip), so x here is the pre-norm sum.
+// epilogue (gemm_tile.hpp), so x here is the pre-norm sum.
 //
 // HBM-bound streaming kernels: 8-byte vector loads (4 x 16-bit per lane → a 256-wide row is one
 // fully coalesced 512-byte wave access), all statistics in fp32 registers, two-pass variance.

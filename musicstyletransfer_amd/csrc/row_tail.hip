@@ -887,12 +887,8 @@ static int row_tail_fwd_impl(const mst_row_tail_args* args, const mst_gemm_args*
       const int wi = (q.D == 256 ? 0 : 1) + (tiles < 0 ? 2 : 0);
       typedef void (*kern_t)(mst_row_tail_args, mst_gemm_args, int, uint32_t*, TailShadow);
       const kern_t fns[4] = {&row_tail_fwd_kernel<T, 256, 128>, &row_tail_fwd_kernel<T, 128, 128>, &row_tail_fwd_kernel<T, 256, 256>, &row_tail_fwd_kernel<T, 128, 256>};
-      static size_t opted[4] = {0, 0, 0, 0};
-      if (rlds > opted[wi]) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fns[wi]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds);
-        if (e != hipSuccess) { set_error("row_tail_fwd_kernel (riders): LDS opt-in of %zu bytes: %s", rlds, hipGetErrorString(e)); return MST_ERR_LAUNCH; }
-        opted[wi] = rlds;
-      }
+      static size_t granted[4] = {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024};
+      if (const int rc = lds_opt_in(reinterpret_cast<const void*>(fns[wi]), rlds, &granted[wi], "row_tail_fwd_kernel (riders)")) return rc;
       const unsigned grid = ride_grid(q.D / 16, tiles < 0 ? -tiles : tiles);
       hipLaunchKernelGGL(fns[wi], dim3(grid), dim3(1024), rlds, s, q, *rider, tiles < 0 ? -tiles : tiles, queue, shadow);
     } else if (q.D == 256) hipLaunchKernelGGL((row_tail_fwd_kernel<T, 256>), dim3(16 * TAIL_OVERSUBSCRIBE), dim3(1024), 0, s, q, none, 0, (uint32_t*)nullptr, TailShadow{});
@@ -946,16 +942,12 @@ static int row_tail_bwd_impl(const mst_row_tail_bwd_args* args, const mst_gemm_a
       ride_shape(*rider, tiles, rlds);
       if (rlds > lds) lds = rlds;
     }
-    static size_t opted[6] = {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024};
+    static size_t granted[6] = {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024};
     const int wi = (q.D == 256 ? 0 : 1) + (rider ? (tiles < 0 ? 4 : 2) : 0);
     typedef void (*kern_t)(mst_row_tail_bwd_args, mst_gemm_args, int, uint32_t*);
     const kern_t fns[6] = {&row_tail_bwd_kernel<T, 256>, &row_tail_bwd_kernel<T, 128>, &row_tail_bwd_kernel<T, 256, 128>, &row_tail_bwd_kernel<T, 128, 128>,
                            &row_tail_bwd_kernel<T, 256, 256>, &row_tail_bwd_kernel<T, 128, 256>};
-    if (lds > opted[wi]) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fns[wi]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) { set_error("row_tail_bwd_kernel: LDS opt-in of %zu bytes: %s", lds, hipGetErrorString(e)); return MST_ERR_LAUNCH; }
-      opted[wi] = lds;
-    }
+    if (const int rc = lds_opt_in(reinterpret_cast<const void*>(fns[wi]), lds, &granted[wi], "row_tail_bwd_kernel")) return rc;
     if (rider) {
       const unsigned grid = ride_grid(q.D / 16, tiles < 0 ? -tiles : tiles);
       hipLaunchKernelGGL(fns[wi], dim3(grid), dim3(1024), lds, s, q, *rider, tiles < 0 ? -tiles : tiles, queue);

@@ -57,7 +57,7 @@ def test_wide_engine_two_ranks_share_the_card_with_the_one_launch_tails(gpu, dp_
     per = W.B_GLOBAL // 2
     assert np.array_equal(r0["wide_eps1"], ref["eps1"][:per]) and np.array_equal(r1["wide_eps1"], ref["eps1"][per:])
     # At these widths the feed-forward launches are the fused ones, whose workgroups walk the hidden chunks in an order rotated by
-    # their position in the launch (gemm_nt.hip, the rotated chunk order: 8 us per step): the fp32 sum of FFN2 runs in another order for a row
+    # their position in the launch (ffn_ln.hpp, the rotated chunk order: 8 us per step): the fp32 sum of FFN2 runs in another order for a row
     # block that sits elsewhere in the launch, i.e. a shard equals the global batch to a rounding of the activation type (most
     # samples bit for bit, a few elements one bf16 ulp apart), not bit for bit as at the narrow widths above
     np.testing.assert_allclose(np.concatenate([r0["wide_total1"], r1["wide_total1"]]), ref["total1"], rtol=2e-3)

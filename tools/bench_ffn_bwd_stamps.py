@@ -1,5 +1,5 @@
 """Per-stage timeline of ONE workgroup of mst_ffn_ln_bwd_lead at the step's shape (M 16384, width 256, hidden 1024).
-Build with MST_EXTRA_FLAGS="gemm_nt.hip=-DMST_FFN_STAMPS" (GPU box)."""
+Build with MST_EXTRA_FLAGS="ffn_ln.hip=-DMST_FFN_STAMPS" (GPU box)."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

@@ -1,5 +1,5 @@
 """Per-stage timeline of ONE workgroup of mst_ffn_ln_fwd / _bwd at the step's shape (M 16384, 256 -> 1024 -> 256).
-Build with MST_EXTRA_FLAGS="gemm_nt.hip=-DMST_FFN_STAMPS" (GPU box)."""
+Build with MST_EXTRA_FLAGS="ffn_ln.hip=-DMST_FFN_STAMPS" (GPU box)."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

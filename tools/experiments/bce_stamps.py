@@ -1,5 +1,5 @@
 """Phases of one workgroup of mst_gemm_sigmoid_bce_dgrad_ln at configs[1]'s shape. Needs a -DMST_FFN_STAMPS build with TEMPORARY stamps in
-gemm_nt.hip (not in the tree): gemm_bce_dgrad_ln_kernel — FFN_STAMP(0) + FFN_RT(190) at its start, (1) behind gemm_bce_tile, (2) behind the second
+gemm_bce.hip / gemm_bce.hpp (not in the tree; the stamp array is per unit, so mst_debug_ffn_stamps moves there too): gemm_bce_dgrad_ln_kernel — FFN_STAMP(0) + FFN_RT(190) at its start, (1) behind gemm_bce_tile, (2) behind the second
 K loop, (3) + FFN_RT(191) at its end; gemm_bce_tile<KEEP> — (8) behind its K loop, (9) / (10) around the sweep.
 Measured (r04): workgroup 14.7 us = K loop 3.5 (two cold stages), staging 0.4, BCE sweep 2.0, loss sum + barrier 2.3, second GEMM 1.6, LayerNorm
 epilogue 4.9 — nothing dominant; the launch is 23 us in the step."""
