@@ -195,6 +195,15 @@ int mst_gemm_nt_ln(const mst_gemm_args* args, const mst_ln_args* ln, mst_stream_
 int mst_gemm_sigmoid_bce_dgrad_ln(const mst_gemm_args* args, const mst_bce_args* bce, const mst_gemm_args* dgrad,
                                   const mst_ln_args* ln, mst_stream_t stream);
 int64_t mst_gemm_nt_ln_parts(int64_t M);
+/* What mst_gemm_sigmoid_bce(args, bce) launches (dgrad = ln = NULL), or mst_gemm_sigmoid_bce_dgrad_ln(args, bce, dgrad, ln): decided on the
+ * host from the arguments alone, no HIP call, no device needed (pointers are looked at for NULL, alignment and dgrad->A == args->C
+ * only). The launches take the same decisions through the same code. form is a host array of 4 entries:
+ *   form[0]  BN, the width of a column tile: 128 (128 pitches) or 256
+ *   form[1]  column tiles per 64-row block, N / BN (above 1: the tiles of a row block share the sample's loss atomic)
+ *   form[2]  0 without dgrad / ln; 1: mst_gemm_sigmoid_bce_dgrad_ln is one launch; 2: it is the two launches
+ * Returns 0; invalid arguments: what the launch returns for them, same message. */
+int mst_gemm_sigmoid_bce_form(const mst_gemm_args* args, const mst_bce_args* bce, const mst_gemm_args* dgrad, const mst_ln_args* ln,
+                              int64_t* form);
 
 /* The whole feed-forward block of a Transformer layer in one launch (transformer.py:38-40 with :152-158 or :194-200):
  *     mst_gemm_nt(ff1)              a  = dropout(relu(x W1^T + b1))       — written (the backward pass needs it), never re-read
@@ -774,6 +783,7 @@ int mst_bce_from_probs(int dtype, int64_t B, int64_t n_per_sample, const void* p
  *   w_b = n_pos_b / (n_neg_b + 1e-12) (loss.py:50-54,58-81); npos is int32 [B] scratch.
  *   probs  : optional act dtype [B*T, ldp] (sigmoid output = reconstructed piano-roll)
  *   dlogits: optional act dtype, d(sum_b loss_b)/dlogit * gscale
+ *   Columns P..roundup4(P) of probs and dlogits are written as zeros; the pad columns of logits may hold anything.
  * ------------------------------------------------------------------------ */
 int mst_sigmoid_bce(int dtype, int64_t B, int64_t T, int64_t P,
                     const void* logits, int64_t ld, const uint8_t* labels,
@@ -781,6 +791,22 @@ int mst_sigmoid_bce(int dtype, int64_t B, int64_t T, int64_t P,
                     float* loss, void* probs, int64_t ldp,
                     void* dlogits, int64_t ldd, float gscale,
                     int pre_zeroed /* as in mst_softmax_ce */, mst_stream_t stream);
+/* What mst_sigmoid_bce launches for the same arguments: decided on the host, no HIP call, no device needed (the pointers are looked at
+ * for NULL and alignment only). The kernel's choice of the vector width is the same function. form is a host array of 8 entries:
+ *   form[0]  pitches a thread sweeps at a time: 8 (P, ld, ldp, ldd multiples of 8, logits / probs / dlogits on 16-byte and labels on
+ *            8-byte boundaries) or 4
+ *   form[1]  bytes of a label load: 8 (with form[0] = 8), 4 (P % 4 == 0) or 1
+ *   form[2]  how sample 0's positives are counted: 8 bytes at a time (its labels start on an 8-byte boundary) or 1; 0 without down-weighting
+ *   form[3]  the same for sample 1 (0 when B = 1): the samples' labels are T * P bytes apart
+ *   form[4]  workgroups per sample, grid.x: min(ceil(512 / B), ceil(T * ceil(P / 4) / 1024)). At 1 a sample's loss is a single atomic
+ *            and the launch is bit-reproducible in loss too
+ * Entries not listed are 0. Returns 0; invalid arguments: what mst_sigmoid_bce returns for them, same message. */
+int mst_sigmoid_bce_form(int dtype, int64_t B, int64_t T, int64_t P,
+                         const void* logits, int64_t ld, const uint8_t* labels,
+                         float label_smoothing, int downweight, int32_t* npos,
+                         float* loss, void* probs, int64_t ldp,
+                         void* dlogits, int64_t ldd, float gscale,
+                         int pre_zeroed, int64_t* form);
 
 /* ------------------------------------------------------------------------
  * K15/K21: total[b] = recon[b] + kl_weight * kl[b]; metric_acc[0] += sum_b kl, [1] += sum_b total,

@@ -78,9 +78,34 @@ int check_gemm_bce(const mst_gemm_args& a, const mst_bce_args& q) {
   return MST_OK;
 }
 
+// one launch of mst_gemm_sigmoid_bce_dgrad_ln: 128 pitches, width 128, whole 64-row tiles, and the second GEMM's A operand IS the first
+// one's logit gradient
+static bool bce_dgrad_ln_one_launch(const mst_gemm_args& a, const mst_gemm_args& g2, const mst_ln_args& l) {
+  return a.N == 128 && g2.N == 128 && g2.K == 128 && g2.M == a.M && a.M % 64 == 0 && l.mode == 2 && a.C && g2.A == a.C &&
+         g2.lda == a.ldc && g2.dtype == a.dtype && g2.a_rows_per_group <= 0 && !g2.a_u8;
+}
+
 }  // namespace mst
 
 using namespace mst;
+
+extern "C" int mst_gemm_sigmoid_bce_form(const mst_gemm_args* args, const mst_bce_args* bce, const mst_gemm_args* dgrad,
+                                         const mst_ln_args* ln, int64_t* form) {
+  MST_CHECK_ARG(form != nullptr, "mst_gemm_sigmoid_bce_form: null form");
+  const bool pair = dgrad != nullptr || ln != nullptr;
+  if (pair) MST_CHECK_ARG(args != nullptr && bce != nullptr && dgrad != nullptr && ln != nullptr, "mst_gemm_sigmoid_bce_dgrad_ln: null args");
+  else MST_CHECK_ARG(args != nullptr && bce != nullptr, "mst_gemm_sigmoid_bce: null args");
+  int rc = check_gemm_bce(*args, *bce);
+  if (rc == MST_OK && pair) rc = check_gemm_ln(*dgrad, *ln);
+  if (rc) return rc;
+  return dispatch_act(args->dtype, [&](auto) -> int {
+    const int64_t BN = args->N % 256 == 0 ? 256 : 128;
+    form[0] = BN;
+    form[1] = args->N / BN;
+    form[2] = !pair ? 0 : bce_dgrad_ln_one_launch(*args, *dgrad, *ln) ? 1 : 2;
+    return MST_OK;
+  });
+}
 
 extern "C" int mst_gemm_sigmoid_bce(const mst_gemm_args* args, const mst_bce_args* bce, mst_stream_t stream) {
   MST_CHECK_ARG(args != nullptr && bce != nullptr, "mst_gemm_sigmoid_bce: null args");
@@ -105,10 +130,7 @@ extern "C" int mst_gemm_sigmoid_bce_dgrad_ln(const mst_gemm_args* args, const ms
   int rc = check_gemm_bce(a, q);
   if (rc == MST_OK) rc = check_gemm_ln(g2, l);
   if (rc) return rc;
-  // one launch: 128 pitches, width 128, whole 64-row tiles, and the second GEMM's A operand IS the first one's logit gradient
-  const bool one = a.N == 128 && g2.N == 128 && g2.K == 128 && g2.M == a.M && a.M % 64 == 0 && l.mode == 2 && a.C && g2.A == a.C &&
-                   g2.lda == a.ldc && g2.dtype == a.dtype && g2.a_rows_per_group <= 0 && !g2.a_u8;
-  if (!one) {
+  if (!bce_dgrad_ln_one_launch(a, g2, l)) {
     rc = mst_gemm_sigmoid_bce(args, bce, stream);
     return rc != MST_OK ? rc : mst_gemm_nt_ln(dgrad, ln, stream);
   }

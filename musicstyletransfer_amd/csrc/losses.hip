@@ -109,6 +109,15 @@ __global__ __launch_bounds__(256) void ce_probs_kernel(int64_t B, int64_t T_len,
 // per sample) were half the kernel's time. Every workgroup counts the sample's positives itself (32 KB of labels)
 // instead of a counting launch + atomics in front.
 constexpr int BCE_THREADS = 1024;
+// Whether a launch sweeps 8 pitches per thread (16-byte logit / probability / gradient accesses, one 8-byte label load) or 4: the
+// kernel's own choice and entry [0] of mst_sigmoid_bce_form, from this one function. Absent outputs are passed as 0.
+__host__ __device__ inline bool sigmoid_bce_wide(int P, int64_t ld, uintptr_t logits, uintptr_t labels, uintptr_t probs, int64_t ldp,
+                                                 uintptr_t dlogits, int64_t ldd) {
+  return P % 8 == 0 && ld % 8 == 0 && (!probs || ldp % 8 == 0) && (!dlogits || ldd % 8 == 0) && ((logits | probs | dlogits) & 15) == 0 &&
+         (labels & 7) == 0;
+}
+// the positive count of a sample reads its labels 8 bytes at a time where they start on an 8-byte boundary, else byte by byte
+__host__ __device__ inline bool bce_count_by_words(const uint8_t* base) { return (reinterpret_cast<uintptr_t>(base) & 7) == 0; }
 __device__ __forceinline__ float block_sum_1024(float v, float* red) {
   v = wave_sum(v);
   __syncthreads();  // red may still be read from a previous use
@@ -135,7 +144,7 @@ __global__ __launch_bounds__(BCE_THREADS) void sigmoid_bce_kernel(int64_t rows_p
   if (downweight) {  // labels are {0,1} bytes
     const uint8_t* base = labels + b * per_sample;
     int cnt = 0;
-    if ((reinterpret_cast<uintptr_t>(base) & 7) == 0) {
+    if (bce_count_by_words(base)) {
       for (int64_t i = (int64_t)tid * 8; i < per_sample; i += (int64_t)BCE_THREADS * 8) {
         if (i + 8 <= per_sample) cnt += __popcll(*reinterpret_cast<const uint64_t*>(base + i) & 0x0101010101010101ull);
         else for (int64_t j = i; j < per_sample; ++j) cnt += (base[j] == 1);
@@ -216,8 +225,7 @@ __global__ __launch_bounds__(BCE_THREADS) void sigmoid_bce_kernel(int64_t rows_p
       }
     }
   };
-  const bool wide = P % 8 == 0 && ld % 8 == 0 && (!probs || ldp % 8 == 0) && (!dlogits || ldd % 8 == 0) &&
-                    (((uintptr_t)logits | (uintptr_t)probs | (uintptr_t)dlogits) & 15) == 0 && ((uintptr_t)labels & 7) == 0;
+  const bool wide = sigmoid_bce_wide(P, ld, (uintptr_t)logits, (uintptr_t)labels, (uintptr_t)probs, ldp, (uintptr_t)dlogits, ldd);
   typedef std::integral_constant<int, 8> V8;
   typedef std::integral_constant<int, 4> V4;
   if (downweight) { if (wide) sweep(std::true_type(), V8()); else sweep(std::true_type(), V4()); }
@@ -348,10 +356,9 @@ extern "C" int mst_bce_from_probs(int dtype, int64_t B, int64_t n_per_sample, co
   });
 }
 
-extern "C" int mst_sigmoid_bce(int dtype, int64_t B, int64_t T, int64_t P, const void* logits, int64_t ld,
-                               const uint8_t* labels, float label_smoothing, int downweight, int32_t* npos,
-                               float* loss, void* probs, int64_t ldp, void* dlogits, int64_t ldd, float gscale,
-                               int pre_zeroed, mst_stream_t stream) {
+// what mst_sigmoid_bce and mst_sigmoid_bce_form refuse, and the launch's grid.x: both entry points go through these two and nothing else
+static int check_sigmoid_bce(int64_t B, int64_t T, int64_t P, const void* logits, int64_t ld, const uint8_t* labels, int downweight,
+                             const int32_t* npos, const float* loss, const void* probs, int64_t ldp, const void* dlogits, int64_t ldd) {
   MST_CHECK_ARG(B > 0 && T > 0 && P > 0, "mst_sigmoid_bce: B,T,P must be positive");
   MST_CHECK_ARG(logits && labels && loss, "mst_sigmoid_bce: null pointer");
   MST_CHECK_ARG(ld % 4 == 0 && ld >= P, "mst_sigmoid_bce: ld must be a multiple of 4 and >= P");
@@ -360,16 +367,46 @@ extern "C" int mst_sigmoid_bce(int dtype, int64_t B, int64_t T, int64_t P, const
   MST_CHECK_ARG(!downweight || npos, "mst_sigmoid_bce: down-weighting needs the npos scratch");
   MST_CHECK_ARG(B <= 65535, "mst_sigmoid_bce: B too large for grid.y");
   MST_CHECK_ARG(T * ((P + 3) / 4) < (1ll << 31), "mst_sigmoid_bce: T * P / 4 must stay below 2^31");
+  return MST_OK;
+}
+// enough workgroups to put ~2 on every CU, at least one 4-pitch vector per thread
+static int64_t sigmoid_bce_gx(int64_t B, int64_t T, int64_t P) {
+  const int64_t nvec = T * ((P + 3) / 4);
+  int64_t gx = cdiv(512, B);
+  if (gx > cdiv(nvec, BCE_THREADS)) gx = cdiv(nvec, BCE_THREADS);
+  return gx < 1 ? 1 : gx;
+}
+
+extern "C" int mst_sigmoid_bce_form(int dtype, int64_t B, int64_t T, int64_t P, const void* logits, int64_t ld, const uint8_t* labels,
+                                    float label_smoothing, int downweight, int32_t* npos, float* loss, void* probs, int64_t ldp,
+                                    void* dlogits, int64_t ldd, float gscale, int pre_zeroed, int64_t* form) {
+  (void)label_smoothing; (void)gscale; (void)pre_zeroed;
+  MST_CHECK_ARG(form != nullptr, "mst_sigmoid_bce_form: null form");
+  const int rc = check_sigmoid_bce(B, T, P, logits, ld, labels, downweight, npos, loss, probs, ldp, dlogits, ldd);
+  if (rc) return rc;
+  return dispatch_act(dtype, [&](auto) -> int {
+    const bool wide = sigmoid_bce_wide((int)P, ld, (uintptr_t)logits, (uintptr_t)labels, (uintptr_t)probs, ldp, (uintptr_t)dlogits, ldd);
+    form[0] = wide ? 8 : 4;
+    form[1] = wide ? 8 : P % 4 == 0 ? 4 : 1;
+    form[2] = !downweight ? 0 : bce_count_by_words(labels) ? 8 : 1;
+    form[3] = (!downweight || B < 2) ? 0 : bce_count_by_words(labels + T * P) ? 8 : 1;
+    form[4] = sigmoid_bce_gx(B, T, P);
+    return MST_OK;
+  });
+}
+
+extern "C" int mst_sigmoid_bce(int dtype, int64_t B, int64_t T, int64_t P, const void* logits, int64_t ld,
+                               const uint8_t* labels, float label_smoothing, int downweight, int32_t* npos,
+                               float* loss, void* probs, int64_t ldp, void* dlogits, int64_t ldd, float gscale,
+                               int pre_zeroed, mst_stream_t stream) {
+  const int rc = check_sigmoid_bce(B, T, P, logits, ld, labels, downweight, npos, loss, probs, ldp, dlogits, ldd);
+  if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   if (!pre_zeroed) {
     hipError_t e = hipMemsetAsync(loss, 0, sizeof(float) * B, s);
     if (e != hipSuccess) { set_error("mst_sigmoid_bce: memset: %s", hipGetErrorString(e)); return MST_ERR_LAUNCH; }
   }
-  // enough workgroups to put ~2 on every CU, at least one 4-pitch vector per thread
-  const int64_t nvec = T * ((P + 3) / 4);
-  int64_t gx = cdiv(512, B);
-  if (gx > cdiv(nvec, BCE_THREADS)) gx = cdiv(nvec, BCE_THREADS);
-  if (gx < 1) gx = 1;
+  const int64_t gx = sigmoid_bce_gx(B, T, P);
   return dispatch_act(dtype, [&](auto tag) -> int {
     typedef decltype(tag) TT;
     hipLaunchKernelGGL((sigmoid_bce_kernel<TT>), dim3((unsigned)gx, (unsigned)B), dim3(BCE_THREADS), 0, s, T, (int)P, (const TT*)logits,

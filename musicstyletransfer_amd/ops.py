@@ -215,6 +215,15 @@ def gemm_sigmoid_bce(A, B, labels, loss, T, dgrad=None, **kw):
         call("mst_gemm_sigmoid_bce_dgrad_ln", C.byref(g), C.byref(q), C.byref(g2), C.byref(l), stream())
 
 
+def gemm_sigmoid_bce_form(g, q, g2=None, l=None):
+    """what mst_gemm_sigmoid_bce(g, q) — with g2 / l: mst_gemm_sigmoid_bce_dgrad_ln(g, q, g2, l) — launches for these argument structs
+    (mst_gemm_sigmoid_bce_form in include/mst_hip.h); no launch, no device. -> dict(BN, col_tiles, launches (0 without g2 / l))"""
+    form = (C.c_int64 * 4)()
+    call("mst_gemm_sigmoid_bce_form", C.byref(g), C.byref(q), C.byref(g2) if g2 is not None else None, C.byref(l) if l is not None else None,
+         form)
+    return dict(BN=form[0], col_tiles=form[1], launches=form[2])
+
+
 def can_fuse_ln(D):
     """row widths the LayerNorm-fused GEMM exists for (mst_gemm_nt_ln)"""
     return D in (128, 256)
@@ -780,6 +789,21 @@ def sigmoid_bce(logits, labels, loss, B, T, P, label_smoothing=0.0, downweight=F
     call("mst_sigmoid_bce", dt(logits), B, T, P, ptr(logits), ld(logits), ptr(labels), label_smoothing,
          1 if downweight else 0, ptr(npos), ptr(loss), ptr(probs), (ld(probs) if probs is not None else 0),
          ptr(dlogits), (ld(dlogits) if dlogits is not None else 0), gscale, 1 if pre_zeroed else 0, stream())
+
+
+def _addr(t):
+    return t.data_ptr() if isinstance(t, torch.Tensor) else t
+
+
+def sigmoid_bce_form(dtype, B, T, P, logits, ld_logits, labels, label_smoothing=0.0, downweight=False, npos=None, loss=None, probs=None,
+                     ldp=0, dlogits=None, ldd=0, gscale=1.0, pre_zeroed=False):
+    """what sigmoid_bce launches for these arguments (mst_sigmoid_bce_form in include/mst_hip.h); no launch, no device. logits, labels,
+    npos, loss, probs, dlogits: tensors or plain addresses (None: absent), looked at for alignment only.
+    -> dict(vec (8 or 4), label_bytes (8, 4 or 1), count0, count1 (8, 1, or 0 where nothing is counted), gx)"""
+    form = (C.c_int64 * 8)()
+    call("mst_sigmoid_bce_form", dt(dtype), B, T, P, _addr(logits), ld_logits, _addr(labels), label_smoothing, 1 if downweight else 0,
+         _addr(npos), _addr(loss), _addr(probs), ldp, _addr(dlogits), ldd, gscale, 1 if pre_zeroed else 0, form)
+    return dict(vec=form[0], label_bytes=form[1], count0=form[2], count1=form[3], gx=form[4])
 
 
 def _step_metrics(metrics):
