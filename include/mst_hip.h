@@ -675,6 +675,16 @@ typedef struct mst_row_tail_bwd_args {
 } mst_row_tail_bwd_args;
 int mst_row_tail_bwd(const mst_row_tail_bwd_args* args, mst_stream_t stream);
 int mst_row_tail_bwd_ride(const mst_row_tail_bwd_args* args, const mst_gemm_args* rider, uint32_t* queue, mst_stream_t stream);
+/* What the five tail launches above take for a width and a rider, from the host functions the launches themselves decide with; no
+ * HIP call, no pointer of `rider` is followed (they are looked at for null and alignment, as the launch does). backward: 0 the
+ * forward tail, 1 the backward one; rider: NULL for the plain launches; sh_tiles: the shadow list's 32 x 32 tiles behind the rider
+ * (mst_row_tail_fwd_ride_shadows' sh_tiles; 0: none; forward with a rider only). form: six entries,
+ *   [0] kernel index: (D == 256 ? 0 : 1) + (no rider 0, 128-row rider tiles 2, 256-row rider tiles 4)
+ *   [1] rider tile rows: 0 (no rider), 128, or 256 (more than 208 tiles of 128 rows, M and the row-remap groups multiples of 256)
+ *   [2] rider tiles of that height        [3] workgroups launched (D / 16 of them on one XCD run the chain)
+ *   [4] dynamic LDS bytes                 [5] shadow tickets (sixteen tiles each) queued behind the rider's tiles
+ * D, the activation type and the rider are validated as the launches validate them: same status, same message. */
+int mst_row_tail_form(int backward, int dtype, int64_t D, const mst_gemm_args* rider, int64_t sh_tiles, int64_t* form);
 
 /* ------------------------------------------------------------------------
  * Incremental decode (inference; model.py:259-272, transformer.py:70-77,242-249): the new position's query against the

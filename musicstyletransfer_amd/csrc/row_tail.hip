@@ -857,6 +857,48 @@ static void ride_shape(const mst_gemm_args& g, int& tiles_signed, size_t& lds) {
   // (negative: 256-row tiles)
 }
 
+// What a valid call launches (the entries of mst_row_tail_form, include/mst_hip.h): kernel index = (D == 256 ? 0 : 1) + (no rider: 0,
+// 128-row rider tiles: 2, 256-row: 4) in both directions. The launches below validate their arguments and take everything else from here.
+struct TailForm { int kernel, ride_rows, tiles; unsigned grid; size_t lds; int tickets; };
+static int tail_form_common(const char* who, const char* who_ride, int dtype, int64_t D, const mst_gemm_args* rider, TailForm& f) {
+  MST_CHECK_ARG(D == 128 || D == 256, "%s: width must be 128 or 256 (got %lld)", who, (long long)D);
+  if (const int rc = dispatch_act(dtype, [](auto) -> int { return MST_OK; })) return rc;  // (another type: the launch's own refusal)
+  f = TailForm{D == 256 ? 0 : 1, 0, 0, (unsigned)((D / 16) * TAIL_OVERSUBSCRIBE), 0, 0};
+  if (rider) {
+    if (const int rc = check_rider(who_ride, *rider, dtype)) return rc;
+    int tiles;
+    ride_shape(*rider, tiles, f.lds);
+    f.ride_rows = tiles < 0 ? 256 : 128;
+    f.tiles = tiles < 0 ? -tiles : tiles;
+    f.kernel += tiles < 0 ? 4 : 2;
+    f.grid = ride_grid(D / 16, f.tiles);
+  }
+  return MST_OK;
+}
+static int row_tail_fwd_form(int dtype, int64_t D, const mst_gemm_args* rider, int64_t sh_tiles, TailForm& f) {
+  if (const int rc = tail_form_common("mst_row_tail_fwd", "mst_row_tail_fwd_ride", dtype, D, rider, f)) return rc;
+  MST_CHECK_ARG(sh_tiles == 0 || (rider && sh_tiles > 0 && sh_tiles < (1ll << 30)), "mst_row_tail_fwd_ride_shadows: shadow tiles need a rider (got %lld)",
+                (long long)sh_tiles);
+  f.tickets = (int)((sh_tiles + 15) / 16);  // sixteen shadow tiles per ticket
+  if (f.tickets > 0 && f.lds < (size_t)16 * 32 * 33 * 4) f.lds = (size_t)16 * 32 * 33 * 4;
+  return MST_OK;
+}
+static int row_tail_bwd_form(int dtype, int64_t D, const mst_gemm_args* rider, TailForm& f) {
+  if (const int rc = tail_form_common("mst_row_tail_bwd", "mst_row_tail_bwd_ride", dtype, D, rider, f)) return rc;
+  // (a workgroup is a participant or a rider: one region)
+  const size_t lds = (size_t)2 * 64 * ((size_t)D + 8) * 2 + (size_t)16 * 2 * D * 4 + (size_t)4 * 64 * 16 * 4 + (size_t)2 * D * 4;
+  if (lds > f.lds) f.lds = lds;
+  return MST_OK;
+}
+extern "C" int mst_row_tail_form(int backward, int dtype, int64_t D, const mst_gemm_args* rider, int64_t sh_tiles, int64_t* form) {
+  MST_CHECK_ARG(form != nullptr, "mst_row_tail_form: null form");
+  MST_CHECK_ARG(!backward || sh_tiles == 0, "mst_row_tail_form: the backward tail takes no shadow tiles");
+  TailForm f;
+  if (const int rc = backward ? row_tail_bwd_form(dtype, D, rider, f) : row_tail_fwd_form(dtype, D, rider, sh_tiles, f)) return rc;
+  form[0] = f.kernel; form[1] = f.ride_rows; form[2] = f.tiles; form[3] = f.grid; form[4] = (int64_t)f.lds; form[5] = f.tickets;
+  return MST_OK;
+}
+
 static int row_tail_fwd_impl(const mst_row_tail_args* args, const mst_gemm_args* rider, uint32_t* queue, mst_stream_t stream,
                              const TailShadow& shadow = TailShadow{}) {
   MST_CHECK_ARG(args != nullptr, "mst_row_tail_fwd: null args");
@@ -871,28 +913,20 @@ static int row_tail_fwd_impl(const mst_row_tail_args* args, const mst_gemm_args*
                   (uintptr_t)q.a | (uintptr_t)q.h2 | (uintptr_t)q.x2 | (uintptr_t)q.bp | (uintptr_t)q.b1 | (uintptr_t)q.b2) % 16) == 0,
                 "mst_row_tail_fwd: operands must be 16-byte aligned");
   MST_CHECK_ARG(q.dropout_p >= 0.f && q.dropout_p < 1.f && q.phys_stride > 0 && q.stat_stride > 0, "mst_row_tail_fwd: bad dropout / strides");
-  if (rider) {
-    const int rc = check_rider("mst_row_tail_fwd_ride", *rider, q.dtype);
-    if (rc) return rc;
-  }
+  TailForm f;
+  if (const int rc = row_tail_fwd_form(q.dtype, q.D, rider, shadow.tiles, f)) return rc;
+  TailShadow sh = shadow;
+  sh.n_groups = f.tickets;
   hipStream_t s = (hipStream_t)stream;
   const mst_gemm_args none = {};
   return dispatch_act(q.dtype, [&](auto tag) -> int {
     typedef decltype(tag) T;
-    if (rider) {
-      int tiles;
-      size_t rlds;
-      ride_shape(*rider, tiles, rlds);
-      if (shadow.n_groups > 0 && rlds < (size_t)16 * 32 * 33 * 4) rlds = (size_t)16 * 32 * 33 * 4;  // sixteen shadow tiles per ticket
-      const int wi = (q.D == 256 ? 0 : 1) + (tiles < 0 ? 2 : 0);
-      typedef void (*kern_t)(mst_row_tail_args, mst_gemm_args, int, uint32_t*, TailShadow);
-      const kern_t fns[4] = {&row_tail_fwd_kernel<T, 256, 128>, &row_tail_fwd_kernel<T, 128, 128>, &row_tail_fwd_kernel<T, 256, 256>, &row_tail_fwd_kernel<T, 128, 256>};
-      static size_t granted[4] = {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024};
-      if (const int rc = lds_opt_in(reinterpret_cast<const void*>(fns[wi]), rlds, &granted[wi], "row_tail_fwd_kernel (riders)")) return rc;
-      const unsigned grid = ride_grid(q.D / 16, tiles < 0 ? -tiles : tiles);
-      hipLaunchKernelGGL(fns[wi], dim3(grid), dim3(1024), rlds, s, q, *rider, tiles < 0 ? -tiles : tiles, queue, shadow);
-    } else if (q.D == 256) hipLaunchKernelGGL((row_tail_fwd_kernel<T, 256>), dim3(16 * TAIL_OVERSUBSCRIBE), dim3(1024), 0, s, q, none, 0, (uint32_t*)nullptr, TailShadow{});
-    else hipLaunchKernelGGL((row_tail_fwd_kernel<T, 128>), dim3(8 * TAIL_OVERSUBSCRIBE), dim3(1024), 0, s, q, none, 0, (uint32_t*)nullptr, TailShadow{});
+    typedef void (*kern_t)(mst_row_tail_args, mst_gemm_args, int, uint32_t*, TailShadow);
+    const kern_t fns[6] = {&row_tail_fwd_kernel<T, 256>,      &row_tail_fwd_kernel<T, 128>,      &row_tail_fwd_kernel<T, 256, 128>,
+                           &row_tail_fwd_kernel<T, 128, 128>, &row_tail_fwd_kernel<T, 256, 256>, &row_tail_fwd_kernel<T, 128, 256>};
+    static size_t granted[6] = {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024};
+    if (const int rc = lds_opt_in(reinterpret_cast<const void*>(fns[f.kernel]), f.lds, &granted[f.kernel], "row_tail_fwd_kernel (riders)")) return rc;
+    hipLaunchKernelGGL(fns[f.kernel], dim3(f.grid), dim3(1024), f.lds, s, q, rider ? *rider : none, f.tiles, rider ? queue : (uint32_t*)nullptr, sh);
     MST_CHECK_LAUNCH("row_tail_fwd_kernel");
     return MST_OK;
   });
@@ -910,7 +944,7 @@ extern "C" int mst_row_tail_fwd_ride_shadows(const mst_row_tail_args* args, cons
                 "mst_row_tail_fwd_ride_shadows: bad shadow list (mst_transpose_shadows' arguments, in the tail's activation type)");
   TailShadow sh;
   sh.w = sh_w; sh.wt16 = sh_wt16; sh.desc = sh_desc; sh.prefix = sh_prefix; sh.n_mat = (int)sh_n_mat; sh.tiles = sh_tiles;
-  sh.n_groups = (int)((sh_tiles + 15) / 16);
+  sh.n_groups = 0;  // (row_tail_fwd_form: the tickets)
   return row_tail_fwd_impl(args, rider, queue, stream, sh);
 }
 
@@ -927,32 +961,18 @@ static int row_tail_bwd_impl(const mst_row_tail_bwd_args* args, const mst_gemm_a
                   (uintptr_t)q.dh | (uintptr_t)q.dhm | (uintptr_t)q.dx1 | (uintptr_t)q.dh1m | (uintptr_t)q.dpre | (uintptr_t)q.dh1 | (uintptr_t)q.datt) % 16) == 0,
                 "mst_row_tail_bwd: operands must be 16-byte aligned");
   MST_CHECK_ARG(q.dropout_p >= 0.f && q.dropout_p < 1.f && q.phys_stride > 0 && q.stat_stride > 0, "mst_row_tail_bwd: bad dropout / strides");
-  if (rider) {
-    const int rc = check_rider("mst_row_tail_bwd_ride", *rider, q.dtype);
-    if (rc) return rc;
-  }
+  TailForm f;
+  if (const int rc = row_tail_bwd_form(q.dtype, q.D, rider, f)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const mst_gemm_args none = {};
   return dispatch_act(q.dtype, [&](auto tag) -> int {
     typedef decltype(tag) T;
-    size_t lds = (size_t)2 * 64 * ((size_t)q.D + 8) * 2 + (size_t)16 * 2 * q.D * 4 + (size_t)4 * 64 * 16 * 4 + (size_t)2 * q.D * 4;
-    int tiles = 0;
-    if (rider) {  // (a workgroup is a participant or a rider: one region)
-      size_t rlds;
-      ride_shape(*rider, tiles, rlds);
-      if (rlds > lds) lds = rlds;
-    }
     static size_t granted[6] = {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024};
-    const int wi = (q.D == 256 ? 0 : 1) + (rider ? (tiles < 0 ? 4 : 2) : 0);
     typedef void (*kern_t)(mst_row_tail_bwd_args, mst_gemm_args, int, uint32_t*);
     const kern_t fns[6] = {&row_tail_bwd_kernel<T, 256>, &row_tail_bwd_kernel<T, 128>, &row_tail_bwd_kernel<T, 256, 128>, &row_tail_bwd_kernel<T, 128, 128>,
                            &row_tail_bwd_kernel<T, 256, 256>, &row_tail_bwd_kernel<T, 128, 256>};
-    if (const int rc = lds_opt_in(reinterpret_cast<const void*>(fns[wi]), lds, &granted[wi], "row_tail_bwd_kernel")) return rc;
-    if (rider) {
-      const unsigned grid = ride_grid(q.D / 16, tiles < 0 ? -tiles : tiles);
-      hipLaunchKernelGGL(fns[wi], dim3(grid), dim3(1024), lds, s, q, *rider, tiles < 0 ? -tiles : tiles, queue);
-    } else if (q.D == 256) hipLaunchKernelGGL((row_tail_bwd_kernel<T, 256>), dim3(16 * TAIL_OVERSUBSCRIBE), dim3(1024), lds, s, q, none, 0, (uint32_t*)nullptr);
-    else hipLaunchKernelGGL((row_tail_bwd_kernel<T, 128>), dim3(8 * TAIL_OVERSUBSCRIBE), dim3(1024), lds, s, q, none, 0, (uint32_t*)nullptr);
+    if (const int rc = lds_opt_in(reinterpret_cast<const void*>(fns[f.kernel]), f.lds, &granted[f.kernel], "row_tail_bwd_kernel")) return rc;
+    hipLaunchKernelGGL(fns[f.kernel], dim3(f.grid), dim3(1024), f.lds, s, q, rider ? *rider : none, f.tiles, rider ? queue : (uint32_t*)nullptr);
     MST_CHECK_LAUNCH("row_tail_bwd_kernel");
     return MST_OK;
   });

@@ -121,14 +121,16 @@ def row_tail_barriers(D):
 
 
 def row_tail_fwd(att, resid, Wp, bp, g1, be1, W1, b1, W2, b2, g2, be2, h1, x1, a, h2, x2, mean1, rstd1, mean2, rstd2, sync, stat_stride,
-                 phys_stride, eps=1e-5, dropout_p=0.0, dropout_seed_ptr=None, site0=0, status=None, rider=None, queue=None, shadows=None):
+                 phys_stride, eps=1e-5, dropout_p=0.0, dropout_seed_ptr=None, site0=0, status=None, rider=None, queue=None, shadows=None,
+                 dropout_seed=0):
     """att / resid / h1 / x1 / a / h2 / x2: [B, width] row views (stride(0) = the row stride in elements) of the layer's
     buffers; sync: THREE zeroed int32 device words (barrier counter — 3 * D / 16 after a complete launch —, claimed XCD,
     roles handed out); status: optional sticky int32 device word the kernel ORs _lib.TAIL_* flags into when it cannot
     finish. rider: dict(A=, B=, C_out=, **gemm_nt keywords) — one GEMM nothing in the chain reads, computed by the launch's
     workgroups on the other seven XCDs (mst_row_tail_fwd_ride); queue: its tile queue, ONE zeroed int32 device word in a
     cache line of its own (not sync's); shadows: dict(w=, wt16=, desc=, prefix=, n_mat=, tiles=) — transpose_shadows' list, rebuilt by
-    the riders behind the GEMM's tiles (mst_row_tail_fwd_ride_shadows; needs a rider)"""
+    the riders behind the GEMM's tiles (mst_row_tail_fwd_ride_shadows; needs a rider); dropout_seed: the host half of the seed, XORed
+    with the word behind dropout_seed_ptr (as gemm_nt's)"""
     assert sync.numel() >= 3 and (rider is None or queue is not None) and (shadows is None or rider is not None)
     q = _lib.RowTailArgs()
     q.dtype, q.B, q.D = dt(att), att.shape[0], Wp.shape[0]
@@ -138,7 +140,7 @@ def row_tail_fwd(att, resid, Wp, bp, g1, be1, W1, b1, W2, b2, g2, be2, h1, x1, a
     assert h1.stride(0) == x1.stride(0) == h2.stride(0) == x2.stride(0)
     q.h1, q.x1, q.h2, q.x2, q.rs_d, q.a, q.rs_a = ptr(h1), ptr(x1), ptr(h2), ptr(x2), h1.stride(0), ptr(a), a.stride(0)
     q.mean1, q.rstd1, q.mean2, q.rstd2, q.stat_stride = ptr(mean1), ptr(rstd1), ptr(mean2), ptr(rstd2), stat_stride
-    q.eps, q.dropout_p, q.dropout_seed, q.dropout_seed_ptr, q.site0 = eps, dropout_p, 0, ptr(dropout_seed_ptr), site0
+    q.eps, q.dropout_p, q.dropout_seed, q.dropout_seed_ptr, q.site0 = eps, dropout_p, dropout_seed, ptr(dropout_seed_ptr), site0
     q.phys_stride, q.sync, q.status = phys_stride, ptr(sync), ptr(status)
     if shadows is not None:
         call("mst_row_tail_fwd_ride_shadows", C.byref(q), C.byref(_gemm_args(**rider)), ptr(queue), dt(shadows["wt16"]), ptr(shadows["w"]),
@@ -150,10 +152,11 @@ def row_tail_fwd(att, resid, Wp, bp, g1, be1, W1, b1, W2, b2, g2, be2, h1, x1, a
 
 
 def row_tail_bwd(dy, h2, h1, a, mean1, rstd1, mean2, rstd2, g1, g2, W2t, W1t, Wpt, dh, dhm, dx1, dh1m, dpre, dh1, datt, dg1, db1, dg2, db2,
-                 sync, stat_stride, phys_stride, dropout_p=0.0, dropout_seed_ptr=None, site0=0, status=None, rider=None, queue=None):
+                 sync, stat_stride, phys_stride, dropout_p=0.0, dropout_seed_ptr=None, site0=0, status=None, rider=None, queue=None,
+                 dropout_seed=0):
     """backward of row_tail_fwd's chain in one launch (mst_row_tail_bwd); dy / h2 / h1 / a / dh1 / datt: [B, width] row views,
     dh / dhm / dx1 / dh1m / dpre: compact [B, width] scratch; sync: THREE zeroed int32 device words (the barrier counter
-    ends at 2 * D / 16); status, rider, queue: as row_tail_fwd"""
+    ends at 2 * D / 16); status, rider, queue, dropout_seed: as row_tail_fwd"""
     assert sync.numel() >= 3 and (rider is None or queue is not None)
     q = _lib.RowTailBwdArgs()
     q.dtype, q.B, q.D = dt(dy), dy.shape[0], Wpt.shape[0]
@@ -167,12 +170,21 @@ def row_tail_bwd(dy, h2, h1, a, mean1, rstd1, mean2, rstd2, g1, g2, W2t, W1t, Wp
     q.dh, q.dhm, q.dx1, q.dh1m, q.rs_c = ptr(dh), ptr(dhm), ptr(dx1), ptr(dh1m), dh.stride(0)
     q.dpre, q.rs_dpre, q.dh1, q.rs_dh1, q.datt, q.rs_datt = ptr(dpre), dpre.stride(0), ptr(dh1), dh1.stride(0), ptr(datt), datt.stride(0)
     q.dg1, q.db1, q.dg2, q.db2 = ptr(dg1), ptr(db1), ptr(dg2), ptr(db2)
-    q.dropout_p, q.dropout_seed, q.dropout_seed_ptr, q.site0 = dropout_p, 0, ptr(dropout_seed_ptr), site0
+    q.dropout_p, q.dropout_seed, q.dropout_seed_ptr, q.site0 = dropout_p, dropout_seed, ptr(dropout_seed_ptr), site0
     q.phys_stride, q.sync, q.status = phys_stride, ptr(sync), ptr(status)
     if rider is not None:
         call("mst_row_tail_bwd_ride", C.byref(q), C.byref(_gemm_args(**rider)), ptr(queue), stream())
     else:
         call("mst_row_tail_bwd", C.byref(q), stream())
+
+
+def row_tail_form(backward, dtype, D, rider=None, sh_tiles=0):
+    """what row_tail_fwd / row_tail_bwd launch for a width and a rider (mst_row_tail_form in include/mst_hip.h); no launch. rider: the
+    dict row_tail_* take, or an _lib.GemmArgs. -> dict(kernel, ride_rows, tiles, grid, lds, tickets)"""
+    form = (C.c_int64 * 6)()
+    g = None if rider is None else C.byref(rider if isinstance(rider, GemmArgs) else _gemm_args(**rider))
+    call("mst_row_tail_form", 1 if backward else 0, dt(dtype), D, g, sh_tiles, form)
+    return dict(zip(("kernel", "ride_rows", "tiles", "grid", "lds", "tickets"), form))
 
 
 def can_fuse_bce(P, T, downweight=False):

@@ -43,7 +43,11 @@ subnormal: + 2^-25):
            (+ sum e |xh| where dy carries e);  dbeta: 2 (M + 16) u (sum|dy| + |initial|) (+ sum e)
 No constant above was chosen after looking at a GPU result.
 
-The dropout keep decision is imported from gemm_refs (checked there against csrc/common.hpp), not restated."""
+The dropout keep decision is imported from gemm_refs (checked there against csrc/common.hpp), not restated.
+
+Other reference modules build on this one (tests/tail_refs.py: the one-launch position-0 tails): they register the plan of their own
+case kinds in PLANS, give a buffer a row stride of its own (Buf.stride) where a launch takes one per tensor, and share check(),
+intact(), the stages and the bounds. None of that changes what the cases of this module compute."""
 import os
 import sys
 import zlib
@@ -197,9 +201,12 @@ def n_parts(c):
     return ln_bwd_parts(c.M, c.D) if c.kind == "ln" else (c.M + 63) // 64
 
 
-def rows(c):
-    """-> (physical row of every logical row, number of physical rows)"""
+def rows(c, spec=None):
+    """-> (physical row of every logical row, number of physical rows). spec: a buffer with a row stride of its own (Buf.stride:
+    logical row m at row m * stride of that buffer, whatever the case's groups say)"""
     m = np.arange(c.M, dtype=np.int64)
+    if spec is not None and spec.stride:
+        return m * spec.stride, c.M * spec.stride
     if c.groups is None:
         return m, c.M
     rpg, stride, off = c.groups
@@ -214,6 +221,7 @@ class Buf:
     out: bool
     n: int = 0     # w: rows; parts: rows
     free: bool = False  # an output no stage here checks (the loss arithmetic's)
+    stride: int = 0     # phys / stat: a row stride of this buffer's own (0: the case's physical rows)
 
 
 @dataclass(frozen=True)
@@ -259,8 +267,13 @@ class LnBwd:
     parts: str = None
 
 
+PLANS = {}  # kind -> plan function of the case kinds other modules add (tests/tail_refs.py)
+
+
 def plan(c):
     """-> (buffers: name -> Buf, stages in launch order)"""
+    if c.kind in PLANS:
+        return PLANS[c.kind](c)
     D, F = c.D, c.F
     b, st = {}, []
 
@@ -375,15 +388,16 @@ def hard_rows(g, n, width, dtype, shift=0):
     """activation rows made to be hard (fp64, 16-bit-exact): unit-scale rows; every 8th row (3, 11, ...) a common offset 8 with a
     spread of sixteenths (exact in bf16 and fp16); row 5 + shift constant (variance 0: only eps under the root); row 6 + shift small
     with one large element. (shift: the two LayerNorms of one launch get their constant rows at different rows — rstd = 316 twice
-    in a chain leaves fp16's range)"""
+    in a chain leaves fp16's range). With fewer than 7 + shift rows: the hard rows that fit"""
     x = torch.randn((n, width), generator=g).double().numpy()
     off = np.arange(n) % 8 == 3
     k = torch.randint(-2, 3, (n, width), generator=g).double().numpy()
     x[off] = 8.0 + k[off] / 16.0
-    assert n > 6 + shift
-    x[5 + shift] = 3.0
-    x[6 + shift] = 0.1 * x[6 + shift]
-    x[6 + shift, width // 3] = 32.0
+    if n > 5 + shift:
+        x[5 + shift] = 3.0
+    if n > 6 + shift:
+        x[6 + shift] = 0.1 * x[6 + shift]
+        x[6 + shift, width // 3] = 32.0
     return _r16(x, dtype)
 
 
@@ -399,7 +413,7 @@ def _gamma(g, D):
 
 
 def _alloc(c, spec, fill):
-    _, P = rows(c)
+    _, P = rows(c, spec)
     guard = GUARD if spec.out else 0
     if spec.rows in ("log", "phys"):
         return torch.full(((c.M if spec.rows == "log" else P) + guard, spec.width + PAD), fill, dtype=c.dtype)
@@ -414,7 +428,7 @@ def _alloc(c, spec, fill):
 
 def owned(c, spec):
     """boolean mask over a buffer: the elements the launch owns (reads of an input, stores of an output)"""
-    pm, _ = rows(c)
+    pm, _ = rows(c, spec)
     t = _alloc(c, spec, 0.0)
     m = np.zeros(tuple(t.shape), dtype=bool)
     if spec.rows == "log":
@@ -496,7 +510,7 @@ def outputs(c):
 
 def gather(c, spec, t):
     """a buffer's logical rows as fp64 [M, width] ([M] for statistics)"""
-    pm, _ = rows(c)
+    pm, _ = rows(c, spec)
     a = t.double().numpy()
     if spec.rows == "log":
         return a[:c.M, :spec.width]
@@ -510,7 +524,7 @@ def gather(c, spec, t):
 
 
 def scatter(c, spec, t, v):
-    pm, _ = rows(c)
+    pm, _ = rows(c, spec)
     v = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(t.dtype)
     if spec.rows == "log":
         t[:c.M, :spec.width] = v

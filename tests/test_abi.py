@@ -48,7 +48,7 @@ def test_exports_are_exactly_the_declarations(lib):
 
 
 def test_version_and_error_string(lib):
-    assert lib.mst_version() >= 110  # 110: mst_sigmoid_bce_form, mst_gemm_sigmoid_bce_form
+    assert lib.mst_version() >= 111  # 111: mst_row_tail_form
     assert isinstance(lib.mst_last_error(), bytes)
 
 
@@ -107,6 +107,7 @@ def test_parser_known_answers():
         "mst_attn_fwd_form": (ci, [ci, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, ci, i64, i64, vp]),
         "mst_attn_bwd_form": (ci, [ci, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, vp]),
         "mst_latent_form": (ci, [i64, i64, i64, i64, vp, vp]),
+        "mst_row_tail_form": (ci, [ci, ci, i64, P(_lib.GemmArgs), i64, vp]),
         "mst_sigmoid_bce": (ci, [ci, i64, i64, i64, vp, i64, vp, f32, ci, vp, vp, vp, i64, vp, i64, f32, ci, vp]),
         "mst_sigmoid_bce_form": (ci, [ci, i64, i64, i64, vp, i64, vp, f32, ci, vp, vp, vp, i64, vp, i64, f32, ci, vp]),
         "mst_gemm_sigmoid_bce": (ci, [P(_lib.GemmArgs), P(_lib.BceArgs), vp]),
