@@ -922,6 +922,37 @@ int mst_adam_flat_gnorm(int dtype, int64_t n, float* w, const float* grad, float
                         const mst_step_metrics* metrics, const float* sched, int64_t base, const int64_t* emb, int64_t n_emb,
                         void* wt16, const float* parts, int64_t n_parts, float max_norm, float* gstat, mst_stream_t stream);
 
+/* An exponential moving average of the weights, kept by the Adam launch itself: two entry points.
+ *
+ * mst_adam_flat_ema: mst_adam_flat_gnorm in which `parts` may be NULL too (no clipping: n_parts, max_norm and gstat are then
+ * ignored; given, they are checked as there) — with `sched` and n_emb optional as there, ONE entry point for every form of the Adam
+ * launch, advance_step = 0 — whose threads also fold each weight they have just written into ema[0..n) (fp32, 16-byte aligned,
+ * the flat offsets of `w`):
+ *   t    = step_state[0], Adam's step count after the step's increment (1-based)
+ *   d_t  = fminf(decay, (1.f + t) / (10.f + t))      fp32, t converted to fp32 first, a correctly rounded division: the usual
+ *          warm-up, so the first steps do not average in the initial weights
+ *   omd  = 1.f - d_t
+ *   e_i <- fl(fl(d_t * e_i) + fl(omd * w_i'))        w_i' the fp32 weight this thread stores: two rounded products and one
+ *          rounded sum, in this order, never contracted into an FMA (engine.ema_decay_at / engine.ema_update state the same in
+ *          np.float32; the result is theirs bit for bit)
+ * w, m, v, w16 and the transposed shadows are exactly what the launch without `ema` writes. The average follows the launch's own
+ * skip predicate: on a step the step guard, the non-finite guard or the non-finite-norm guard skips, ema stays as it was, like
+ * w, m and v. Reading t is race-free: in this launch only the bookkeeping thread ever writes step_state, and only to take the
+ * count back on a skipped step, where every thread returns before the read; on a step that counts nobody writes it (the
+ * increment is mst_step_begin's, earlier in the stream). Both ranges of a two-range fp16 step read the same t, hence the same d_t.
+ * ema non-NULL and 16-byte aligned and 0 < decay < 1 are checked before any HIP call.
+ *
+ * mst_ema_swap: ONE launch that exchanges w[i] <-> ema[i] over the bucket (16-byte loads and stores, a grid-stride loop, the
+ * up-to-three tail elements on the last workgroup) and writes w16[i] (may be NULL) from the new w[i], the cast the Adam launch
+ * writes. Contents move, pointers do not: captured graphs stay valid. Exact: two calls restore every bit of w and ema. The
+ * transposed shadows are the caller's to refresh (mst_transpose_shadows). */
+int mst_adam_flat_ema(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
+                      double beta2, float eps, float wd, float rescale, float clip, int32_t* step_state,
+                      const mst_step_metrics* metrics, const float* sched, int64_t base, const int64_t* emb, int64_t n_emb,
+                      void* wt16, const float* parts, int64_t n_parts, float max_norm, float* gstat, float* ema, float decay,
+                      mst_stream_t stream);
+int mst_ema_swap(int dtype, int64_t n, float* w, float* ema, void* w16, mst_stream_t stream);
+
 /* 16-bit shadow + transposed shadow refresh for a list of matrices.
  * desc: int64 [n_mat, 4] on device = {src_offset, dst_offset, rows, cols}; dst is [cols, ld_t] with
  * ld_t = roundup8(rows), pad columns zeroed. tiles: int64 prefix sums [n_mat+1] of 32x32 tile counts. */

@@ -3,7 +3,7 @@
 The flag set is the reference's, name for name and default for default (config.py:19-70), because
 scripts/train-vae.sh passes them; unknown flags are ignored as there (parse_known_args, :73-75). The flags
 are declared as a table. The additions (group MI355X) are all off by default: --pianoroll (attach the piano-roll ends), --dtype,
---d-causal, the training schedules and --clip-global-norm."""
+--d-causal, the training schedules, --clip-global-norm and --ema-decay."""
 import argparse
 import copy
 import inspect
@@ -71,6 +71,9 @@ _FLAGS = [
     # bound on the global L2 norm of the batch-mean gradient, applied on the device inside the captured step (engine.clip_scale); a
     # step whose norm is not finite is skipped. 0: off. Independent of the per-element clip_gradient of --optimizer-params.
     ("MI355X", ("--clip-global-norm",), dict(type=float, default=0.0)),
+    # decay of an exponential moving average of the weights, kept by the optimizer launch inside the captured step (engine.ema_update);
+    # validation, early stopping and the periodic samples then use the averaged weights, and generate.py --ema loads them. 0: off.
+    ("MI355X", ("--ema-decay",), dict(type=float, default=0.0)),
 ]
 
 

@@ -25,7 +25,7 @@ def create_toy_model_config(data):
 
 
 def create_toy_train_config(max_steps=0, **schedule):
-    """main.py:41-55; schedule: the training-schedule fields of TrainConfig (the --kl-warmup-steps ... flags) and clip_global_norm"""
+    """main.py:41-55; schedule: the training-schedule fields of TrainConfig (the --kl-warmup-steps ... flags), clip_global_norm and ema_decay"""
     return trainer.TrainConfig(batch_size=1, sampling_frequency=500, checkpoint_frequency=1000, num_checkpoints_not_improved=-1,
                                kl_loss=1.0, optimizer=trainer.OptimizerConfig(learning_rate=1e-3, optimizer="adam",
                                                                               optimizer_params="clip_gradient:1.0"),
@@ -39,7 +39,8 @@ def main_toy(context, args):
     model_folder = os.path.join(args.model_output if args.model_output != "models" else "/tmp/music-style-transfer/toy", "model")
     create_directory_if_not_present(model_folder)
     config.save(os.path.join(model_folder, "config"))
-    schedule = {k: getattr(args, k) for k in ("kl_warmup_steps", "kl_cycle_steps", "kl_free_bits", "lr_warmup_steps", "clip_global_norm")}
+    schedule = {k: getattr(args, k) for k in ("kl_warmup_steps", "kl_cycle_steps", "kl_free_bits", "lr_warmup_steps", "clip_global_norm",
+                                              "ema_decay")}
     t = trainer.Trainer(config=create_toy_train_config(args.max_steps, **schedule), context=context, model=m, sampler=None)
     t.fit(dataset=dataset, validation_dataset=dataset, model_folder=model_folder, epochs=20000 if not args.max_steps else args.max_steps)
     return t
@@ -56,7 +57,7 @@ def create_train_config(args):
                                verbose=args.verbose, dtype=args.dtype, max_steps=args.max_steps,
                                kl_warmup_steps=args.kl_warmup_steps, kl_cycle_steps=args.kl_cycle_steps,
                                kl_free_bits=args.kl_free_bits, lr_warmup_steps=args.lr_warmup_steps,
-                               clip_global_norm=args.clip_global_norm)
+                               clip_global_norm=args.clip_global_norm, ema_decay=args.ema_decay)
 
 
 def create_model_config(args, dataset):

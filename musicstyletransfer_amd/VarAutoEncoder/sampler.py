@@ -306,8 +306,10 @@ class InterpolationSampler(_GeneratorSampler):
         return files
 
 
-def load_inference_model(model_folder, context, checkpoint):
-    """sampler.py:17-38: the saved YAML configuration, a Model built from it, the checkpoint's parameters (-1: latest)"""
+def load_inference_model(model_folder, context, checkpoint, ema=False):
+    """sampler.py:17-38: the saved YAML configuration, a Model built from it, the checkpoint's parameters (-1: latest).
+    ema: the checkpoint's AVERAGED weights instead (the `ema` array a run with --ema-decay leaves in optimizer.N.npz); ValueError if the
+    checkpoint holds none"""
     from . import model, utils
     from .config import Config
     c = Config.load(os.path.join(model_folder, "config"))
@@ -317,6 +319,21 @@ def load_inference_model(model_folder, context, checkpoint):
     if checkpoint == -1:
         checkpoint = utils.get_latest_checkpoint_index(model_folder)
     utils.load_model_parameters(m, os.path.join(model_folder, "params.{}".format(checkpoint)), context)
+    if ema:
+        import numpy as np
+        import torch
+        opt = os.path.join(model_folder, "optimizer.{}.npz".format(checkpoint))
+        flat = None
+        if os.path.exists(opt):
+            with np.load(opt) as z:
+                flat = np.asarray(z["ema"], np.float32) if "ema" in z.files else None
+        if flat is None:
+            raise ValueError("checkpoint {} of {} holds no averaged weights (no `ema` array in optimizer.{}.npz): train with --ema-decay, "
+                             "or drop --ema".format(checkpoint, model_folder, checkpoint))
+        if flat.shape != (m.store.n,):
+            raise ValueError("the `ema` array of optimizer.{}.npz has {} values, the model's bucket {}".format(checkpoint, flat.size, m.store.n))
+        m.store.w.copy_(torch.from_numpy(flat))  # (the bucket's own layout, as m and v are saved)
+        m.store.refresh_shadows()
     return m
 
 

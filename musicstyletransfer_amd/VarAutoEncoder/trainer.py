@@ -8,6 +8,7 @@ side stream while the previous step ran; with several ranks the flat gradient bu
 ranges, the first one under the rest of the backward pass. All five metrics of the reference (ppl, acc, topk, kl_loss,
 total_loss) accumulate on the device and are read at log time only (the reference syncs three times per step,
 trainer.py:181-186)."""
+import contextlib
 import os
 from time import time
 
@@ -17,7 +18,7 @@ import torch
 from . import utils
 from .config import Config
 from .. import parallel
-from ..engine import check_clip, check_schedule
+from ..engine import check_clip, check_ema, check_schedule
 from ..pianoroll import PinnedBatchPipeline
 
 
@@ -39,16 +40,20 @@ class OptimizerConfig(Config):
 class TrainConfig(Config):
     """kl_warmup_steps / kl_cycle_steps / kl_free_bits / lr_warmup_steps: the training schedules (engine.schedule_values), all off at
     their defaults. clip_global_norm: bound on the global L2 norm of the gradient, applied inside the step (engine.clip_scale); 0: off.
+    ema_decay: decay of the exponential moving average of the weights the step keeps (engine.ema_update), which validation, early
+    stopping and the periodic samples then use; 0: off.
     YAML-serialisable (Config): a file written before a field existed loads with that field's default."""
 
     def __init__(self, batch_size: int, sampling_frequency: int, checkpoint_frequency: int, num_checkpoints_not_improved: int,
                  optimizer: OptimizerConfig, kl_loss: float, label_smoothing: float, negative_label_downscaling: bool,
                  verbose: bool, dtype: str = "bf16", max_steps: int = 0, kl_warmup_steps: int = 0, kl_cycle_steps: int = 0,
-                 kl_free_bits: float = 0.0, lr_warmup_steps: int = 0, clip_global_norm: float = 0.0):
+                 kl_free_bits: float = 0.0, lr_warmup_steps: int = 0, clip_global_norm: float = 0.0, ema_decay: float = 0.0):
         super().__init__()
         check_schedule(kl_warmup_steps, kl_cycle_steps, kl_free_bits, lr_warmup_steps)
         check_clip(clip_global_norm)
         self.clip_global_norm = clip_global_norm
+        check_ema(ema_decay)
+        self.ema_decay = ema_decay
         self.kl_warmup_steps, self.kl_cycle_steps = kl_warmup_steps, kl_cycle_steps
         self.kl_free_bits, self.lr_warmup_steps = kl_free_bits, lr_warmup_steps
         self.batch_size = batch_size
@@ -98,6 +103,9 @@ class Trainer:
         with torch.cuda.stream(self.stream):
             self._initialize_model()
         self._initialize_optimizers()
+        if self.ema_decay > 0:
+            with torch.cuda.stream(self.stream):
+                self.model.store.enable_ema()  # (a copy of the initial weights; a checkpoint found by fit() replaces it)
         self.stream.synchronize()
         self._graphs = {}
         self._tail_gen = 0
@@ -135,6 +143,11 @@ class Trainer:
         check_clip(self.clip_global_norm)
         if self.clip_global_norm > 0:
             self.hyper["clip_global_norm"] = self.clip_global_norm
+        # ... and the exponential moving average of the weights
+        self.ema_decay = float(getattr(self.config, "ema_decay", 0.0))
+        check_ema(self.ema_decay)
+        if self.ema_decay > 0:
+            self.hyper["ema_decay"] = self.ema_decay
         self.opt_extra = {k: v for k, v in extra.items() if k in ("beta1", "beta2", "epsilon", "wd")}
 
     # ------------------------------------------------------------------ the hot loop
@@ -169,6 +182,11 @@ class Trainer:
         for k in [k for k in self._graphs if k[0] == id(plan)]:
             del self._graphs[k]
         self.pipeline.drop(plan)
+
+    def _averaged(self):
+        """the context validation and the periodic sampler run in: the averaged weights swapped in (ParamStore.ema_weights, on the
+        trainer's stream), or nothing at all without ema_decay"""
+        return self.model.store.ema_weights() if self.ema_decay > 0 else contextlib.nullcontext()
 
     def _shard(self, batch):
         return parallel.shard_bounds(len(batch.data[1]), self.world, self.rank) if self.world > 1 else None
@@ -241,7 +259,7 @@ class Trainer:
                         return
                 if (self.sampler is not None and self.config.sampling_frequency > 0
                         and self.train_state.n_batches % self.config.sampling_frequency == 0):
-                    with torch.cuda.stream(self.stream):  # ordered behind the step that just updated the weights
+                    with torch.cuda.stream(self.stream), self._averaged():  # ordered behind the step that just updated the weights
                         self.sampler.update_parameters(self.model)
                         self.sampler.process_batch(batch, os.path.join(model_folder, "samples/step-{}".format(self.train_state.n_batches)),
                                                    dataset.num_classes())
@@ -351,12 +369,19 @@ class Trainer:
             utils.load_model_parameters(self.model, os.path.join(model_folder, "params.{}".format(latest)), self.context)
             self.train_state = utils.load_object(os.path.join(model_folder, "train_state.pkl"))
             opt = os.path.join(model_folder, "optimizer.{}.npz".format(latest))
+            averaged = False
             if os.path.exists(opt):  # Adam moments + step count (the reference does not save optimizer state)
                 st = self.model.store
                 with np.load(opt) as z:
                     st.m.copy_(torch.from_numpy(z["m"]))
                     st.v.copy_(torch.from_numpy(z["v"]))
                     st.step_state.copy_(torch.from_numpy(z["step_state"]))
+                    if self.ema_decay > 0 and "ema" in z.files:
+                        st.ema.copy_(torch.from_numpy(z["ema"]))
+                        averaged = True
+            if self.ema_decay > 0 and not averaged:  # (a run that did not average wrote it)
+                self.model.store.load_ema_numpy(None)
+                print("Checkpoint {} holds no averaged weights: the average starts from its parameters.".format(latest))
         self.stream.synchronize()
 
     def _checkpoint(self, model_folder, validation_dataset):
@@ -369,14 +394,16 @@ class Trainer:
                 utils.save_model(self.model, os.path.join(model_folder, "params.{}".format(n)))
                 utils.save_object(self.train_state, os.path.join(model_folder, "train_state.pkl"))
                 st = self.model.store
+                ema = dict(ema=st.ema.cpu().numpy()) if self.ema_decay > 0 else {}  # (params.N stays the raw weights)
                 np.savez(os.path.join(model_folder, "optimizer.{}.npz".format(n)), m=st.m.cpu().numpy(), v=st.v.cpu().numpy(),
-                         step_state=st.step_state.cpu().numpy())
+                         step_state=st.step_state.cpu().numpy(), **ema)
         self.collect_metrics(reset=True)
         if validation_dataset is None:
             return
-        for batch in validation_dataset:
-            self._step(batch, is_train=False)
-        vals = self.collect_metrics(reset=True)
+        with torch.cuda.stream(self.stream), self._averaged():  # (with ema_decay: the averaged model is what early stopping compares)
+            for batch in validation_dataset:
+                self._step(batch, is_train=False)
+            vals = self.collect_metrics(reset=True)
         loss = vals["total_loss"]
         if loss < self.train_state.best_resconstruction_loss:
             print("Loss improved from {} to {}.".format(self.train_state.best_resconstruction_loss, loss))

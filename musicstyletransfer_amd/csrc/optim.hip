@@ -6,7 +6,8 @@
 //   g   = clip(grad * rescale + wd * w, ±clip)            (clip < 0: no clipping)
 //   m   = b1*m + (1-b1)*g ;  v = b2*v + (1-b2)*g*g
 //   w  -= lr * sqrt(1-b2^t)/(1-b1^t) * m / (sqrt(v) + eps)
-// HBM-bound: 16 B/param read (w,g,m,v) + 12 B/param written (w,m,v) + 2 B/param 16-bit shadow.
+// HBM-bound: 16 B/param read (w,g,m,v) + 12 B/param written (w,m,v) + 2 B/param 16-bit shadow; in the averaging form
+// (mst_adam_flat_ema) 4 + 4 B/param more for the exponential moving average of the weights, which the same thread keeps.
 // The step counter lives on the device and is advanced by a 1-thread kernel in the same stream,
 // so a captured graph replays with the right bias correction.
 #include <math.h>
@@ -91,15 +92,55 @@ __device__ __forceinline__ float gnorm_clip_scale(float norm, float max_norm) {
   return c < 1.f ? c : 1.f;
 }
 
+// the average of mst_adam_flat_ema: the shadow bucket and the configured decay (ema == nullptr in every other form)
+struct AdamEma {
+  float* ema;
+  float decay;
+};
+
+// d_t of the average at Adam's step count t (engine.ema_decay_at states the same in np.float32): the warm-up (1 + t) / (10 + t), one
+// correctly rounded fp32 division, capped at the configured decay
+__device__ __forceinline__ float ema_decay_at(int32_t t, float decay) {
+  const float tf = (float)t;
+  return fminf(decay, (1.f + tf) / (10.f + tf));
+}
+// e <- fl(fl(d * e) + fl(omd * w)), omd = fl(1 - d): two rounded products and one rounded sum, never contracted into an FMA
+// (engine.ema_update states the same in np.float32, and the tests ask for its bits)
+__device__ __forceinline__ float ema_mix(float d, float omd, float e, float w) {
+#pragma clang fp contract(off)
+  const float a = d * e;
+  const float b = omd * w;
+  return a + b;
+}
+
+// One element of the update for the averaging form, its operations and their order stated: exactly what contraction makes of the
+// expressions in adam_flat_kernel's other instantiations (read off their ISA, main loop and tail alike; tests/test_ema_gpu.py holds the
+// two to the same bits). Those keep their expressions, so that their instructions stay what they were; the averaging form cannot: with
+// the average's products next to them its tail came out with both products of g rounded.
+//   g = fma(grad, rescale, fl(wd * w)), clipped;  m = fma(b1, m, fl((1 - b1) * g));  v = fma(b2, v, fl(fl((1 - b2) * g) * g))
+//   w = w - fl(lr_t * m) / (sqrtf(v) + eps)
+__device__ __forceinline__ void adam_elem(float& w, float grad, float& m, float& v, float rescale, float wd, float clip, float beta1,
+                                          float beta2, float lr_t, float eps) {
+#pragma clang fp contract(off)
+  float g = fmaf(grad, rescale, wd * w);
+  if (clip >= 0.f) g = fminf(fmaxf(g, -clip), clip);
+  m = fmaf(beta1, m, (1.f - beta1) * g);
+  v = fmaf(beta2, v, ((1.f - beta2) * g) * g);
+  w = w - (lr_t * m) / (sqrtf(v) + eps);
+}
+
 // SCHED (mst_adam_flat_sched): the bookkeeping takes the KL weight and the free bits from the device schedule block
 // GNORM (mst_adam_flat_gnorm): the gradient is clipped by its global L2 norm, and a step whose norm is not finite is skipped
-template <typename T, bool SCHED, bool GNORM>
+// EMA (mst_adam_flat_ema): every thread folds the weight it has just written into the exponential moving average em.ema. t is read
+// from state[0] behind the guards: only the bookkeeping thread of this launch ever writes that word, and only on a step the guards
+// skip — where every thread has returned before this read — so on a step that counts nobody writes it while it is read
+template <typename T, bool SCHED, bool GNORM, bool EMA = false>
 __global__ __launch_bounds__(256) void adam_flat_kernel(int64_t n, float* __restrict__ w, const float* __restrict__ grad,
                                                         float* __restrict__ m, float* __restrict__ v,
                                                         T* __restrict__ w16, const int32_t* __restrict__ state,
                                                         float beta1, float beta2, float eps, float wd, float rescale,
                                                         float clip, mst_step_metrics mt, int32_t* state_rw, AdamEmb emb,
-                                                        const float* __restrict__ sched, AdamGnorm gn) {
+                                                        const float* __restrict__ sched, AdamGnorm gn, AdamEma em) {
   __shared__ float red[2][4];
   f32x4 gp;
   if constexpr (GNORM) gp = reinterpret_cast<const f32x4*>(gn.parts)[threadIdx.x & 63];  // (asked for ahead of the guards' loads)
@@ -147,20 +188,35 @@ __global__ __launch_bounds__(256) void adam_flat_kernel(int64_t n, float* __rest
     else loss_combine_wg(mt.B, mt.recon, mt.kl, mt.kl_weight, mt.total, mt.metric, red);
   }
   const float lr_t = reinterpret_cast<const float*>(state)[1];
+  float ema_d = 0.f, ema_omd = 0.f;
+  if constexpr (EMA) {
+    ema_d = ema_decay_at(state[0], em.decay);
+    ema_omd = 1.f - ema_d;
+  }
   const int64_t nvec = n / 4;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
     f32x4 wv = reinterpret_cast<const f32x4*>(w)[i];
     f32x4 gv = reinterpret_cast<const f32x4*>(grad)[i];
     f32x4 mv = reinterpret_cast<const f32x4*>(m)[i];
     f32x4 vv = reinterpret_cast<const f32x4*>(v)[i];
+    f32x4 ev;
+    if constexpr (EMA) ev = reinterpret_cast<const f32x4*>(em.ema)[i];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      float g = gv[e] * rescale + wd * wv[e];
-      if (clip >= 0.f) g = fminf(fmaxf(g, -clip), clip);
-      mv[e] = beta1 * mv[e] + (1.f - beta1) * g;
-      vv[e] = beta2 * vv[e] + (1.f - beta2) * g * g;
-      wv[e] = wv[e] - lr_t * mv[e] / (sqrtf(vv[e]) + eps);
+      if constexpr (EMA) {
+        float ww = wv[e], mm = mv[e], v2 = vv[e];
+        adam_elem(ww, gv[e], mm, v2, rescale, wd, clip, beta1, beta2, lr_t, eps);
+        wv[e] = ww; mv[e] = mm; vv[e] = v2;
+      } else {
+        float g = gv[e] * rescale + wd * wv[e];
+        if (clip >= 0.f) g = fminf(fmaxf(g, -clip), clip);
+        mv[e] = beta1 * mv[e] + (1.f - beta1) * g;
+        vv[e] = beta2 * vv[e] + (1.f - beta2) * g * g;
+        wv[e] = wv[e] - lr_t * mv[e] / (sqrtf(vv[e]) + eps);
+      }
+      if constexpr (EMA) ev[e] = ema_mix(ema_d, ema_omd, ev[e], wv[e]);
     }
+    if constexpr (EMA) reinterpret_cast<f32x4*>(em.ema)[i] = ev;
     reinterpret_cast<f32x4*>(w)[i] = wv;
     reinterpret_cast<f32x4*>(m)[i] = mv;
     reinterpret_cast<f32x4*>(v)[i] = vv;
@@ -178,12 +234,19 @@ __global__ __launch_bounds__(256) void adam_flat_kernel(int64_t n, float* __rest
   // tail (n not a multiple of 4)
   if (blockIdx.x == 0) {
     for (int64_t i = nvec * 4 + threadIdx.x; i < n; i += 256) {
-      float g = grad[i] * rescale + wd * w[i];
-      if (clip >= 0.f) g = fminf(fmaxf(g, -clip), clip);
-      const float mm = beta1 * m[i] + (1.f - beta1) * g;
-      const float vv = beta2 * v[i] + (1.f - beta2) * g * g;
-      const float ww = w[i] - lr_t * mm / (sqrtf(vv) + eps);
+      float ww, mm, vv;
+      if constexpr (EMA) {
+        ww = w[i]; mm = m[i]; vv = v[i];
+        adam_elem(ww, grad[i], mm, vv, rescale, wd, clip, beta1, beta2, lr_t, eps);
+      } else {
+        float g = grad[i] * rescale + wd * w[i];
+        if (clip >= 0.f) g = fminf(fmaxf(g, -clip), clip);
+        mm = beta1 * m[i] + (1.f - beta1) * g;
+        vv = beta2 * v[i] + (1.f - beta2) * g * g;
+        ww = w[i] - lr_t * mm / (sqrtf(vv) + eps);
+      }
       m[i] = mm; v[i] = vv; w[i] = ww;
+      if constexpr (EMA) em.ema[i] = ema_mix(ema_d, ema_omd, em.ema[i], ww);
       if (w16) w16[i] = from_f32<T>(ww);
       adam_emb_store<T>(emb, i, ww);
     }
@@ -230,7 +293,7 @@ static unsigned grid_for(int64_t n, int per_thread) {
 static int adam_flat_impl(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr,
                           double beta1, double beta2, float eps, float wd, float rescale, float clip,
                           int32_t* step_state, int advance_step, const mst_step_metrics* metrics, const AdamEmb& emb, const float* sched,
-                          mst_stream_t stream, const AdamGnorm* gnorm = nullptr) {
+                          mst_stream_t stream, const AdamGnorm* gnorm = nullptr, const AdamEma* ema = nullptr) {
   MST_CHECK_ARG(n > 0 && w && grad && m && v && step_state, "mst_adam_flat: bad argument");
   mst_step_metrics mt = {};
   if (metrics) {
@@ -248,18 +311,33 @@ static int adam_flat_impl(int dtype, int64_t n, float* w, const float* grad, flo
   return dispatch_act(dtype, [&](auto tag) -> int {
     typedef decltype(tag) T;
     const AdamGnorm gn = gnorm ? *gnorm : AdamGnorm{};
-    if (gnorm && sched)
+    const AdamEma em = ema ? *ema : AdamEma{};
+    if (ema) {  // (the averaging form: the same four, with the fourth switch)
+      const dim3 grid(grid_for(n, 4));
+      if (gnorm && sched)
+        hipLaunchKernelGGL((adam_flat_kernel<T, true, true, true>), grid, dim3(256), 0, s, n, w, grad, m, v, (T*)w16, step_state,
+                           (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, sched, gn, em);
+      else if (gnorm)
+        hipLaunchKernelGGL((adam_flat_kernel<T, false, true, true>), grid, dim3(256), 0, s, n, w, grad, m, v, (T*)w16, step_state,
+                           (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, (const float*)nullptr, gn, em);
+      else if (sched)
+        hipLaunchKernelGGL((adam_flat_kernel<T, true, false, true>), grid, dim3(256), 0, s, n, w, grad, m, v, (T*)w16, step_state,
+                           (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, sched, gn, em);
+      else
+        hipLaunchKernelGGL((adam_flat_kernel<T, false, false, true>), grid, dim3(256), 0, s, n, w, grad, m, v, (T*)w16, step_state,
+                           (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, (const float*)nullptr, gn, em);
+    } else if (gnorm && sched)
       hipLaunchKernelGGL((adam_flat_kernel<T, true, true>), dim3(grid_for(n, 4)), dim3(256), 0, s, n, w, grad, m, v, (T*)w16, step_state,
-                         (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, sched, gn);
+                         (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, sched, gn, em);
     else if (gnorm)
       hipLaunchKernelGGL((adam_flat_kernel<T, false, true>), dim3(grid_for(n, 4)), dim3(256), 0, s, n, w, grad, m, v, (T*)w16, step_state,
-                         (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, (const float*)nullptr, gn);
+                         (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, (const float*)nullptr, gn, em);
     else if (sched)
       hipLaunchKernelGGL((adam_flat_kernel<T, true, false>), dim3(grid_for(n, 4)), dim3(256), 0, s, n, w, grad, m, v, (T*)w16, step_state,
-                         (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, sched, gn);
+                         (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, sched, gn, em);
     else
       hipLaunchKernelGGL((adam_flat_kernel<T, false, false>), dim3(grid_for(n, 4)), dim3(256), 0, s, n, w, grad, m, v, (T*)w16, step_state,
-                         (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, (const float*)nullptr, gn);
+                         (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, (const float*)nullptr, gn, em);
     MST_CHECK_LAUNCH("adam_flat_kernel");
     return MST_OK;
   });
@@ -284,7 +362,7 @@ extern "C" int mst_adam_flat_sched(int dtype, int64_t n, float* w, const float* 
 static int adam_flat_emb_impl(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
                               double beta2, float eps, float wd, float rescale, float clip, int32_t* step_state,
                               const mst_step_metrics* metrics, const float* sched, int64_t base, const int64_t* emb, int64_t n_emb,
-                              void* wt16, mst_stream_t stream, const AdamGnorm* gnorm = nullptr) {
+                              void* wt16, mst_stream_t stream, const AdamGnorm* gnorm = nullptr, const AdamEma* ema = nullptr) {
   MST_CHECK_ARG(n_emb >= 0 && n_emb <= 2 && (n_emb == 0 || (emb && wt16)) && base >= 0, "mst_adam_flat_emb: up to two matrices, with their table and wt16");
   AdamEmb e = {};
   for (int j = 0; j < (int)n_emb; ++j) {
@@ -295,7 +373,7 @@ static int adam_flat_emb_impl(int dtype, int64_t n, float* w, const float* grad,
     ++e.n;
   }
   e.wt16 = wt16;
-  return adam_flat_impl(dtype, n, w, grad, m, v, w16, lr, beta1, beta2, eps, wd, rescale, clip, step_state, 0, metrics, e, sched, stream, gnorm);
+  return adam_flat_impl(dtype, n, w, grad, m, v, w16, lr, beta1, beta2, eps, wd, rescale, clip, step_state, 0, metrics, e, sched, stream, gnorm, ema);
 }
 
 extern "C" int mst_adam_flat_emb(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
@@ -326,6 +404,65 @@ extern "C" int mst_adam_flat_gnorm(int dtype, int64_t n, float* w, const float* 
   const AdamGnorm gn = {parts, max_norm, gstat};
   return adam_flat_emb_impl(dtype, n, w, grad, m, v, w16, lr, beta1, beta2, eps, wd, rescale, clip, step_state, metrics, sched, base, emb, n_emb,
                             wt16, stream, &gn);
+}
+
+extern "C" int mst_adam_flat_ema(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
+                                 double beta2, float eps, float wd, float rescale, float clip, int32_t* step_state,
+                                 const mst_step_metrics* metrics, const float* sched, int64_t base, const int64_t* emb, int64_t n_emb,
+                                 void* wt16, const float* parts, int64_t n_parts, float max_norm, float* gstat, float* ema, float decay,
+                                 mst_stream_t stream) {
+  MST_CHECK_ARG(ema != nullptr && (uintptr_t)ema % 16 == 0, "mst_adam_flat_ema: ema must be given and 16-byte aligned");
+  MST_CHECK_ARG(decay > 0.f && decay < 1.f, "mst_adam_flat_ema: decay must lie in (0, 1)");
+  const AdamEma em = {ema, decay};
+  if (!parts)  // (no clipping: n_parts, max_norm and gstat are ignored)
+    return adam_flat_emb_impl(dtype, n, w, grad, m, v, w16, lr, beta1, beta2, eps, wd, rescale, clip, step_state, metrics, sched, base, emb,
+                              n_emb, wt16, stream, nullptr, &em);
+  MST_CHECK_ARG((uintptr_t)parts % 16 == 0, "mst_adam_flat_ema: parts must be 16-byte aligned");
+  MST_CHECK_ARG(n_parts == kGnormParts, "mst_adam_flat_ema: n_parts must be mst_grad_sumsq_parts() = %d", kGnormParts);
+  MST_CHECK_ARG(max_norm > 0.f && max_norm <= 3.0e38f, "mst_adam_flat_ema: max_norm must be positive and finite");
+  const AdamGnorm gn = {parts, max_norm, gstat};
+  return adam_flat_emb_impl(dtype, n, w, grad, m, v, w16, lr, beta1, beta2, eps, wd, rescale, clip, step_state, metrics, sched, base, emb, n_emb,
+                            wt16, stream, &gn, &em);
+}
+
+// w[i] <-> ema[i] over the flat bucket, w16[i] from the new w[i] (the cast the Adam launch writes): 16-byte loads and stores over a
+// grid-stride loop, the up-to-three tail elements on the last workgroup (as grad_sumsq_kernel takes them)
+template <typename T>
+__global__ __launch_bounds__(256) void ema_swap_kernel(int64_t n, float* __restrict__ w, float* __restrict__ ema, T* __restrict__ w16) {
+  const int64_t nvec = n / 4;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
+    const f32x4 wv = reinterpret_cast<const f32x4*>(w)[i];
+    const f32x4 ev = reinterpret_cast<const f32x4*>(ema)[i];
+    reinterpret_cast<f32x4*>(w)[i] = ev;
+    reinterpret_cast<f32x4*>(ema)[i] = wv;
+    if (w16) {
+      u32x2 o;
+      o[0] = (uint32_t)f32_to_bits<T>(ev[0]) | ((uint32_t)f32_to_bits<T>(ev[1]) << 16);
+      o[1] = (uint32_t)f32_to_bits<T>(ev[2]) | ((uint32_t)f32_to_bits<T>(ev[3]) << 16);
+      reinterpret_cast<u32x2*>(w16)[i] = o;
+    }
+  }
+  if (blockIdx.x == gridDim.x - 1) {
+    const int64_t k = nvec * 4 + threadIdx.x;
+    if (k < n) {
+      const float ww = w[k], ee = ema[k];
+      w[k] = ee;
+      ema[k] = ww;
+      if (w16) w16[k] = from_f32<T>(ee);
+    }
+  }
+}
+
+extern "C" int mst_ema_swap(int dtype, int64_t n, float* w, float* ema, void* w16, mst_stream_t stream) {
+  MST_CHECK_ARG(n > 0 && w && ema && w != ema, "mst_ema_swap: bad argument (n > 0, w and ema given and distinct)");
+  MST_CHECK_ARG(((uintptr_t)w % 16 == 0) && ((uintptr_t)ema % 16 == 0) && ((uintptr_t)w16 % 8 == 0),
+                "mst_ema_swap: w and ema must be 16-byte aligned, w16 8-byte aligned");
+  return dispatch_act(dtype, [&](auto tag) -> int {
+    typedef decltype(tag) T;
+    hipLaunchKernelGGL((ema_swap_kernel<T>), dim3(grid_for(n, 4)), dim3(256), 0, (hipStream_t)stream, n, w, ema, (T*)w16);
+    MST_CHECK_LAUNCH("ema_swap_kernel");
+    return MST_OK;
+  });
 }
 
 // sums of squares of the rescaled flat gradient for mst_adam_flat_gnorm: workgroup j leaves parts[j]. Per thread an fp32 chain over

@@ -15,6 +15,7 @@ Layout in HBM
 There is no torch autograd, no torch operator and no CPU fallback on this path: backward is written
 out by hand below, mirroring the forward line by line.
 """
+import contextlib
 import math
 import os
 import warnings
@@ -218,6 +219,10 @@ class ParamStore:
         self.sched = self._metric_buf[8:12]
         self.gstat = self._metric_buf[12:20]
         self._grad_parts = None
+        # the exponential moving average of the weights (enable_ema): a second fp32 bucket at w's offsets, kept by the Adam launches of
+        # a plan with ema_decay. None for a store that does not average: it allocates what it always did
+        self.ema = None
+        self.ema_swapped = False      # True while w holds the averaged weights (swap_ema / ema_weights)
         self.nonfinite_steps = 0      # steps skipped for a non-finite loss since the store was made (read_metrics adds them up)
         self.tail_fused = os.environ.get("MST_ROW_TAIL", "1") != "0"  # False: the five-launch form of the position-0 tails
         self.tail_checked = False     # row_tail_selfcheck() ran for this store
@@ -243,6 +248,33 @@ class ParamStore:
         if self._grad_parts is None:
             self._grad_parts = torch.zeros(o.grad_sumsq_parts(), dtype=torch.float32, device=self.device)
         return self._grad_parts
+
+    def enable_ema(self):
+        """the average, made for the first plan (or trainer) that asks: a copy of w as it is now — at allocation time, never inside a
+        capture — and never freed or moved: captured graphs keep the pointer"""
+        if self.ema is None:
+            self.ema = self.w.clone()
+        return self.ema
+
+    def swap_ema(self):
+        """exchange the contents of w and ema in one launch (mst_ema_swap, which also writes w16 from the new w), then the shadow
+        refresh, so that every kernel consumes what a store loaded with those weights would. Contents move, pointers do not: every
+        captured graph stays valid. Exact: a second call puts back every bit."""
+        if self.ema is None:
+            raise RuntimeError("this store keeps no average of its weights (StepPlan(ema_decay=...) / enable_ema())")
+        o.ema_swap(self.w, self.ema, self.w16)
+        self.refresh_shadows()
+        self.ema_swapped = not self.ema_swapped
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """with store.ema_weights(): ... — the averaged weights swapped in for validation, sampling or a forward pass, and the raw
+        iterate back on exit (also after an exception). No training step may run inside: it would update the average as the weights."""
+        self.swap_ema()
+        try:
+            yield self
+        finally:
+            self.swap_ema()
 
     def rng_state_inference(self):
         """the RNG state inference-mode forward passes advance (eps of Model.__call__ when none is given): never the
@@ -420,6 +452,9 @@ class ParamStore:
         self.refresh_shadows()
 
     def to_numpy(self, which="w"):
+        """name -> host copy of the tensor's part of a flat fp32 bucket: 'w', 'g', 'm', 'v', or 'ema' (a store that averages)"""
+        if which == "ema" and self.ema is None:
+            raise RuntimeError("this store keeps no average of its weights (StepPlan(ema_decay=...) / enable_ema())")
         host = getattr(self, which).detach().cpu().numpy()
         return OrderedDict((n, host[self.offsets[n]: self.offsets[n] + int(np.prod(s))].reshape(s).copy())
                            for n, s in self.shapes.items())
@@ -445,6 +480,19 @@ class ParamStore:
             s = self.shapes[n]
             w[n] = w16[self.offsets[n]: self.offsets[n] + int(np.prod(s))].reshape(s).copy()
         return w
+
+    def load_ema_numpy(self, params_np=None):
+        """set the average from name -> array (a checkpoint's), or to a copy of w (None)"""
+        self.enable_ema()
+        if params_np is None:
+            self.ema.copy_(self.w)
+            return
+        host = np.zeros(self.n, np.float32)
+        for name, shape in self.shapes.items():
+            a = np.asarray(params_np[name], np.float32)
+            assert tuple(a.shape) == tuple(shape), f"{name}: expected {shape}, got {a.shape}"
+            host[self.offsets[name]: self.offsets[name] + a.size] = a.reshape(-1)
+        self.ema.copy_(torch.from_numpy(host))
 
     def refresh_shadows(self):
         o.cast_to_act(self.w, self.w16)
@@ -701,7 +749,8 @@ def row_tail_selfcheck(store, B=64, S=2):
 # sched — the latent block's backward launch and the step-closing bookkeeping in their scheduled forms (training schedules on).
 # dec_tail — the last decoder layer's row-wise block, the loss launch and the block's backward as ONE launch (a training step with gradient).
 # gnorm — the optimizer clips by the global gradient norm: one mst_grad_sumsq launch ahead of the Adam launches in their gnorm form.
-Forms = namedtuple("Forms", "tails riders shadows fuse_bce bce_dgrad skip_row0 cls_fold ffn_e ffn_d ln_bwd_e ln_bwd_d sched dec_tail gnorm")
+# ema — the Adam launches in their averaging form (mst_adam_flat_ema): the same launches in the same order, none added.
+Forms = namedtuple("Forms", "tails riders shadows fuse_bce bce_dgrad skip_row0 cls_fold ffn_e ffn_d ln_bwd_e ln_bwd_d sched dec_tail gnorm ema")
 
 
 def check_schedule(kl_warmup_steps=0, kl_cycle_steps=0, kl_free_bits=0.0, lr_warmup_steps=0):
@@ -731,6 +780,31 @@ def clip_scale(norm, max_norm):
     return c if c < np.float32(1) else np.float32(1)
 
 
+def check_ema(ema_decay=0.0):
+    """ema_decay: 0 (off) or the decay of the weights' exponential moving average, in (0, 1); raises ValueError otherwise (a NaN too)"""
+    if not (0 <= ema_decay < 1):
+        raise ValueError(f"ema_decay must be 0 (off) or lie in (0, 1), not {ema_decay!r}")
+
+
+def ema_decay_at(t, decay):
+    """d_t, the decay the average applies at training step t (Adam's step count after the step's increment, 1-based) — the rule as the
+    device evaluates it (mst_adam_flat_ema), stated once for the host in np.float32 arithmetic: min(decay, (1 + t) / (10 + t)), the usual
+    warm-up, so that the first steps do not average in the initial weights"""
+    tf = np.float32(t)
+    d = (np.float32(1) + tf) / (np.float32(10) + tf)
+    return min(np.float32(decay), d)
+
+
+def ema_update(e, w_new, d):
+    """the average after a step: fl(fl(d * e) + fl((1 - d) * w_new)) in np.float32 — two rounded products and one rounded sum, in this
+    order and never fused, which is what mst_adam_flat_ema computes (include/mst_hip.h) bit for bit. e, w_new: fp32 arrays (or scalars)"""
+    d = np.float32(d)
+    omd = np.float32(1) - d
+    a = d * np.asarray(e, np.float32)
+    b = omd * np.asarray(w_new, np.float32)
+    return a + b
+
+
 def schedule_values(t, kl_weight=1.0, kl_warmup_steps=0, kl_cycle_steps=0, lr_warmup_steps=0):
     """(beta_t, f_lr) of training step t (Adam's step count after the step's increment, 1-based) — the formulas the device evaluates
     (step_begin.hpp), stated once for the host. Double arithmetic; beta_t is rounded once, to fp32, and returned as that value:
@@ -749,11 +823,13 @@ class StepPlan:
     def __init__(self, store, B, T, lr=3e-4, clip_gradient=1.0, kl_weight=1.0, label_smoothing=0.0,
                  negative_label_downscaling=False, global_batch=None, gscale=None, want_probs=False, seed=0,
                  internal_eps=False, optimizer_params=None, sample_offset=0, site_base=0,
-                 kl_warmup_steps=0, kl_cycle_steps=0, kl_free_bits=0.0, lr_warmup_steps=0, clip_global_norm=0.0):
+                 kl_warmup_steps=0, kl_cycle_steps=0, kl_free_bits=0.0, lr_warmup_steps=0, clip_global_norm=0.0, ema_decay=0.0):
         """kl_warmup_steps / kl_cycle_steps / kl_free_bits / lr_warmup_steps: the training schedules (schedule_values),
         evaluated on the device from Adam's step count. All zero (the default): the plain launches with their constants.
         clip_global_norm: bound on the global L2 norm of the batch-mean gradient, applied on the device ahead of Adam (clip_scale;
         DESIGN §12); a step whose norm is not finite is skipped. 0 (the default): off, the optimizer launches as they were.
+        ema_decay: decay of an exponential moving average of the weights kept by the Adam launch(es) themselves in store.ema (ema_decay_at,
+        ema_update). 0 (the default): off, the optimizer launches as they were.
         sample_offset: index of this plan's first sample in the global batch (data parallel: rank * B) — the in-graph eps
         is drawn per GLOBAL sample index, so the result does not depend on the sharding.
         site_base: added to every dropout site id (data parallel: a different value per rank gives every rank its own
@@ -769,6 +845,10 @@ class StepPlan:
         check_clip(clip_global_norm)
         self.clip_global_norm = float(clip_global_norm)
         self.grad_parts = store.grad_parts() if self.clip_global_norm > 0 else None  # (allocated here, never inside a capture)
+        check_ema(ema_decay)
+        self.ema_decay = float(ema_decay)
+        if self.ema_decay > 0:
+            store.enable_ema()  # (a copy of w, made here, never inside a capture)
         self.ls, self.nld = label_smoothing, negative_label_downscaling
         self.global_batch = global_batch or B
         self.sample_offset, self.site_base = int(sample_offset), int(site_base)
@@ -983,7 +1063,9 @@ class StepPlan:
             # validation step keeps the constants: its objective must not move with the schedule)
             sched=self.scheduled,
             # clipping by the global gradient norm: a sum-of-squares launch ahead of Adam, the Adam launches in their gnorm form
-            gnorm=self.clip_global_norm > 0)
+            gnorm=self.clip_global_norm > 0,
+            # the exponential moving average of the weights: the Adam launches in their averaging form
+            ema=self.ema_decay > 0)
 
     def _guard(self):
         """step guard of the launches that close a step (optimizer / loss_combine): the barrier counters of the one-launch
@@ -1495,13 +1577,15 @@ class StepPlan:
         # Off: no extra keyword, the calls as they were
         gn = ((lambda a: dict(gnorm=dict(parts=self.grad_parts, max_norm=self.clip_global_norm, gstat=st.gstat if a == 0 else None)))
               if self.forms.gnorm else (lambda a: {}))
+        # the average: each Adam launch folds the weights of its own range into the same range of store.ema. Off: no extra keyword
+        av = (lambda a, b: dict(ema=dict(buf=st.ema[a:b], decay=self.ema_decay))) if self.forms.ema else (lambda a, b: {})
         if self.gscale == self.gscale_enc:
             r = 1.0 / (self.global_batch * self.gscale)
             if self.forms.gnorm:
                 o.grad_sumsq(st.g, 0, r, r, self.grad_parts)
             o.adam_flat(st.w, st.g, st.m, st.v, st.w16, st.step_state, lr=self.lr,
                         rescale=r, clip=clip, advance_step=False, metrics=mt, emb=emb(0),
-                        sched=sched, **gn(0), **self.opt)
+                        sched=sched, **gn(0), **av(0, st.n), **self.opt)
         else:
             # encoder.* tensors come first in the flat buffers; everything from decoder.latent2hid on is decoder-side.
             # NOTE the latent_proj gradients are produced by latent_bwd_vec at the encoder-side scale.
@@ -1512,7 +1596,8 @@ class StepPlan:
             for a, b, gs, adv in rng:
                 o.adam_flat(st.w[a:b], st.g[a:b], st.m[a:b], st.v[a:b], st.w16[a:b], st.step_state, lr=self.lr,
                             rescale=1.0 / (self.global_batch * gs), clip=clip, advance_step=adv,
-                            metrics=mt if a == 0 else (guard or None), emb=emb(a), sched=sched if a == 0 else None, **gn(a), **self.opt)
+                            metrics=mt if a == 0 else (guard or None), emb=emb(a), sched=sched if a == 0 else None, **gn(a),
+                            **av(a, b), **self.opt)
         if not deferred:  # (deferred: the next step's first launch rebuilds them, forward())
             o.transpose_shadows(st.w, st.wt16, st.t_desc, st.t_prefix, len(st.t_specs), st.t_tiles)
 

@@ -327,6 +327,7 @@ def build_parser():
                                 description="Generate .mid files from the latent space of a trained model.")
     p.add_argument("--model-output", required=True, help="the model folder of the training run (config + params.N)")
     p.add_argument("--checkpoint", type=int, default=-1, help="checkpoint index (-1: the latest)")
+    p.add_argument("--ema", action="store_true", help="decode with the checkpoint's averaged weights (a run trained with --ema-decay)")
     p.add_argument("--mode", required=True, choices=MODES)
     src = p.add_mutually_exclusive_group()
     src.add_argument("--data", default=None, help="MIDI folder (one sub-folder per class); the first batch is used")
@@ -372,7 +373,12 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     from .VarAutoEncoder.sampler import load_inference_model
     from .VarAutoEncoder.utils import gpu
-    model = load_inference_model(args.model_output, gpu(args.device), args.checkpoint)
+    try:
+        model = load_inference_model(args.model_output, gpu(args.device), args.checkpoint, ema=args.ema)
+    except ValueError as e:
+        if not args.ema:
+            raise
+        raise SystemExit("--ema: {}".format(e))
     cfg = model.engine_config
     gen = LatentGenerator(model, seed=args.seed, temperature=args.temperature, decoder=args.decoder, beam_size=args.beam_size,
                           max_rows=args.max_rows, sample_temperature=args.sample_temperature, top_k=args.top_k, top_p=args.top_p)

@@ -849,17 +849,32 @@ def loss_combine(recon, kl, kl_weight, total=None, metric_acc=None, guard=None):
 
 # --------------------------------------------------------------------------- optimizer / shadows
 def adam_flat(w, grad, m, v, w16, step_state, lr, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.0, rescale=1.0, clip=-1.0,
-              advance_step=True, metrics=None, emb=None, sched=None, gnorm=None):
+              advance_step=True, metrics=None, emb=None, sched=None, gnorm=None, ema=None):
     """metrics: dict(recon, kl, kl_weight, total, metric) -> loss_combine's bookkeeping runs in this launch;
     + status / expect: the step guard (_step_metrics).
     sched: the device schedule block of step_begin {beta_t, tau, ...} — the bookkeeping charges total = recon + beta_t * max(kl - tau, 0)
     instead of recon + kl_weight * kl (mst_adam_flat_sched / mst_adam_flat_emb_sched; the step count is step_begin's: no advance_step)
     gnorm: dict(parts, max_norm[, gstat]) — clipping by the global norm grad_sumsq() left in `parts`, and the skip of a step whose norm
-    is not finite (mst_adam_flat_gnorm, which takes emb and sched or neither; gstat: on the launch that carries the bookkeeping)"""
+    is not finite (mst_adam_flat_gnorm, which takes emb and sched or neither; gstat: on the launch that carries the bookkeeping)
+    ema: dict(buf, decay) — the launch in its averaging form (mst_adam_flat_ema, which takes emb, sched and gnorm or none of them): buf, the
+    fp32 average at w's offsets, takes in every weight the launch writes (engine.ema_update at engine.ema_decay_at of the step count)"""
     mt = _step_metrics(metrics) if metrics is not None else None
     if sched is not None:
         assert not advance_step and sched.dtype == torch.float32 and sched.numel() >= 4
     block = () if sched is None else (ptr(sched),)
+    if ema is not None:
+        buf = ema["buf"]
+        assert not advance_step and buf.dtype == torch.float32 and buf.numel() == w.numel()
+        parts, gstat = (gnorm["parts"], gnorm.get("gstat")) if gnorm is not None else (None, None)
+        assert parts is None or parts.dtype == torch.float32
+        assert gstat is None or (gstat.dtype == torch.float32 and gstat.numel() >= 6)
+        flat = [int(x) for spec in emb["specs"] for x in spec] if emb is not None else []
+        call("mst_adam_flat_ema", dt(w16), w.numel(), ptr(w), ptr(grad), ptr(m), ptr(v), ptr(w16), lr, beta1, beta2, eps, wd, rescale, clip,
+             ptr(step_state), C.byref(mt) if mt is not None else None, ptr(sched), emb.get("base", 0) if emb is not None else 0,
+             (_lib.c_i64 * len(flat))(*flat) if flat else None, len(flat) // 4, ptr(emb["wt16"]) if emb is not None else None,
+             ptr(parts), parts.numel() if parts is not None else 0, gnorm["max_norm"] if gnorm is not None else 0.0, ptr(gstat),
+             ptr(buf), ema["decay"], stream())
+        return
     if gnorm is not None:
         assert not advance_step and gnorm["parts"].dtype == torch.float32
         gstat = gnorm.get("gstat")
@@ -895,6 +910,12 @@ def grad_sumsq(grad, cut, rescale_lo, rescale_hi, parts):
     fixed order (mst_grad_sumsq): what adam_flat(gnorm=) clips by"""
     assert grad.dtype == parts.dtype == torch.float32 and parts.numel() == grad_sumsq_parts()
     call("mst_grad_sumsq", grad.numel(), ptr(grad), int(cut), rescale_lo, rescale_hi, ptr(parts), stream())
+
+
+def ema_swap(w, ema, w16):
+    """w <-> ema over the flat bucket in one launch, w16 = the 16-bit cast of the new w (mst_ema_swap); two calls are the identity"""
+    assert w.dtype == ema.dtype == torch.float32 and w.numel() == ema.numel() == w16.numel()
+    call("mst_ema_swap", dt(w16), w.numel(), ptr(w), ptr(ema), ptr(w16), stream())
 
 
 def transpose_shadows(w, wt16, desc, tile_prefix, n_mat, total_tiles):

@@ -3,6 +3,7 @@
 # class, from one encode. Other modes: --mode prior|posterior|interpolate|blend (python -m ...generate --help); whatever the caller
 # passes in "$@" is appended (e.g. --mode interpolate --pair 0 3 --steps 9 --decoder greedy). The draw of --decoder sampling is the raw
 # softmax as set below; flags in "$@" come later and win, e.g. scripts/generate-vae.sh --sample-temperature 0.9 --top-k 40 --top-p 0.9.
+# --ema (also through "$@") decodes with the checkpoint's averaged weights, for a model trained with --ema-decay.
 cd "$(dirname "$0")/.." || exit 1
 
 python -m music_style_transfer.VarAutoEncoder.generate \
