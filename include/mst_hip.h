@@ -404,6 +404,17 @@ int mst_attn_keysoftmax_bwd(int dtype, int64_t B, int64_t S, int64_t H, int64_t 
                                                zeros — results are bit-identical to the dense computation; the
                                                streaming kernels read dout in full, so the rows must really be zero */,
                             mst_stream_t stream);
+/* The layer's W_proj INPUT GRADIENT and its attention backward in one call, the mirror of mst_attn_qkv_fwd:
+ * dO = dproj wt^T with dproj [B*S, ld_dproj] the gradient behind the projection and wt [D, ld_wt] the TRANSPOSED 16-bit weights
+ * (row c = column c of dO, contiguous over the contraction; D = H * dh), then mst_attn_keysoftmax_bwd on that dO (dense). Where
+ * mst_attn_bwd_form reports form[7] = 1 every (batch, head) workgroup forms its own [S, dh] tile of dO INSIDE the resident launch,
+ * with the arithmetic of mst_gemm_nt (same instruction, same K order, one rounding): dqkv and delta are bit-identical to the two
+ * calls. dout_out (may be null there) then also receives dO, the bits mst_gemm_nt stores. Other shapes run mst_gemm_nt into
+ * dout_out (required) followed by the launches of mst_attn_keysoftmax_bwd. */
+int mst_attn_proj_bwd(int dtype, int64_t B, int64_t S, int64_t H, int64_t dh, const void* qkv, int64_t ld_qkv, int64_t k_off,
+                      int64_t q_off, int64_t v_off, const uint8_t* keymask, const float* lse, const void* dproj, int64_t ld_dproj,
+                      const void* wt, int64_t ld_wt, void* dout_out, int64_t ld_dout, void* dqkv, int64_t ld_dqkv, float* delta,
+                      mst_stream_t stream);
 
 /* What mst_attn_keysoftmax_fwd (fused = 0) or mst_attn_qkv_fwd (fused = 1; ld_x and ld_w are looked at then only) launches for these
  * arguments, and what mst_attn_keysoftmax_bwd launches: decided on the host from the shape alone (and the MST_ATTN_PATH=stream
@@ -430,6 +441,9 @@ int mst_attn_keysoftmax_bwd(int dtype, int64_t B, int64_t S, int64_t H, int64_t 
  *   form[4]  1 when the last row of a 32 n + 1 sequence is handled apart (head size 16, dense, resident)
  *   form[5]  key chunks of the chunked dQ launch (path 1: 1, 2 or 4; else 0)
  *   form[6]  waves per workgroup of the chunked dQ launch (path 1: 8; else 0)
+ *   form[7]  1 when mst_attn_proj_bwd forms dO inside the resident launch for this shape (path 0, dense, head sizes 16 and 32, a wave
+ *            per 32-row owner block, D a multiple of 64, two workgroups' LDS per CU), 0 when it runs mst_gemm_nt first. That launch
+ *            takes max(form[2], 144 * 32 * ceil(S / 32) + 2 * dh * (D + 8)) bytes of LDS. mst_attn_keysoftmax_bwd does not look at it
  * Entries not listed are 0. Returns 0; invalid arguments: MST_ERR_INVALID, or MST_ERR_UNSUPPORTED for the dtype. */
 int mst_attn_fwd_form(int dtype, int64_t B, int64_t S, int64_t H, int64_t dh, int64_t ld_qkv, int64_t k_off, int64_t q_off,
                       int64_t v_off, int64_t ld_out, int64_t q_limit, int fused, int64_t ld_x, int64_t ld_w, int64_t* form);

@@ -1230,8 +1230,145 @@ __global__ __launch_bounds__((FWD_MAX_WAVES<DH, QKV || CHUNKED> * 64)) __attribu
   }
 }
 
-template <typename T, int DH, bool SPARSE>
+// ---- the W_proj INPUT GRADIENT of ONE (batch, head) inside the attention backward launch (head sizes 16 and 32). The dO tile the
+// workgroup stages, dproj[b] (S x D) . Wt[hd dh .. hd dh + dh, :]^T, is one column tile of the GEMM that used to write `datt` (6.4 and
+// 8.9 us as launches of their own at configs[1], and 12.6 MB written and read straight back): no sum crosses heads. Every wave forms
+// the rows of ITS 32-row block — the rows nobody else needs before the tile is complete —, so the contraction loop has no workgroup
+// barrier: a wave stages its own 32 x 64 slice of dproj through LDS with whole-line loads (8 lanes x 16 bytes per row) one slice
+// ahead in registers, and only the head's weight panel [dh][D] (staged once, up front) is shared. The product is gemm_mainloop's:
+// mfma16 with the weights as the A operand, 32-deep steps in ascending K, one rounding to the activation type — the bits of the
+// GEMM launch. The slices borrow the LDS of the Q / dO tiles and the per-key arrays (free until phase A); the launch is given
+// max(the kernel's own LDS, res_lds_bwd_proj) bytes, two workgroups per CU still fit (attn_bwd_proj_rule).
+// The lone row (lone_row_shape): the last wave also forms the 16-row sub-tile that holds row S - 1.
+// On return the dO tile (zeros in rows >= S) is in bufB and Q in bufA, as stage_pair leaves them; the caller's barrier completes them.
+constexpr int DOP_KC = 64;            // contraction slice staged per step
+constexpr int DOP_LDS = DOP_KC + 8;   // row stride (elements) of a staged slice: 144-byte rows
+__device__ __forceinline__ void wave_lds_fence() {  // LDS traffic of ONE wave is in order: only the compiler has to be held
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+template <typename T, int DH>
+__device__ __forceinline__ void dout_prologue(const AttnArgs& a, unsigned char* smem, T* bufA, T* bufB, const T* __restrict__ Qg, int64_t b,
+                                              int64_t hd, int NB, bool lone) {
+  constexpr int LD = LdsLd<DH>::V, TN = DH / 16, TMX = DH <= 16 ? 3 : 2, CPR = DH / 8;
+  typedef typename Act<T>::vec8 vec8;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nthr = blockDim.x, NW = nthr >> 6;
+  const int64_t S = a.S;
+  const int SP = NB * 32, D = (int)a.Dm, LDW = D + 8, nch = D / DOP_KC;
+  T* const sX = reinterpret_cast<T*>(smem);  // [SP][72]: wave w owns rows 32 w .. 32 w + 31 (the last one the lone row's block too)
+  T* const sW = sX + SP * DOP_LDS;           // [DH][D + 8]
+  const T* xg = reinterpret_cast<const T*>(a.x) + b * S * a.ld_x;
+  const T* wg = reinterpret_cast<const T*>(a.w) + hd * DH * a.ld_w;
+  // this wave's slice pieces of 16 bytes: piece q = (row q / 8 of the block, chunk q % 8), four per lane. Rows beyond the sequence read
+  // the last row (their results are zeroed below); every load is unconditional, as in qkv_prologue
+  const int rb0 = wave * 32;
+  const T* xsrc[4]; T* xdst[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int q = lane + 64 * i, r = rb0 + (q >> 3), ch = q & 7;
+    xsrc[i] = xg + (int64_t)(r < S ? r : S - 1) * a.ld_x + ch * 8;
+    xdst[i] = sX + r * DOP_LDS + ch * 8;
+  }
+  const bool extra = TMX == 3 && lone && wave == NW - 1;  // (wave-uniform) rows 32 NW .. 32 NW + 7: row S - 1 and seven copies of it
+  const int re = 32 * NW + (lane >> 3);
+  const T* const xsrc_e = xg + (int64_t)(re < S ? re : S - 1) * a.ld_x + (lane & 7) * 8;
+  T* const xdst_e = sX + re * DOP_LDS + (lane & 7) * 8;
+  u32x4 xr[4], xe = {0u, 0u, 0u, 0u};
+  auto load_slice = [&](int kc) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) xr[i] = *reinterpret_cast<const u32x4*>(xsrc[i] + kc * DOP_KC);
+    if (extra) xe = *reinterpret_cast<const u32x4*>(xsrc_e + kc * DOP_KC);
+  };
+  auto store_slice = [&]() {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) *reinterpret_cast<u32x4*>(xdst[i]) = xr[i];
+    if (extra) *reinterpret_cast<u32x4*>(xdst_e) = xe;
+  };
+  load_slice(0);
+  // Q: requested now, stored after the contraction (two pieces per thread cover the SP x DH tile: NW >= NB - 1)
+  u32x4 qr[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int c = tid + i * nthr, row = c / CPR, ch = c % CPR;
+    const bool ok = c < SP * CPR && row < S;
+    const u32x4 v = *reinterpret_cast<const u32x4*>(Qg + (int64_t)(ok ? row : 0) * a.ld_qkv + (ok ? ch : 0) * 8);
+    qr[i] = ok ? v : u32x4{0u, 0u, 0u, 0u};
+  }
+  {  // the head's weight panel
+    const int wpr = D / 8;
+    for (int p = tid; p < DH * wpr; p += nthr) {
+      const int r = p / wpr, ch = p - r * wpr;
+      *reinterpret_cast<u32x4*>(sW + r * LDW + ch * 8) = *reinterpret_cast<const u32x4*>(wg + (int64_t)r * a.ld_w + ch * 8);
+    }
+  }
+  store_slice();
+  __syncthreads();
+  f32x4 acc[TN][TMX];
+#pragma unroll
+  for (int j = 0; j < TN; ++j)
+#pragma unroll
+    for (int i = 0; i < TMX; ++i) acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int frow = lane & 15, fq = lane >> 4;
+  const T* const fx = sX + (rb0 + frow) * DOP_LDS + 8 * fq;
+  const T* const fxe = sX + (32 * NW + frow) * DOP_LDS + 8 * fq;
+  const T* const fw = sW + frow * LDW + 8 * fq;
+  for (int kc = 0; kc < nch; ++kc) {
+    if (kc + 1 < nch) load_slice(kc + 1);
+#pragma unroll
+    for (int ks = 0; ks < DOP_KC / 32; ++ks) {
+      vec8 xf[2], wf[TN];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) xf[i] = __builtin_bit_cast(vec8, *reinterpret_cast<const u32x4*>(fx + i * 16 * DOP_LDS + 32 * ks));
+#pragma unroll
+      for (int j = 0; j < TN; ++j) wf[j] = __builtin_bit_cast(vec8, *reinterpret_cast<const u32x4*>(fw + j * 16 * LDW + kc * DOP_KC + 32 * ks));
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) acc[j][i] = Act<T>::mfma16(wf[j], xf[i], acc[j][i]);
+      if constexpr (TMX == 3) {
+        if (extra) {
+          const vec8 xf2 = __builtin_bit_cast(vec8, *reinterpret_cast<const u32x4*>(fxe + 32 * ks));
+#pragma unroll
+          for (int j = 0; j < TN; ++j) acc[j][2] = Act<T>::mfma16(wf[j], xf2, acc[j][2]);
+        }
+      }
+    }
+    wave_lds_fence();  // this wave has read its slice
+    if (kc + 1 < nch) store_slice();
+    wave_lds_fence();
+  }
+  __syncthreads();  // every wave is done with the slices and the panel: the tiles may be written over them
+  // one rounding (gemm_epilogue's, alpha 1, no bias): lane (frow, fq) holds columns 16 j + 4 fq .. + 3 of row frow of each sub-tile
+#pragma unroll
+  for (int i = 0; i < TMX; ++i) {
+    if (i == 2 && !(lone && wave == NW - 1)) break;
+    const int row = i == 2 ? 32 * NW + frow : rb0 + 16 * i + frow;
+    const bool in = row < S;
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      u32x2 o = {0u, 0u};
+      if (in) {
+        o[0] = (uint32_t)f32_to_bits<T>(acc[j][i][0]) | ((uint32_t)f32_to_bits<T>(acc[j][i][1]) << 16);
+        o[1] = (uint32_t)f32_to_bits<T>(acc[j][i][2]) | ((uint32_t)f32_to_bits<T>(acc[j][i][3]) << 16);
+      }
+      *reinterpret_cast<u32x2*>(bufB + row * LD + 16 * j + 4 * fq) = o;
+      if (i == 2) *reinterpret_cast<u32x2*>(bufB + (row + 16) * LD + 16 * j + 4 * fq) = u32x2{0u, 0u};  // (the block's other sixteen rows)
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int c = tid + i * nthr, row = c / CPR, ch = c % CPR;
+    if (c < SP * CPR) *reinterpret_cast<u32x4*>(bufA + row * LD + ch * 8) = qr[i];
+  }
+}
+
+// PROJ: dO is formed in the launch (dout_prologue) instead of read: a.x / a.ld_x = dproj, a.w / a.ld_w = the transposed W_proj shadow,
+// a.Dm = D, a.out / a.ld_out = where to store the dO tile as well (may be null); a.dout is not looked at. Dense, head sizes 16 and 32,
+// one wave per owner block (attn_bwd_proj_rule). A separate instantiation: the other kernels keep their registers and instructions.
+template <typename T, int DH, bool SPARSE, bool PROJ = false>
 __global__ __launch_bounds__(RES_MAX_WAVES<DH> * 64) __attribute__((amdgpu_waves_per_eu(DH == 16 ? ATT16_WAVES : (DH == 64 ? 2 : 4)))) void attn_bwd_res_kernel(AttnArgs a) {
+  static_assert(!PROJ || (!SPARSE && DH <= 32), "the projection prologue: dense, head sizes 16 and 32");
   constexpr int KS = DH / 16, DB = (DH + 31) / 32, LD = LdsLd<DH>::V;
   extern __shared__ __attribute__((aligned(16))) unsigned char att_smem[];
   const int64_t S = a.S;
@@ -1266,8 +1403,18 @@ __global__ __launch_bounds__(RES_MAX_WAVES<DH> * 64) __attribute__((amdgpu_waves
     vf[s] = glb_row_frag<T>(Vg, a.ld_qkv, wave * 32 + (lane & 31), S, s, lane);
   }
   ATT_STAMP(0);
-  stage_pair<T, DH>(bufA, Qg, a.ld_qkv, S, bufB, dOg, a.ld_dout, do_rows, SP, tid, nthr);
+  if constexpr (PROJ) dout_prologue<T, DH>(a, att_smem, bufA, bufB, Qg, b, hd, NB, lone);
+  else stage_pair<T, DH>(bufA, Qg, a.ld_qkv, S, bufB, dOg, a.ld_dout, do_rows, SP, tid, nthr);
   __syncthreads();
+  if constexpr (PROJ) {
+    if (a.out) {  // the dO tile as the GEMM launch stored it (the engine passes null: nothing else reads it)
+      T* const og = reinterpret_cast<T*>(a.out) + b * S * a.ld_out + hd * DH;
+      for (int c = tid; c < (int)S * (DH / 8); c += nthr) {
+        const int row = c / (DH / 8), ch = c % (DH / 8);
+        *reinterpret_cast<u32x4*>(og + (int64_t)row * a.ld_out + ch * 8) = *reinterpret_cast<const u32x4*>(bufB + row * LD + ch * 8);
+      }
+    }
+  }
   ATT_STAMP(1);
   const int nq0 = sparse ? 1 : NBo;  // (whole) query tiles that contribute to pass 0
 
@@ -1410,7 +1557,11 @@ __global__ __launch_bounds__(RES_MAX_WAVES<DH> * 64) __attribute__((amdgpu_waves
 #pragma unroll
   for (int s = 0; s < KS; ++s) {
     qf[s] = glb_row_frag<T>(Qg, a.ld_qkv, wave * 32 + (lane & 31), S, s, lane);
-    dof[s] = glb_row_frag<T>(dOg, a.ld_dout, wave * 32 + (lane & 31), do_rows, s, lane);
+    if constexpr (PROJ) dof[s] = lds_row_frag<T, DH>(bufB, wave * 32, s, lane);  // (dO is in no other place; same elements, zero beyond S)
+    else dof[s] = glb_row_frag<T>(dOg, a.ld_dout, wave * 32 + (lane & 31), do_rows, s, lane);
+  }
+  if constexpr (PROJ && DH <= 16) {  // the lone query's dO row, kept for its dQ sweep behind phase B (a corner of sRed no reduction uses)
+    if (lone && tid < DH) sRed[LONE_RED / 2 + DH + tid] = to_f32(bufB[(S - 1) * LD + tid]);
   }
   __syncthreads();  // every wave is done with the staged Q and dO
   stage_pair<T, DH>(bufA, Kg, a.ld_qkv, S, bufB, Vg, a.ld_qkv, S, SP, tid, nthr);
@@ -1425,7 +1576,7 @@ __global__ __launch_bounds__(RES_MAX_WAVES<DH> * 64) __attribute__((amdgpu_waves
 #pragma unroll
       for (int s = 0; s < KS; ++s) {
         qf[s] = glb_row_frag<T>(Qg, a.ld_qkv, q_lane, S, s, lane);
-        dof[s] = glb_row_frag<T>(dOg, a.ld_dout, q_lane, do_rows, s, lane);
+        if constexpr (!PROJ) dof[s] = glb_row_frag<T>(dOg, a.ld_dout, q_lane, do_rows, s, lane);  // (PROJ: one block per wave, never here)
       }
     }
     f32x16 acc[DB];
@@ -1456,7 +1607,11 @@ __global__ __launch_bounds__(RES_MAX_WAVES<DH> * 64) __attribute__((amdgpu_waves
       const int64_t e = S - 1;
       float qe[DH], doe[DH], acc[DH];
 #pragma unroll
-      for (int f = 0; f < DH; ++f) { qe[f] = to_f32(Qg[e * a.ld_qkv + f]); doe[f] = to_f32(dOg[e * a.ld_dout + f]); acc[f] = 0.f; }
+      for (int f = 0; f < DH; ++f) {
+        qe[f] = to_f32(Qg[e * a.ld_qkv + f]); acc[f] = 0.f;
+        if constexpr (PROJ) doe[f] = sRed[LONE_RED / 2 + DH + f];
+        else doe[f] = to_f32(dOg[e * a.ld_dout + f]);
+      }
       for (int k = tid; k < S; k += nthr) {
         const float x = lds_row_dot<T, DH>(bufA + k * LD, qe);
         const float ps = exact ? exact_prob(x, a.scale, sMadd[k], sMax[k], sLogl[k]) * a.scale : fast_exp2(fmaf(x, sSk[k], sCk[k]));
@@ -1595,6 +1750,8 @@ static int choose_resident(int64_t S, int64_t n_wg, size_t lds_bytes, int waves_
 // dynamic LDS of the resident kernels: the staged tiles ([SP][dh + 8] 16-bit each, LdsLd), the per-key fp32 arrays, the lone row's scratch
 static size_t res_lds_fwd(int dh, int64_t S, int tiles) { const size_t SP = (size_t)cdiv(S, 32) * 32; return (size_t)tiles * SP * (dh + 8) * 2 + 5 * SP * 4 + LONE_RED * 4; }
 static size_t res_lds_bwd(int dh, int64_t S) { const size_t SP = (size_t)cdiv(S, 32) * 32; return 2 * SP * (dh + 8) * 2 + 6 * SP * 4 + LONE_RED * 4; }
+// ... of dout_prologue's staged operands: a 64-deep slice of dproj for every row, the head's weight panel
+static size_t res_lds_bwd_proj(int dh, int64_t S, int64_t Dm) { const size_t SP = (size_t)cdiv(S, 32) * 32; return SP * DOP_LDS * 2 + (size_t)dh * (Dm + 8) * 2; }
 static int res_max_waves(int dh) { return dh == 64 ? RES_MAX_WAVES<64> : RES_MAX_WAVES<32>; }
 
 static int attn_check(int64_t B, int64_t S, int64_t H, int64_t dh, int64_t ld, int64_t k_off, int64_t q_off, int64_t v_off) {
@@ -1639,7 +1796,7 @@ static int64_t bwd_q_limit(int64_t q_limit, int64_t S) { return (q_limit > 0 && 
 enum { ATT_FWD_RES3 = 0, ATT_FWD_RES2 = 1, ATT_FWD_CHUNKED = 2, ATT_FWD_FUSED = 3, ATT_FWD_STREAM = 4 };
 enum { ATT_BWD_RES = 0, ATT_BWD_STREAM_CHUNKQ = 1, ATT_BWD_STREAM = 2 };
 struct AttnFwdForm { int path, waves; size_t lds; int lone, restage; int64_t grid_stats, grid_out; };
-struct AttnBwdForm { int path, waves; size_t lds; int sparse, lone, dq_chunks, dq_waves; };
+struct AttnBwdForm { int path, waves; size_t lds; int sparse, lone, dq_chunks, dq_waves; int proj; size_t lds_proj; };
 constexpr int ATT_DQ_OBM = 4, ATT_DQ_NW = 8;  // chunked dQ: owner blocks per wave, waves per workgroup
 
 // q_limit: fwd_q_limit's. fused_call: mst_attn_qkv_fwd (the projection inside the launch where the shape takes it, else the
@@ -1703,6 +1860,17 @@ static AttnBwdForm attn_bwd_form(int dh, int64_t S, int64_t n_wg, int64_t q_limi
   }
   return f;
 }
+// mst_attn_proj_bwd: does the W_proj input gradient run INSIDE the resident launch (f.proj, with f.lds_proj bytes of LDS), or as the
+// GEMM launch ahead of the kernel attn_bwd_form chose? Inside for the dense resident kernel at head sizes 16 and 32 when every owner
+// block has a wave of its own (dout_prologue forms a block's rows in its wave; phase B takes the block's dO fragments from the LDS
+// tile), the model width is whole 64-deep slices and two workgroups per CU still fit. Both step shapes of configs[1] measured faster
+// this way than with their two launches (docs/kernel_notes.md). f: attn_bwd_form's, for the same shape.
+static void attn_bwd_proj_rule(AttnBwdForm& f, int dh, int64_t S, int64_t Dm) {
+  const int NBo = (int)cdiv(S, 32) - f.lone;
+  const size_t need = res_lds_bwd_proj(dh, S, Dm), lds = need > f.lds ? need : f.lds;
+  f.proj = f.path == ATT_BWD_RES && !f.sparse && dh <= 32 && f.waves == NBo && Dm % DOP_KC == 0 && 2 * lds <= 160 * 1024;
+  f.lds_proj = f.proj ? lds : 0;
+}
 
 template <typename T, int DH>
 static int launch_fwd(const AttnArgs& a_in, const AttnFwdForm& f, hipStream_t s) {
@@ -1752,7 +1920,18 @@ static int launch_fwd(const AttnArgs& a_in, const AttnFwdForm& f, hipStream_t s)
   return MST_ERR_INVALID;
 }
 template <typename T, int DH>
-static int launch_bwd(const AttnArgs& a, const AttnBwdForm& f, hipStream_t s) {
+static int launch_bwd(const AttnArgs& a, const AttnBwdForm& f, hipStream_t s, bool proj = false) {
+  if (proj) {  // (mst_attn_proj_bwd with f.proj)
+    if constexpr (DH <= 32) {
+      static size_t granted = 64 * 1024;
+      if (const int rc = lds_opt_in(reinterpret_cast<const void*>(&attn_bwd_res_kernel<T, DH, false, true>), f.lds_proj, &granted, "attn_bwd_res_kernel (fused projection)")) return rc;
+      hipLaunchKernelGGL((attn_bwd_res_kernel<T, DH, false, true>), dim3((unsigned)(a.B * a.H)), dim3(f.waves * 64), f.lds_proj, s, a);
+      MST_CHECK_LAUNCH("attn_bwd_res_kernel (fused projection)");
+      return MST_OK;
+    }
+    set_error("attention backward: the fused projection has no kernel at head size %d", DH);
+    return MST_ERR_INVALID;
+  }
   if (f.path == ATT_BWD_RES) {
     static size_t granted[2] = {64 * 1024, 64 * 1024};
     const void* fn = f.sparse ? reinterpret_cast<const void*>(&attn_bwd_res_kernel<T, DH, true>)
@@ -1887,8 +2066,9 @@ extern "C" int mst_attn_bwd_form(int dtype, int64_t B, int64_t S, int64_t H, int
   int rc = attn_check_bwd(B, S, H, dh, ld_qkv, k_off, q_off, v_off, ld_dout, ld_dqkv);
   if (rc == MST_OK) rc = check_act_dtype(dtype);
   if (rc) return rc;
-  const AttnBwdForm f = attn_bwd_form((int)dh, S, B * H, bwd_q_limit(q_limit, S));
-  const int64_t v[8] = {f.path, f.waves, (int64_t)f.lds, f.sparse, f.lone, f.dq_chunks, f.dq_waves, 0};
+  AttnBwdForm f = attn_bwd_form((int)dh, S, B * H, bwd_q_limit(q_limit, S));
+  attn_bwd_proj_rule(f, (int)dh, S, H * dh);
+  const int64_t v[8] = {f.path, f.waves, (int64_t)f.lds, f.sparse, f.lone, f.dq_chunks, f.dq_waves, f.proj};
   for (int i = 0; i < 8; ++i) form[i] = v[i];
   return MST_OK;
 }
@@ -1955,6 +2135,48 @@ extern "C" int mst_attn_keysoftmax_bwd(int dtype, int64_t B, int64_t S, int64_t 
     if (dh == 16) return launch_bwd<T, 16>(a, f, s);
     if (dh == 32) return launch_bwd<T, 32>(a, f, s);
     return launch_bwd<T, 64>(a, f, s);
+  });
+}
+
+extern "C" int mst_attn_proj_bwd(int dtype, int64_t B, int64_t S, int64_t H, int64_t dh, const void* qkv, int64_t ld_qkv, int64_t k_off,
+                                 int64_t q_off, int64_t v_off, const uint8_t* keymask, const float* lse, const void* dproj, int64_t ld_dproj,
+                                 const void* wt, int64_t ld_wt, void* dout_out, int64_t ld_dout, void* dqkv, int64_t ld_dqkv, float* delta,
+                                 mst_stream_t stream) {
+  int rc = attn_check(B, S, H, dh, ld_qkv, k_off, q_off, v_off);
+  if (rc) return rc;
+  const int64_t Dm = H * dh;
+  MST_CHECK_ARG(qkv && keymask && lse && dproj && wt && dqkv && delta, "mst_attn_proj_bwd: null pointer");
+  MST_CHECK_ARG(ld_dproj % 8 == 0 && ld_dproj >= Dm && ld_wt % 8 == 0 && ld_wt >= Dm && ld_dqkv % 8 == 0 &&
+                (!dout_out || (ld_dout % 8 == 0 && ld_dout >= Dm)), "mst_attn_proj_bwd: bad leading dims");
+  MST_CHECK_ARG(((uintptr_t)dproj % 16 == 0) && ((uintptr_t)wt % 16 == 0) && ((uintptr_t)dout_out % 16 == 0) && ((uintptr_t)qkv % 16 == 0),
+                "mst_attn_proj_bwd: operands must be 16-byte aligned");
+  rc = check_act_dtype(dtype);
+  if (rc) return rc;
+  AttnArgs a = {};
+  a.B = B; a.S = S; a.H = H; a.qkv = qkv; a.ld_qkv = ld_qkv; a.k_off = k_off; a.q_off = q_off; a.v_off = v_off;
+  a.keymask = keymask; a.lse = const_cast<float*>(lse); a.dqkv = dqkv; a.ld_dqkv = ld_dqkv; a.delta = delta;
+  a.q_limit = 0;
+  a.scale = 1.f / sqrtf((float)dh);
+  AttnBwdForm f = attn_bwd_form((int)dh, S, B * H, 0);
+  attn_bwd_proj_rule(f, (int)dh, S, Dm);
+  if (f.proj) {
+    a.x = dproj; a.ld_x = ld_dproj; a.w = wt; a.ld_w = ld_wt; a.Dm = Dm; a.out = dout_out; a.ld_out = ld_dout;
+  } else {
+    // shapes the fused form does not take: the input gradient as the GEMM it is, then the plain backward launches
+    MST_CHECK_ARG(dout_out != nullptr, "mst_attn_proj_bwd: this shape runs the GEMM launch first and needs dout_out");
+    mst_gemm_args g = {};
+    g.dtype = dtype; g.M = B * S; g.N = Dm; g.K = Dm;
+    g.A = dproj; g.lda = ld_dproj; g.B = wt; g.ldb = ld_wt; g.C = dout_out; g.ldc = ld_dout; g.alpha = 1.f;
+    rc = mst_gemm_nt(&g, stream);
+    if (rc) return rc;
+    a.dout = dout_out; a.ld_dout = ld_dout;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  return dispatch_act(dtype, [&](auto tag) -> int {
+    typedef decltype(tag) T;
+    if (dh == 16) return launch_bwd<T, 16>(a, f, s, f.proj != 0);
+    if (dh == 32) return launch_bwd<T, 32>(a, f, s, f.proj != 0);
+    return launch_bwd<T, 64>(a, f, s, f.proj != 0);
   });
 }
 

@@ -603,7 +603,7 @@ def ffn_bwd_kw(P, L, t, drop, partials_buf, row_groups=None):
                 resid=None if P.self_resid else t.dh, partials=partials_buf, row_groups=row_groups, **ln1)
 
 
-def row_block_bwd(P, L, t, dy, rows, drop, form, partials, dy_done=False, row_groups=None, tail=None, launch=True):
+def row_block_bwd(P, L, t, dy, rows, drop, form, partials, dy_done=False, row_groups=None, tail=None, launch=True, proj_dgrad=True):
     """Backward of row_block_fwd on the same rows: LayerNorm-2/3 backward of dy, both FFN dgrads, LayerNorm-1 backward, the W_proj
     dgrad. t: the layer's backward buffers — dh, dhm, dx1, dh1m, dpre indexed by the block's own rows, dh1 and datt by the layer's
     (written through `rows`). partials(norm, n_workgroups) -> the partials buffer of one LayerNorm-backward launch, or None
@@ -615,7 +615,9 @@ def row_block_bwd(P, L, t, dy, rows, drop, form, partials, dy_done=False, row_gr
       'tail'      one launch, mst_row_tail_bwd (position-0 rows; tail: its keywords)
     dy_done: the producer of dy already ran the leading LayerNorm backward (t.dh / t.dhm are filled; not with 'tail').
     launch=False ('fused' with dy_done only): the one-launch block itself is not issued — it ran as a phase of ops.dec_tail_step, from
-    ffn_bwd_kw's arguments —; the partial-sum job is registered and the W_proj dgrad issued as always."""
+    ffn_bwd_kw's arguments —; the partial-sum job is registered and the W_proj dgrad issued as always.
+    proj_dgrad=False (not with 'tail'): the W_proj dgrad is left to the caller's attention-backward launch (ops.attn_proj_bwd on dproj);
+    t.datt is not written."""
     D, v = P.proj.w.shape[0], rows.view
     if form == "tail":
         o.row_tail_bwd(v(dy), v(L.h2), v(L.h1), v(L.a), L.mean1, L.rstd1, L.mean2, L.rstd2, P.ln1.gamma, P.ln2.gamma, P.ff2.t, P.ff1.t,
@@ -655,7 +657,8 @@ def row_block_bwd(P, L, t, dy, rows, drop, form, partials, dy_done=False, row_gr
             o.layernorm_bwd(v(L.h1), P.ln1.gamma, L.mean1, L.rstd1, t.dx1, v(t.dh1), P.ln1.dgamma, P.ln1.dbeta, D=D,
                             partials=partials(P.ln1, o.layernorm_bwd_parts(M, D)), **rows.ln, **ln1)
     dproj = t.dh1m if drop.p > 0 else v(t.dh1)
-    o.gemm_nt(dproj, P.proj.t, t.datt, N=D, K=D, c_remap=rows.c_remap)
+    if proj_dgrad:
+        o.gemm_nt(dproj, P.proj.t, t.datt, N=D, K=D, c_remap=rows.c_remap)
     return dff, dproj
 
 
@@ -750,7 +753,10 @@ def row_tail_selfcheck(store, B=64, S=2):
 # dec_tail — the last decoder layer's row-wise block, the loss launch and the block's backward as ONE launch (a training step with gradient).
 # gnorm — the optimizer clips by the global gradient norm: one mst_grad_sumsq launch ahead of the Adam launches in their gnorm form.
 # ema — the Adam launches in their averaging form (mst_adam_flat_ema): the same launches in the same order, none added.
-Forms = namedtuple("Forms", "tails riders shadows fuse_bce bce_dgrad skip_row0 cls_fold ffn_e ffn_d ln_bwd_e ln_bwd_d sched dec_tail gnorm ema")
+# attn_proj_e / attn_proj_d — the W_proj input gradient of an encoder layer below the top one / of a (non-causal) decoder layer is formed
+# inside its attention-backward launch (mst_attn_proj_bwd) instead of by a GEMM launch that writes datt.
+Forms = namedtuple("Forms", "tails riders shadows fuse_bce bce_dgrad skip_row0 cls_fold ffn_e ffn_d ln_bwd_e ln_bwd_d sched dec_tail gnorm ema "
+                            "attn_proj_e attn_proj_d")
 
 
 def check_schedule(kl_warmup_steps=0, kl_cycle_steps=0, kl_free_bits=0.0, lr_warmup_steps=0):
@@ -1065,7 +1071,13 @@ class StepPlan:
             # clipping by the global gradient norm: a sum-of-squares launch ahead of Adam, the Adam launches in their gnorm form
             gnorm=self.clip_global_norm > 0,
             # the exponential moving average of the weights: the Adam launches in their averaging form
-            ema=self.ema_decay > 0)
+            ema=self.ema_decay > 0,
+            # the W_proj input gradient inside the attention-backward launch, where the library takes the shape that way
+            # (mst_attn_bwd_form; the causal decoder has kernels of its own)
+            attn_proj_e=self._attn_proj(T, cfg.e_heads, De), attn_proj_d=not cfg.d_causal and self._attn_proj(T + 1, cfg.d_heads, Dd))
+
+    def _attn_proj(self, S, H, D):
+        return bool(o.attn_bwd_form(self.adt, self.B, S, H, D // H, 0, D, 2 * D, 3 * D, D, 3 * D, proj=True)["proj"])
 
     def _guard(self):
         """step guard of the launches that close a step (optimizer / loss_combine): the barrier counters of the one-launch
@@ -1411,10 +1423,14 @@ class StepPlan:
         ffn, ln = (F.ffn_e, F.ln_bwd_e) if side == "encoder" else (F.ffn_d, F.ln_bwd_d)
         # (Forms.dec_tail: the last decoder layer's one-launch block already ran inside the loss launch, losses())
         in_loss = F.dec_tail and side == "decoder" and i == self.cfg.d_layers - 1
+        proj = F.attn_proj_e if side == "encoder" else F.attn_proj_d
         dff, dproj = row_block_bwd(P, L, t, dy, ALL_ROWS, self._dropout(p, site0), "fused" if ffn else ("ln_fused" if ln else "launches"),
-                                   self._ln_partials, dy_done=dy_done, row_groups=self._row0_groups(side, i), launch=not in_loss)
+                                   self._ln_partials, dy_done=dy_done, row_groups=self._row0_groups(side, i), launch=not in_loss,
+                                   proj_dgrad=not proj)
         if side == "decoder" and self.cfg.d_causal:
             o.attn_causal_bwd(L.qkv, keymask, L.lse, t.datt, t.dqkv, t.delta, self.B, S, H, D // H, 0, D, 2 * D)
+        elif proj:  # dO = dproj W_proj is formed by the (batch, head) workgroups themselves; nothing else reads t.datt
+            o.attn_proj_bwd(L.qkv, keymask, L.lse, dproj, P.proj.t, t.dqkv, t.delta, self.B, S, H, D // H, 0, D, 2 * D)
         else:
             o.attn_bwd(L.qkv, keymask, L.lse, t.datt, t.dqkv, t.delta, self.B, S, H, D // H, 0, D, 2 * D)
         handed = None

@@ -545,6 +545,13 @@ def attn_bwd(qkv, keymask, lse, dout, dqkv, delta, B, S, H, dh, k_off, q_off, v_
          ptr(lse), ptr(dout), ld(dout), ptr(dqkv), ld(dqkv), ptr(delta), q_limit, stream())
 
 
+def attn_proj_bwd(qkv, keymask, lse, dproj, Wt, dqkv, delta, B, S, H, dh, k_off, q_off, v_off, dout_out=None):
+    """dO = dproj Wt^T (the W_proj input gradient) and attn_bwd on it, the product inside the attention launch where
+    attn_bwd_form(..., proj=True)["proj"] says so (mst_attn_proj_bwd); dout_out (optional there) also receives dO"""
+    call("mst_attn_proj_bwd", dt(qkv), B, S, H, dh, ptr(qkv), ld(qkv), k_off, q_off, v_off, ptr(keymask), ptr(lse), ptr(dproj), ld(dproj),
+         ptr(Wt), ld(Wt), ptr(dout_out), ld(dout_out) if dout_out is not None else 0, ptr(dqkv), ld(dqkv), ptr(delta), stream())
+
+
 ATTN_FWD_PATHS = ("resident-3", "resident-2", "chunked", "fused", "stream")
 ATTN_BWD_PATHS = ("resident", "stream+chunked-dq", "stream")
 
@@ -557,13 +564,17 @@ def attn_fwd_form(dtype, B, S, H, dh, k_off, q_off, v_off, ld_qkv, ld_out, q_lim
     return dict(path=ATTN_FWD_PATHS[form[0]], waves=form[1], lds=form[2], lone=form[3], grid_stats=form[4], grid_out=form[5])
 
 
-def attn_bwd_form(dtype, B, S, H, dh, k_off, q_off, v_off, ld_qkv, ld_dout, ld_dqkv, q_limit=0):
+def attn_bwd_form(dtype, B, S, H, dh, k_off, q_off, v_off, ld_qkv, ld_dout, ld_dqkv, q_limit=0, proj=False):
     """what attn_bwd launches for these arguments (mst_attn_bwd_form); no launch, no device.
-    -> dict(path (one of ATTN_BWD_PATHS), waves, lds, sparse, lone, dq_chunks, dq_waves)"""
+    -> dict(path (one of ATTN_BWD_PATHS), waves, lds, sparse, lone, dq_chunks, dq_waves)
+    proj: also `proj`, 1 when attn_proj_bwd forms dO inside that launch for this shape, 0 when it runs the GEMM launch first"""
     form = (C.c_int64 * 8)()
     call("mst_attn_bwd_form", dt(dtype), B, S, H, dh, ld_qkv, k_off, q_off, v_off, ld_dout, ld_dqkv, q_limit, form)
-    return dict(path=ATTN_BWD_PATHS[form[0]], waves=form[1], lds=form[2], sparse=form[3], lone=form[4], dq_chunks=form[5],
-                dq_waves=form[6])
+    d = dict(path=ATTN_BWD_PATHS[form[0]], waves=form[1], lds=form[2], sparse=form[3], lone=form[4], dq_chunks=form[5],
+             dq_waves=form[6])
+    if proj:
+        d["proj"] = form[7]
+    return d
 
 
 def attn_causal_fwd(qkv, keymask, lse, out, B, S, H, dh, k_off, q_off, v_off):
