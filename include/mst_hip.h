@@ -153,7 +153,19 @@ typedef struct mst_bce_args {
   void* probs; int64_t ldp;   /* optional act dtype [M, ldp]: sigmoid output */
   void* logits; int64_t ldl;  /* optional act dtype [M, ldl] */
   float gscale;
+  uint64_t* counts;           /* optional [MST_ROLL_SLOTS][4], 16-byte aligned: the piano-roll counts below, ADDED to */
 } mst_bce_args;
+/* Piano-roll counts (ABI 114), kept on the device by every launch that computes the BCE: each (frame, pitch) cell a launch computes a
+ * loss term for (row m < M, column < P; padded frames count as the loss counts them, pad columns never) adds to four integers
+ *   [0] tp    label == 1 and predicted      [1] pred  predicted      [2] pos  label == 1      [3] cells  every cell counted
+ * where "predicted" is: the 16-bit logit the loss arithmetic uses is strictly greater than 0 (+0, -0 and NaN are not). Label
+ * smoothing, down-weighting and gscale play no part. A workgroup sums its cells exactly (integers) and one thread adds the four
+ * numbers to slot (linear workgroup id % MST_ROLL_SLOTS) with 64-bit atomics: the totals over the slots are bit-reproducible, and
+ * the 256 slots keep same-address serialisation away. Launches ADD; the caller clears the buffer when it reads (as tok_parts) and
+ * sums the slots: precision = tp / pred, recall = tp / pos, F1 = 2 tp / (pred + pos). With counts == NULL a launch stores exactly
+ * what it stored before (mst_gemm_sigmoid_bce, mst_gemm_sigmoid_bce_dgrad_ln — also as its two launches — and mst_dec_tail_step
+ * read the field; their form queries do not depend on it). */
+#define MST_ROLL_SLOTS 256
 int mst_gemm_sigmoid_bce(const mst_gemm_args* args, const mst_bce_args* bce, mst_stream_t stream);
 
 /* ------------------------------------------------------------------------
@@ -815,6 +827,15 @@ int mst_sigmoid_bce(int dtype, int64_t B, int64_t T, int64_t P,
                     float* loss, void* probs, int64_t ldp,
                     void* dlogits, int64_t ldd, float gscale,
                     int pre_zeroed /* as in mst_softmax_ce */, mst_stream_t stream);
+/* The same launch (mst_sigmoid_bce is this call with counts = NULL) which also ADDS the piano-roll counts of its cells — see
+ * mst_bce_args — to counts: uint64 [MST_ROLL_SLOTS][4], 16-byte aligned, slot = (sample * grid.x + workgroup) % MST_ROLL_SLOTS.
+ * Pad columns P..ld are not counted. The launch form is the one mst_sigmoid_bce_form reports. */
+int mst_sigmoid_bce_counts(int dtype, int64_t B, int64_t T, int64_t P,
+                           const void* logits, int64_t ld, const uint8_t* labels,
+                           float label_smoothing, int downweight, int32_t* npos,
+                           float* loss, void* probs, int64_t ldp,
+                           void* dlogits, int64_t ldd, float gscale,
+                           int pre_zeroed, uint64_t* counts, mst_stream_t stream);
 /* What mst_sigmoid_bce launches for the same arguments: decided on the host, no HIP call, no device needed (the pointers are looked at
  * for NULL and alignment only). The kernel's choice of the vector width is the same function. form is a host array of 8 entries:
  *   form[0]  pitches a thread sweeps at a time: 8 (P, ld, ldp, ldd multiples of 8, logits / probs / dlogits on 16-byte and labels on

@@ -18,7 +18,7 @@ import torch
 from . import utils
 from .config import Config
 from .. import parallel
-from ..engine import check_clip, check_ema, check_schedule
+from ..engine import check_clip, check_ema, check_schedule, roll_scores
 from ..pianoroll import PinnedBatchPipeline
 
 
@@ -162,6 +162,7 @@ class Trainer:
                 if src in self.opt_extra:
                     plan.opt[dst] = self.opt_extra[src]
             plan.track_token_metrics = plan.cfg.kind == "token"  # ppl / acc / topk sums ride on the CE launch
+            plan.track_roll_metrics = plan.cfg.kind == "pianoroll"  # tp / pred / pos / cells counts ride on the BCE launch
             plan._trainer_set = True
         return plan
 
@@ -269,7 +270,8 @@ class Trainer:
     # ------------------------------------------------------------------ metrics / logging
     def collect_metrics(self, reset=True):
         """the reference's five metrics over every step since the last reset (trainer.py:107-120,181-186): kl_loss /
-        total_loss batch means and, for the token ends, masked ppl / acc / topk — all accumulated on the device by the
+        total_loss batch means and, for the token ends, masked ppl / acc / topk, for the piano-roll ends precision / recall / f1 / cell_acc
+        of the predicted notes (engine.roll_scores of the counts the loss launches keep; early stopping still compares total_loss) — all accumulated on the device by the
         steps themselves and read here with one synchronisation. kl_weight / lr_scale: the KL weight and the learning-rate factor
         of the last training step, from the device schedule block in the same read (the configured constants without schedules;
         computed per rank from the same step count, so there is nothing to reduce). With clip_global_norm on, also grad_norm (the mean
@@ -287,7 +289,8 @@ class Trainer:
         kl_weight, lr_scale = ((m.get("kl_weight", self.config.kl_loss_weight), m.get("lr_scale", 1.0)) if self.scheduled
                                else (self.config.kl_loss_weight, 1.0))
         gnorm = {k: m[k] for k in ("grad_norm", "grad_norm_max", "clip_frac") if k in m} if self.clip_global_norm > 0 else {}
-        keys = [k for k in ("kl_sum", "total_sum", "count", "nll_sum", "acc_hits", "topk_hits", "n_tokens") if k in m]
+        keys = [k for k in ("kl_sum", "total_sum", "count", "nll_sum", "acc_hits", "topk_hits", "n_tokens", "roll_tp", "roll_pred", "roll_pos",
+                            "roll_cells") if k in m]  # (the counts: float64 is exact far beyond any run's)
         if self.dist is not None:
             with torch.cuda.stream(self.stream):
                 t = torch.tensor([m[k] for k in keys] + [1.0 if failure is not None else 0.0], dtype=torch.float64,
@@ -305,6 +308,8 @@ class Trainer:
             out["ppl"] = float(np.exp(m["nll_sum"] / n)) if n else float("nan")
             out["acc"] = m["acc_hits"] / n if n else float("nan")
             out["topk"] = m["topk_hits"] / n if n else float("nan")
+        if "roll_cells" in m:  # piano-roll ends: precision / recall / f1 / cell_acc of the notes the decoder predicts (logit > 0)
+            out.update(roll_scores(*(int(m[k]) for k in ("roll_tp", "roll_pred", "roll_pos", "roll_cells"))))
         n = max(m["count"], 1.0)
         out["kl_loss"] = m["kl_sum"] / n
         out["total_loss"] = m["total_sum"] / n

@@ -112,6 +112,7 @@ globals().update({cls.__name__: cls for cls in STRUCTS.values()})  # GemmArgs, L
 MST_BF16, MST_F16, MST_F32 = _consts["MST_BF16"], _consts["MST_F16"], _consts["MST_F32"]
 ACT_NONE, ACT_RELU = _consts["MST_ACT_NONE"], _consts["MST_ACT_RELU"]
 CE_MAX_WORKGROUPS = _consts["MST_CE_MAX_WORKGROUPS"]  # rows of mst_softmax_ce's token-metric partials
+ROLL_SLOTS = _consts["MST_ROLL_SLOTS"]  # slots of the BCE launches' piano-roll counts
 # flags of the sticky step-status word
 TAIL_SPIN_FWD, TAIL_SPIN_BWD, STEP_INCOMPLETE = (_consts[k] for k in ("MST_TAIL_SPIN_FWD", "MST_TAIL_SPIN_BWD", "MST_STEP_INCOMPLETE"))
 

@@ -60,4 +60,48 @@ __device__ __forceinline__ void bce_fast(float x, float y, float s1 /* s for y =
   }
 }
 
+// ---- piano-roll counts (mst_hip.h: mst_bce_args.counts, mst_sigmoid_bce_counts). A cell is "predicted" where the 16-bit logit the
+// loss is computed from is > 0 (false for +-0 and NaN); labels are {0,1} bytes; the four counts are tp, pred, pos, cells.
+// roll_predicted: byte e = 1 where cell e (of the first n of VEC consecutive ones) is predicted — the layout the label bytes have
+template <int VEC>
+__device__ __forceinline__ uint64_t roll_predicted(const float (&x)[VEC], int n) {
+  uint64_t pm = 0;
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) pm |= (e < n && x[e] > 0.f) ? 1ull << (8 * e) : 0ull;
+  return pm;
+}
+// the counts of up to 8 cells in four fields of BITS bits, tp | pred << BITS | pos << 2 BITS | cells << 3 BITS (lab: no byte set
+// beyond cell n)
+template <int BITS>
+__device__ __forceinline__ uint64_t roll_pack(uint64_t pm, uint64_t lab, int n) {
+  const uint64_t pos = lab & 0x0101010101010101ull;
+  return (uint64_t)__popcll(pm & pos) | (uint64_t)__popcll(pm) << BITS | (uint64_t)__popcll(pos) << (2 * BITS) | (uint64_t)n << (3 * BITS);
+}
+// one thread adds the workgroup's four counts to its slot, linear workgroup id % MST_ROLL_SLOTS: ordinary 64-bit vector atomics,
+// integer sums, so the totals over the slots do not depend on the arrival order
+__device__ __forceinline__ void roll_add_slot(uint64_t* counts, uint64_t tp, uint64_t pred, uint64_t pos, uint64_t cells) {
+  const unsigned wg = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+  unsigned long long* slot = reinterpret_cast<unsigned long long*>(counts) + (size_t)(wg % MST_ROLL_SLOTS) * 4;
+  atomicAdd(slot + 0, (unsigned long long)tp);
+  atomicAdd(slot + 1, (unsigned long long)pred);
+  atomicAdd(slot + 2, (unsigned long long)pos);
+  atomicAdd(slot + 3, (unsigned long long)cells);
+}
+// The threads' packed counts (roll_pack<16>) of a workgroup with at most 2^15 cells: every field's sum over the workgroup stays below
+// 2^16, so fp32 sums (wave_sum's DPP butterflies) are exact integers. roll_wave16: all lanes; lane 0 stores the wave's four sums at
+// part[4 wave ..]. roll_total16: ONE thread, behind a barrier, adds the NW waves' sums to the slot.
+__device__ __forceinline__ void roll_wave16(uint64_t roll, float* part) {
+  float v[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) v[k] = wave_sum((float)(uint32_t)((roll >> (16 * k)) & 0xFFFFull));
+  if ((threadIdx.x & 63) == 0) *reinterpret_cast<f32x4*>(part + (threadIdx.x >> 6) * 4) = f32x4{v[0], v[1], v[2], v[3]};
+}
+template <int NW>
+__device__ __forceinline__ void roll_total16(const float* part, uint64_t* counts) {
+  f32x4 t = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int i = 0; i < NW; ++i) t += *reinterpret_cast<const f32x4*>(part + i * 4);
+  roll_add_slot(counts, (uint64_t)t[0], (uint64_t)t[1], (uint64_t)t[2], (uint64_t)t[3]);
+}
+
 }  // namespace mst

@@ -79,13 +79,13 @@ constexpr size_t DEC_TAIL_BODY_LDS = (size_t)2 * 128 * 64 * 2 + (size_t)2 * 64 *
 constexpr size_t DEC_TAIL_LDS = DEC_TAIL_BODY_LDS + ((size_t)128 + 3 * 128 + DEC_TAIL_F + 3 * 128) * 4;
 static_assert(DEC_TAIL_LDS <= (size_t)48 * 1024 + (size_t)2 * (64 + 128) * 64 * 2 + (size_t)3 * 128 * 4, "no more LDS than the loss launch takes");
 
-template <typename T>
+template <typename T, bool CNT>
 __global__ __launch_bounds__(512) void dec_tail_kernel(mst_gemm_args proj, mst_ln_args ln1, mst_gemm_args ff1, mst_gemm_args ff2, mst_ln_args ln3,
                                                        mst_gemm_args out, mst_bce_args bce, mst_gemm_args odg, mst_ln_args ln3b,
                                                        mst_gemm_args f2d, mst_gemm_args f1d, mst_ln_args ln1b) {
   constexpr int BM = 64, BN = 128, WGM = 2, WGN = 4, LDA = BN + 8, F = (int)DEC_TAIL_F;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ float red[512 / 64];
+  __shared__ __attribute__((aligned(16))) float red[bce_red_words(CNT)];
   T* sX = reinterpret_cast<T*>(smem + (size_t)2 * BN * 64 * 2 + (size_t)BM * LDA * 2);  // ffn_ln_body's x tile
   // behind the forward block's own LDS: the parameters of the three later phases — cold lines after every optimizer step, requested now
   float* sBiasO = reinterpret_cast<float*>(smem + DEC_TAIL_BODY_LDS);  // [BN] the output layer's bias
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(512) void dec_tail_kernel(mst_gemm_args proj, mst_l
     float bias8[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) bias8[e] = sBiasO[(tid % (BN / 8)) * 8 + e];
-    bce_tile_finish<T, BN, 2>(out, bce, smem, red, reinterpret_cast<u32x4*>(sX), acc, m0, 0, bias8);
+    bce_tile_finish<T, BN, 2, CNT>(out, bce, smem, red, reinterpret_cast<u32x4*>(sX), acc, m0, 0, bias8);
   }
   __syncthreads();  // the logit-gradient tile is complete, the staging tile dead
   // ---- 3: the output layer's input gradient + LayerNorm-3 backward; dh also lands in the x tile
@@ -130,13 +130,13 @@ __global__ __launch_bounds__(512) void dec_tail_kernel(mst_gemm_args proj, mst_l
   ffn_ln_body<T, BN, WGM, WGN, 2, false, true, false, true, false, true>(smem, f2d, f1d, ln1b, no_lead, no_gemm, no_ln, sPar4, [] {});
 }
 
-template <typename T>
+template <typename T, bool CNT>
 static int launch_dec_tail(const mst_gemm_args& proj, const mst_ln_args& ln1, const mst_gemm_args& ff1, const mst_gemm_args& ff2,
                            const mst_ln_args& ln3, const mst_gemm_args& out, const mst_bce_args& bce, const mst_gemm_args& odg,
                            const mst_ln_args& ln3b, const mst_gemm_args& f2d, const mst_gemm_args& f1d, const mst_ln_args& ln1b, hipStream_t s) {
   static size_t granted = 64 * 1024;
-  if (const int rc = lds_opt_in(reinterpret_cast<const void*>(&dec_tail_kernel<T>), DEC_TAIL_LDS, &granted, "dec_tail_kernel")) return rc;
-  hipLaunchKernelGGL((dec_tail_kernel<T>), dim3((unsigned)(out.M / 64)), dim3(512), DEC_TAIL_LDS, s, proj, ln1, ff1, ff2, ln3, out, bce, odg,
+  if (const int rc = lds_opt_in(reinterpret_cast<const void*>(&dec_tail_kernel<T, CNT>), DEC_TAIL_LDS, &granted, "dec_tail_kernel")) return rc;
+  hipLaunchKernelGGL((dec_tail_kernel<T, CNT>), dim3((unsigned)(out.M / 64)), dim3(512), DEC_TAIL_LDS, s, proj, ln1, ff1, ff2, ln3, out, bce, odg,
                      ln3b, f2d, f1d, ln1b);
   MST_CHECK_LAUNCH("dec_tail_kernel");
   return MST_OK;
@@ -182,6 +182,7 @@ extern "C" int mst_dec_tail_step(const mst_gemm_args* proj, const mst_ln_args* l
   hipStream_t s = (hipStream_t)stream;
   return dispatch_act(o.dtype, [&](auto tag) -> int {
     typedef decltype(tag) T_;
-    return launch_dec_tail<T_>(*proj, *ln1, *ff1, *ff2, *ln3, o, *bce, g, *ln3_bwd, d2, *ff1_dgrad, *ln1_bwd, s);
+    if (bce->counts) return launch_dec_tail<T_, true>(*proj, *ln1, *ff1, *ff2, *ln3, o, *bce, g, *ln3_bwd, d2, *ff1_dgrad, *ln1_bwd, s);
+    return launch_dec_tail<T_, false>(*proj, *ln1, *ff1, *ff2, *ln3, o, *bce, g, *ln3_bwd, d2, *ff1_dgrad, *ln1_bwd, s);
   });
 }

@@ -6,11 +6,11 @@
 
 namespace mst {
 
-template <typename T, int BN>
+template <typename T, int BN, bool CNT>
 __global__ __launch_bounds__(512) void gemm_bce_kernel(mst_gemm_args a, mst_bce_args q) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ float red[512 / 64];
-  gemm_bce_tile<T, BN, false>(a, q, smem, red, nullptr);
+  __shared__ __attribute__((aligned(16))) float red[bce_red_words(CNT)];
+  gemm_bce_tile<T, BN, false, CNT>(a, q, smem, red, nullptr);
 }
 
 // mst_gemm_sigmoid_bce_dgrad_ln: the loss launch above followed IN THE SAME WORKGROUP by the first launch of the backward pass — the
@@ -19,19 +19,19 @@ __global__ __launch_bounds__(512) void gemm_bce_kernel(mst_gemm_args a, mst_bce_
 // weight-gradient launch reads it) but is not read back here, and a launch of the dependent chain disappears.
 // LDS: [0, 48 K) the first GEMM's stages, then its fp32 staging tile (33.8 K), later the LayerNorm epilogue's; [48 K, 64 K) the kept
 // logit-gradient tile (two 64 x 64 stages); [64 K, 96 K) the second GEMM's weight stages; then bias | gamma | beta.
-template <typename T>
+template <typename T, bool CNT>
 __global__ __launch_bounds__(512) void gemm_bce_dgrad_ln_kernel(mst_gemm_args a, mst_bce_args q, mst_gemm_args g2, mst_ln_args l) {
   constexpr int BM = 64, BN = 128, WGM = 2, WGN = 4;
   constexpr size_t OFF2 = 48 * 1024, END2 = OFF2 + (size_t)2 * (BM + BN) * 64 * 2;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ float red[512 / 64];
+  __shared__ __attribute__((aligned(16))) float red[bce_red_words(CNT)];
   float* sPar = reinterpret_cast<float*>(smem + END2);
   for (int i = threadIdx.x; i < BN; i += 512) {  // (cold lines: requested now, read by the LayerNorm epilogue)
     sPar[i] = g2.bias ? g2.bias[i] : 0.f;
     sPar[BN + i] = l.gamma[i];
     sPar[2 * BN + i] = 0.f;
   }
-  gemm_bce_tile<T, BN, true>(a, q, smem, red, reinterpret_cast<u32x4*>(smem + OFF2));
+  gemm_bce_tile<T, BN, true, CNT>(a, q, smem, red, reinterpret_cast<u32x4*>(smem + OFF2));
   __syncthreads();  // the kept tile is complete, the staging tile dead
   f32x4 acc[(BN / WGN) / 16][(BM / WGM) / 16];
   int64_t m0, n0;
@@ -39,23 +39,23 @@ __global__ __launch_bounds__(512) void gemm_bce_dgrad_ln_kernel(mst_gemm_args a,
   gemm_epilogue_ln<T, BM, BN, WGM, WGN, 2>(g2, l, smem, acc, m0, nullptr, 0, nullptr, 0, sPar);
 }
 
-template <typename T>
+template <typename T, bool CNT>
 static int launch_gemm_bce_dgrad_ln(const mst_gemm_args& a, const mst_bce_args& q, const mst_gemm_args& g2, const mst_ln_args& l, hipStream_t s) {
   const size_t lds = (size_t)48 * 1024 + (size_t)2 * (64 + 128) * 64 * 2 + (size_t)3 * 128 * 4;
   static size_t granted = 64 * 1024;
-  if (const int rc = lds_opt_in(reinterpret_cast<const void*>(&gemm_bce_dgrad_ln_kernel<T>), lds, &granted, "gemm_bce_dgrad_ln_kernel")) return rc;
-  hipLaunchKernelGGL((gemm_bce_dgrad_ln_kernel<T>), dim3((unsigned)cdiv(a.M, 64)), dim3(512), lds, s, a, q, g2, l);
+  if (const int rc = lds_opt_in(reinterpret_cast<const void*>(&gemm_bce_dgrad_ln_kernel<T, CNT>), lds, &granted, "gemm_bce_dgrad_ln_kernel")) return rc;
+  hipLaunchKernelGGL((gemm_bce_dgrad_ln_kernel<T, CNT>), dim3((unsigned)cdiv(a.M, 64)), dim3(512), lds, s, a, q, g2, l);
   MST_CHECK_LAUNCH("gemm_bce_dgrad_ln_kernel");
   return MST_OK;
 }
 
-template <typename T, int BN>
+template <typename T, int BN, bool CNT>
 static int launch_gemm_bce(const mst_gemm_args& a, const mst_bce_args& q, hipStream_t s) {
   const size_t lds_loop = (size_t)2 * (64 + BN) * 64 * 2, lds_epi = (size_t)64 * (BN + 4) * 4;
   const size_t lds = lds_loop > lds_epi ? lds_loop : lds_epi;
   static size_t granted = 64 * 1024;
-  if (const int rc = lds_opt_in(reinterpret_cast<const void*>(&gemm_bce_kernel<T, BN>), lds, &granted, "gemm_bce_kernel")) return rc;
-  hipLaunchKernelGGL((gemm_bce_kernel<T, BN>), dim3((unsigned)(cdiv(a.M, 64) * (a.N / BN))), dim3(512), lds, s, a, q);
+  if (const int rc = lds_opt_in(reinterpret_cast<const void*>(&gemm_bce_kernel<T, BN, CNT>), lds, &granted, "gemm_bce_kernel")) return rc;
+  hipLaunchKernelGGL((gemm_bce_kernel<T, BN, CNT>), dim3((unsigned)(cdiv(a.M, 64) * (a.N / BN))), dim3(512), lds, s, a, q);
   MST_CHECK_LAUNCH("gemm_bce_kernel");
   return MST_OK;
 }
@@ -75,6 +75,7 @@ int check_gemm_bce(const mst_gemm_args& a, const mst_bce_args& q) {
   MST_CHECK_ARG(!a.C || (a.ldc % 8 == 0 && a.ldc >= a.N && (uintptr_t)a.C % 16 == 0), "mst_gemm_sigmoid_bce: bad dlogits layout");
   MST_CHECK_ARG(!q.probs || (q.ldp % 8 == 0 && q.ldp >= a.N && (uintptr_t)q.probs % 16 == 0), "mst_gemm_sigmoid_bce: bad probs layout");
   MST_CHECK_ARG(!q.logits || (q.ldl % 8 == 0 && q.ldl >= a.N && (uintptr_t)q.logits % 16 == 0), "mst_gemm_sigmoid_bce: bad logits layout");
+  MST_CHECK_ARG((uintptr_t)q.counts % 16 == 0, "mst_gemm_sigmoid_bce: counts must be 16-byte aligned");
   return MST_OK;
 }
 
@@ -116,8 +117,8 @@ extern "C" int mst_gemm_sigmoid_bce(const mst_gemm_args* args, const mst_bce_arg
   hipStream_t s = (hipStream_t)stream;
   return dispatch_act(a.dtype, [&](auto tag) -> int {
     typedef decltype(tag) T;
-    if (a.N % 256 == 0) return launch_gemm_bce<T, 256>(a, q, s);
-    return launch_gemm_bce<T, 128>(a, q, s);
+    if (q.counts) return a.N % 256 == 0 ? launch_gemm_bce<T, 256, true>(a, q, s) : launch_gemm_bce<T, 128, true>(a, q, s);
+    return a.N % 256 == 0 ? launch_gemm_bce<T, 256, false>(a, q, s) : launch_gemm_bce<T, 128, false>(a, q, s);
   });
 }
 
@@ -137,6 +138,6 @@ extern "C" int mst_gemm_sigmoid_bce_dgrad_ln(const mst_gemm_args* args, const ms
   hipStream_t s = (hipStream_t)stream;
   return dispatch_act(a.dtype, [&](auto tag) -> int {
     typedef decltype(tag) T;
-    return launch_gemm_bce_dgrad_ln<T>(a, q, g2, l, s);
+    return q.counts ? launch_gemm_bce_dgrad_ln<T, true>(a, q, g2, l, s) : launch_gemm_bce_dgrad_ln<T, false>(a, q, g2, l, s);
   });
 }

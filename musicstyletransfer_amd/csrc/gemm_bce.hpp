@@ -20,7 +20,14 @@ namespace mst {
 // gemm_mainloop's stage layout (BK = 64: columns [64 s, 64 s + 64) in stage buffer s, 16-byte chunks XOR-swizzled by the row)
 // bce_tile_finish: the tile's epilogue, from the fp32 accumulators of the 64 x BN logit tile at (m0, n0). KEEP 1: the stage layout
 // above; KEEP 2: the kept tile is row-major with a row stride of BN + 8 elements (ffn_ln_body's x tile: dec_tail_kernel).
-template <typename T, int BN, int KEEP>
+// `red`, the static LDS a kernel hands to bce_tile_finish (16-byte aligned): a word per wave for the loss and the positive count, then
+// (CNT) four per wave for the piano-roll counts
+constexpr int BCE_RED_LOSS = 512 / 64;
+constexpr int bce_red_words(bool cnt) { return cnt ? 5 * BCE_RED_LOSS : BCE_RED_LOSS; }
+// CNT: the launch keeps the piano-roll counts (q.counts is set). A compile-time switch: as a run-time test of the pointer the counting
+// code cost dec_tail_kernel six more spilled SGPRs and 2.1 us with counts == NULL (docs/kernel_notes.md); without CNT the code is the
+// kernel's of before.
+template <typename T, int BN, int KEEP, bool CNT>
 __device__ __forceinline__ void bce_tile_finish(const mst_gemm_args& a, const mst_bce_args& q, unsigned char* smem, float* red, u32x4* keepA,
                                                 f32x4 (&acc)[(BN / 4) / 16][(64 / 2) / 16], int64_t m0, int64_t n0, const float (&bias8)[8]) {
   constexpr int BM = 64, WGM = 2, WGN = 4, NT = 512;
@@ -56,6 +63,9 @@ __device__ __forceinline__ void bce_tile_finish(const mst_gemm_args& a, const ms
   const int64_t gc = n0 + nc;                   // this thread's 8 pitches in the frame
   const float inv_n = 1.f / ((float)q.T * (float)P), ls = q.label_smoothing;
   float lsum = 0.f;
+  // the piano-roll counts of this thread's live cells (mst_bce_args.counts), 16 bits each: tp | pred << 16 | pos << 32 | cells << 48
+  // (a tile has 64 BN <= 2^14 cells, so the workgroup's sums stay inside their fields)
+  uint64_t roll = 0;
   const float s1 = (1.f - ls) + 0.5f * ls, s0 = 0.5f * ls;
   auto sweep = [&](auto dwc) {
     constexpr bool DW = decltype(dwc)::value;
@@ -78,6 +88,7 @@ __device__ __forceinline__ void bce_tile_finish(const mst_gemm_args& a, const ms
         in_dom = in_dom && bce_fast_domain(x8[e]);
       }
       const bool fast = __all(in_dom || !live);  // wave-uniform (bce_math.hpp: three transcendental instructions per element, not six)
+      if (CNT && live) roll += roll_pack<16>(roll_predicted<8>(x8, 8), lab8, 8);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const float y = (float)((lab8 >> (8 * e)) & 0xFFull);
@@ -104,16 +115,18 @@ __device__ __forceinline__ void bce_tile_finish(const mst_gemm_args& a, const ms
   if (q.downweight) sweep(std::true_type()); else sweep(std::false_type());
   lsum = wave_sum(lsum);
   if (lane == 0) red[wave] = lsum;
+  if constexpr (CNT) roll_wave16(roll, red + BCE_RED_LOSS);
   __syncthreads();
   if (tid == 0) {
     float tot = 0.f;
 #pragma unroll
     for (int i = 0; i < NT / 64; ++i) tot += red[i];
     atomicAdd(q.loss + b, tot * inv_n);
+    if constexpr (CNT) roll_total16<NT / 64>(red + BCE_RED_LOSS, q.counts);
   }
 }
 
-template <typename T, int BN, bool KEEP>
+template <typename T, int BN, bool KEEP, bool CNT>
 __device__ __forceinline__ void gemm_bce_tile(const mst_gemm_args& a, const mst_bce_args& q, unsigned char* smem, float* red, u32x4* keepA) {
   constexpr int BM = 64, WGM = 2, WGN = 4;
   f32x4 acc[(BN / WGN) / 16][(BM / WGM) / 16];
@@ -121,7 +134,7 @@ __device__ __forceinline__ void gemm_bce_tile(const mst_gemm_args& a, const mst_
   float bias8[8];
   gemm_bias_preload<BM, BN>(a, bias8);
   gemm_mainloop<T, BM, BN, WGM, WGN, 64>(a, smem, acc, m0, n0);
-  bce_tile_finish<T, BN, KEEP ? 1 : 0>(a, q, smem, red, keepA, acc, m0, n0, bias8);
+  bce_tile_finish<T, BN, KEEP ? 1 : 0, CNT>(a, q, smem, red, keepA, acc, m0, n0, bias8);
 }
 
 }  // namespace mst

@@ -134,7 +134,8 @@ __global__ __launch_bounds__(BCE_THREADS) void sigmoid_bce_kernel(int64_t rows_p
                                                                   int64_t ld, const uint8_t* __restrict__ labels, float ls,
                                                                   int downweight, int32_t* __restrict__ npos,
                                                                   float* __restrict__ loss, T* __restrict__ probs, int64_t ldp,
-                                                                  T* __restrict__ dlogits, int64_t ldd, float gscale) {
+                                                                  T* __restrict__ dlogits, int64_t ldd, float gscale,
+                                                                  uint64_t* __restrict__ counts) {
   __shared__ float red[BCE_THREADS / 64];
   const int64_t b = blockIdx.y;
   const int tid = threadIdx.x;
@@ -161,6 +162,15 @@ __global__ __launch_bounds__(BCE_THREADS) void sigmoid_bce_kernel(int64_t rows_p
   // 8-byte label load) where the rows allow, else 4
   const float s1 = (1.f - ls) + 0.5f * ls, s0 = 0.5f * ls;
   float acc = 0.f;
+  // the piano-roll counts of this thread's cells, four 8-bit fields in one register (bce_math.hpp: roll_pack<8>). A thread may sweep
+  // any number of cells, so one that reaches 128 adds its fields to the workgroup's 64-bit sums in LDS and starts again (cells is the
+  // largest field and grows by at most 8: no field passes 135). At the shapes the engine runs a thread sweeps 64 cells or fewer.
+  __shared__ unsigned long long roll_wg[4];
+  uint32_t roll = 0;
+  if (counts) {  // (wave-uniform)
+    if (tid < 4) roll_wg[tid] = 0;
+    __syncthreads();
+  }
   auto sweep = [&](auto dwc, auto vecc) {
     constexpr bool DW = decltype(dwc)::value;
     constexpr int VEC = decltype(vecc)::value;
@@ -190,6 +200,15 @@ __global__ __launch_bounds__(BCE_THREADS) void sigmoid_bce_kernel(int64_t rows_p
 #pragma unroll
           for (int e = 0; e < 4; ++e)
             if (c0 + e < P) lab |= (uint64_t)labels[r * P + c0 + e] << (8 * e);
+        }
+      }
+      if (counts) {  // (wave-uniform; pad columns are not cells)
+        const int n = VEC == 8 ? 8 : (P - c0 < VEC ? P - c0 : VEC);
+        roll += (uint32_t)roll_pack<8>(roll_predicted<VEC>(x, n), lab, n);
+        if ((int32_t)roll < 0) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) atomicAdd(roll_wg + k, (unsigned long long)((roll >> (8 * k)) & 0xFFu));
+          roll = 0;
         }
       }
       bool in_dom = true;  // (pad columns hold zero logits)
@@ -230,8 +249,20 @@ __global__ __launch_bounds__(BCE_THREADS) void sigmoid_bce_kernel(int64_t rows_p
   typedef std::integral_constant<int, 4> V4;
   if (downweight) { if (wide) sweep(std::true_type(), V8()); else sweep(std::true_type(), V4()); }
   else { if (wide) sweep(std::false_type(), V8()); else sweep(std::false_type(), V4()); }
+  if (counts) {  // a wave's fields sum to less than 2^14: exact in fp32; block_sum_1024's barriers order the LDS sums before their reader
+    float v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = wave_sum((float)((roll >> (8 * k)) & 0xFFu));
+    if ((tid & 63) == 0) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) atomicAdd(roll_wg + k, (unsigned long long)v[k]);
+    }
+  }
   const float total = block_sum_1024(acc, red);
-  if (tid == 0) atomicAdd(loss + b, total * inv_n);
+  if (tid == 0) {
+    atomicAdd(loss + b, total * inv_n);
+    if (counts) roll_add_slot(counts, roll_wg[0], roll_wg[1], roll_wg[2], roll_wg[3]);
+  }
 }
 
 // BinaryCrossEntropy(from_sigmoid=True) (loss.py:40-56): `pred` already holds probabilities. Forward only; one
@@ -395,12 +426,13 @@ extern "C" int mst_sigmoid_bce_form(int dtype, int64_t B, int64_t T, int64_t P, 
   });
 }
 
-extern "C" int mst_sigmoid_bce(int dtype, int64_t B, int64_t T, int64_t P, const void* logits, int64_t ld,
-                               const uint8_t* labels, float label_smoothing, int downweight, int32_t* npos,
-                               float* loss, void* probs, int64_t ldp, void* dlogits, int64_t ldd, float gscale,
-                               int pre_zeroed, mst_stream_t stream) {
+extern "C" int mst_sigmoid_bce_counts(int dtype, int64_t B, int64_t T, int64_t P, const void* logits, int64_t ld,
+                                      const uint8_t* labels, float label_smoothing, int downweight, int32_t* npos,
+                                      float* loss, void* probs, int64_t ldp, void* dlogits, int64_t ldd, float gscale,
+                                      int pre_zeroed, uint64_t* counts, mst_stream_t stream) {
   const int rc = check_sigmoid_bce(B, T, P, logits, ld, labels, downweight, npos, loss, probs, ldp, dlogits, ldd);
   if (rc) return rc;
+  MST_CHECK_ARG((uintptr_t)counts % 16 == 0, "mst_sigmoid_bce_counts: counts must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   if (!pre_zeroed) {
     hipError_t e = hipMemsetAsync(loss, 0, sizeof(float) * B, s);
@@ -410,10 +442,18 @@ extern "C" int mst_sigmoid_bce(int dtype, int64_t B, int64_t T, int64_t P, const
   return dispatch_act(dtype, [&](auto tag) -> int {
     typedef decltype(tag) TT;
     hipLaunchKernelGGL((sigmoid_bce_kernel<TT>), dim3((unsigned)gx, (unsigned)B), dim3(BCE_THREADS), 0, s, T, (int)P, (const TT*)logits,
-                       ld, labels, label_smoothing, downweight, npos, loss, (TT*)probs, ldp, (TT*)dlogits, ldd, gscale);
+                       ld, labels, label_smoothing, downweight, npos, loss, (TT*)probs, ldp, (TT*)dlogits, ldd, gscale, counts);
     MST_CHECK_LAUNCH("sigmoid_bce_kernel");
     return MST_OK;
   });
+}
+
+extern "C" int mst_sigmoid_bce(int dtype, int64_t B, int64_t T, int64_t P, const void* logits, int64_t ld,
+                               const uint8_t* labels, float label_smoothing, int downweight, int32_t* npos,
+                               float* loss, void* probs, int64_t ldp, void* dlogits, int64_t ldd, float gscale,
+                               int pre_zeroed, mst_stream_t stream) {
+  return mst_sigmoid_bce_counts(dtype, B, T, P, logits, ld, labels, label_smoothing, downweight, npos, loss, probs, ldp, dlogits, ldd, gscale,
+                                pre_zeroed, nullptr, stream);
 }
 
 extern "C" int mst_reparam_kl_fwd(int64_t B, int64_t Z, const float* mu, const float* sigma, const float* eps,

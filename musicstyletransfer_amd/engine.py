@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import ops as o
-from ._lib import CE_MAX_WORKGROUPS
+from ._lib import CE_MAX_WORKGROUPS, ROLL_SLOTS
 from .ops import roundup
 
 
@@ -231,6 +231,8 @@ class ParamStore:
         self._tail_listeners = []
         self._rng_state_infer = None
         self.tok_parts = torch.zeros(CE_MAX_WORKGROUPS, 4, **f32) if cfg.kind == "token" else None
+        # roll_counts = the piano-roll ends' slots of {tp, pred, pos, cells} the BCE launches add to (mst_bce_args.counts)
+        self.roll_counts = torch.zeros(ROLL_SLOTS, 4, dtype=torch.int64, device=device) if cfg.kind == "pianoroll" else None
         if params_np is None:
             params_np = xavier_init(cfg, np.random.default_rng(seed))
         self.load_numpy(params_np)
@@ -344,7 +346,8 @@ class ParamStore:
 
     def read_metrics(self, reset=True):
         """one device->host read of the running sums: {'kl_sum', 'total_sum', 'count'} and, for the token ends,
-        {'nll_sum', 'acc_hits', 'topk_hits', 'n_tokens'} (the caller orders this after the steps it wants included).
+        {'nll_sum', 'acc_hits', 'topk_hits', 'n_tokens'}, for the piano-roll ends the counts {'roll_tp', 'roll_pred', 'roll_pos',
+        'roll_cells'} as ints (roll_scores turns them into precision / recall / F1) (the caller orders this after the steps it wants included).
         The step-status words travel in the same copy: a set flag is handled here (handle_step_status). So does the schedule
         block: once a plan with training schedules has run, 'kl_weight' (beta_t) and 'lr_scale' (f_lr) of the last such step.
         (The last step that RAN: after a step the guards skipped, whose step count was taken back, the block still holds that
@@ -374,12 +377,17 @@ class ParamStore:
         if self.tok_parts is not None:
             t = self.tok_parts.cpu().double().sum(0).tolist()
             out.update(nll_sum=t[0], acc_hits=t[1], topk_hits=t[2], n_tokens=t[3])
+        if self.roll_counts is not None:
+            c = self.roll_counts.cpu().sum(0).tolist()
+            out.update(roll_tp=int(c[0]), roll_pred=int(c[1]), roll_pos=int(c[2]), roll_cells=int(c[3]))
         if reset:
             o.zero(self.metric_acc)
             if g_steps > 0:
                 o.zero(self.gstat[2:6])
             if self.tok_parts is not None:
                 o.zero(self.tok_parts)
+            if self.roll_counts is not None:
+                o.zero(self.roll_counts)
         return out
 
     def wgrad_scratch(self, n_floats=16 * 1024 * 1024 + 256 * 256):
@@ -759,6 +767,15 @@ Forms = namedtuple("Forms", "tails riders shadows fuse_bce bce_dgrad skip_row0 c
                             "attn_proj_e attn_proj_d")
 
 
+def roll_scores(tp, pred, pos, cells):
+    """the piano-roll counts of ParamStore.read_metrics (a cell is predicted where its logit is > 0) as scores: precision = tp / pred,
+    recall = tp / pos, f1 = 2 tp / (pred + pos), cell_acc = (cells - pred - pos + 2 tp) / cells; NaN where a denominator is 0"""
+    nan = float("nan")
+    return dict(precision=tp / pred if pred else nan, recall=tp / pos if pos else nan,
+                f1=2 * tp / (pred + pos) if pred + pos else nan,
+                cell_acc=(cells - pred - pos + 2 * tp) / cells if cells else nan)
+
+
 def check_schedule(kl_warmup_steps=0, kl_cycle_steps=0, kl_free_bits=0.0, lr_warmup_steps=0):
     """the combinations of training-schedule settings that mean something; raises ValueError otherwise"""
     for name, val in (("kl_warmup_steps", kl_warmup_steps), ("kl_cycle_steps", kl_cycle_steps), ("lr_warmup_steps", lr_warmup_steps)):
@@ -951,6 +968,7 @@ class StepPlan:
         self.ride_queues = self._recon_buf[nb4 + 32:].view(torch.int32)  # [0]: forward tail's riders, [32]: backward tail's
         self.metric_acc = store.metric_acc  # [sum kl, sum total, count]  (trainer.py:115-116)
         self.track_token_metrics = False  # Trainer: accumulate ppl / acc / topk sums on the device in the CE launch
+        self.track_roll_metrics = False   # Trainer: count tp / pred / pos / cells on the device in whichever launch computes the BCE
         self.logits = None if self.forms.fuse_bce else act(B * T, cfg.out_dim)  # (fused: the logits never reach HBM)
         self.dlogits = act(B * T, cfg.out_dim)
         if cfg.kind == "token":
@@ -1341,6 +1359,7 @@ class StepPlan:
         """combine=False: the total loss / running metric sums are left to optimizer() (they ride on the Adam launch)"""
         cfg, B, T, F = self.cfg, self.B, self.T, self.forms
         dl = self.dlogits if with_grad else None
+        counts = self.store.roll_counts if self.track_roll_metrics else None
         if cfg.kind == "token":
             o.softmax_ce(self.logits, self.labels, self.recon, B, T, cfg.out_dim, probs=self.probs, dlogits=dl,
                          gscale=self.gscale, pre_zeroed=True,
@@ -1359,7 +1378,7 @@ class StepPlan:
                                                 self.bd_l[last], B * T))
             loss = dict(A=self.dec_out, B=self.store.h("decoder.output_layer.weight"), labels=self.labels, loss=self.recon, T=T,
                         dlogits=dl, probs=self.probs, label_smoothing=self.ls, downweight=self.nld, gscale=self.gscale, M=B * T,
-                        K=cfg.d_model, bias=self.store.p("decoder.output_layer.bias"), a_remap=(T, T + 1, 1))
+                        K=cfg.d_model, bias=self.store.p("decoder.output_layer.bias"), a_remap=(T, T + 1, 1), counts=counts)
             if F.dec_tail:
                 # ... and around it, in the same workgroups again, the last decoder layer's row-wise block (forward() left it out) and
                 # that block's backward (backward_early skips its launch, and registers its partial sums and weight gradients as ever)
@@ -1373,7 +1392,7 @@ class StepPlan:
         else:
             o.sigmoid_bce(self.logits, self.labels, self.recon, B, T, cfg.out_dim, label_smoothing=self.ls,
                           downweight=self.nld, npos=self.npos, probs=self.probs, dlogits=dl, gscale=self.gscale,
-                          pre_zeroed=True)
+                          pre_zeroed=True, counts=counts)
         if combine:
             o.loss_combine(self.recon, self.kl, self.kl_weight, self.total, self.metric_acc, guard=self._guard())
 

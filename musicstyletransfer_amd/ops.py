@@ -202,7 +202,15 @@ def bce_fusion_pays(P):
     return P <= 256
 
 
-def _gemm_bce_args(A, B, labels, loss, T, dlogits=None, probs=None, logits=None, label_smoothing=0.0, downweight=False, gscale=1.0, **kw):
+def _roll_counts(counts):
+    """counts: int64 [ROLL_SLOTS, 4], the running piano-roll counts {tp, pred, pos, cells} a BCE launch adds to (see the header)"""
+    if counts is not None:
+        assert counts.dtype == torch.int64 and counts.is_contiguous() and tuple(counts.shape) == (_lib.ROLL_SLOTS, 4)
+    return ptr(counts)
+
+
+def _gemm_bce_args(A, B, labels, loss, T, dlogits=None, probs=None, logits=None, label_smoothing=0.0, downweight=False, gscale=1.0,
+                   counts=None, **kw):
     g = _gemm_args(A, B, dlogits if dlogits is not None else A, N=B.shape[0], **kw)
     if dlogits is None:
         g.C, g.ldc = None, 0
@@ -211,12 +219,13 @@ def _gemm_bce_args(A, B, labels, loss, T, dlogits=None, probs=None, logits=None,
     q.probs, q.ldp = ptr(probs), (ld(probs) if probs is not None else 0)
     q.logits, q.ldl = ptr(logits), (ld(logits) if logits is not None else 0)
     q.gscale = gscale
+    q.counts = _roll_counts(counts)
     return g, q
 
 
 def gemm_sigmoid_bce(A, B, labels, loss, T, dgrad=None, **kw):
     """loss[b] += BCE(sigmoid(A @ B^T + bias), labels) and dlogits = its gradient, in one launch; **kw: dlogits, probs, logits,
-    label_smoothing, downweight, gscale and the GEMM's M, K, bias, a_remap.
+    label_smoothing, downweight, gscale, counts (_roll_counts) and the GEMM's M, K, bias, a_remap.
     dgrad: keyword arguments of gemm_nt_ln_bwd whose A operand is that dlogits — the output layer's input gradient + LayerNorm
     backward ride on the same launch where the shapes allow (mst_gemm_sigmoid_bce_dgrad_ln)"""
     g, q = _gemm_bce_args(A, B, labels, loss, T, **kw)
@@ -808,10 +817,15 @@ def bce_from_probs(probs, labels, loss, label_smoothing=0.0, downweight=False):
 
 
 def sigmoid_bce(logits, labels, loss, B, T, P, label_smoothing=0.0, downweight=False, npos=None, probs=None,
-                dlogits=None, gscale=1.0, pre_zeroed=False):
-    call("mst_sigmoid_bce", dt(logits), B, T, P, ptr(logits), ld(logits), ptr(labels), label_smoothing,
-         1 if downweight else 0, ptr(npos), ptr(loss), ptr(probs), (ld(probs) if probs is not None else 0),
-         ptr(dlogits), (ld(dlogits) if dlogits is not None else 0), gscale, 1 if pre_zeroed else 0, stream())
+                dlogits=None, gscale=1.0, pre_zeroed=False, counts=None):
+    """counts (_roll_counts): the launch also adds its cells' piano-roll counts (mst_sigmoid_bce_counts)"""
+    args = (dt(logits), B, T, P, ptr(logits), ld(logits), ptr(labels), label_smoothing,
+            1 if downweight else 0, ptr(npos), ptr(loss), ptr(probs), (ld(probs) if probs is not None else 0),
+            ptr(dlogits), (ld(dlogits) if dlogits is not None else 0), gscale, 1 if pre_zeroed else 0)
+    if counts is None:
+        call("mst_sigmoid_bce", *args, stream())
+    else:
+        call("mst_sigmoid_bce_counts", *args, _roll_counts(counts), stream())
 
 
 def _addr(t):
