@@ -472,6 +472,8 @@ int mst_attn_bwd_form(int dtype, int64_t B, int64_t S, int64_t H, int64_t dh, in
  * rowsum(dO * O) and dQ | dK | dV into dqkv (the qkv layout). Key blocks above the diagonal are skipped,
  * nothing S x S reaches HBM, no atomics: identical calls give identical bits. dh in {16, 32, 64}; qkv, out,
  * dout and dqkv 16-byte aligned with leading dimensions that are multiples of 8.
+ * A query without an admissible key (key 0 masked, or every key up to it) gets out = 0, lse = -inf in both planes
+ * and delta = 0, and contributes to no gradient: its dQ row is 0 (a contract, held by tests/causal_refs.py).
  * ------------------------------------------------------------------------ */
 int mst_attn_causal_fwd(int dtype, int64_t B, int64_t S, int64_t H, int64_t dh,
                         const void* qkv, int64_t ld_qkv, int64_t k_off, int64_t q_off, int64_t v_off,

@@ -5,6 +5,8 @@
 //   logit[q,k] = Q[q]·K[k] / sqrt(dh)              for k <= q and keymask[b,k]; excluded (P = 0) otherwise
 //   P[q,:]     = softmax over k of the non-excluded logits
 //   O[q]       = sum_k P[q,k] V[k]
+// A query without an admissible key (key 0 masked, or every key up to it): O[q] = 0, lse = -inf in both planes (m stays -inf, l stays
+// 0, logf(0)), delta = 0, and no pair of its row is admitted by the backward, so it reaches no gradient and its dQ row is 0.
 // This is the model DecodePlan(attention="key") samples from (attention.hip attn_decode_kernel, mode 1).
 //
 // Three kernels on v_mfma_f32_32x32x16, one wave per workgroup and per 32-row block, the blocks of a (batch, head) walked in a
