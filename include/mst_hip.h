@@ -329,6 +329,23 @@ int mst_outer_jobs(const mst_outer_job* jobs, int n, mst_stream_t stream);
 int mst_gemm_wgrad_batch_flush(const mst_wgrad_args* list, int n, float* scratch, int64_t scratch_bytes,
                                const mst_partial_sum* sums, int n_sums, const mst_outer_job* outers, int n_outers,
                                mst_stream_t stream);
+/* The decoder class table's gradient, dcls[classes[b], j] += tvec[b, j] (b < B in batch order, j < Dd), as a launch of its own:
+ * classes int32 [B], tvec fp32 [B, Dd] contiguous (scratch[0 .. B*Dd) of mst_latent_bwd_vec), dcls fp32 [n_classes, ld_cls >= Dd],
+ * accumulated into. No atomics: a 256-thread workgroup owns 64 columns, its four waves take a quarter of the batch each and the
+ * quarters are added in order. What mst_latent_bwd_vec launches behind its own kernel when it is given dcls_d. */
+int mst_class_table_grad(const int32_t* classes, const float* tvec, float* dcls, int64_t ld_cls, int64_t B, int64_t Dd,
+                         mst_stream_t stream);
+/* mst_gemm_wgrad_batch_flush (ABI 115) with that class-table job taken along, for a caller that passed mst_latent_bwd_vec no table
+ * (dcls_d NULL): nothing but the optimizer reads the table's gradient, so it need not be a launch inside the backward pass's dependent
+ * chain. cls_classes, cls_tvec, cls_dcls, cls_ld, cls_B, cls_Dd: mst_class_table_grad's arguments (all NULL / 0: no job, and the
+ * call is mst_gemm_wgrad_batch_flush). With a reduction pass, cdiv(cls_Dd, 64) more workgroups of it run the job behind the
+ * column-sum and outer-product jobs; else it is one mst_class_table_grad launch after the weight gradients (and after the sums' and
+ * outers' launches). Either way the same workgroups in the same order: bit-identical to the launch. mst_gemm_wgrad_plan's plan[3]
+ * bit 0 says which. The job is validated before any HIP call. */
+int mst_gemm_wgrad_batch_flush_cls(const mst_wgrad_args* list, int n, float* scratch, int64_t scratch_bytes,
+                                   const mst_partial_sum* sums, int n_sums, const mst_outer_job* outers, int n_outers,
+                                   const int32_t* cls_classes, const float* cls_tvec, float* cls_dcls, int64_t cls_ld,
+                                   int64_t cls_B, int64_t cls_Dd, mst_stream_t stream);
 /* What mst_gemm_wgrad_batch_flush(list, n, scratch, scratch_bytes, ...) launches, decided on the host from the arguments alone (no
  * HIP call, no device needed; the pointers are looked at for NULL and alignment only, and a scratch buffer is present when
  * scratch_bytes > 0). The flush calls the same decision and nothing else. plan is a host array of 4 + 16 entries:
@@ -574,7 +591,9 @@ int mst_latent_rows(int dtype, int64_t N, int64_t M, int64_t Z, int64_t Dd,
  * gscale is the encoder-side loss scale, enc_scale = gscale / the decoder-side loss scale. Leaves t = alpha_d * d(dec_in[b, 0, :]) at
  * scratch[0 .. B*Dd) and d[mu | sigma] at scratch[B*Dd .. B*(Dd + 2Z)) (fp32), writes d(enc_out) row 0. The remaining parameter
  * gradients are two mst_outer_job of the caller's weight-gradient flush:
- *   dWl[2Z, De] += dlat^T enc_out[:, 0, :], dbl += sum_b dlat;   dWh[Dd, Z] += t^T z, dbh += sum_b t. */
+ *   dWl[2Z, De] += dlat^T enc_out[:, 0, :], dbl += sum_b dlat;   dWh[Dd, Z] += t^T z, dbh += sum_b t.
+ * dcls_d may be NULL (ABI 115; in all four forms): the class table's gradient is then not computed here (one launch less) and the
+ * caller takes it from scratch later, as the class-table job of mst_gemm_wgrad_batch_flush_cls or by mst_class_table_grad. */
 int mst_latent_bwd_vec(int dtype, int64_t B, int64_t De, int64_t Z, int64_t Dd, const float* Wl, const float* eps, const float* Wh,
                        const int32_t* classes, const float* mu, const float* sigma, const void* d_dec_in, int64_t dec_sample_stride,
                        float alpha_d, float kl_weight, float gscale, float enc_scale, float* dcls_d, int64_t ld_cls,

@@ -14,6 +14,7 @@
 #include "common.hpp"
 #include "partial_sums.hpp"
 #include "outer_jobs.hpp"
+#include "class_job.hpp"
 
 namespace mst {
 
@@ -478,12 +479,18 @@ __global__ __launch_bounds__(WGN * WGK * 64) void wgrad_kernel(WgradBatch b) {
 // dW[n, k] += scale * sum over the M-slabs (in slab order) of the tiles wgrad_kernel left in the scratch buffer.
 // grid = (tile elements / 1024, tiles); a thread owns 4 consecutive k of one n.
 template <int BN, int BKO>
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(WgradBatch b, PartialSumBatch ps, OuterBatch ob) {
-  if (blockIdx.y >= (unsigned)b.tile_prefix[b.n]) {  // rows of workgroups past the tiles: the caller's column-sum / outer-product jobs
-    __shared__ f32x4 red[16][16];
+// (waves_per_eu: the tiles' workgroups need 60 VGPRs and are ten waves per SIMD deep at configs[1]. The class-table branch holds the
+// classes of a 16-row chunk in scalar registers, 106 of them, which alone would take the whole launch to seven waves per SIMD; held
+// to eight it keeps 62 VGPRs and no scratch, and that branch moves some scalars through VGPR lanes)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void wgrad_reduce_kernel(WgradBatch b, PartialSumBatch ps,
+                                                                                                  OuterBatch ob, ClassJob cj) {
+  if (blockIdx.y >= (unsigned)b.tile_prefix[b.n]) {  // rows of workgroups past the tiles: the caller's column-sum / outer-product /
+    __shared__ f32x4 red[16][16];                    // class-table jobs, in that order
     const int wg = (int)((blockIdx.y - (unsigned)b.tile_prefix[b.n]) * gridDim.x + blockIdx.x);
-    if (wg < ps.wg_prefix[ps.n]) partial_sums_wg(ps, wg, red);
-    else if (wg - ps.wg_prefix[ps.n] < ob.wg_prefix[ob.n]) outer_jobs_wg(ob, wg - ps.wg_prefix[ps.n], reinterpret_cast<float(*)[64]>(&red[0][0]));
+    const int wo = wg - ps.wg_prefix[ps.n], wc = wo - ob.wg_prefix[ob.n];
+    if (wo < 0) partial_sums_wg(ps, wg, red);
+    else if (wc < 0) outer_jobs_wg(ob, wo, reinterpret_cast<float(*)[64]>(&red[0][0]));
+    else if (wc < cj.wgs) class_table_block(wc, threadIdx.x, cj.B, cj.Dd, cj.tvec, cj.classes, cj.dcls, cj.ld_cls);  // (its own LDS)
     return;
   }
   const int64_t tile_lin = blockIdx.y;
@@ -528,11 +535,12 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(WgradBatch b, Partial
   if (bias_here) a.db[n] += sb * a.scale;  // (slabs in order, as the tile)
 }
 
-static_assert(sizeof(WgradBatch) + sizeof(PartialSumBatch) + sizeof(OuterBatch) <= 4096, "kernel arguments of the reduction pass");
+static_assert(sizeof(WgradBatch) + sizeof(PartialSumBatch) + sizeof(OuterBatch) + sizeof(ClassJob) <= 4096, "kernel arguments of the reduction pass");
 
-// *ps_done: the column-sum jobs were taken along by the reduction pass
+// *ps_done: the column-sum, outer-product and class-table jobs were taken along by the reduction pass
 template <typename T>
-static int launch_wgrad(const WgradBatch& b, int big, const PartialSumBatch* ps, bool* ps_done, hipStream_t s, const OuterBatch& ob) {
+static int launch_wgrad(const WgradBatch& b, int big, const PartialSumBatch* ps, bool* ps_done, hipStream_t s, const OuterBatch& ob,
+                        const ClassJob& cj) {
   const int64_t total = cdiv(b.item_prefix[b.n], 8) * 8;  // padded to whole XCD rounds (see the kernel)
   if (big == 3) {
     constexpr int BN = 256, BKO = 256;
@@ -547,9 +555,9 @@ static int launch_wgrad(const WgradBatch& b, int big, const PartialSumBatch* ps,
       none.n = 0;
       for (int i = 0; i <= PS_MAXJ; ++i) none.wg_prefix[i] = 0;
       const PartialSumBatch& pb = ps ? *ps : none;
-      const unsigned extra = (unsigned)cdiv(pb.wg_prefix[pb.n] + ob.wg_prefix[ob.n], GX);
-      hipLaunchKernelGGL((wgrad_reduce_kernel<BN, BKO>), dim3(GX, (unsigned)b.tile_prefix[b.n] + extra), dim3(256), 0, s, b, pb, ob);
-      *ps_done = true;  // (the column sums and the outer products)
+      const unsigned extra = (unsigned)cdiv(pb.wg_prefix[pb.n] + ob.wg_prefix[ob.n] + cj.wgs, GX);
+      hipLaunchKernelGGL((wgrad_reduce_kernel<BN, BKO>), dim3(GX, (unsigned)b.tile_prefix[b.n] + extra), dim3(256), 0, s, b, pb, ob, cj);
+      *ps_done = true;  // (the column sums, the outer products and the class table)
     }
   } else if (big == 2) {
     constexpr int BN = 256, BKO = 128;
@@ -678,12 +686,18 @@ static int wgrad_plan(const mst_wgrad_args* list, int n, bool have_scratch, int6
 
 using namespace mst;
 
-extern "C" int mst_gemm_wgrad_batch_flush(const mst_wgrad_args* list, int n, float* scratch, int64_t scratch_bytes,
-                                          const mst_partial_sum* sums, int n_sums, const mst_outer_job* outers, int n_outers,
-                                          mst_stream_t stream) {
+extern "C" int mst_gemm_wgrad_batch_flush_cls(const mst_wgrad_args* list, int n, float* scratch, int64_t scratch_bytes,
+                                              const mst_partial_sum* sums, int n_sums, const mst_outer_job* outers, int n_outers,
+                                              const int32_t* cls_classes, const float* cls_tvec, float* cls_dcls, int64_t cls_ld,
+                                              int64_t cls_B, int64_t cls_Dd, mst_stream_t stream) {
   OuterBatch ob;
   {
     int rc = pack_outer_jobs(outers, n_outers, ob);
+    if (rc) return rc;
+  }
+  ClassJob cj;
+  {
+    int rc = pack_class_job(cls_classes, cls_tvec, cls_dcls, cls_ld, cls_B, cls_Dd, cj);
     if (rc) return rc;
   }
   MST_CHECK_ARG(n_sums >= 0 && (n_sums == 0 || sums != nullptr), "mst_gemm_wgrad_batch_flush: bad column-sum job list");
@@ -705,11 +719,19 @@ extern "C" int mst_gemm_wgrad_batch_flush(const mst_wgrad_args* list, int n, flo
   bool ps_done = false;
   int rc = dispatch_act(list[0].dtype, [&](auto tag) -> int {
     typedef decltype(tag) T;
-    return launch_wgrad<T>(b, pl.form, n_sums > 0 ? &ps : nullptr, &ps_done, s, ob);
+    return launch_wgrad<T>(b, pl.form, n_sums > 0 ? &ps : nullptr, &ps_done, s, ob, cj);
   });
   if (rc == MST_OK && n_sums > 0 && !ps_done) rc = mst_partial_sums(sums, n_sums, stream);  // no reduction pass: own launch
   if (rc == MST_OK && n_outers > 0 && !ps_done) rc = mst_outer_jobs(outers, n_outers, stream);
+  if (rc == MST_OK && cj.wgs > 0 && !ps_done) rc = mst_class_table_grad(cls_classes, cls_tvec, cls_dcls, cls_ld, cls_B, cls_Dd, stream);
   return rc;
+}
+
+extern "C" int mst_gemm_wgrad_batch_flush(const mst_wgrad_args* list, int n, float* scratch, int64_t scratch_bytes,
+                                          const mst_partial_sum* sums, int n_sums, const mst_outer_job* outers, int n_outers,
+                                          mst_stream_t stream) {
+  return mst_gemm_wgrad_batch_flush_cls(list, n, scratch, scratch_bytes, sums, n_sums, outers, n_outers, nullptr, nullptr, nullptr, 0, 0, 0,
+                                        stream);
 }
 
 extern "C" int mst_gemm_wgrad_plan(const mst_wgrad_args* list, int n, int64_t scratch_bytes, int64_t* plan) {

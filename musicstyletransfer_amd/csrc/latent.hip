@@ -17,6 +17,7 @@
 #include <type_traits>
 #include "common.hpp"
 #include "outer_jobs.hpp"
+#include "class_job.hpp"
 #include "latent_fwd.hpp"
 
 namespace mst {
@@ -306,65 +307,8 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_bwd_vec_kernel(int De, int
 }
 
 // (batch_outer: outer_jobs.hpp)
-// dcls[class_b, j] += t[b, j] (the decoder class table's gradient) without fp32 atomics, whose arrival order made the table's
-// gradient — and, through Adam, whole training runs — differ in the last bits from run to run. A 256-thread block owns 64
-// columns; as in batch_outer its four waves take a quarter of the batch each, 16 rows of loads in flight, and the quarters are
-// added in order through LDS. Classes go four at a time in registers (the class index selects, so nothing is indexed
-// dynamically); the table here has two.
-constexpr int CT_ROWS = 16, CT_CLS = 4;
-__device__ __forceinline__ void class_table_block(int blk, int tid, int64_t B, int Dd, const float* __restrict__ tvec,
-                                                  const int32_t* __restrict__ classes, float* __restrict__ dcls, int64_t ld_cls) {
-  __shared__ int s_ncls;
-  __shared__ float red[CT_CLS][4][64];
-  const int o = tid & 63, part = tid >> 6, j = blk * 64 + o;
-  const bool col = j < Dd;
-  const int64_t per = (B + 3) / 4, b0 = part * per, b1 = b0 + per < B ? b0 + per : B;
-  if (tid == 0) s_ncls = 0;
-  __syncthreads();
-  // the number of classes comes out of the first pass's own loads (an integer max in LDS: order-free); a table of more than
-  // CT_CLS classes takes more passes over the batch
-  for (int c0 = 0, n_cls = CT_CLS; c0 < n_cls; c0 += CT_CLS) {
-    float acc[CT_CLS];
-#pragma unroll
-    for (int q = 0; q < CT_CLS; ++q) acc[q] = 0.f;
-    int mx = 0;
-    int64_t b = b0;
-    for (; b + CT_ROWS <= b1; b += CT_ROWS) {  // whole chunks: every load of the chunk in flight at once
-      float v[CT_ROWS];
-      int cl[CT_ROWS];
-#pragma unroll
-      for (int u = 0; u < CT_ROWS; ++u) {
-        cl[u] = classes[b + u];
-        v[u] = col ? tvec[(b + u) * Dd + j] : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < CT_ROWS; ++u) {
-        mx = max(mx, cl[u] + 1);
-#pragma unroll
-        for (int q = 0; q < CT_CLS; ++q) acc[q] += cl[u] - c0 == q ? v[u] : 0.f;  // (rows in batch order; x + 0 is exact)
-      }
-    }
-    for (; b < b1; ++b) {
-      const int cl = classes[b];
-      const float v = col ? tvec[b * Dd + j] : 0.f;
-      mx = max(mx, cl + 1);
-#pragma unroll
-      for (int q = 0; q < CT_CLS; ++q) acc[q] += cl - c0 == q ? v : 0.f;
-    }
-    if (c0 == 0) atomicMax(&s_ncls, mx);
-#pragma unroll
-    for (int q = 0; q < CT_CLS; ++q) red[q][part][o] = acc[q];
-    __syncthreads();
-    n_cls = s_ncls;
-    if (part == 0 && col)
-#pragma unroll
-      for (int q = 0; q < CT_CLS; ++q)
-        if (c0 + q < n_cls) dcls[(int64_t)(c0 + q) * ld_cls + j] += ((red[q][0][o] + red[q][1][o]) + red[q][2][o]) + red[q][3][o];
-    __syncthreads();
-  }
-}
-
-// the class table's gradient as a launch of its own (mst_latent_bwd_vec): grid cdiv(Dd, 64), 256 threads
+// (class_table_block: class_job.hpp)
+// the class table's gradient as a launch of its own (mst_latent_bwd_vec with a table, mst_class_table_grad): grid cdiv(Dd, 64), 256 threads
 __global__ __launch_bounds__(256) void class_table_grad_kernel(int64_t B, int Dd, const float* __restrict__ tvec,
                                                                const int32_t* __restrict__ classes, float* __restrict__ dcls,
                                                                int64_t ld_cls) {
@@ -466,7 +410,7 @@ static int latent_bwd_vec_impl(int dtype, int64_t B, int64_t De, int64_t Z, int6
                                float* scratch, const LatentDx0& x0, const float* sched, const float* kl, mst_stream_t stream) {
   MST_CHECK_ARG(B > 0 && De > 0 && Z > 0 && Dd > 0, "mst_latent_bwd_vec: sizes must be positive");
   MST_CHECK_ARG(!sched == !kl, "mst_latent_bwd_vec_sched: the schedule block and the per-sample KL go together");
-  MST_CHECK_ARG(Wl && eps && Wh && classes && mu && sigma && (d_dec_in || x0.dq) && dcls_d && d_enc_out && scratch, "mst_latent_bwd_vec: null pointer");
+  MST_CHECK_ARG(Wl && eps && Wh && classes && mu && sigma && (d_dec_in || x0.dq) && d_enc_out && scratch, "mst_latent_bwd_vec: null pointer");
   int64_t form[3];
   // (a projection of no columns is refused like any other width that is not 384 or 768)
   int frc = latent_bwd_form(De, Z, Dd, x0.dq ? (x0.nq ? x0.nq : -1) : 0, Wl, form);
@@ -489,7 +433,9 @@ static int latent_bwd_vec_impl(int dtype, int64_t B, int64_t De, int64_t Z, int6
     else if (sched) launch(std::false_type{}, std::true_type{});
     else launch(std::false_type{}, std::false_type{});
     MST_CHECK_LAUNCH("latent_bwd_vec_kernel");
-    // the class table's gradient from the rows the kernel left in scratch (tvec), in batch order
+    // the class table's gradient from the rows the kernel left in scratch (tvec), in batch order. Without a table (dcls_d NULL) the
+    // caller takes it from the same rows later: a class-table job of its weight-gradient flush (mst_gemm_wgrad_batch_flush_cls)
+    if (!dcls_d) return MST_OK;
     hipLaunchKernelGGL(class_table_grad_kernel, dim3((unsigned)cdiv(Dd, 64)), dim3(256), 0, (hipStream_t)stream, B, (int)Dd,
                        (const float*)scratch, classes, dcls_d, ld_cls);
     MST_CHECK_LAUNCH("class_table_grad_kernel");
@@ -535,6 +481,18 @@ extern "C" int mst_latent_bwd_vec_proj_sched(int dtype, int64_t B, int64_t De, i
   LatentDx0 x0 = {dq0, dq_sample_stride, Wq, ld_wq, (int)nq, resid0, resid_sample_stride};
   return latent_bwd_vec_impl(dtype, B, De, Z, Dd, Wl, eps, Wh, classes, mu, sigma, nullptr, 0, alpha_d, 0.f, gscale, enc_scale, dcls_d, ld_cls,
                              d_enc_out, denc_sample_stride, scratch, x0, sched, kl, stream);
+}
+
+extern "C" int mst_class_table_grad(const int32_t* classes, const float* tvec, float* dcls, int64_t ld_cls, int64_t B, int64_t Dd,
+                                    mst_stream_t stream) {
+  ClassJob c;
+  MST_CHECK_ARG(classes || tvec || dcls || B || Dd, "mst_class_table_grad: null pointer");
+  int rc = pack_class_job(classes, tvec, dcls, ld_cls, B, Dd, c);
+  if (rc) return rc;
+  hipLaunchKernelGGL(class_table_grad_kernel, dim3((unsigned)c.wgs), dim3(256), 0, (hipStream_t)stream, c.B, c.Dd, c.tvec, c.classes, c.dcls,
+                     c.ld_cls);
+  MST_CHECK_LAUNCH("class_table_grad_kernel");
+  return MST_OK;
 }
 
 namespace mst {

@@ -933,6 +933,7 @@ class StepPlan:
         self.eps = torch.zeros(B, Z, **f32)
         self.rng_state = store.rng_state(seed)
         self._outers = []
+        self._cls_job = None
 
         self.pos_e = torch.from_numpy(positional_table(De, Se)).to(dev)
         self.pos_d = torch.from_numpy(positional_table(Dd, Sd)).to(dev)
@@ -1293,7 +1294,7 @@ class StepPlan:
         De, Dd = cfg.e_model, cfg.d_model
         Se, Sd = T, T + 1
         sq_e, sq_d = math.sqrt(float(De)), math.sqrt(float(Dd))
-        self._wgrads, self._psums, self._outers = [], [], []  # deferred gradient work of this step
+        self._wgrads, self._psums, self._outers, self._cls_job = [], [], [], None  # deferred gradient work of this step
         # one bookkeeping launch: RNG seed of this step, Adam's step count / lr_t, eps, both padding masks
         need_rng = self.e_p > 0 or self.d_p > 0 or self.internal_eps
         rng = st.rng_state_inference() if self._infer else self.rng_state
@@ -1418,9 +1419,9 @@ class StepPlan:
 
     def _flush_grads(self):
         """the weight gradients collected so far in one wgrad launch; the LayerNorm column sums ride on its reduction pass"""
-        o.gemm_wgrad_batch(self._wgrads, scratch=self.wgrad_scratch, sums=self._psums, outers=self._outers)
+        o.gemm_wgrad_batch(self._wgrads, scratch=self.wgrad_scratch, sums=self._psums, outers=self._outers, cls=self._cls_job)
         self.last_wgrad_launch = (self._wgrads, self._psums)  # (bench.py re-launches the step's own wgrad batch to time it)
-        self._wgrads, self._psums, self._outers = [], [], []
+        self._wgrads, self._psums, self._outers, self._cls_job = [], [], [], None
 
     def _out_ln_bwd(self, side, i, L, p, site0, t, M):
         """The LayerNorm backward a layer's backward pass STARTS with (LN2 of an encoder layer, LN3 of a decoder layer),
@@ -1557,11 +1558,13 @@ class StepPlan:
         # gradient w.r.t. the encoder output: zero except position 0 of every sample
         d_enc = self.d_enc_out
         # nothing but the optimizer reads the latent block's parameter gradients: they ride on the weight-gradient flush (extra
-        # workgroups of its reduction pass) instead of being a launch in the middle of the backward pass's dependent chain
+        # workgroups of its reduction pass) instead of being a launch in the middle of the backward pass's dependent chain — the
+        # decoder class table's too (dcls_d None: no class-table launch behind the latent block's), as the flush's class-table job
         o.latent_bwd_vec(st.p("encoder.latent_proj.weight"), self.eps, st.p("decoder.latent2hid.weight"), self.classes, self.mu,
                          self.sigma, d_x0_d.view(B, Sd, -1), sq_d, self.kl_weight, self.gscale_enc,
-                         st.grad("decoder.class2hid.weight"), d_enc.view(B, Se, -1), self.lat_scratch,
+                         None, d_enc.view(B, Se, -1), self.lat_scratch,
                          enc_scale=self.gscale_enc / self.gscale, proj=dx0, sched=(st.sched, self.kl) if F.sched else None)
+        self._cls_job = o.class_job(self.classes, self.lat_scratch, st.grad("decoder.class2hid.weight"), B, Dd)
         self._outers += o.latent_outer_jobs(self.lat_scratch, self.enc_out.view(B, Se, -1), self.z,
                                             st.grad("encoder.latent_proj.weight"), st.grad("encoder.latent_proj.bias"),
                                             st.grad("decoder.latent2hid.weight"), st.grad("decoder.latent2hid.bias"))

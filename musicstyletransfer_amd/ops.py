@@ -501,25 +501,46 @@ def outer_jobs(jobs):
         call("mst_outer_jobs", (OuterJob * len(chunk))(*chunk), len(chunk), stream())
 
 
-def gemm_wgrad_batch(problems, scratch=None, sums=None, outers=None):
+def class_job(classes, scratch, dcls, B, Dd):
+    """the decoder class table's gradient as a deferred job (mst_class_table_grad's arguments): dcls[classes[b], :] += t[b, :] from the
+    rows latent_bwd_vec(..., dcls_d=None) left at the front of its scratch buffer. For gemm_wgrad_batch(cls=...) or class_table_grad"""
+    assert classes.dtype == torch.int32 and classes.numel() == B and scratch.dtype == dcls.dtype == torch.float32
+    assert scratch.is_contiguous() and scratch.numel() >= B * Dd and dcls.stride(1) == 1 and dcls.shape[1] >= Dd
+    return (ptr(classes), ptr(scratch), ptr(dcls), dcls.stride(0), B, Dd)
+
+
+def class_table_grad(job):
+    """a class_job as one launch of its own (mst_class_table_grad)"""
+    call("mst_class_table_grad", *job, stream())
+
+
+def gemm_wgrad_batch(problems, scratch=None, sums=None, outers=None, cls=None):
     """dW_i[N,K] += A_i^T @ B_i for a list of problems, 16 per launch (mst_gemm_wgrad_batch_flush). scratch: optional fp32 work
     buffer for the atomic-free two-pass reduction of big batches. sums: column-sum jobs (partial_sum_job), outers: batch outer
-    products (outer_job), to execute along with the weight gradients."""
+    products (outer_job), cls: the class-table job (class_job), to execute along with the weight gradients
+    (mst_gemm_wgrad_batch_flush_cls)."""
     sums, outers = list(sums or []), list(outers or [])
     for i in range(0, len(problems), WGRAD_MAX_PROBLEMS):
         chunk = problems[i:i + WGRAD_MAX_PROBLEMS]
-        take, tko = [], []
+        take, tko, tkc = [], [], None
         if i + WGRAD_MAX_PROBLEMS >= len(problems):  # the last launch takes (the first 20 of) the sums along
             take, sums = sums[:PARTIAL_SUM_MAX_JOBS], sums[PARTIAL_SUM_MAX_JOBS:]
             tko, outers = outers[:OUTER_MAX_JOBS], outers[OUTER_MAX_JOBS:]
-        call("mst_gemm_wgrad_batch_flush", (WgradArgs * len(chunk))(*chunk), len(chunk), ptr(scratch),
-             (scratch.numel() * scratch.element_size() if scratch is not None else 0),
-             (PartialSum * len(take))(*take) if take else None, len(take),
-             (OuterJob * len(tko))(*tko) if tko else None, len(tko), stream())
+            tkc, cls = cls, None
+        head = ((WgradArgs * len(chunk))(*chunk), len(chunk), ptr(scratch),
+                (scratch.numel() * scratch.element_size() if scratch is not None else 0),
+                (PartialSum * len(take))(*take) if take else None, len(take),
+                (OuterJob * len(tko))(*tko) if tko else None, len(tko))
+        if tkc is not None:
+            call("mst_gemm_wgrad_batch_flush_cls", *head, *tkc, stream())
+        else:
+            call("mst_gemm_wgrad_batch_flush", *head, stream())
     if sums:
         partial_sums(sums)
     if outers:
         outer_jobs(outers)
+    if cls is not None:  # (no weight-gradient problem to go with)
+        class_table_grad(cls)
 
 
 def gemm_wgrad_plan(problems, scratch_bytes=0):
@@ -529,6 +550,12 @@ def gemm_wgrad_plan(problems, scratch_bytes=0):
     plan = (C.c_int64 * (4 + WGRAD_MAX_PROBLEMS))()
     call("mst_gemm_wgrad_plan", (WgradArgs * len(problems))(*problems), len(problems), scratch_bytes, plan)
     return dict(form=plan[0], narrow=plan[1], items=plan[2], two_pass=plan[3], splits=list(plan[4:4 + len(problems)]))
+
+
+def flush_jobs_ride(problems, scratch_bytes=0):
+    """whether the jobs given to gemm_wgrad_batch(problems, scratch, sums, outers, cls) ride on the flush's reduction pass (True) or are
+    launches of their own behind the weight gradients (False): bit 0 of the plan's two_pass; no launch, no device"""
+    return bool(gemm_wgrad_plan(problems, scratch_bytes)["two_pass"] & 1)
 
 
 def gemm_wgrad(A, B, dW, db=None, **kw):
@@ -751,7 +778,8 @@ def latent_rows(zsrc, ssrc, a, b, w, ca, cb, cw, Wh, bh, cls_d, pos_d, alpha_d, 
 def latent_bwd_vec(Wl, eps, Wh, classes, mu, sigma, d_dec_in3, alpha_d, kl_weight, gscale, dcls_d, d_enc_out3, scratch, enc_scale=1.0,
                    proj=None, sched=None):
     """the latent block's backward pass with the decoder class table's gradient folded in (mst_latent_bwd_vec); the other parameter
-    gradients are latent_outer_jobs(...) of the caller's weight-gradient flush.
+    gradients are latent_outer_jobs(...) of the caller's weight-gradient flush. dcls_d None: the class table's gradient is left to the
+    caller too (class_job(...) on that flush): one launch instead of two.
     proj = (dqkv3 [B, S, >= nq], Wt [Dd, nq] the transposed 16-bit weight, resid3 [B, S, Dd] or None): d(dec_in[:, 0, :]) is computed
     here from the projection's gradient at position 0 instead of being read from d_dec_in3 (mst_latent_bwd_vec_proj).
     sched = (block, kl): the scheduled forms (mst_latent_bwd_vec*_sched) — the device schedule block of step_begin {beta_t, tau, ...}
@@ -761,14 +789,15 @@ def latent_bwd_vec(Wl, eps, Wh, classes, mu, sigma, d_dec_in3, alpha_d, kl_weigh
         assert sched[0].dtype == sched[1].dtype == torch.float32 and sched[0].numel() >= 4 and sched[1].numel() == B
     weight = (kl_weight,) if sched is None else (ptr(sched[0]), ptr(sched[1]))
     suffix = "" if sched is None else "_sched"
+    ld_cls = dcls_d.stride(0) if dcls_d is not None else 0
     if proj is not None:
         dq3, Wt, r3 = proj
         call("mst_latent_bwd_vec_proj" + suffix, dt(dq3), B, De, Z, Dd, ptr(Wl), ptr(eps), ptr(Wh), ptr(classes), ptr(mu), ptr(sigma),
              ptr(dq3), dq3.stride(0), ptr(Wt), ld(Wt), 3 * Dd, ptr(r3), (r3.stride(0) if r3 is not None else 0), alpha_d, *weight,
-             gscale, enc_scale, ptr(dcls_d), dcls_d.stride(0), ptr(d_enc_out3), d_enc_out3.stride(0), ptr(scratch), stream())
+             gscale, enc_scale, ptr(dcls_d), ld_cls, ptr(d_enc_out3), d_enc_out3.stride(0), ptr(scratch), stream())
         return
     call("mst_latent_bwd_vec" + suffix, dt(d_dec_in3), B, De, Z, Dd, ptr(Wl), ptr(eps), ptr(Wh), ptr(classes), ptr(mu), ptr(sigma),
-         ptr(d_dec_in3), d_dec_in3.stride(0), alpha_d, *weight, gscale, enc_scale, ptr(dcls_d), dcls_d.stride(0), ptr(d_enc_out3),
+         ptr(d_dec_in3), d_dec_in3.stride(0), alpha_d, *weight, gscale, enc_scale, ptr(dcls_d), ld_cls, ptr(d_enc_out3),
          d_enc_out3.stride(0), ptr(scratch), stream())
 
 
