@@ -246,6 +246,25 @@ typedef struct mst_ln_bwd_in {
 } mst_ln_bwd_in;
 int mst_ffn_ln_bwd_lead(const mst_ln_bwd_in* lead, const mst_gemm_args* ff2_dgrad, const mst_gemm_args* ff1_dgrad,
                         const mst_ln_args* ln, mst_stream_t stream);
+/* mst_ffn_ln_bwd_lead with the gradient it starts from computed in the launch too (ABI 116): the K | Q | V input gradient of the encoder
+ * layer ABOVE (MultiHeadDotAttention's three input Dense layers, transformer.py:57-64, backward) —
+ *     mst_gemm_nt(kqv_dgrad)               dy = d(qkv) W_kqv + d(h1 of the layer above)   [M, width], K = 3 width, residual
+ *     mst_ffn_ln_bwd_lead(lead, ...)       with lead->dy = that result
+ * as ONE launch where mst_kqv_ffn_ln_bwd_form says so: the workgroup that owns a 64-row tile computes its dy tile first, with
+ * mst_gemm_nt's arithmetic (same MFMA order per element, the residual added in fp32, one rounding), and every tensor the two launches
+ * store comes out bit for bit. kqv_dgrad->C (= lead->dy, which is not read) is OPTIONAL there: NULL, the gradient is never stored;
+ * set, it receives dy. Every other valid shape runs exactly the two launches inside the call and needs kqv_dgrad->C.
+ * mst_kqv_ffn_ln_bwd_form: that decision, on the host from the arguments alone (no HIP call, no device; pointers are looked at for NULL
+ * and alignment only; ff2_dgrad / ff1_dgrad for M, the width and row groups). form is a host array of 1 entry:
+ *   form[0]  1: one launch — width 128 or 256, N = width, K = 3 width, M and dtype the block's, a residual, no other epilogue feature
+ *               of mst_gemm_nt (bias, alpha, gate, activation, dropout, row-indexed adds, remaps, fp32 C, uint8 A), no row groups on
+ *               the block, A / B / residual / C 16-byte aligned with leading dimensions that are multiples of 8 and hold a row
+ *            0: the two launches
+ * Returns 0; a head without operands or of another M / width than the block: MST_ERR_INVALID, as the launch. */
+int mst_kqv_ffn_ln_bwd(const mst_gemm_args* kqv_dgrad, const mst_ln_bwd_in* lead, const mst_gemm_args* ff2_dgrad,
+                       const mst_gemm_args* ff1_dgrad, const mst_ln_args* ln, mst_stream_t stream);
+int mst_kqv_ffn_ln_bwd_form(const mst_gemm_args* kqv_dgrad, const mst_gemm_args* ff2_dgrad, const mst_gemm_args* ff1_dgrad,
+                            int64_t* form);
 /* The attention output projection joins the block (MultiHeadDotAttention's W_proj Dense, transformer.py:65-68,105-106, and the
  * residual LayerNorm behind it, transformer.py:154-156 / 191-193):
  * in FRONT of mst_ffn_ln_fwd —

@@ -1,6 +1,6 @@
 // ffn_ln.hip — the feed-forward block of a Transformer layer in one launch (ffn_ln.hpp: ffn_ln_body, where the design is described):
 // mst_ffn_ln_fwd / mst_ffn_ln_bwd, with the attention output projection in front (mst_proj_ffn_ln_fwd) or the layer's leading LayerNorm
-// backward in front (mst_ffn_ln_bwd_lead).
+// backward in front (mst_ffn_ln_bwd_lead), and with the K | Q | V input gradient of the layer above in front of that (mst_kqv_ffn_ln_bwd).
 #include "ffn_ln.hpp"
 #include "gemm_checks.hpp"
 
@@ -22,14 +22,16 @@ static int launch_ffn_ln(const mst_gemm_args& g1, const mst_gemm_args& g2, const
   const size_t lds_epi = (size_t)BM * (BN + 4) * 4;
   const size_t lds = lds_loop > lds_epi ? lds_loop : lds_epi;
   const int full = g1.M % BM == 0 ? 1 : 0;
-  // [forward | backward | backward with the leading LayerNorm] x [row guards | whole tiles], then the forward form with the projection head
-  const int mi = ex ? 6 + full : (lead ? 2 : (ln.mode == 2 ? 1 : 0)) * 2 + full;
+  // [forward | backward | backward with the leading LayerNorm] x [row guards | whole tiles], then the forward form with the projection
+  // head, then the backward form with the leading LayerNorm and the K | Q | V dgrad head
+  const int mi = ex ? (ln.mode == 2 ? 8 : 6) + full : (lead ? 2 : (ln.mode == 2 ? 1 : 0)) * 2 + full;
   typedef void (*kern_t)(mst_gemm_args, mst_gemm_args, mst_ln_args, mst_ln_bwd_in, mst_gemm_args, mst_ln_args);
-  const kern_t fns[8] = {&ffn_ln_kernel<T, BN, 2, 4, 1, false, false>, &ffn_ln_kernel<T, BN, 2, 4, 1, false, true>,
+  const kern_t fns[10] = {&ffn_ln_kernel<T, BN, 2, 4, 1, false, false>, &ffn_ln_kernel<T, BN, 2, 4, 1, false, true>,
                          &ffn_ln_kernel<T, BN, 2, 4, 2, false, false>, &ffn_ln_kernel<T, BN, 2, 4, 2, false, true>,
                          &ffn_ln_kernel<T, BN, 2, 4, 2, true, false>, &ffn_ln_kernel<T, BN, 2, 4, 2, true, true>,
-                         &ffn_ln_kernel<T, BN, 2, 4, 1, false, false, true>, &ffn_ln_kernel<T, BN, 2, 4, 1, false, true, true>};
-  static size_t granted[8] = {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024};
+                         &ffn_ln_kernel<T, BN, 2, 4, 1, false, false, true>, &ffn_ln_kernel<T, BN, 2, 4, 1, false, true, true>,
+                          &ffn_ln_kernel<T, BN, 2, 4, 2, true, false, true>, &ffn_ln_kernel<T, BN, 2, 4, 2, true, true, true>};
+  static size_t granted[10] = {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024};
   if (const int rc = lds_opt_in(reinterpret_cast<const void*>(fns[mi]), lds, &granted[mi], "ffn_ln_kernel")) return rc;
   const mst_ln_bwd_in none = {};
   const mst_gemm_args no_gemm = {};
@@ -87,8 +89,10 @@ int check_ffn_ln(const char* who, const mst_gemm_args* first, const mst_gemm_arg
   if (lead) {
     const mst_ln_bwd_in& q = *lead;
     MST_CHECK_ARG(mode == 2, "%s: a leading LayerNorm belongs to the backward form", who);
-    MST_CHECK_ARG(q.dy && q.x && q.gamma && q.mean && q.rstd && q.dx && (q.partials || (q.dgamma && q.dbeta)), "%s: leading LayerNorm: null pointer", who);
-    MST_CHECK_ARG(q.ld_dy % 8 == 0 && q.ld_x % 8 == 0 && q.ld_dx % 8 == 0 && q.ld_dy >= b.N && q.ld_x >= b.N && q.ld_dx >= b.N &&
+    const bool dy_on_chip = extra != nullptr;  // (the head computes dy: q.dy is not read)
+    MST_CHECK_ARG((q.dy || dy_on_chip) && q.x && q.gamma && q.mean && q.rstd && q.dx && (q.partials || (q.dgamma && q.dbeta)),
+                  "%s: leading LayerNorm: null pointer", who);
+    MST_CHECK_ARG((dy_on_chip || (q.ld_dy % 8 == 0 && q.ld_dy >= b.N)) && q.ld_x % 8 == 0 && q.ld_dx % 8 == 0 && q.ld_x >= b.N && q.ld_dx >= b.N &&
                   ((uintptr_t)q.dy | (uintptr_t)q.x | (uintptr_t)q.dx | (uintptr_t)q.partials) % 16 == 0, "%s: leading LayerNorm: bad layout", who);
     MST_CHECK_ARG(q.mask_mode == 0 || (q.mask_mode == 1 && q.dx_masked && q.ld_dxm % 8 == 0 && q.ld_dxm >= b.N && (uintptr_t)q.dx_masked % 16 == 0),
                   "%s: leading LayerNorm: mask_mode must be 0 or 1 (with dx_masked)", who);
@@ -97,7 +101,10 @@ int check_ffn_ln(const char* who, const mst_gemm_args* first, const mst_gemm_arg
     const int64_t tile_ld = q.mask_mode == 1 ? q.ld_dxm : q.ld_dx;
     MST_CHECK_ARG(a.A == tile && a.lda == tile_ld, "%s: the first GEMM's A operand must be the leading LayerNorm's (masked) output", who);
   }
-  if (extra) {
+  if (extra && mode == 2) {
+    // the K | Q | V dgrad head: mst_kqv_ffn_ln_bwd takes this path only with a head its form rule accepted (kqv_head_form: shape,
+    // layout, a residual and no other epilogue feature) — nothing is left to check here
+  } else if (extra) {
     const mst_gemm_args& x = *extra;
     rc = check_gemm_common(x);
     if (rc) return rc;
@@ -143,6 +150,55 @@ extern "C" int mst_ffn_ln_bwd_lead(const mst_ln_bwd_in* lead, const mst_gemm_arg
                                    const mst_ln_args* ln, mst_stream_t stream) {
   MST_CHECK_ARG(lead != nullptr, "mst_ffn_ln_bwd_lead: null args");
   return ffn_ln_impl("mst_ffn_ln_bwd_lead", ff2_dgrad, ff1_dgrad, ln, 2, stream, lead);
+}
+
+// mst_kqv_ffn_ln_bwd: does the K | Q | V input gradient run as the head of the feed-forward backward launch (1), or as the GEMM
+// launch in front of mst_ffn_ln_bwd_lead (0)? From the arguments alone (pointers: NULL and alignment only); the one decision the
+// launch and mst_kqv_ffn_ln_bwd_form share. The head exists for the plain K = 3 width dgrad with a residual on whole-width rows:
+// anything mst_gemm_nt would do beyond that (a bias, alpha, a gate, row-indexed adds, remaps, an fp32 or 4-column-aligned C, a
+// residual it would read element by element) keeps the GEMM launch.
+static int kqv_head_form(const mst_gemm_args& x, const mst_gemm_args& a, const mst_gemm_args& b) {
+  const bool shape = (b.N == 256 || b.N == 128) && x.N == b.N && x.K == 3 * b.N && x.M == a.M && x.dtype == a.dtype;
+  const bool plain = !x.c_f32 && !x.a_u8 && !x.bias && !x.gate && !x.rowadd && !x.grpadd && x.act == MST_ACT_NONE && x.alpha == 1.f &&
+                     x.dropout_p == 0.f && !x.self_resid && x.a_rows_per_group <= 0 && x.c_rows_per_group <= 0 && a.a_rows_per_group <= 0;
+  const bool layout = x.resid && ((uintptr_t)x.A | (uintptr_t)x.B | (uintptr_t)x.resid | (uintptr_t)x.C) % 16 == 0 && x.lda % 8 == 0 &&
+                      x.lda >= x.K && x.ldb % 8 == 0 && x.ldb >= x.K && x.ldr % 8 == 0 && x.ldr >= x.N &&
+                      (!x.C || (x.ldc % 8 == 0 && x.ldc >= x.N)) && (uint64_t)x.N * (uint64_t)x.ldb < (1ull << 32);
+  return shape && plain && layout ? 1 : 0;
+}
+
+static int check_kqv_head_call(const char* who, const mst_gemm_args* head, const mst_gemm_args* ff2_dgrad, const mst_gemm_args* ff1_dgrad) {
+  MST_CHECK_ARG(head != nullptr && ff2_dgrad != nullptr && ff1_dgrad != nullptr, "%s: null args", who);
+  MST_CHECK_ARG(head->M > 0 && head->N > 0 && head->K > 0, "%s: the head's M,N,K must be positive (got %lld,%lld,%lld)", who,
+                (long long)head->M, (long long)head->N, (long long)head->K);
+  MST_CHECK_ARG(head->A && head->B, "%s: the head's A and B operands are missing", who);
+  MST_CHECK_ARG(head->M == ff2_dgrad->M && head->N == ff1_dgrad->N, "%s: the head's result is the block's incoming gradient: M x width (got %lld x %lld)",
+                who, (long long)head->M, (long long)head->N);
+  return MST_OK;
+}
+
+extern "C" int mst_kqv_ffn_ln_bwd_form(const mst_gemm_args* kqv_dgrad, const mst_gemm_args* ff2_dgrad, const mst_gemm_args* ff1_dgrad,
+                                       int64_t* form) {
+  MST_CHECK_ARG(form != nullptr, "mst_kqv_ffn_ln_bwd_form: null form");
+  if (const int rc = check_kqv_head_call("mst_kqv_ffn_ln_bwd_form", kqv_dgrad, ff2_dgrad, ff1_dgrad)) return rc;
+  form[0] = kqv_head_form(*kqv_dgrad, *ff2_dgrad, *ff1_dgrad);
+  return MST_OK;
+}
+
+extern "C" int mst_kqv_ffn_ln_bwd(const mst_gemm_args* kqv_dgrad, const mst_ln_bwd_in* lead, const mst_gemm_args* ff2_dgrad,
+                                  const mst_gemm_args* ff1_dgrad, const mst_ln_args* ln, mst_stream_t stream) {
+  if (const int rc = check_kqv_head_call("mst_kqv_ffn_ln_bwd", kqv_dgrad, ff2_dgrad, ff1_dgrad)) return rc;
+  MST_CHECK_ARG(lead != nullptr, "mst_kqv_ffn_ln_bwd: null args");
+  MST_CHECK_ARG(lead->dy == kqv_dgrad->C && (!lead->dy || lead->ld_dy == kqv_dgrad->ldc),
+                "mst_kqv_ffn_ln_bwd: lead->dy is the head's C (both NULL: the gradient is not stored)");
+  if (kqv_head_form(*kqv_dgrad, *ff2_dgrad, *ff1_dgrad))
+    return ffn_ln_impl("mst_kqv_ffn_ln_bwd", ff2_dgrad, ff1_dgrad, ln, 2, stream, lead, kqv_dgrad);
+  // the two launches; every argument is checked before the first one is issued
+  MST_CHECK_ARG(kqv_dgrad->C != nullptr, "mst_kqv_ffn_ln_bwd: this shape runs the GEMM launch first and needs the head's C");
+  if (const int rc = check_ffn_ln("mst_kqv_ffn_ln_bwd", ff2_dgrad, ff1_dgrad, ln, 2, lead)) return rc;
+  if (const int f = mst_gemm_nt_form(kqv_dgrad); f < 0) return f;  // (mst_gemm_nt's own checks and message)
+  if (const int rc = mst_gemm_nt(kqv_dgrad, stream)) return rc;
+  return ffn_ln_impl("mst_kqv_ffn_ln_bwd", ff2_dgrad, ff1_dgrad, ln, 2, stream, lead);
 }
 
 extern "C" int mst_ffn_ln_fwd(const mst_gemm_args* ff1, const mst_gemm_args* ff2, const mst_ln_args* ln, mst_stream_t stream) {

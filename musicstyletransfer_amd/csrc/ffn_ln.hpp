@@ -29,12 +29,18 @@ namespace mst {
 // weight ring — the launch is bound by a single workgroup's serial latency (35 us for ONE workgroup, 42 for 256), so
 // every such drain is a full L2 round trip on the critical path. Hence also: bias of the first GEMM read from LDS
 // (it was a global load + vmcnt(0) inside the chunk epilogue), prefetches issued unconditionally (clamped).
-// EXTRA: one more width x width GEMM on the workgroup's rows in the same launch (gx; its weights are extra stages of the
-// same stream). Forward (mst_proj_ffn_ln_fwd): the attention output projection + residual + LayerNorm in FRONT — the input
+// EXTRA: one more GEMM on the workgroup's rows in FRONT, in the same launch (gx; its weights are extra stages of the same stream).
+// Forward (mst_proj_ffn_ln_fwd): the attention output projection (width x width) + residual + LayerNorm — the input
 // tile is the attention output, the block's input x1 = LayerNorm(h1) is computed by mst_gemm_nt_ln's forward epilogue
-// (gx, lnx) into the x tile (and stored, with h1 and the statistics, for the backward pass). (The mirror image — the projection's
-// dgrad behind the backward block — and a form with every wave loading its own weight fragments straight into MFMA operand
-// registers were built, measured slower / not worth a third shadow layout, and removed: docs/kernel_notes.md.)
+// (gx, lnx) into the x tile (and stored, with h1 and the statistics, for the backward pass).
+// Backward, with LEAD (mst_kqv_ffn_ln_bwd): the K | Q | V input gradient of the layer ABOVE (width x 3 width, + residual) — the
+// gradient tile LEAD starts from is not loaded but computed, with mst_gemm_nt's arithmetic (K ascending, one rounding behind the
+// residual add), into the x tile; LEAD then takes its dy pieces from there. Twelve more stages of the same stream at width 256; the
+// 64 x 3 width A operand passes through the two activation tiles in three slices (x tile, hidden tile, x tile), the third slice
+// and the residual waiting in registers from the prologue on — no load inside the head's stage loop but the weight ring's.
+// (The mirror image of the forward head — the projection's dgrad behind the backward block — and a form with every wave loading
+// its own weight fragments straight into MFMA operand registers were built, measured slower / not worth a third shadow layout,
+// and removed: docs/kernel_notes.md.)
 // The block is a device function (ffn_ln_body) so that a launch can run it as one of several phases of a workgroup (dec_tail_kernel):
 //   X_IN_LDS   the input tile already sits in the x tile (the previous phase's epilogue left it there): it is not loaded
 //   KEEP_OUT   the last epilogue's result rows ALSO stay in the x tile (gemm_epilogue_ln's lds_out), for the phase that follows
@@ -46,15 +52,16 @@ template <typename T, int BN, int WGM, int WGN, int MODE, bool LEAD, bool FULL, 
 __device__ __forceinline__ void ffn_ln_body(unsigned char* smem, mst_gemm_args g1, mst_gemm_args g2, const mst_ln_args ln,
                                             const mst_ln_bwd_in lead, mst_gemm_args gx, const mst_ln_args lnx, float* par,
                                             Hook&& before_epilogue) {
-  constexpr bool HEAD = EXTRA;
+  constexpr bool HEAD = EXTRA, FHEAD = EXTRA && MODE == 1, BHEAD = EXTRA && MODE == 2;  // (HEAD: what both heads share — the stream)
   static_assert(!(X_IN_LDS && (LEAD || EXTRA)), "a tile left in LDS is the block's own input");
-  static_assert(!EXTRA || MODE == 1, "the extra GEMM is the forward form's head");
+  static_assert(!BHEAD || LEAD, "the backward form's head computes the gradient tile of the leading LayerNorm backward");
   constexpr int BM = 64, BK = 64, CHUNKS = BK / 8;
   constexpr int NT = WGM * WGN * 64;
   constexpr int WTM = BM / WGM, WTN = BN / WGN, TM = WTM / 16, TN = WTN / 16;
   constexpr int B_CH = BN * CHUNKS / NT;  // 16-byte pieces of a weight stage per thread
   constexpr int LDA = BN + 8;                  // row stride (elements) of the two activation tiles: conflict-free b128 reads
   constexpr int KST = BN / BK;                 // K stages of one GEMM of a chunk (K = BN for both)
+  constexpr int XST = BHEAD ? 3 * KST : KST;   // K stages of the head GEMM (forward: K = BN; backward: K = 3 BN)
   static_assert(BN * CHUNKS % NT == 0 && (BM * BN / 8) % NT == 0, "tile/threads mismatch");
   typedef typename Act<T>::vec8 vec8;
   // [weight stages 2 x BN x 64][hidden chunk 64 x LDA][x tile 64 x LDA]; the LayerNorm epilogue's fp32 staging tile reuses
@@ -87,13 +94,13 @@ __device__ __forceinline__ void ffn_ln_body(unsigned char* smem, mst_gemm_args g
     *reinterpret_cast<f32x4*>(sBias1 + i) = g1.bias ? *reinterpret_cast<const f32x4*>(g1.bias + i) : f32x4{0.f, 0.f, 0.f, 0.f};
   // (the step's dropout seed words too: a scalar load at an epilogue's start is one more exposed round trip)
   const uint64_t seed2 = g2.dropout_seed ^ ((g2.dropout_p > 0.f && g2.dropout_seed_ptr) ? g2.dropout_seed_ptr[0] : 0ull);
-  const uint64_t seedx = EXTRA ? gx.dropout_seed ^ ((gx.dropout_p > 0.f && gx.dropout_seed_ptr) ? gx.dropout_seed_ptr[0] : 0ull) : 0ull;
+  const uint64_t seedx = FHEAD ? gx.dropout_seed ^ ((gx.dropout_p > 0.f && gx.dropout_seed_ptr) ? gx.dropout_seed_ptr[0] : 0ull) : 0ull;
   if constexpr (!PAR_READY)
   for (int i = tid; i < BN; i += NT) {
     sPar[i] = g2.bias ? g2.bias[i] : 0.f;
     sPar[BN + i] = ln.gamma[i];
     sPar[2 * BN + i] = (MODE == 1) ? ln.beta[i] : 0.f;
-    if constexpr (HEAD) {
+    if constexpr (FHEAD) {
       sPar[3 * BN + i] = gx.bias ? gx.bias[i] : 0.f;
       sPar[4 * BN + i] = lnx.gamma[i];
       sPar[5 * BN + i] = lnx.beta[i];
@@ -164,7 +171,7 @@ __device__ __forceinline__ void ffn_ln_body(unsigned char* smem, mst_gemm_args g
     auto pro = [&](auto jc) {
       constexpr int j = decltype(jc)::value;
       if constexpr (HEAD) {
-        static_assert(!HEAD || AHEAD <= KST, "the head GEMM's stages cover the prologue");
+        static_assert(!HEAD || AHEAD <= XST, "the head GEMM's stages cover the prologue");
         if (j < AHEAD) load_stage(-1, j, ring[j % RING]);
       } else {
         if (j < AHEAD && (j < SPC || n_chunks > 1)) load_stage(j / SPC, j % SPC, ring[j % RING]);
@@ -175,29 +182,56 @@ __device__ __forceinline__ void ffn_ln_body(unsigned char* smem, mst_gemm_args g
     pro(std::integral_constant<int, 6>());
     static_assert(AHEAD <= 7, "the prologue list covers seven stages");
   }
-  if constexpr (LEAD) {
-    // ---- the input tile = LayerNorm backward of the incoming gradient (the arithmetic of gemm_epilogue_ln's mode 2 on dy)
-    constexpr int CPR = BN / 8, RSTEP = NT / CPR, ITERS = BM / RSTEP;
-    const int ch = tid % CPR, nc = ch * 8, row0 = tid / CPR;
-    const float inv_n = 1.f / (float)BN;
+  // ---- LEAD: the input tile = LayerNorm backward of the incoming gradient (the arithmetic of gemm_epilogue_ln's mode 2 on dy).
+  // A thread owns the 16-byte pieces (row lrow0 + it * L_RSTEP, columns lnc..lnc+7) of the tile. Two parts: the loads (everything
+  // the rows need from global memory), then the rows themselves — back to back, or (BHEAD) with the head GEMM in between, whose
+  // stages then run over the latency of x, mean and rstd.
+  constexpr int L_CPR = BN / 8, L_RSTEP = NT / L_CPR, L_ITERS = BM / L_RSTEP;
+  const int lnc = (tid % L_CPR) * 8, lrow0 = tid / L_CPR;
+  uint32_t ldkey = 0u, ldthr = 0u;
+  float linv_keep = 1.f, gam8[8], dg8[8], db8[8];
+  u32x4 dyv[L_ITERS], xv[L_ITERS];
+  float mean_r[L_ITERS], rstd_r[L_ITERS];
+  // BHEAD: the third K-slice of the head's A operand and the head's residual tile, in registers until their LDS tile is free
+  u32x4 ha2[L_ITERS], hres[L_ITERS];
+  auto lead_loads = [&] {
+    constexpr int RSTEP = L_RSTEP, ITERS = L_ITERS;
+    const int nc = lnc, row0 = lrow0;
     const bool has_drop = lead.dropout_p > 0.f && lead.mask_mode == 1;
     const uint64_t dseed = lead.dropout_seed ^ ((has_drop && lead.dropout_seed_ptr) ? lead.dropout_seed_ptr[0] : 0ull);
-    const uint32_t dkey = dropout_key(dseed, lead.dropout_site), dthr = dropout_thr(lead.dropout_p);
-    const float inv_keep = dropout_inv_keep(lead.dropout_p);
-    float gam8[8], dg8[8], db8[8];
+    ldkey = dropout_key(dseed, lead.dropout_site); ldthr = dropout_thr(lead.dropout_p);
+    linv_keep = dropout_inv_keep(lead.dropout_p);
 #pragma unroll
     for (int e = 0; e < 8; ++e) { gam8[e] = lead.gamma[nc + e]; dg8[e] = 0.f; db8[e] = 0.f; }
-    u32x4 dyv[ITERS], xv[ITERS];
-    float mean_r[ITERS], rstd_r[ITERS];
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
       const int64_t m = m0 + row0 + it * RSTEP;
       dyv[it] = u32x4{0u, 0u, 0u, 0u}; xv[it] = dyv[it]; mean_r[it] = 0.f; rstd_r[it] = 0.f;
       if (m < Mg) {
-        dyv[it] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(lead.dy) + m * lead.ld_dy + nc);
+        if constexpr (!BHEAD) dyv[it] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(lead.dy) + m * lead.ld_dy + nc);
         xv[it] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(lead.x) + m * lead.ld_x + nc);
         mean_r[it] = lead.mean[m];
         rstd_r[it] = lead.rstd[m];
+      }
+    }
+  };
+  auto lead_rows = [&] {
+    constexpr int CPR = L_CPR, RSTEP = L_RSTEP, ITERS = L_ITERS;
+    const int nc = lnc, row0 = lrow0;
+    const float inv_n = 1.f / (float)BN;
+    const bool has_drop = lead.dropout_p > 0.f && lead.mask_mode == 1;
+    const uint32_t dkey = ldkey, dthr = ldthr;
+    const float inv_keep = linv_keep;
+    if constexpr (BHEAD) {
+      // the head left the rounded gradient tile in the x tile (published by its barrier); gx.C, when given, receives it
+#pragma unroll
+      for (int it = 0; it < ITERS; ++it) {
+        const int row = row0 + it * RSTEP;
+        const int64_t m = m0 + row;
+        if (m < Mg) {
+          dyv[it] = *reinterpret_cast<const u32x4*>(sX + row * LDA + nc);
+          if (gx.C) *reinterpret_cast<u32x4*>(reinterpret_cast<T*>(gx.C) + m * gx.ldc + nc) = dyv[it];
+        }
       }
     }
 #pragma unroll
@@ -255,6 +289,36 @@ __device__ __forceinline__ void ffn_ln_body(unsigned char* smem, mst_gemm_args g
       else atomicAdd((which ? lead.dbeta : lead.dgamma) + col, sm);
     }
     __syncthreads();  // the scratch becomes the first weight stage
+  };
+  if constexpr (BHEAD) {
+    // ---- the head's A operand (64 x 3 BN) and residual tile, all requested here: slices 0 and 1 go to the x tile and the hidden
+    // tile (dead until the first chunk), slice 2 and the residual wait in registers (extra_gemm stores them once their tile is free)
+    constexpr int RSTEP = L_RSTEP, ITERS = L_ITERS;
+    const T* HA = reinterpret_cast<const T*>(gx.A);
+    const T* HR = reinterpret_cast<const T*>(gx.resid);
+    u32x4 ha0[ITERS], ha1[ITERS];
+#pragma unroll
+    for (int it = 0; it < ITERS; ++it) {
+      const int64_t m = m0 + lrow0 + it * RSTEP;
+      ha0[it] = u32x4{0u, 0u, 0u, 0u}; ha1[it] = ha0[it]; ha2[it] = ha0[it]; hres[it] = ha0[it];
+      if (m < Mg) {
+        const T* ap = HA + m * gx.lda + lnc;
+        ha0[it] = *reinterpret_cast<const u32x4*>(ap);
+        ha1[it] = *reinterpret_cast<const u32x4*>(ap + BN);
+        ha2[it] = *reinterpret_cast<const u32x4*>(ap + 2 * BN);
+        hres[it] = *reinterpret_cast<const u32x4*>(HR + m * gx.ldr + lnc);  // (the head always has a residual: host check)
+      }
+    }
+    lead_loads();
+#pragma unroll
+    for (int it = 0; it < ITERS; ++it) {
+      const int row = lrow0 + it * RSTEP;
+      *reinterpret_cast<u32x4*>(sX + row * LDA + lnc) = ha0[it];
+      *reinterpret_cast<u32x4*>(sH + row * LDA + lnc) = ha1[it];
+    }
+  } else if constexpr (LEAD) {
+    lead_loads();
+    lead_rows();
   } else if constexpr (!X_IN_LDS)
   // ---- the x tile (rows past M read as zero)
   {
@@ -321,7 +385,9 @@ __device__ __forceinline__ void ffn_ln_body(unsigned char* smem, mst_gemm_args g
   for (int i = 0; i < TM; ++i) rowmul[i] = (uint32_t)(m0 + wm * WTM + i * 16 + frow) * (uint32_t)(F >> 1) * DROPOUT_MUL;
   T* Aout = reinterpret_cast<T*>(g1.C);
 
-  // the KST stages of the extra GEMM (stream position `cx` = -1: in front of the chunks) into acc1
+  // the XST stages of the extra GEMM (stream position `cx` = -1: in front of the chunks) into acc1. K-slice s / KST of its A operand
+  // sits in the x tile (even slices) or the hidden tile (odd ones); BHEAD: behind the barrier that ends a slice's last stage, the
+  // tile it frees takes what waited in registers for it — slice 2 the x tile, the residual the hidden tile
   auto extra_gemm = [&](int cx) {
 #pragma unroll
     for (int j = 0; j < TN; ++j)
@@ -331,20 +397,50 @@ __device__ __forceinline__ void ffn_ln_body(unsigned char* smem, mst_gemm_args g
     __syncthreads();
     auto xstage = [&](auto sc) {
       constexpr int s = decltype(sc)::value;
-      if constexpr (s < KST) {
+      if constexpr (s < XST) {
         constexpr int t = s + AHEAD;
-        if constexpr (t < KST) load_stage(cx, t, ring[t % RING]);
-        else if constexpr (HEAD) load_stage(0, t - KST, ring[t % RING]);  // the first chunk's stages follow (KST % RING == 0)
-        mma_stage(acc1, sX + s * BK, s & 1, ring[s % RING], no_hook);
-        if constexpr (s + 1 < KST) store_stage((s + 1) & 1, ring[(s + 1) % RING]);
+        if constexpr (t < XST) load_stage(cx, t, ring[t % RING]);
+        else if constexpr (HEAD) load_stage(0, t - XST, ring[t % RING]);  // the first chunk's stages follow (XST % RING == 0)
+        mma_stage(acc1, (((s / KST) & 1) ? sH : sX) + (s % KST) * BK, s & 1, ring[s % RING], no_hook);
+        if constexpr (s + 1 < XST) store_stage((s + 1) & 1, ring[(s + 1) % RING]);
         __syncthreads();
+        if constexpr (BHEAD && (s == KST - 1 || s == 2 * KST - 1)) {
+#pragma unroll
+          for (int it = 0; it < L_ITERS; ++it)
+            *reinterpret_cast<u32x4*>((s == KST - 1 ? sX : sH) + (lrow0 + it * L_RSTEP) * LDA + lnc) = s == KST - 1 ? ha2[it] : hres[it];
+        }
       }
     };
-    static_assert(!EXTRA || (KST <= 4 && KST % RING == 0), "the extra GEMM stage list / ring slots");
+    // (an even stage count: the first chunk starts in LDS buffer 0, as without a head)
+    static_assert(!EXTRA || (XST <= 12 && XST % RING == 0 && XST % 2 == 0), "the extra GEMM stage list / ring slots");
     xstage(std::integral_constant<int, 0>()); xstage(std::integral_constant<int, 1>());
     xstage(std::integral_constant<int, 2>()); xstage(std::integral_constant<int, 3>());
+    xstage(std::integral_constant<int, 4>()); xstage(std::integral_constant<int, 5>());
+    xstage(std::integral_constant<int, 6>()); xstage(std::integral_constant<int, 7>());
+    xstage(std::integral_constant<int, 8>()); xstage(std::integral_constant<int, 9>());
+    xstage(std::integral_constant<int, 10>()); xstage(std::integral_constant<int, 11>());
   };
-  if constexpr (HEAD) {
+  if constexpr (BHEAD) {
+    // dy = round16(acc + resid): gemm_epilogue's residual add and its one rounding, in accumulator layout (the residual tile sits
+    // in the hidden tile, the result goes to the x tile, both free behind the last stage's barrier); then the LayerNorm backward
+    extra_gemm(-1);
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+        const int row = wm * WTM + i * 16 + frow, n = wn * WTN + j * 16 + fq * 4;
+        const u32x2 rb = *reinterpret_cast<const u32x2*>(sH + row * LDA + n);
+        uint16_t hb[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          hb[e] = f32_to_bits<T>(acc1[j][i][e] + bits_to_f32<T>((uint16_t)(rb[e >> 1] >> ((e & 1) * 16))));
+        *reinterpret_cast<u32x2*>(sX + row * LDA + n) =
+            u32x2{(uint32_t)hb[0] | ((uint32_t)hb[1] << 16), (uint32_t)hb[2] | ((uint32_t)hb[3] << 16)};
+      }
+    __syncthreads();
+    lead_rows();
+  }
+  if constexpr (FHEAD) {
     // h1 = epi(att Wp^T) (+ x), x1 = LayerNorm(h1): mst_gemm_nt_ln's forward epilogue; x1 also lands in the x tile
     extra_gemm(-1);
     gemm_epilogue_ln<T, BM, BN, WGM, WGN, 1>(gx, lnx, smem, acc1, m0, nullptr, 0, sX, LDA, sPar + 3 * BN, &seedx);

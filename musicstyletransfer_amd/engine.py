@@ -611,7 +611,8 @@ def ffn_bwd_kw(P, L, t, drop, partials_buf, row_groups=None):
                 resid=None if P.self_resid else t.dh, partials=partials_buf, row_groups=row_groups, **ln1)
 
 
-def row_block_bwd(P, L, t, dy, rows, drop, form, partials, dy_done=False, row_groups=None, tail=None, launch=True, proj_dgrad=True):
+def row_block_bwd(P, L, t, dy, rows, drop, form, partials, dy_done=False, row_groups=None, tail=None, launch=True, proj_dgrad=True,
+                  head=None):
     """Backward of row_block_fwd on the same rows: LayerNorm-2/3 backward of dy, both FFN dgrads, LayerNorm-1 backward, the W_proj
     dgrad. t: the layer's backward buffers — dh, dhm, dx1, dh1m, dpre indexed by the block's own rows, dh1 and datt by the layer's
     (written through `rows`). partials(norm, n_workgroups) -> the partials buffer of one LayerNorm-backward launch, or None
@@ -625,7 +626,9 @@ def row_block_bwd(P, L, t, dy, rows, drop, form, partials, dy_done=False, row_gr
     launch=False ('fused' with dy_done only): the one-launch block itself is not issued — it ran as a phase of ops.dec_tail_step, from
     ffn_bwd_kw's arguments —; the partial-sum job is registered and the W_proj dgrad issued as always.
     proj_dgrad=False (not with 'tail'): the W_proj dgrad is left to the caller's attention-backward launch (ops.attn_proj_bwd on dproj);
-    t.datt is not written."""
+    t.datt is not written.
+    head ('fused' with the leading LayerNorm backward in its prologue only; dy is then not read): dict(A, B, resid) — dy = A B^T + resid,
+    the K | Q | V input gradient of the layer above, is formed by the one launch itself (ops.ffn_ln_bwd head=)."""
     D, v = P.proj.w.shape[0], rows.view
     if form == "tail":
         o.row_tail_bwd(v(dy), v(L.h2), v(L.h1), v(L.a), L.mean1, L.rstd1, L.mean2, L.rstd2, P.ln1.gamma, P.ln2.gamma, P.ff2.t, P.ff1.t,
@@ -635,7 +638,8 @@ def row_block_bwd(P, L, t, dy, rows, drop, form, partials, dy_done=False, row_gr
     M = L.h1.shape[0]
     lead = None
     if not dy_done and form == "fused" and P.mask_mode == 1:
-        lead = dict(dy=dy, x=L.h2, gamma=P.ln2.gamma, mean=L.mean2, rstd=L.rstd2, dx=t.dh, dgamma=P.ln2.dgamma, dbeta=P.ln2.dbeta,
+        lead = dict(dy=None if head is not None else dy, x=L.h2, gamma=P.ln2.gamma, mean=L.mean2, rstd=L.rstd2, dx=t.dh,
+                    dgamma=P.ln2.dgamma, dbeta=P.ln2.dbeta,
                     partials=partials(P.ln2, o.gemm_nt_ln_parts(M)), **_lead_mask(P, t, drop))
     elif not dy_done:
         mask = _lead_mask(P, t, drop)
@@ -651,8 +655,10 @@ def row_block_bwd(P, L, t, dy, rows, drop, form, partials, dy_done=False, row_gr
     ln1 = dict(dx_masked=t.dh1m, mask_mode=1, **drop.at(0)) if drop.p > 0 else {}
     if form == "fused":
         buf = partials(P.ln1, ffn_bwd_parts(L, row_groups))
+        if head is not None and (lead is None or not launch):
+            raise ValueError("row_block_bwd(head=) needs the one launch that starts with the leading LayerNorm backward")
         if launch:
-            o.ffn_ln_bwd(lead=lead, **ffn_bwd_kw(P, L, t, drop, buf, row_groups))
+            o.ffn_ln_bwd(lead=lead, head=head, **ffn_bwd_kw(P, L, t, drop, buf, row_groups))
         elif lead is not None:
             raise ValueError("row_block_bwd(launch=False) needs dy_done: the block that ran elsewhere has no leading LayerNorm backward")
     else:
@@ -763,8 +769,10 @@ def row_tail_selfcheck(store, B=64, S=2):
 # ema — the Adam launches in their averaging form (mst_adam_flat_ema): the same launches in the same order, none added.
 # attn_proj_e / attn_proj_d — the W_proj input gradient of an encoder layer below the top one / of a (non-causal) decoder layer is formed
 # inside its attention-backward launch (mst_attn_proj_bwd) instead of by a GEMM launch that writes datt.
+# kqv_head_e — the K | Q | V input gradient of an encoder layer above another one is formed inside that layer's feed-forward backward launch
+# (mst_kqv_ffn_ln_bwd), in front of the leading LayerNorm backward, instead of by a GEMM launch that writes the gradient.
 Forms = namedtuple("Forms", "tails riders shadows fuse_bce bce_dgrad skip_row0 cls_fold ffn_e ffn_d ln_bwd_e ln_bwd_d sched dec_tail gnorm ema "
-                            "attn_proj_e attn_proj_d")
+                            "attn_proj_e attn_proj_d kqv_head_e")
 
 
 def roll_scores(tp, pred, pos, cells):
@@ -911,6 +919,9 @@ class StepPlan:
         # the last decoder layer's row-wise block, the loss and the block's backward in one launch where the shape has that form
         # (ops.dec_tail_pays) and the step is a training step; False: the three launches (diagnostics, tests)
         self.dec_tail = True
+        # an encoder layer's K | Q | V input gradient inside the feed-forward backward launch of the layer below, where the library takes
+        # the shape that way (ops.kqv_head_pays); False: the GEMM launch (diagnostics, tests)
+        self.kqv_head = True
         self.n_cu = torch.cuda.get_device_properties(self.dev).multi_processor_count if self.dev.type == "cuda" else 0
         # the launch forms of the sequence issued last (resolved again by every forward(); here: the buffers below follow from them)
         self.forms = self._resolve_forms()
@@ -1041,10 +1052,10 @@ class StepPlan:
         return 0.0 if self._infer else self.cfg.d_dropout
 
     def _resolve_forms(self, with_grad=False):
-        """Which form every launch of the sequence about to be issued takes: from the shape, and from the five attributes diagnostics
+        """Which form every launch of the sequence about to be issued takes: from the shape, and from the six attributes diagnostics
         set before the first forward() / capture() (store.tail_fused — which a failed tail also clears —, store.shadows_deferred,
-        plan.ride, plan.shadows_on_tail, plan.dec_tail). forward() resolves them; every phase of the step reads this record and nothing
-        else. with_grad: the forward pass of a training step whose caller issues losses(with_grad=True) next (fwd_bwd_kernels)."""
+        plan.ride, plan.shadows_on_tail, plan.dec_tail, plan.kqv_head). forward() resolves them; every phase of the step reads this record
+        and nothing else. with_grad: the forward pass of a training step whose caller issues losses(with_grad=True) next (fwd_bwd_kernels)."""
         cfg, st, B, T = self.cfg, self.store, self.B, self.T
         De, Dd = cfg.e_model, cfg.d_model
         roll = cfg.kind == "pianoroll"
@@ -1093,7 +1104,11 @@ class StepPlan:
             ema=self.ema_decay > 0,
             # the W_proj input gradient inside the attention-backward launch, where the library takes the shape that way
             # (mst_attn_bwd_form; the causal decoder has kernels of its own)
-            attn_proj_e=self._attn_proj(T, cfg.e_heads, De), attn_proj_d=not cfg.d_causal and self._attn_proj(T + 1, cfg.d_heads, Dd))
+            attn_proj_e=self._attn_proj(T, cfg.e_heads, De), attn_proj_d=not cfg.d_causal and self._attn_proj(T + 1, cfg.d_heads, Dd),
+            # the K | Q | V input gradient of an encoder layer as the head of the one-launch backward block below it (which then starts
+            # with its leading LayerNorm backward: row_block_bwd 'fused' with a lead), where the library takes the shape that way
+            kqv_head_e=bool(self.kqv_head and cfg.e_layers >= 2 and o.ffn_fusion_pays(De, 4 * De) and not o.ln_bwd_fusion_pays(De) and
+                            o.kqv_head_pays(self.adt, B * T, De)))
 
     def _attn_proj(self, S, H, D):
         return bool(o.attn_bwd_form(self.adt, self.B, S, H, D // H, 0, D, 2 * D, 3 * D, D, 3 * D, proj=True)["proj"])
@@ -1431,14 +1446,16 @@ class StepPlan:
         return dict(x=L.h2, gamma=P.ln2.gamma, mean=L.mean2, rstd=L.rstd2, dgamma=P.ln2.dgamma, dbeta=P.ln2.dbeta,
                     partials=self._ln_partials(P.ln2, o.gemm_nt_ln_parts(M)), **_lead_mask(P, t, self._dropout(p, site0)))
 
-    def _layer_bwd(self, side, i, L, x_in, dy, dx_in, keymask, D, H, S, p, site0, t, dy_done=False, next_ln=None, ride=False):
+    def _layer_bwd(self, side, i, L, x_in, dy, dx_in, keymask, D, H, S, p, site0, t, dy_done=False, next_ln=None, ride=False, head=None):
         """dy: gradient w.r.t. the layer output x2; writes the gradient w.r.t. x_in into dx_in.
         dy_done: the producer of dy already ran this layer's leading LayerNorm backward (t.dh / t.dhm are filled).
         next_ln: (_out_ln_bwd(...) of the layer below, its scratch): run THAT layer's leading LayerNorm backward in the
         epilogue of this layer's last GEMM instead of writing dx_in.
         ride (decoder layer 0 when the backward tail takes a rider): rows 1..T of dx_in — which only the decoder embedding's weight
         gradient reads — are left to that launch and row 0 to the latent block's backward launch; returns (the rider's GEMM,
-        latent_bwd_vec's proj= triple) for backward_early to hand them on. Else returns None."""
+        latent_bwd_vec's proj= triple) for backward_early to hand them on.
+        head (Forms.kqv_head_e): the K | Q | V dgrad the layer ABOVE left to this layer's one-launch block (row_block_bwd head=; dy is not
+        read). An encoder layer above another one leaves its own the same way and returns it: dx_in is not written. Else returns None."""
         F, P = self.forms, self.store.layer(side, i)
         ffn, ln = (F.ffn_e, F.ln_bwd_e) if side == "encoder" else (F.ffn_d, F.ln_bwd_d)
         # (Forms.dec_tail: the last decoder layer's one-launch block already ran inside the loss launch, losses())
@@ -1446,7 +1463,7 @@ class StepPlan:
         proj = F.attn_proj_e if side == "encoder" else F.attn_proj_d
         dff, dproj = row_block_bwd(P, L, t, dy, ALL_ROWS, self._dropout(p, site0), "fused" if ffn else ("ln_fused" if ln else "launches"),
                                    self._ln_partials, dy_done=dy_done, row_groups=self._row0_groups(side, i), launch=not in_loss,
-                                   proj_dgrad=not proj)
+                                   proj_dgrad=not proj, head=head)
         if side == "decoder" and self.cfg.d_causal:
             o.attn_causal_bwd(L.qkv, keymask, L.lse, t.datt, t.dqkv, t.delta, self.B, S, H, D // H, 0, D, 2 * D)
         elif proj:  # dO = dproj W_proj is formed by the (batch, head) workgroups themselves; nothing else reads t.datt
@@ -1457,6 +1474,8 @@ class StepPlan:
         if next_ln is not None:  # the layer below starts its backward pass with a LayerNorm backward: run it here
             kw, t_below = next_ln
             o.gemm_nt_ln_bwd(t.dqkv, P.kqv.t, t_below.dh, N=D, K=3 * D, resid=t.dh1, **kw)
+        elif side == "encoder" and i > 0 and F.kqv_head_e:  # the layer below forms it in front of its leading LayerNorm backward
+            handed = dict(A=t.dqkv, B=P.kqv.t, resid=t.dh1, N=D, K=3 * D)
         elif ride:
             T_ = self.T
             handed = (dict(A=t.dqkv, B=P.kqv.t, C_out=dx_in, M=self.B * T_, N=D, K=3 * D, resid=t.dh1, resid_phys=True,
@@ -1473,9 +1492,11 @@ class StepPlan:
         """_layer_bwd for the LAST encoder layer, on the B rows (position 0 of each sample) that carry gradient: LayerNorm-2 backward,
         both FFN dgrads, LayerNorm-1 backward and the W_proj dgrad of those rows as one launch (with `rider`, a GEMM for its idle
         workgroups) or five; then attention backward (dO is zero outside position 0), the K | Q | V dgrad and the layer's deferred
-        weight gradients."""
+        weight gradients. With Forms.kqv_head_e and a layer below, the K | Q | V dgrad is not issued here: it is left in self._kqv_head
+        for backward_late's first _layer_bwd (dx_in is not written)."""
         cfg, st, B, S, F = self.cfg, self.store, self.B, self.T, self.forms
         D, H = cfg.e_model, cfg.e_heads
+        self._kqv_head = None
         P, c, rows = st.layer("encoder", i), self.top, position0_rows(B, S)
         self._tail_used["bwd"] = F.tails
         tail = None
@@ -1489,6 +1510,8 @@ class StepPlan:
         if next_ln is not None:  # as in _layer_bwd: the layer below's LayerNorm-2 backward rides on this GEMM
             kw, t_below = next_ln
             o.gemm_nt_ln_bwd(c.dqkv, P.kqv.t, t_below.dh, N=D, K=3 * D, resid=c.dh1, **kw)
+        elif i > 0 and F.kqv_head_e:  # as in _layer_bwd: left to the one-launch block of the layer below (the first launch of backward_late)
+            self._kqv_head = dict(A=c.dqkv, B=P.kqv.t, resid=c.dh1, N=D, K=3 * D)
         else:
             o.gemm_nt(c.dqkv, P.kqv.t, dx_in, N=D, K=3 * D, resid=c.dh1)
         self._wgrads += layer_wgrads(P, L, c, x_in, dff, dproj, rows)
@@ -1582,10 +1605,12 @@ class StepPlan:
         sq_e = math.sqrt(float(De))
         dy, pingpong = self.be_l[0].dx_a, (self.be_l[0].dx_b, self.be_l[0].dx_a)  # the top layer wrote dx_a
         # (F.ln_bwd_e: every layer's leading LayerNorm backward already ran in the GEMM above it)
+        head = self._kqv_head  # (Forms.kqv_head_e: the top layer's K | Q | V dgrad, formed by the launch that reads it)
         for n, i in enumerate(reversed(range(cfg.e_layers - 1))):
             x_in = self.enc[i - 1].x2 if i > 0 else self.x0_e
-            self._layer_bwd("encoder", i, self.enc[i], x_in, dy, pingpong[n % 2], self.keymask_e, De, cfg.e_heads, Se, cfg.e_dropout,
-                            self._site_e(i), self.be_l[i], dy_done=F.ln_bwd_e, next_ln=self._below("encoder", i, F.ln_bwd_e))
+            head = self._layer_bwd("encoder", i, self.enc[i], x_in, dy, pingpong[n % 2], self.keymask_e, De, cfg.e_heads, Se, cfg.e_dropout,
+                                   self._site_e(i), self.be_l[i], dy_done=F.ln_bwd_e, next_ln=self._below("encoder", i, F.ln_bwd_e),
+                                   head=head)
             dy = pingpong[n % 2]
         d_x0_e = dy
         if cfg.kind == "token":

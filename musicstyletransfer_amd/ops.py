@@ -380,20 +380,67 @@ def dec_tail_step(fwd, loss, dgrad, bwd):
          C.byref(l3b), C.byref(b1), C.byref(b2), C.byref(l1b), stream())
 
 
+def _kqv_head_args(A, B, C_out=None, **kw):
+    """the K | Q | V dgrad head of ffn_ln_bwd as mst_gemm_args; C_out None: the head's result is not stored"""
+    g = _gemm_args(A, B, A if C_out is None else C_out, **kw)
+    if C_out is None:
+        g.C, g.ldc = None, 0
+    return g
+
+
+def ffn_ln_bwd_head_form(head, dff, W2t, dpre_out, gate, W1t, dx_out, row_groups=None):
+    """1 when ffn_ln_bwd(..., head=head) computes the head's GEMM inside its one launch for these arguments, 0 when it runs the GEMM
+    launch first (mst_kqv_ffn_ln_bwd_form); no launch"""
+    rg = {}
+    if row_groups is not None:
+        M, remap = _row_groups(dff.shape[0], row_groups)
+        rg = dict(M=M, a_remap=remap)
+    g1 = _gemm_args(dff, W2t, dpre_out, gate=gate, **rg)
+    g2 = _gemm_args(dpre_out, W1t, dx_out, **({"M": rg["M"]} if rg else {}))
+    form = (C.c_int64 * 1)()
+    call("mst_kqv_ffn_ln_bwd_form", C.byref(_kqv_head_args(**head)), C.byref(g1), C.byref(g2), form)
+    return int(form[0])
+
+
+def kqv_head_pays(dtype, M, D):
+    """whether the K | Q | V dgrad of M rows at width D (transposed shadow [D, 3 D], contiguous operands) goes into the feed-forward
+    backward launch below it: the library's rule (mst_kqv_ffn_ln_bwd_form) on stand-in arguments of that layout; no device"""
+    g = lambda m, n, k, lda, ldb, ldc: _plain_gemm_args(dtype, m, n, k, lda, ldb, ldc)
+    head = g(M, D, 3 * D, 3 * D, 3 * D, 0)
+    head.C, head.resid, head.ldr = None, 4096, D
+    form = (C.c_int64 * 1)()
+    call("mst_kqv_ffn_ln_bwd_form", C.byref(head), C.byref(g(M, 4 * D, D, D, D, 4 * D)), C.byref(g(M, D, 4 * D, 4 * D, 4 * D, D)), form)
+    return bool(form[0])
+
+
+def _plain_gemm_args(dtype, M, N, K, lda, ldb, ldc):
+    """mst_gemm_args of a plain GEMM for the host-side form queries: aligned stand-in addresses, nothing is launched"""
+    g = GemmArgs()
+    g.dtype, g.M, g.N, g.K, g.alpha = dt(dtype), M, N, K, 1.0
+    g.A, g.lda, g.B, g.ldb, g.C, g.ldc = 4096, lda, 4096, ldb, 4096, ldc
+    return g
+
+
 def ffn_ln_bwd(dff, W2t, dpre_out, gate, W1t, dx_out, x, gamma, mean, rstd, dgamma, dbeta, alpha=1.0, dx_masked=None, mask_mode=0,
-               partials=None, lead=None, row_groups=None, **kw):
+               partials=None, lead=None, row_groups=None, head=None, **kw):
     """dpre_out = ((dff @ W2t^T) * alpha) gated by gate > 0; dx_out = LayerNorm-backward(dpre_out @ W1t^T + resid; x, mean, rstd,
     gamma) in one launch (mst_ffn_ln_bwd). W2t / W1t: the transposed 16-bit weights ([F, D] and [D, F]); **kw: resid and the
     dropout fields of the LayerNorm-backward mask, as for gemm_nt_ln_bwd.
     lead: dict(dy, x, gamma, mean, rstd, dx, [dx_masked, dropout_*], [dgamma, dbeta | partials]) -> the layer's leading
-    LayerNorm backward runs in the prologue (mst_ffn_ln_bwd_lead); dff must then be lead's dx_masked (or dx)."""
+    LayerNorm backward runs in the prologue (mst_ffn_ln_bwd_lead); dff must then be lead's dx_masked (or dx).
+    head (with lead, whose dy it replaces): dict(A, B, resid, [C_out]) -> lead's incoming gradient is A @ B^T + resid, the K | Q | V
+    input gradient of the layer above (K = 3 x width), computed by the same launch where ffn_ln_bwd_head_form says so
+    (mst_kqv_ffn_ln_bwd) and stored only when C_out is given; every other shape needs C_out and runs gemm_nt into it first."""
     g1, g2, l = _ffn_ln_bwd_args(dff, W2t, dpre_out, gate, W1t, dx_out, x, gamma, mean, rstd, dgamma, dbeta, alpha, dx_masked, mask_mode,
                                  partials, row_groups, **kw)
     if lead is None:
+        if head is not None:
+            raise ValueError("ffn_ln_bwd(head=) computes lead's incoming gradient: it needs lead=")
         call("mst_ffn_ln_bwd", C.byref(g1), C.byref(g2), C.byref(l), stream())
         return
     q = LnBwdIn()
-    q.dy, q.ld_dy = ptr(lead["dy"]), ld(lead["dy"])
+    dy = lead.get("dy") if head is None else head.get("C_out")
+    q.dy, q.ld_dy = ptr(dy), (ld(dy) if dy is not None else 0)
     q.x, q.ld_x = ptr(lead["x"]), ld(lead["x"])
     q.gamma, q.mean, q.rstd = ptr(lead["gamma"]), ptr(lead["mean"]), ptr(lead["rstd"])
     q.dx, q.ld_dx = ptr(lead["dx"]), ld(lead["dx"])
@@ -405,6 +452,9 @@ def ffn_ln_bwd(dff, W2t, dpre_out, gate, W1t, dx_out, x, gamma, mean, rstd, dgam
     q.dropout_seed_ptr, q.dropout_site = ptr(lead.get("dropout_seed_ptr")), lead.get("dropout_site", 0)
     if lead.get("partials") is not None:
         assert lead["partials"].shape[0] >= gemm_nt_ln_parts(g1.M) and lead["partials"].shape[1] == 2 * g2.N
+    if head is not None:
+        call("mst_kqv_ffn_ln_bwd", C.byref(_kqv_head_args(**head)), C.byref(q), C.byref(g1), C.byref(g2), C.byref(l), stream())
+        return
     call("mst_ffn_ln_bwd_lead", C.byref(q), C.byref(g1), C.byref(g2), C.byref(l), stream())
 
 
