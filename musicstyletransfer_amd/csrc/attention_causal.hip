@@ -1,5 +1,6 @@
 // attention_causal.hip — causal self-attention with a softmax over the KEY axis, forward and backward (the decoder's opt-in
-// causal mode, VAEConfig.d_causal; the reference's own key-row softmax lives in attention.hip and is not touched here).
+// causal mode, VAEConfig.d_causal; the reference's own key-row softmax lives in attention.hip and its units attention_fwd.hip /
+// attention_bwd.hip and is not touched here).
 //
 // Per (batch b, head h), with keymask[b,k] the decoder's mask k < seq_len[b] + 1:
 //   logit[q,k] = Q[q]·K[k] / sqrt(dh)              for k <= q and keymask[b,k]; excluded (P = 0) otherwise

@@ -15,14 +15,15 @@ OBJ_DIR = os.path.join(HERE, "_obj")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
-# Per-file code generation switches. attention.hip: MFMA results feed VALU work (exp, scaling) at once, so the
-# accumulators should live in VGPRs, not AGPRs: no v_accvgpr_read copies and 150 instead of 184 registers per
+# Per-file code generation switches. The units of key-row attention: MFMA results feed VALU work (exp, scaling) at once, so
+# the accumulators should live in VGPRs, not AGPRs: no v_accvgpr_read copies and 150 instead of 184 registers per
 # lane (3 waves/SIMD instead of 2).
 # -fno-slp-vectorize: left to itself hipcc pairs the per-element fp32 multiplies of a probability tile into v_pk_mul_f32
 # one register off the MFMA accumulator's pairs (fourteen v_mov + eight v_alignbit / v_perm per tile to repair them), and
 # packed fp32 beside MFMAs costs more issue time than the two scalar instructions it replaces anyway
 # (MI355X_MICROARCH: "an anti-lever beside MFMAs"). In-call A/B, scalar vs hand-packed vs compiler-packed: kernel_notes.
-FILE_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"]}
+ATTENTION_UNITS = ("attention.hip", "attention_fwd.hip", "attention_bwd.hip")
+FILE_FLAGS = {f: ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"] for f in ATTENTION_UNITS}
 for _kv in os.environ.get("MST_EXTRA_FLAGS", "").split(";"):  # "file.hip=-flag -flag;..." for experiments
     if "=" in _kv:
         FILE_FLAGS.setdefault(_kv.split("=", 1)[0], []).extend(_kv.split("=", 1)[1].split())

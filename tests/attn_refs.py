@@ -2,7 +2,7 @@
 tolerance every output element is held to, the launch decision restated, and the table of cases that reaches every launch form
 (mst_attn_fwd_form / mst_attn_bwd_form in include/mst_hip.h).
 
-The operation (csrc/attention.hip's header), per (batch b, head h), on the 16-bit-rounded operands:
+The operation (csrc/attention.hip's header; the kernels are in attention_fwd.hip / attention_bwd.hip, their tiles in attention.hpp), per (batch b, head h), on the 16-bit-rounded operands:
     x[k, q] = K[k] . Q[q]                      t[k, q] = fl32(fl32(x * scale) + madd[k]),   madd = 0, or -1e9 for a padded key
     P[k, :] = softmax over q of t[k, :]        out[q]  = sum_k P[k, q] V[k]                 (queries q < q_limit only)
     dV[k] = sum_q P dO[q]     dP[k, q] = dO[q] . V[k]     delta[k] = sum_q P dP     g = scale P (dP - delta)
@@ -235,7 +235,7 @@ def head_ref(K, Q, V, valid, dO, q_limit, dh, dtype=None, mut=None, emulate=None
     if dtype is None or mut is not None or emulate is not None:
         return r
     # ---- the bound. Every term is a unit roundoff times the fp64 sum of absolute values of what is summed; the counts are read off
-    # csrc/attention.hip and named where they enter.
+    # the tile functions of csrc/attention.hpp and named where they enter.
     u, uT, eta = U32, UT[dtype], ETA[dtype]
     SP, NT = cdiv(S, 32) * 32, cdiv(S, 32)
     unp = valid.astype(np.float64)

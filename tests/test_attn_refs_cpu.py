@@ -261,6 +261,27 @@ def test_rejected_arguments(ops):
     assert b"multiples of 8" in lib.mst_last_error()
 
 
+def test_the_launches_check_in_a_fixed_order_and_say_which_check_failed():
+    """Every launching entry point, called with nothing but null pointers (each check returns before any HIP call): the code and the
+    whole text of a bad head size, of a null pointer, and of a bad leading dimension together with a null pointer. The shape is
+    looked at first; then the pointers, then the leading dimensions — but for mst_attn_qkv_fwd, whose leading dimensions come first."""
+    from musicstyletransfer_amd import _lib
+    lib = _lib.load()
+    N = None
+    # (dh, ld of the first operand that has one beside ld_qkv) -> the call
+    calls = {
+        "mst_attn_keysoftmax_fwd": lambda dh, ld: lib.mst_attn_keysoftmax_fwd(0, 2, 64, 2, dh, N, 192, 0, 64, 128, N, N, N, ld, 0, N),
+        "mst_attn_qkv_fwd": lambda dh, ld: lib.mst_attn_qkv_fwd(0, 2, 64, 2, dh, N, ld, N, 64, N, N, 192, 0, 64, 128, N, N, N, 64, 0, N),
+        "mst_attn_keysoftmax_bwd": lambda dh, ld: lib.mst_attn_keysoftmax_bwd(0, 2, 64, 2, dh, N, 192, 0, 64, 128, N, N, N, ld, N, 192, N, 0, N),
+        "mst_attn_proj_bwd": lambda dh, ld: lib.mst_attn_proj_bwd(0, 2, 64, 2, dh, N, 192, 0, 64, 128, N, N, N, ld, N, 64, N, 64, N, 192, N, N),
+    }
+    for name, call in calls.items():
+        null = name.encode() + b": null pointer"
+        both = b"mst_attn_qkv_fwd: leading dimensions must be multiples of 8 and cover the model width" if name == "mst_attn_qkv_fwd" else null
+        for (dh, ld), text in (((48, 64), b"attention: head size must be 16, 32 or 64 (got 48)"), ((32, 64), null), ((32, 56), both)):
+            assert call(dh, ld) == -1 and lib.mst_last_error() == text, (name, dh, ld, lib.mst_last_error())
+
+
 # ------------------------------------------------------------------------------------------ the bound
 SMALLEST = ("d32-res3-s100-qlS+5", "d64-res2-s353", "d32-chunk-s865", "d32-fused-s161", "d32-forced-s70", "d64-forced-b3-s100")
 """the smallest ragged case of every forward path (three tiles, two tiles, chunked, fused, streaming), which between them take every

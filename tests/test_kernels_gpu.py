@@ -1089,7 +1089,7 @@ def test_attention_bwd_q_limit_is_bit_identical_to_dense(gpu, monkeypatch, B, S,
         res.append((dqkv.clone(), delta.clone()))
     if dh == 16 and S % 32 == 1 and S > 32:
         # the dense kernel handles the LAST row of a 32 n + 1 sequence apart (partner rows on the lanes, fp32 probabilities:
-        # attention.hip, lone_row_shape): its delta, which every query's dQ uses, agrees to rounding, not bit for bit
+        # attention.hpp, lone_row_shape): its delta, which every query's dQ uses, agrees to rounding, not bit for bit
         sc = res[1][0].float().abs().max().item()
         close(res[0][0], res[1][0], 2e-2, 1e-2 * sc, "gradients")
         assert (res[0][0] != res[1][0]).float().mean().item() < 0.05

@@ -1,6 +1,6 @@
 """Per-loop instruction mix of the gfx950 code of one csrc/*.hip file (not a test; runs without a GPU).
 
-    python tools/asm_loops.py attention.hip [mangled-name-substring ...]
+    python tools/asm_loops.py attention_bwd.hip [mangled-name-substring ...]
 
 Compiles the file to assembly with the flags musicstyletransfer_amd/csrc/build.py uses for it and, for every kernel whose mangled
 name contains one of the substrings (all kernels without any), lists each loop that holds an MFMA — the instructions between a label

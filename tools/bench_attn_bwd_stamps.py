@@ -1,4 +1,4 @@
-"""Phases of the resident attention BACKWARD kernel per workgroup (build with MST_EXTRA_FLAGS="attention.hip=-DMST_ATT_STAMPS"):
+"""Phases of the resident attention BACKWARD kernel per workgroup (build with MST_EXTRA_FLAGS="attention_bwd.hip=-DMST_ATT_STAMPS"):
 start -> Q / dO staged -> dV + delta of wave 0's key block -> dK (phase A done) -> K / V staged -> dQ stored.
 argv[1] = 'enc' (B 64, S 256, 8 heads of 32), 'sparse' (same, q_limit 1) or 'dec' (S 257, 8 heads of 16)."""
 import ctypes as C, os, sys

@@ -1,4 +1,4 @@
-"""Phases of the resident attention forward kernel per workgroup (build with MST_EXTRA_FLAGS="attention.hip=-DMST_ATT_STAMPS"):
+"""Phases of the resident attention forward kernel per workgroup (build with MST_EXTRA_FLAGS="attention_fwd.hip=-DMST_ATT_STAMPS"):
 start -> [projection loop done] -> operands staged in LDS -> key-row statistics done -> outputs stored. configs[1] encoder shapes
 (B 64, S 256, 8 heads of 32); argv[1] = 'fused' (mst_attn_qkv_fwd) or 'plain' (mst_attn_keysoftmax_fwd on a given qkv)."""
 import ctypes as C, os, sys

@@ -4,7 +4,7 @@ process, alternating the two in rounds, HIP events around every replay. Prints o
     python tools/bench_causal.py [--config 1] [--steps 200] [--warmup 20] [--rounds 4]
 
 Same inputs, weights, dropout and step options as bench.py's resident-data run of that config. The two steps differ only in
-the decoder's attention launches (attention.hip vs attention_causal.hip) and, in the causal one, a projection GEMM where a
+the decoder's attention launches (attention_fwd.hip / attention_bwd.hip vs attention_causal.hip) and, in the causal one, a projection GEMM where a
 decoder layer other than the first takes the fused projection + attention launch."""
 import argparse
 import json
