@@ -820,6 +820,32 @@ int mst_frame_step(int dtype, int64_t N, int64_t P, int64_t i, int64_t L, const 
 int mst_token_step(int dtype, int64_t N, int64_t V, int64_t i, int64_t L, const void* logits, int64_t ldl, float tau, int32_t top_k,
                    float top_p, const uint64_t* seed_ptr, int32_t* seqs, float* scores, int32_t* word, int32_t* active,
                    int32_t* kept_out, int32_t eos, int32_t pad, mst_stream_t stream);
+/* Constrained decoding: the two draws above with some cells GIVEN. The decoder is fed a held cell as if it had drawn it, and only the
+ * free cells are drawn; the held cells' -log p is kept apart from the drawn cells', in held_scores (fp32 [N], ADDED to: the caller
+ * zeroes it before a piece). Same launch shape (one wave per sequence, no atomics on the sums, a fixed order), capturable: the mask
+ * and the piece are device data, so one captured graph serves every mask and piece.
+ *
+ * mst_frame_step_held: given and hold are uint8 [N, L, ldg] / [N, L, ldh] in the roll's indexing — row (n, i - 1) belongs to
+ *   position i, columns >= P are never read. Cell (n, j) is held where hold != 0; its frame is given != 0, stored as 0 or 1. A free
+ *   cell is mst_frame_step's, random number (*seed_ptr, i, n * P + j) included: what it draws does not depend on which other cells
+ *   are held. frames, roll and probs_out are written for every cell as above; scores[n] += the sum over the FREE cells,
+ *   held_scores[n] += -sum over the HELD cells of log max(frame ? p : 1 - p, 1e-30) — what the model thinks of what it was given.
+ *   With hold all zero every output is bitwise mst_frame_step's and held_scores is unchanged. Refuses what mst_frame_step refuses,
+ *   a null given, hold or held_scores, and ldg or ldh below P. */
+int mst_frame_step_held(int dtype, int64_t N, int64_t P, int64_t i, int64_t L, const void* logits, int64_t ldl, float tau, int mode,
+                        float thr, const uint64_t* seed_ptr, uint8_t* frames, int64_t ldf, uint8_t* roll, int64_t ldr, float* scores,
+                        float* probs_out, const uint8_t* given, int64_t ldg, const uint8_t* hold, int64_t ldh, float* held_scores,
+                        mst_stream_t stream);
+/* mst_token_step_held: given int32 [N, L] and hold uint8 [N, L] in seqs' indexing. Where hold[n, i] != 0: seqs[n, i] = word[n] =
+ *   given[n, i] whatever the sequence's state; unless the sequence is finished, held_scores[n] += -log max(softmax(logit)[given],
+ *   1e-30) (the model's distribution: temperature 1, uncut); active[i] counts the token by the usual rule (neither EOS nor PAD);
+ *   kept_out[n] = 0 (nothing was drawn; the cuts are not evaluated). A given token outside [0, V) never indexes the row: PAD is
+ *   written and nothing is charged (callers refuse such input). Where hold[n, i] == 0 the position is mst_token_step's bit for bit
+ *   (seqs, scores, word, active, kept_out). Refuses what mst_token_step refuses and a null given, hold or held_scores. */
+int mst_token_step_held(int dtype, int64_t N, int64_t V, int64_t i, int64_t L, const void* logits, int64_t ldl, float tau, int32_t top_k,
+                        float top_p, const uint64_t* seed_ptr, int32_t* seqs, float* scores, int32_t* word, int32_t* active,
+                        int32_t* kept_out, int32_t eos, int32_t pad, const int32_t* given, const uint8_t* hold, float* held_scores,
+                        mst_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * K12/K13: softmax over V + SoftmaxCrossEntropy (model.py:256; loss.py:15-23).

@@ -2,7 +2,7 @@
 //   mst_beam_step   : per sample, the K best of its K x V continuations (score = summed -log p; a finished hypothesis continues
 //                     with PAD only, at no cost: sampler.py:218-221), the re-ranked token rows, the words fed to the next position
 //   mst_beam_gather : the decoder layers' K | Q | V cache rows of the re-ranked hypotheses (sampler.py:236-238)
-//   mst_sample_step / mst_frame_step : ancestral sampling's draw of a position — a token by inverse CDF, a piano-roll frame by a
+//   mst_sample_step / mst_frame_step(_held) : ancestral sampling's draw of a position — a token by inverse CDF, a piano-roll frame by a
 //                     Bernoulli draw (or a threshold) per pitch from the position's logits
 // With these two the whole position — decoder step, ranking, cache reorder — is device work inside ONE captured graph; the host
 // version spent 98 % of a position in its own top-k over beam x V and the copies around it (2.6 ms against 55 us of device time).
@@ -194,11 +194,18 @@ __global__ __launch_bounds__(256) void sample_step_kernel(int64_t N, int64_t V, 
 // frame does not lose its digits in 1 - p. mode 0 draws frame = u < p with u = (dropout_hash(seed, i, n * P + j) >> 8) * 2^-24 in
 // [0, 1); mode 1 thresholds x > thr_logit (no random number). The frame goes to frames[n, :P] (the next position's input) and to
 // roll[n, i - 1, :P]; scores[n] += -sum_j log max(frame ? p : 1 - p, 1e-30) (one wave owns a sequence: no atomics, a fixed order).
-template <typename T>
+//
+// HELD (mst_frame_step_held): a cell with hold[n, i - 1, j] != 0 is not drawn — its frame is given[n, i - 1, j] != 0, and its
+// -log p goes to held_scores[n] instead of scores[n]. A free cell is computed exactly as above, its random number still indexed by
+// (seed, i, n P + j), so what it draws does not depend on which other cells are held; with nothing held the free sum has the same
+// terms in the same order. Two more bytes are read per cell; still one wave per sequence and no atomics.
+template <typename T, bool HELD>
 __global__ __launch_bounds__(256) void frame_step_kernel(int64_t N, int64_t P, int64_t i, int64_t L, const T* __restrict__ logits, int64_t ldl,
                                                          float tau, int mode, float thr_logit, const uint64_t* __restrict__ seed_ptr,
                                                          uint8_t* __restrict__ frames, int64_t ldf, uint8_t* __restrict__ roll, int64_t ldr,
-                                                         float* __restrict__ scores, float* __restrict__ probs_out) {
+                                                         float* __restrict__ scores, float* __restrict__ probs_out,
+                                                         const uint8_t* __restrict__ given, int64_t ldg, const uint8_t* __restrict__ hold,
+                                                         int64_t ldh, float* __restrict__ held_scores) {
   const int lane = threadIdx.x & 63;
   const int64_t n = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (n >= N) return;
@@ -207,8 +214,17 @@ __global__ __launch_bounds__(256) void frame_step_kernel(int64_t N, int64_t P, i
   uint8_t* __restrict__ fr = frames + n * ldf;
   uint8_t* __restrict__ rl = roll + (n * L + (i - 1)) * ldr;
   float* __restrict__ po = probs_out ? probs_out + (n * L + (i - 1)) * P : nullptr;
-  float nll = 0.f;
+  const uint8_t* __restrict__ gv = HELD ? given + (n * L + (i - 1)) * ldg : nullptr;
+  const uint8_t* __restrict__ hd = HELD ? hold + (n * L + (i - 1)) * ldh : nullptr;
+  float nll = 0.f, held_nll = 0.f;
   for (int64_t j = lane; j < P; j += 64) {
+    // (both bytes are loaded beside the logit, whatever hold says: a load of given behind the test of hold would put a second
+    // memory round trip — to rows no launch has touched before — into a launch that is all latency)
+    uint8_t hold_j = 0, given_j = 0;
+    if constexpr (HELD) {
+      hold_j = hd[j];
+      given_j = gv[j];
+    }
     const float x = to_f32(row[j]) / tau;
     const float p = 1.f / (1.f + expf(-x)), q = 1.f / (1.f + expf(x));
     bool on;
@@ -218,38 +234,74 @@ __global__ __launch_bounds__(256) void frame_step_kernel(int64_t N, int64_t P, i
     } else {
       on = x > thr_logit;
     }
+    bool held = false;
+    if constexpr (HELD) {
+      held = hold_j != 0;
+      if (held) on = given_j != 0;
+    }
     const uint8_t f = on ? 1 : 0;
     fr[j] = f;
     rl[j] = f;
     if (po) po[j] = p;
-    nll -= logf(fmaxf(on ? p : q, 1e-30f));
+    const float cost = logf(fmaxf(on ? p : q, 1e-30f));
+    if (held) held_nll -= cost;
+    else nll -= cost;
   }
   nll = wave_sum(nll);
-  if (lane == 0) scores[n] += nll;
+  if constexpr (HELD) held_nll = wave_sum(held_nll);
+  if (lane == 0) {
+    scores[n] += nll;
+    if constexpr (HELD) held_scores[n] += held_nll;
+  }
 }
 
 }  // namespace mst
 
 using namespace mst;
 
-extern "C" int mst_frame_step(int dtype, int64_t N, int64_t P, int64_t i, int64_t L, const void* logits, int64_t ldl, float tau, int mode,
-                              float thr, const uint64_t* seed_ptr, uint8_t* frames, int64_t ldf, uint8_t* roll, int64_t ldr, float* scores,
-                              float* probs_out, mst_stream_t stream) {
-  MST_CHECK_ARG(N > 0 && P > 0 && L > 1, "mst_frame_step: sizes must be positive (L >= 2)");
-  MST_CHECK_ARG(i >= 1 && i < L, "mst_frame_step: position i outside [1, L)");
-  MST_CHECK_ARG(tau > 0.f && tau <= 3.0e38f, "mst_frame_step: tau must be positive and finite");
-  MST_CHECK_ARG(mode == 0 || mode == 1, "mst_frame_step: mode must be 0 (draw) or 1 (threshold)");
-  MST_CHECK_ARG(mode == 0 || (thr > 0.f && thr < 1.f), "mst_frame_step: thr outside (0, 1)");
-  MST_CHECK_ARG(logits && frames && roll && scores && (mode == 1 || seed_ptr), "mst_frame_step: null pointer (draw mode needs the seed word)");
-  MST_CHECK_ARG(ldl >= P && ldf >= P && ldr >= P, "mst_frame_step: a row stride below P");
+// the checks and the launch of both entry points (`name`: the one that was called; held: given / hold / held_scores are used)
+static int frame_step_launch(const char* name, bool held, int dtype, int64_t N, int64_t P, int64_t i, int64_t L, const void* logits, int64_t ldl,
+                             float tau, int mode, float thr, const uint64_t* seed_ptr, uint8_t* frames, int64_t ldf, uint8_t* roll, int64_t ldr,
+                             float* scores, float* probs_out, const uint8_t* given, int64_t ldg, const uint8_t* hold, int64_t ldh,
+                             float* held_scores, mst_stream_t stream) {
+  MST_CHECK_ARG(N > 0 && P > 0 && L > 1, "%s: sizes must be positive (L >= 2)", name);
+  MST_CHECK_ARG(i >= 1 && i < L, "%s: position i outside [1, L)", name);
+  MST_CHECK_ARG(tau > 0.f && tau <= 3.0e38f, "%s: tau must be positive and finite", name);
+  MST_CHECK_ARG(mode == 0 || mode == 1, "%s: mode must be 0 (draw) or 1 (threshold)", name);
+  MST_CHECK_ARG(mode == 0 || (thr > 0.f && thr < 1.f), "%s: thr outside (0, 1)", name);
+  MST_CHECK_ARG(logits && frames && roll && scores && (mode == 1 || seed_ptr), "%s: null pointer (draw mode needs the seed word)", name);
+  MST_CHECK_ARG(ldl >= P && ldf >= P && ldr >= P, "%s: a row stride below P", name);
+  if (held) {
+    MST_CHECK_ARG(given && hold && held_scores, "%s: null pointer (given, hold, held_scores)", name);
+    MST_CHECK_ARG(ldg >= P && ldh >= P, "%s: a row stride below P (given, hold)", name);
+  }
   const float thr_logit = mode == 1 ? (float)log((double)thr / (1.0 - (double)thr)) : 0.f;
   return dispatch_act(dtype, [&](auto tag) -> int {
     typedef decltype(tag) T;
-    hipLaunchKernelGGL((frame_step_kernel<T>), dim3((unsigned)cdiv(N, 4)), dim3(256), 0, (hipStream_t)stream, N, P, i, L, (const T*)logits, ldl,
-                       tau, mode, thr_logit, seed_ptr, frames, ldf, roll, ldr, scores, probs_out);
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)cdiv(N, 4)), dim3(256), 0, (hipStream_t)stream, N, P, i, L, (const T*)logits, ldl, tau, mode,
+                         thr_logit, seed_ptr, frames, ldf, roll, ldr, scores, probs_out, given, ldg, hold, ldh, held_scores);
+    };
+    if (held) launch(frame_step_kernel<T, true>);
+    else launch(frame_step_kernel<T, false>);
     MST_CHECK_LAUNCH("frame_step_kernel");
     return MST_OK;
   });
+}
+
+extern "C" int mst_frame_step(int dtype, int64_t N, int64_t P, int64_t i, int64_t L, const void* logits, int64_t ldl, float tau, int mode,
+                              float thr, const uint64_t* seed_ptr, uint8_t* frames, int64_t ldf, uint8_t* roll, int64_t ldr, float* scores,
+                              float* probs_out, mst_stream_t stream) {
+  return frame_step_launch("mst_frame_step", false, dtype, N, P, i, L, logits, ldl, tau, mode, thr, seed_ptr, frames, ldf, roll, ldr, scores,
+                           probs_out, nullptr, 0, nullptr, 0, nullptr, stream);
+}
+
+extern "C" int mst_frame_step_held(int dtype, int64_t N, int64_t P, int64_t i, int64_t L, const void* logits, int64_t ldl, float tau, int mode,
+                                   float thr, const uint64_t* seed_ptr, uint8_t* frames, int64_t ldf, uint8_t* roll, int64_t ldr,
+                                   float* scores, float* probs_out, const uint8_t* given, int64_t ldg, const uint8_t* hold, int64_t ldh,
+                                   float* held_scores, mst_stream_t stream) {
+  return frame_step_launch("mst_frame_step_held", true, dtype, N, P, i, L, logits, ldl, tau, mode, thr, seed_ptr, frames, ldf, roll, ldr,
+                           scores, probs_out, given, ldg, hold, ldh, held_scores, stream);
 }
 
 extern "C" int mst_sample_step(int64_t N, int64_t V, int64_t i, int64_t L, const float* probs, int64_t ldp, int32_t* seqs, float* scores,

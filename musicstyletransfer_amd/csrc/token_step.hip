@@ -39,12 +39,19 @@ constexpr int TOKEN_OWN = 8;  // a lane's ceil(V / 64) tokens stay in registers 
 
 // lane l owns the contiguous columns [l chunk, (l + 1) chunk) as in sample_step_kernel. REGS: keys and masses in registers; otherwise
 // the chunk is walked from memory again in every pass (the row is then in L1 / L2).
-template <typename T, bool REGS>
+//
+// HELD (mst_token_step_held): where hold[n, i] != 0 the token is given[n, i] instead of a draw — written whatever the sequence's state,
+// charged to held_scores[n] (the model's own -log softmax, as for a drawn token) unless the sequence is finished, counted in
+// active[i] by the usual rule, kept_out[n] = 0. The branch is wave-uniform and leaves before the cuts; it costs the five bytes of
+// hold and given per sequence. A given token outside [0, V) is never used as an index: PAD is written and nothing is charged.
+template <typename T, bool REGS, bool HELD>
 __global__ __launch_bounds__(256) void token_step_kernel(int64_t N, int64_t V, int64_t i, int64_t L, const uint16_t* __restrict__ logits,
                                                          int64_t ldl, float tau, int32_t top_k, float top_p,
                                                          const uint64_t* __restrict__ seed_ptr, int32_t* __restrict__ seqs,
                                                          float* __restrict__ scores, int32_t* __restrict__ word, int32_t* __restrict__ active,
-                                                         int32_t* __restrict__ kept_out, int32_t eos, int32_t pad) {
+                                                         int32_t* __restrict__ kept_out, int32_t eos, int32_t pad,
+                                                         const int32_t* __restrict__ given, const uint8_t* __restrict__ hold,
+                                                         float* __restrict__ held_scores) {
   const int lane = threadIdx.x & 63;
   const int64_t n = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (n >= N) return;  // (a whole wave)
@@ -84,6 +91,22 @@ __global__ __launch_bounds__(256) void token_step_kernel(int64_t N, int64_t V, i
     for (int w = lo; w < hi; ++w) psum += expf(bits_to_f32<T>(row[w]) - vmax);
   }
   psum = wave_sum(psum);
+
+  if constexpr (HELD) {
+    if (hold[n * L + i] != 0) {  // (the same for the whole wave)
+      if (lane == 0) {
+        const int32_t g = given[n * L + i];
+        const bool ok = g >= 0 && (int64_t)g < V;
+        const int32_t w = ok ? g : pad;
+        seqs[n * L + i] = w;
+        word[n] = w;
+        if (ok && !fin) held_scores[n] += -logf(fmaxf(expf(bits_to_f32<T>(row[g]) - vmax) / fmaxf(psum, 1e-30f), 1e-30f));
+        if (active && w != eos && w != pad) atomicAdd(active + i, 1);
+        if (kept_out) kept_out[n] = 0;
+      }
+      return;
+    }
+  }
 
   // f(key, mass, column) over this lane's tokens in column order
   auto each = [&](auto&& f) {
@@ -175,25 +198,46 @@ __global__ __launch_bounds__(256) void token_step_kernel(int64_t N, int64_t V, i
 
 using namespace mst;
 
-extern "C" int mst_token_step(int dtype, int64_t N, int64_t V, int64_t i, int64_t L, const void* logits, int64_t ldl, float tau, int32_t top_k,
-                              float top_p, const uint64_t* seed_ptr, int32_t* seqs, float* scores, int32_t* word, int32_t* active,
-                              int32_t* kept_out, int32_t eos, int32_t pad, mst_stream_t stream) {
-  MST_CHECK_ARG(N > 0 && V > 0 && L > 1 && V <= (1ll << 30), "mst_token_step: sizes must be positive (L >= 2, V <= 2^30)");
-  MST_CHECK_ARG(i >= 1 && i < L, "mst_token_step: position i outside [1, L)");
-  MST_CHECK_ARG(tau > 0.f && tau <= 3.0e38f, "mst_token_step: tau must be positive and finite");
-  MST_CHECK_ARG(top_k >= 0, "mst_token_step: top_k must be 0 (off) or at least 1");
-  MST_CHECK_ARG(top_p > 0.f && top_p <= 1.f, "mst_token_step: top_p outside (0, 1]");
-  MST_CHECK_ARG(logits && seed_ptr && seqs && scores && word, "mst_token_step: null pointer (logits, seed word, seqs, scores, word)");
-  MST_CHECK_ARG(ldl >= V, "mst_token_step: a row stride below V");
+// the checks and the launch of both entry points (`name`: the one that was called; held: given / hold / held_scores are used)
+static int token_step_launch(const char* name, bool held, int dtype, int64_t N, int64_t V, int64_t i, int64_t L, const void* logits, int64_t ldl,
+                             float tau, int32_t top_k, float top_p, const uint64_t* seed_ptr, int32_t* seqs, float* scores, int32_t* word,
+                             int32_t* active, int32_t* kept_out, int32_t eos, int32_t pad, const int32_t* given, const uint8_t* hold,
+                             float* held_scores, mst_stream_t stream) {
+  MST_CHECK_ARG(N > 0 && V > 0 && L > 1 && V <= (1ll << 30), "%s: sizes must be positive (L >= 2, V <= 2^30)", name);
+  MST_CHECK_ARG(i >= 1 && i < L, "%s: position i outside [1, L)", name);
+  MST_CHECK_ARG(tau > 0.f && tau <= 3.0e38f, "%s: tau must be positive and finite", name);
+  MST_CHECK_ARG(top_k >= 0, "%s: top_k must be 0 (off) or at least 1", name);
+  MST_CHECK_ARG(top_p > 0.f && top_p <= 1.f, "%s: top_p outside (0, 1]", name);
+  MST_CHECK_ARG(logits && seed_ptr && seqs && scores && word, "%s: null pointer (logits, seed word, seqs, scores, word)", name);
+  MST_CHECK_ARG(ldl >= V, "%s: a row stride below V", name);
+  if (held) MST_CHECK_ARG(given && hold && held_scores, "%s: null pointer (given, hold, held_scores)", name);
   return dispatch_act(dtype, [&](auto tag) -> int {
     typedef decltype(tag) T;
     auto launch = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, dim3((unsigned)cdiv(N, 4)), dim3(256), 0, (hipStream_t)stream, N, V, i, L, (const uint16_t*)logits, ldl, tau,
-                         top_k, top_p, seed_ptr, seqs, scores, word, active, kept_out, eos, pad);
+                         top_k, top_p, seed_ptr, seqs, scores, word, active, kept_out, eos, pad, given, hold, held_scores);
     };
-    if (V <= 64 * TOKEN_OWN) launch(token_step_kernel<T, true>);
-    else launch(token_step_kernel<T, false>);
+    const bool regs = V <= 64 * TOKEN_OWN;
+    if (regs && held) launch(token_step_kernel<T, true, true>);
+    else if (regs) launch(token_step_kernel<T, true, false>);
+    else if (held) launch(token_step_kernel<T, false, true>);
+    else launch(token_step_kernel<T, false, false>);
     MST_CHECK_LAUNCH("token_step_kernel");
     return MST_OK;
   });
+}
+
+extern "C" int mst_token_step(int dtype, int64_t N, int64_t V, int64_t i, int64_t L, const void* logits, int64_t ldl, float tau, int32_t top_k,
+                              float top_p, const uint64_t* seed_ptr, int32_t* seqs, float* scores, int32_t* word, int32_t* active,
+                              int32_t* kept_out, int32_t eos, int32_t pad, mst_stream_t stream) {
+  return token_step_launch("mst_token_step", false, dtype, N, V, i, L, logits, ldl, tau, top_k, top_p, seed_ptr, seqs, scores, word, active,
+                           kept_out, eos, pad, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int mst_token_step_held(int dtype, int64_t N, int64_t V, int64_t i, int64_t L, const void* logits, int64_t ldl, float tau,
+                                   int32_t top_k, float top_p, const uint64_t* seed_ptr, int32_t* seqs, float* scores, int32_t* word,
+                                   int32_t* active, int32_t* kept_out, int32_t eos, int32_t pad, const int32_t* given, const uint8_t* hold,
+                                   float* held_scores, mst_stream_t stream) {
+  return token_step_launch("mst_token_step_held", true, dtype, N, V, i, L, logits, ldl, tau, top_k, top_p, seed_ptr, seqs, scores, word,
+                           active, kept_out, eos, pad, given, hold, held_scores, stream);
 }

@@ -317,7 +317,13 @@ class FrameSampling:
     embedding GEMM reads it and into the roll, and adds the frame's -log p to the scores — are ONE captured graph per position. The
     draw's seed is a device word the host rewrites before a run, so the graphs captured by one run replay for every later one; the
     host sees nothing until the roll is copied back at the end. (The draw forms sigmoid(logit / tau) itself: these graphs have no
-    sigmoid_bce launch.) tau, mode and thr are launch constants of mst_frame_step: a graph is kept per (position, tau, mode, thr)."""
+    sigmoid_bce launch.) tau, mode and thr are launch constants of mst_frame_step: a graph is kept per (position, tau, mode, thr).
+
+    Constrained runs (run(..., given, hold)): cells of the piece are GIVEN — the position's graph ends in mst_frame_step_held, which
+    writes a held cell from `given` instead of drawing it, so the decoder is fed the held cells as if it had drawn them and the caches
+    and the arithmetic are the unconstrained path's. The mask and the piece are device buffers of the sampler (allocated at the first
+    such run): the graph key gains one boolean and nothing else, another mask or piece captures nothing. The held cells' summed
+    -log p is left in self.held_scores (host fp32 [N]) — it is not part of the returned scores."""
 
     def __init__(self, store, N, L, attention="query", keep_probs=False):
         """L positions: the start row + up to L - 1 frames. keep_probs: the per-position probabilities stay in self.probs
@@ -337,20 +343,65 @@ class FrameSampling:
         self.seed_word = torch.zeros(1, dtype=torch.int64, device=dev)
         self._seed_host = torch.zeros(1, dtype=torch.int64).pin_memory()
         self._graphs, self._warm = {}, False
+        self.given = self.hold = self.held_dev = None  # device buffers of constrained runs, allocated by the first one
+        self.held_scores = None                        # host fp32 [N] of the latest constrained run
+        self._warm_held = False
 
-    def _position(self, i, tau, mode, thr):
+    def _position(self, i, tau, mode, thr, held=False):
         p = self.plan
         p._position(i, probs=False)
-        o.frame_step(p.logits, self.P, i, self.seed_word, p.frames, self.roll, self.scores, tau=tau, mode=mode, thr=thr, probs_out=self.probs)
+        if held:
+            o.frame_step_held(p.logits, self.P, i, self.seed_word, p.frames, self.roll, self.scores, self.given, self.hold, self.held_dev,
+                              tau=tau, mode=mode, thr=thr, probs_out=self.probs)
+        else:
+            o.frame_step(p.logits, self.P, i, self.seed_word, p.frames, self.roll, self.scores, tau=tau, mode=mode, thr=thr,
+                         probs_out=self.probs)
 
-    def run(self, row0, length=None, tau=1.0, mode="draw", thr=0.5, seed=0):
+    def _constraint(self, given, hold, length):
+        """(given, hold) as host arrays [N, T, P], T <= length - 1 frames (row k is position k + 1's); frames behind T are free"""
+        if given is None or hold is None:
+            raise ValueError("a constrained run needs both `given` and `hold`")
+        given, hold = np.asarray(given), np.asarray(hold)
+        if given.shape != hold.shape or given.ndim != 3 or given.shape[0] != self.N or given.shape[2] != self.P:
+            raise ValueError(f"given and hold must both be [{self.N}, frames, {self.P}], got {given.shape} and {hold.shape}")
+        if given.shape[1] > length - 1:
+            raise ValueError(f"{given.shape[1]} constrained frames for a run of {length - 1}")
+        return given, hold
+
+    def _load_constraint(self, given, hold):
+        """the piece and the mask into the sampler's device buffers (allocated here at first use), through pinned copies of the
+        buffers' own layout: one contiguous transfer each. A cell is set where the byte is non-zero (the kernel's rule), so byte
+        arrays go in as they are. held_scores is zeroed. Called on the plan's stream."""
+        if self.given is None:
+            self.given, self.hold = torch.zeros_like(self.roll), torch.zeros_like(self.roll)
+            self.held_dev = torch.zeros_like(self.scores)
+            self._given_host, self._hold_host = torch.zeros(self.roll.shape, dtype=torch.uint8).pin_memory(), \
+                torch.zeros(self.roll.shape, dtype=torch.uint8).pin_memory()
+        T = given.shape[1]
+        for src, host, dev in ((given, self._given_host, self.given), (hold, self._hold_host, self.hold)):
+            view = host.numpy()
+            view[:, T:] = 0  # (frames behind T hold nothing; the pad columns stay zero)
+            if src.dtype in (np.uint8, np.bool_):
+                view[:, :T, : self.P] = src.view(np.uint8)
+            else:
+                np.not_equal(src, 0, out=view[:, :T, : self.P])
+            dev.copy_(host, non_blocking=True)
+        o.zero(self.held_dev)
+
+    def run(self, row0, length=None, tau=1.0, mode="draw", thr=0.5, seed=0, given=None, hold=None):
         """row0: [N, >= D] initial decoder rows. Decodes positions 1 .. length - 1 (default: all L - 1) and returns
-        (roll uint8 [N, length - 1, P], scores [N]) as host arrays: frame i - 1 is the draw of position i."""
+        (roll uint8 [N, length - 1, P], scores [N]) as host arrays: frame i - 1 is the draw of position i.
+        given, hold: host arrays [N, T <= length - 1, P] in the returned roll's indexing: cell [n, k, j] of the roll is given[n, k, j]
+        != 0 where hold[n, k, j] != 0 and drawn (or thresholded) elsewhere; the scores then sum the free cells only, and the held
+        cells' cost is left in self.held_scores."""
         p = self.plan
         length = self.L if length is None else int(length)
         if not 2 <= length <= self.L:
             raise ValueError(f"length {length} outside [2, {self.L}]")
         tau, thr = float(tau), float(thr)
+        held = given is not None or hold is not None
+        if held:
+            given, hold = self._constraint(given, hold, length)
         p.reset()
         seed &= 0xFFFFFFFFFFFFFFFF
         self._seed_host[0] = seed - (1 << 64) if seed >= (1 << 63) else seed
@@ -362,21 +413,29 @@ class FrameSampling:
             o.zero(self.scores)
             o.zero(p.frames)
             p.frames[:, 0] = 1  # the start row (pianoroll.pianoroll_arrays)
+            if held:
+                self._load_constraint(given, hold)
             for i in range(1, length):
-                key = (i, tau, mode, thr)
+                key = (i, tau, mode, thr, True) if held else (i, tau, mode, thr)
+                warm = self._warm_held if held else self._warm
                 g = self._graphs.get(key) if p.use_graphs else None
-                if g is None and p.use_graphs and self._warm:
-                    g = self._graphs[key] = o.Graph().capture(lambda: self._position(i, tau, mode, thr))
+                if g is None and p.use_graphs and warm:
+                    g = self._graphs[key] = o.Graph().capture(lambda: self._position(i, tau, mode, thr, held))
                 if g is not None:
                     g.launch()
                 else:
-                    self._position(i, tau, mode, thr)  # (the first position ever runs eagerly: lazy HIP module loads ...
-                    self._warm = True
+                    self._position(i, tau, mode, thr, held)  # (the first position ever runs eagerly: lazy HIP module loads ...
+                    if held:
+                        self._warm_held = True
+                    else:
+                        self._warm = True
                     if p.use_graphs:                   # ... and is captured behind that, so the next run replays it too)
-                        self._graphs[key] = o.Graph().capture(lambda: self._position(i, tau, mode, thr))
+                        self._graphs[key] = o.Graph().capture(lambda: self._position(i, tau, mode, thr, held))
                 p.t = i
             roll = self.roll[:, : length - 1, : self.P].cpu().numpy()
             scores = self.scores.cpu().numpy()
+            if held:
+                self.held_scores = self.held_dev.cpu().numpy()
         p._leave()
         self.positions = length - 1
         return roll, scores
@@ -388,7 +447,11 @@ class TokenSampling:
     and keeps the sampler's books (finished sequences, scores, the `active` counter) — are ONE captured graph per position. The draw's
     seed is a device word the host rewrites before a run, so the graphs captured by one run replay for every later one. (The draw forms
     both softmaxes itself: these graphs have no softmax_ce launch.) tau, top_k and top_p are launch constants of mst_token_step: a
-    graph is kept per (position, tau, top_k, top_p)."""
+    graph is kept per (position, tau, top_k, top_p).
+
+    Constrained runs (run(..., given, hold)) end every position's graph in mst_token_step_held instead: a held position writes the
+    given token, the others draw as ever. As in FrameSampling the mask and the piece are device buffers of the sampler, the graph key
+    gains one boolean, and the held tokens' summed -log p is left in self.held_scores (host fp32 [N])."""
 
     def __init__(self, store, N, L, attention="query", keep_logits=False):
         """L positions: the start row + up to L - 1 tokens. keep_logits: every position's logits stay in self.logits (fp32 [N, L, V],
@@ -411,18 +474,44 @@ class TokenSampling:
         self._seed_host = torch.zeros(1, dtype=torch.int64).pin_memory()
         self._graphs, self._warm = {}, False
         self.positions = 0
+        self.given = self.hold = self.held_dev = None  # device buffers of constrained runs, allocated by the first one
+        self.held_scores = None                        # host fp32 [N] of the latest constrained run
+        self._warm_held = False
 
-    def _position(self, i, tau, top_k, top_p):
+    def _position(self, i, tau, top_k, top_p, held=False):
         p = self.plan
         p._position(i, probs=False)
         if self.logits is not None:
             self.logits[:, i].copy_(p.logits[:, : self.V])  # (a device copy: part of the position's graph)
-        o.token_step(p.logits, self.V, i, self.seed_word, self.seqs, self.scores, p.tokens, self.eos, self.pad, tau=tau, top_k=top_k,
-                     top_p=top_p, active=self.active)
+        if held:
+            o.token_step_held(p.logits, self.V, i, self.seed_word, self.seqs, self.scores, p.tokens, self.eos, self.pad, self.given, self.hold,
+                              self.held_dev, tau=tau, top_k=top_k, top_p=top_p, active=self.active)
+        else:
+            o.token_step(p.logits, self.V, i, self.seed_word, self.seqs, self.scores, p.tokens, self.eos, self.pad, tau=tau, top_k=top_k,
+                         top_p=top_p, active=self.active)
 
-    def run(self, row0, length=None, tau=1.0, top_k=0, top_p=1.0, seed=0, check_every=8):
+    def _constraint(self, given, hold, length):
+        """host copies of (given int32, hold uint8) as [N, T], T <= length, in the sequence's indexing (index 0 is SOS and never held)"""
+        if given is None or hold is None:
+            raise ValueError("a constrained run needs both `given` and `hold`")
+        given, hold = np.asarray(given), np.asarray(hold)
+        if given.shape != hold.shape or given.ndim != 2 or given.shape[0] != self.N:
+            raise ValueError(f"given and hold must both be [{self.N}, tokens], got {given.shape} and {hold.shape}")
+        if given.shape[1] > length:
+            raise ValueError(f"{given.shape[1]} constrained tokens for a run of {length}")
+        hold = (hold != 0).astype(np.uint8)
+        hold[:, :1] = 0
+        bad = (hold != 0) & ((given < 0) | (given >= self.V))
+        if bad.any():
+            raise ValueError(f"a held token outside [0, {self.V}): {np.asarray(given)[bad][:8].tolist()}")
+        return np.where(hold != 0, given, self.pad).astype(np.int32), hold
+
+    def run(self, row0, length=None, tau=1.0, top_k=0, top_p=1.0, seed=0, check_every=8, given=None, hold=None):
         """row0: [N, >= D] initial decoder rows. Decodes positions 1 .. length - 1 (default: all L - 1), stopping early once every
-        sequence has ended (looked at every check_every positions), and returns (token rows [N, n] int32, scores [N]) as host arrays."""
+        sequence has ended (looked at every check_every positions), and returns (token rows [N, n] int32, scores [N]) as host arrays.
+        given, hold: host arrays [N, T <= length] in the returned rows' indexing: token [n, i] is given[n, i] where hold[n, i] != 0
+        (i >= 1) and drawn elsewhere; the scores then sum the drawn tokens only, and the held tokens' cost is left in
+        self.held_scores. A run does not stop before its last held position."""
         p = self.plan
         length = self.L if length is None else int(length)
         if not 2 <= length <= self.L:
@@ -430,6 +519,11 @@ class TokenSampling:
         tau, top_k, top_p = float(tau), int(top_k), float(top_p)
         if not (0.0 < tau < float("inf")) or top_k < 0 or not 0.0 < top_p <= 1.0:
             raise ValueError(f"tau > 0 finite, top_k >= 0 and 0 < top_p <= 1 wanted, got {tau}, {top_k}, {top_p}")
+        held, last_held = given is not None or hold is not None, 0
+        if held:
+            given, hold = self._constraint(given, hold, length)
+            cols = np.nonzero(hold.any(0))[0]
+            last_held = int(cols[-1]) if cols.size else 0
         p.reset()
         seed &= 0xFFFFFFFFFFFFFFFF
         self._seed_host[0] = seed - (1 << 64) if seed >= (1 << 63) else seed
@@ -443,24 +537,40 @@ class TokenSampling:
             o.zero(self.scores)
             o.zero(self.active)
             p.tokens.fill_(self.sos)
+            if held:
+                if self.given is None:
+                    self.given = torch.zeros_like(self.seqs)
+                    self.hold = torch.zeros(self.N, self.L, dtype=torch.uint8, device=self.seqs.device)
+                    self.held_dev = torch.zeros_like(self.scores)
+                T = given.shape[1]
+                o.zero(self.hold)  # (positions behind T hold nothing)
+                self.given[:, :T].copy_(torch.from_numpy(given))
+                self.hold[:, :T].copy_(torch.from_numpy(hold))
+                o.zero(self.held_dev)
             last = 0
             for i in range(1, length):
-                key = (i, tau, top_k, top_p)
+                key = (i, tau, top_k, top_p, True) if held else (i, tau, top_k, top_p)
+                warm = self._warm_held if held else self._warm
                 g = self._graphs.get(key) if p.use_graphs else None
-                if g is None and p.use_graphs and self._warm:
-                    g = self._graphs[key] = o.Graph().capture(lambda: self._position(i, tau, top_k, top_p))
+                if g is None and p.use_graphs and warm:
+                    g = self._graphs[key] = o.Graph().capture(lambda: self._position(i, tau, top_k, top_p, held))
                 if g is not None:
                     g.launch()
                 else:
-                    self._position(i, tau, top_k, top_p)  # (the first position ever runs eagerly: lazy HIP module loads ...
-                    self._warm = True
+                    self._position(i, tau, top_k, top_p, held)  # (the first position ever runs eagerly: lazy HIP module loads ...
+                    if held:
+                        self._warm_held = True
+                    else:
+                        self._warm = True
                     if p.use_graphs:                      # ... and is captured behind that, so the next run replays it too)
-                        self._graphs[key] = o.Graph().capture(lambda: self._position(i, tau, top_k, top_p))
+                        self._graphs[key] = o.Graph().capture(lambda: self._position(i, tau, top_k, top_p, held))
                 p.t = last = i
-                if i % check_every == 0 and int(self.active[i].item()) == 0:
+                if i % check_every == 0 and i >= last_held and int(self.active[i].item()) == 0:
                     break
             seqs = self.seqs[:, : last + 1].cpu().numpy()
             scores = self.scores.cpu().numpy()
+            if held:
+                self.held_scores = self.held_dev.cpu().numpy()
         p._leave()
         self.positions = last
         return seqs, scores

@@ -7,6 +7,18 @@ the CPU tests check), turned into latent vectors and decoder start rows by ONE l
 and decoded by what the samplers use: decode.AncestralSampling / decode.BeamSearch for the token ends (decode.TokenSampling when the
 draw has a temperature, a top-k or a nucleus cut), decode.FrameSampling for the piano-roll ends. The reference stops at `latent_vector = means` (sampler.py:146-148); nothing here has a counterpart there.
 
+Constrained decoding works on a piece that already exists: some cells of the output are GIVEN (a mask from hold_mask), the decoder is
+fed them as if it had drawn them, and only the free cells are drawn — continue_ (hold an opening), repaint (hold any mask) and score
+(hold everything: the piece's negative log-likelihood under a class). The held positions run through the same captured graph per
+position as every other one (decode.FrameSampling / decode.TokenSampling with `given` and `hold`); DESIGN §15.
+
+Index mapping of a piece (the training step's alignment of inputs and labels: decoder row k + 1 is fed input k and scored against
+label k):
+  * piano-roll ends: the piece is the batch's LABEL roll [B, T, P]; position k + 1 emits labels[:, k] (pianoroll.pianoroll_arrays: the
+    input roll is the label roll moved down one frame behind the start row), so mask cell [b, k, j] is frame k, pitch j;
+  * token ends: the piece is the token row with its EOS, [B, T + 1]; position i emits the token at index i, index 0 is SOS and is
+    never held, and the EOS of a row of seq_len tokens (SOS included) sits at index seq_len.
+
     python -m music_style_transfer.VarAutoEncoder.generate --model-output DIR --mode transfer --data MIDI_DIR --out OUT_DIR
 """
 import argparse
@@ -15,7 +27,7 @@ import os
 
 import numpy as np
 
-MODES = ("prior", "posterior", "interpolate", "transfer", "blend")
+MODES = ("prior", "posterior", "interpolate", "transfer", "blend", "continue", "repaint", "score")
 DECODERS = ("sampling", "greedy", "beam")
 
 
@@ -127,6 +139,90 @@ def recipe_class_blend(n_melodies, class_a, class_b, weights):
     return Recipe("blend", a, a, z, z + class_a, z + class_b, wts[k], rows, files)
 
 
+def _own_or_target(batch_classes, target_classes, what):
+    c = np.asarray(batch_classes, np.int64).reshape(-1)
+    return c if target_classes is None else _classes(target_classes, len(c), what)
+
+
+def recipe_continue(batch_classes, n_per_sample=1, target_classes=None):
+    """z = mu of the (encoded opening of the) melody, n_per_sample rows per melody (melody-major: they differ by the draw of the free
+    cells), the melody's own class or target_classes (one for all, or one per melody)"""
+    if n_per_sample <= 0:
+        raise ValueError("continue: n_per_sample must be positive")
+    c = _own_or_target(batch_classes, target_classes, "continue")
+    a = np.repeat(np.arange(len(c)), n_per_sample)
+    d = np.tile(np.arange(n_per_sample), len(c))
+    rows = [dict(melody=int(i), draw=int(k), cls=int(c[i])) for i, k in zip(a, d)]
+    files = ["continue-{}.draw-{}.mid".format(int(i), int(k)) for i, k in zip(a, d)]
+    z = np.zeros(len(a))
+    return Recipe("continue", a, a, z, c[a], c[a], z, rows, files)
+
+
+def recipe_repaint(batch_classes, target_classes=None):
+    """z = mu of the melody, one row per melody, its own class or target_classes (one for all, or one per melody)"""
+    c = _own_or_target(batch_classes, target_classes, "repaint")
+    a = np.arange(len(c))
+    rows = [dict(melody=int(i), cls=int(c[i])) for i in a]
+    files = ["repaint-{}.class-{}.mid".format(int(i), int(c[i])) for i in a]
+    z = np.zeros(len(a))
+    return Recipe("repaint", a, a, z, c, c, z, rows, files)
+
+
+def recipe_score(n_melodies, target_classes):
+    """transfer's rows (every melody x every class, melody-major) under the name 'score'"""
+    r = recipe_transfer(n_melodies, target_classes)
+    r.name = "score"
+    r.files = ["score-{}.class-{}.mid".format(row["melody"], row["cls"]) for row in r.rows]
+    return r
+
+
+def hold_mask(lens, T, P=None, time=None, pitch=None):
+    """the cells of a piece to hold: bool [B, T] (P None: token ends) or [B, T, P] (piano-roll ends), true inside the half-open
+    `time` = (first, behind) range of the piece's time index and, for rolls, inside the half-open `pitch` range; a range that is
+    omitted means everything, an empty one nothing. Never true at or behind a row's `lens`. (The piece's indexing is the module
+    docstring's: frame k of the label roll; token index i of the row, where index 0 is SOS.)"""
+    lens = np.asarray(lens, np.int64).reshape(-1)
+    T = int(T)
+    if T <= 0 or (P is not None and int(P) <= 0):
+        raise ValueError("hold_mask: T and P must be positive")
+    t = np.arange(T)
+    m = t[None, :] < lens[:, None]
+    if time is not None:
+        lo, hi = (int(v) for v in time)
+        m = m & ((t >= lo) & (t < hi))[None, :]
+    if P is None:
+        if pitch is not None:
+            raise ValueError("hold_mask: a pitch range needs P (piano-roll ends)")
+        return m
+    j = np.arange(int(P))
+    pm = np.ones(int(P), bool)
+    if pitch is not None:
+        lo, hi = (int(v) for v in pitch)
+        pm = (j >= lo) & (j < hi)
+    return m[:, :, None] & pm[None, None, :]
+
+
+def token_piece(tokens, seq_lens):
+    """token rows [B, T] (SOS first, PAD behind seq_len) -> the piece [B, T + 1] with EOS at index seq_len"""
+    from .MIDIUtil.defaults import EOS_ID, PAD_ID
+    tokens, lens = np.asarray(tokens, np.int64), np.asarray(seq_lens, np.int64).reshape(-1)
+    B, T = tokens.shape
+    piece = np.full((B, T + 1), PAD_ID, np.int64)
+    piece[:, :T] = np.where(np.arange(T)[None, :] < lens[:, None], tokens, PAD_ID)
+    piece[np.arange(B), np.clip(lens, 0, T)] = EOS_ID
+    return piece
+
+
+def opening(tokens, seq_lens, prime):
+    """what continue_ encodes: the input with everything behind the first `prime` rows zeroed, and seq_lens clipped to prime"""
+    prime = int(prime)
+    if prime < 1:
+        raise ValueError("continue: prime must be at least 1")
+    x = np.array(tokens, copy=True)
+    x[:, prime:] = 0
+    return x, np.minimum(np.asarray(seq_lens, np.int64).reshape(-1), prime)
+
+
 def chunks(n_rows, max_rows):
     """[lo, hi) ranges of at most max_rows rows; the noise of row r is a function of r, so the chunking does not change it"""
     if max_rows <= 0:
@@ -147,11 +243,15 @@ def ids_to_melody(ids):
 class Generated:
     """what a LatentGenerator call returns: `z` (host fp32 [N, Z]), `rows` (what every row is), `sequences` (token ids [N, L], token
     ends) or `rolls` (uint8 [N, frames, P], piano-roll ends), `scores` (summed -log p of what was decoded), `start_rows` (the decoder
-    rows of position 0, host copy in the activation type), `probs` (piano-roll ends with keep_probs: fp32 [N, frames, P])"""
+    rows of position 0, host copy in the activation type), `probs` (piano-roll ends with keep_probs: fp32 [N, frames, P]); of a
+    constrained call also `hold` (bool, the mask of every row in the piece's indexing) and `held_scores` (fp64 [N]: the summed
+    -log p of the held cells, which `scores` then does not contain)"""
 
-    def __init__(self, recipe, z, start_rows, scores, sequences=None, rolls=None, probs=None, slices_per_quarter=4):
+    def __init__(self, recipe, z, start_rows, scores, sequences=None, rolls=None, probs=None, slices_per_quarter=4, held_scores=None,
+                 hold=None):
         self.name, self.rows, self.files = recipe.name, recipe.rows, recipe.files
         self.z, self.start_rows, self.scores = z, start_rows, scores
+        self.held_scores, self.hold = held_scores, hold
         self.sequences, self.rolls, self.probs = sequences, rolls, probs
         self.slices_per_quarter = slices_per_quarter
 
@@ -239,13 +339,77 @@ class LatentGenerator:
         return self._run(recipe_class_blend(len(np.asarray(batch.data[2])), class_a, class_b, weights), mu, None,
                          self._length(batch, length))
 
+    # ------------------------------------------------------------------ constrained decoding (module docstring: the index mapping)
+    def _constrainable(self):
+        if self.decoder == "beam":
+            raise ValueError("beam search takes no constraints: decode a constrained piece with 'sampling' or 'greedy'")
+
+    def _piece(self, batch):
+        """-> (piece, lens, is_token): the label roll [B, T, P] with the rows' lengths, or the token rows with their EOS [B, T + 1] and
+        lens = the index behind the EOS"""
+        tokens, seq_lens = np.asarray(batch.data[0]), np.asarray(batch.data[1], np.int64).reshape(-1)
+        if tokens.ndim == 2:
+            return token_piece(tokens, seq_lens), seq_lens + 1, True
+        if not batch.label:
+            raise ValueError("a piano-roll piece is the batch's label roll: the batch has no label")
+        return (np.asarray(batch.label[0]) != 0).astype(np.uint8), seq_lens, False
+
+    def _constrained(self, recipe, mu, piece, hold, length):
+        piece, hold = np.asarray(piece), np.asarray(hold) != 0
+        if hold.shape[0] != piece.shape[0] or hold.ndim != piece.ndim or hold.shape[2:] != piece.shape[2:] or hold.shape[1] > piece.shape[1]:
+            raise ValueError("the mask {} does not fit the piece {}".format(hold.shape, piece.shape))
+        full = np.zeros(piece.shape, bool)
+        full[:, : hold.shape[1]] = hold
+        n = min(piece.shape[1], length - 1 if piece.ndim == 3 else length)  # a shorter run cuts the piece
+        return self._run(recipe, mu, None, length, given=piece[recipe.a, :n], hold=full[recipe.a, :n])
+
+    def continue_(self, batch, prime, n_per_sample=1, target_classes=None, length=None):
+        """continue an opening: the first `prime` frames (or tokens behind SOS) of every melody are held — for the token ends never at or
+        behind the opening's EOS — and the rest is drawn, n_per_sample times per melody. The latent vector is that of the OPENING ONLY:
+        the encoder sees the input with seq_lens clipped to prime and everything behind zeroed. target_classes restyles the continuation."""
+        self._constrainable()
+        tokens, seq_lens, classes = batch.data[:3]
+        recipe = recipe_continue(classes, n_per_sample, target_classes)
+        x, lens = opening(tokens, seq_lens, prime)
+        piece, piece_lens, token = self._piece(batch)
+        if token:  # indices 1 .. prime, short of the EOS at index piece_lens - 1
+            hold = hold_mask(piece_lens - 1, piece.shape[1], time=(1, int(prime) + 1))
+        else:
+            hold = hold_mask(piece_lens, piece.shape[1], piece.shape[2], time=(0, int(prime)))
+        mu, _ = self.model.encode(x, lens, classes)
+        return self._constrained(recipe, mu, piece, hold, self._length(batch, length))
+
+    def repaint(self, batch, hold, target_classes=None, length=None):
+        """keep the cells of `hold` (hold_mask: [B, T, P] over the label roll, or [B, <= T + 1] over the token row) and redraw the others;
+        the whole piece is encoded"""
+        self._constrainable()
+        recipe = recipe_repaint(batch.data[2], target_classes)
+        piece, _, _ = self._piece(batch)
+        mu, _ = self.encode(batch)
+        return self._constrained(recipe, mu, piece, hold, self._length(batch, length))
+
+    def score(self, batch, target_classes=None):
+        """how well does class c explain this piece: everything up to each row's length is held, for every (melody, class) pair in
+        transfer's order; held_scores[r] of the result is the piece's negative log-likelihood under that class. ONE encode."""
+        self._constrainable()
+        if target_classes is None:
+            target_classes = np.arange(self.model.engine_config.num_classes)
+        recipe = recipe_score(len(np.asarray(batch.data[2]).reshape(-1)), target_classes)
+        piece, lens, token = self._piece(batch)
+        hold = hold_mask(lens, piece.shape[1], time=(1, piece.shape[1])) if token else hold_mask(lens, piece.shape[1], piece.shape[2])
+        mu, _ = self.encode(batch)
+        return self._constrained(recipe, mu, piece, hold, piece.shape[1] if token else piece.shape[1] + 1)
+
     # ------------------------------------------------------------------ recipe -> rows -> decoded pieces
     @staticmethod
     def _length(batch, length):
         return int(length) if length is not None else 2 * np.asarray(batch.data[0]).shape[1]  # (sampler.py:163)
 
-    def _decode(self, row0, length, seed):
-        """-> (sequences or rolls, scores, probs) of one chunk as host arrays"""
+    def _decode(self, row0, length, seed, given=None, hold=None):
+        """-> (sequences or rolls, scores, probs, held_scores) of one chunk as host arrays; given, hold: the chunk's rows of a
+        constrained call (held_scores is None without them)"""
+        if given is not None:
+            self._constrainable()
         from . import decode
         from .VarAutoEncoder.model import resolve_attention
         m, n = self.model, row0.shape[0]
@@ -255,15 +419,19 @@ class LatentGenerator:
                 raise ValueError("top_k and top_p rank tokens; a piano-roll frame is one Bernoulli draw per pitch")
             fs = self.last_sampler = m.frame_sampling_plan(n, length, attention, keep_probs=self.keep_probs)
             roll, scores = fs.run(row0, length, tau=self.frame_temperature, mode="draw" if self.decoder == "sampling" else "threshold",
-                                  thr=0.5, seed=seed)
-            return roll, scores, (fs.probs[:, : length - 1].cpu().numpy() if self.keep_probs else None)
+                                  thr=0.5, seed=seed, given=given, hold=hold)
+            return (roll, scores, (fs.probs[:, : length - 1].cpu().numpy() if self.keep_probs else None),
+                    fs.held_scores if given is not None else None)
         from .MIDIUtil.defaults import PAD_ID
-        if self.decoder == "sampling" and (self.sample_temperature != 1.0 or self.top_k != 0 or self.top_p != 1.0):
+        if given is not None or (self.decoder == "sampling" and (self.sample_temperature != 1.0 or self.top_k != 0 or self.top_p != 1.0)):
+            # (a constrained piece always decodes here; 'greedy' is then the draw among the single most likely token)
+            greedy = self.decoder != "sampling"
             ts = self.last_sampler = m.token_sampling_plan(n, length, attention)
-            got, scores = ts.run(row0, length, tau=self.sample_temperature, top_k=self.top_k, top_p=self.top_p, seed=seed)
+            got, scores = ts.run(row0, length, tau=1.0 if greedy else self.sample_temperature, top_k=1 if greedy else self.top_k,
+                                 top_p=1.0 if greedy else self.top_p, seed=seed, given=given, hold=hold)
             seqs = np.full((n, length), PAD_ID, np.int64)
             seqs[:, : got.shape[1]] = got
-            return seqs, scores, None
+            return seqs, scores, None, (ts.held_scores if given is not None else None)
         if self.decoder == "sampling":
             key = (n, length, attention, id(m.store))
             smp = self._samplers.get(key)
@@ -275,11 +443,11 @@ class LatentGenerator:
             got, scores = smp.run(row0)
             seqs = np.full((n, length), PAD_ID, np.int64)
             seqs[:, : got.shape[1]] = got
-            return seqs, scores, None
+            return seqs, scores, None, None
         K = self.beam_size if self.decoder == "beam" else 1  # (one beam is greedy decoding)
         bs = self.last_sampler = m.beam_search_plan(n, K, length, attention)
         seqs, scores = bs.run(row0.repeat_interleave(K, dim=0).contiguous() if K > 1 else row0)
-        return seqs.astype(np.int64).reshape(n, K, -1)[:, 0], scores.reshape(n, K)[:, 0], None
+        return seqs.astype(np.int64).reshape(n, K, -1)[:, 0], scores.reshape(n, K)[:, 0], None, None
 
     def _rows(self, recipe, mu, ssrc, lo, hi, seed=0):
         """rows [lo, hi) of a recipe through mst_latent_rows -> (z fp32 [n, Z], decoder start rows [n, >= Dd]) on the device"""
@@ -298,7 +466,8 @@ class LatentGenerator:
                       math.sqrt(float(Dd)), z_out, row0, mode=recipe.mode, tau=recipe.tau, seed=seed, row0=lo)
         return z_out, row0
 
-    def _run(self, recipe, mu, sigma, length):
+    def _run(self, recipe, mu, sigma, length, given=None, hold=None):
+        """given, hold: one row per recipe row (constrained calls); every chunk is handed its own rows"""
         import torch
         cfg = self.model.engine_config
         recipe.validate(0 if mu is None else mu.shape[0], cfg.num_classes)
@@ -306,10 +475,12 @@ class LatentGenerator:
             raise ValueError("length must be at least 2 positions")
         self.calls += 1
         seed = (self.seed * 0x9E3779B97F4A7C15 + self.calls) & 0xFFFFFFFFFFFFFFFF
-        zs, rows, outs, scores, probs = [], [], [], [], []
+        zs, rows, outs, scores, probs, held = [], [], [], [], [], []
         for lo, hi in chunks(len(recipe), self.max_rows):
             z_out, row0 = self._rows(recipe, mu, sigma if recipe.use_sigma else None, lo, hi, seed)
-            out, sc, pr = self._decode(row0, length, seed ^ (lo * 0xD1B54A32D192ED03 & 0xFFFFFFFFFFFFFFFF))
+            out, sc, pr, hs = self._decode(row0, length, seed ^ (lo * 0xD1B54A32D192ED03 & 0xFFFFFFFFFFFFFFFF),
+                                           None if given is None else given[lo:hi], None if given is None else hold[lo:hi])
+            held.append(None if hs is None else np.asarray(hs, np.float64))
             zs.append(z_out.cpu().numpy())
             rows.append(row0[:, : cfg.d_model].cpu())
             outs.append(out)
@@ -318,7 +489,8 @@ class LatentGenerator:
         token = cfg.kind == "token"
         return Generated(recipe, np.concatenate(zs), torch.cat(rows), np.concatenate(scores),
                          sequences=np.concatenate(outs) if token else None, rolls=None if token else np.concatenate(outs),
-                         probs=np.concatenate(probs) if probs[0] is not None else None)
+                         probs=np.concatenate(probs) if probs[0] is not None else None,
+                         held_scores=np.concatenate(held) if given is not None else None, hold=hold)
 
 
 # ---------------------------------------------------------------------- command line
@@ -332,8 +504,13 @@ def build_parser():
     src = p.add_mutually_exclusive_group()
     src.add_argument("--data", default=None, help="MIDI folder (one sub-folder per class); the first batch is used")
     src.add_argument("--toy", action="store_true", help="the three toy sequences instead of --data")
-    p.add_argument("--out", required=True, help="folder the .mid files are written to")
-    p.add_argument("--n", type=int, default=4, help="prior: number of pieces; posterior: draws per melody")
+    p.add_argument("--out", default=None, help="folder the .mid files are written to (every mode but score, which prints)")
+    p.add_argument("--n", type=int, default=4, help="prior: number of pieces; posterior: draws per melody; continue: continuations per melody")
+    p.add_argument("--prime", type=int, default=None, metavar="N", help="continue: hold the first N frames / tokens of every melody")
+    p.add_argument("--keep-time", type=int, nargs=2, default=None, metavar=("A", "B"),
+                   help="repaint: keep frames (token indices) A <= t < B and redraw the others (default: all of them)")
+    p.add_argument("--keep-pitch", type=int, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="repaint, piano-roll models: keep pitches LO <= j < HI (with --keep-time: cells inside both ranges)")
     p.add_argument("--steps", type=int, default=8, help="interpolate / blend: number of points, end points included")
     p.add_argument("--pair", type=int, nargs=2, default=(0, 1), metavar=("I", "J"), help="interpolate: the two melodies of the batch")
     p.add_argument("--classes", type=int, nargs="*", default=None, help="prior / transfer: classes (default: all); blend: the two to mix")
@@ -371,6 +548,10 @@ def _first_batch(args, kind):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.mode != "score" and args.out is None:
+        raise SystemExit("--mode {} needs --out DIR".format(args.mode))
+    if args.mode == "continue" and args.prime is None:
+        raise SystemExit("--mode continue needs --prime N")
     from .VarAutoEncoder.sampler import load_inference_model
     from .VarAutoEncoder.utils import gpu
     try:
@@ -393,6 +574,19 @@ def main(argv=None):
             out = gen.interpolate(batch, args.pair[0], args.pair[1], args.steps, mode=args.interpolation, length=args.length)
         elif args.mode == "transfer":
             out = gen.transfer(batch, args.classes or None, length=args.length)
+        elif args.mode == "continue":
+            out = gen.continue_(batch, args.prime, args.n, args.classes or None, length=args.length)
+        elif args.mode == "repaint":
+            piece, lens, token = gen._piece(batch)
+            if token and args.keep_pitch is not None:
+                raise SystemExit("--keep-pitch names piano-roll pitches; a token model keeps --keep-time A B")
+            keep = hold_mask(lens, piece.shape[1], None if token else piece.shape[2], time=args.keep_time, pitch=args.keep_pitch)
+            out = gen.repaint(batch, keep, args.classes or None, length=args.length)
+        elif args.mode == "score":
+            out = gen.score(batch, args.classes or None)
+            lines = ["melody {} class {} nll {:.6f}".format(r["melody"], r["cls"], float(s)) for r, s in zip(out.rows, out.held_scores)]
+            print("\n".join(lines))
+            return lines
         else:
             ca, cb = (args.classes if args.classes and len(args.classes) == 2 else (0, cfg.num_classes - 1))
             out = gen.class_blend(batch, ca, cb, np.linspace(0.0, 1.0, args.steps), length=args.length)

@@ -717,6 +717,32 @@ def token_step(logits, V, i, seed_ptr, seqs, scores, word, eos, pad, tau=1.0, to
          ptr(scores), ptr(word), ptr(active), ptr(kept_out), eos, pad, stream())
 
 
+def frame_step_held(logits, P, i, seed_ptr, frames, roll, scores, given, hold, held_scores, tau=1.0, mode="draw", thr=0.5, probs_out=None):
+    """frame_step with some cells given (mst_frame_step_held): given, hold uint8 [N, L, >= P] in the roll's indexing (row i - 1 is
+    position i's); a held cell's frame is given != 0 and its -log p goes to held_scores fp32 [N] instead of scores"""
+    N, L = roll.shape[0], roll.shape[1]
+    assert roll.is_contiguous() and (probs_out is None or (probs_out.is_contiguous() and tuple(probs_out.shape) == (N, L, P)))
+    for t in (given, hold):
+        assert t.dtype == torch.uint8 and t.is_contiguous() and tuple(t.shape[:2]) == (N, L) and t.shape[2] >= P
+    assert held_scores.dtype == torch.float32 and held_scores.numel() == N
+    call("mst_frame_step_held", dt(logits), N, P, i, L, ptr(logits), ld(logits), tau, FRAME_MODES[mode], thr, ptr(seed_ptr), ptr(frames),
+         ld(frames), ptr(roll), roll.stride(1), ptr(scores), ptr(probs_out), ptr(given), given.stride(1), ptr(hold), hold.stride(1),
+         ptr(held_scores), stream())
+
+
+def token_step_held(logits, V, i, seed_ptr, seqs, scores, word, eos, pad, given, hold, held_scores, tau=1.0, top_k=0, top_p=1.0, active=None,
+                    kept_out=None):
+    """token_step with some positions given (mst_token_step_held): given int32 [N, L], hold uint8 [N, L] in seqs' indexing; a held
+    position writes given[n, i] and charges the model's -log p of it to held_scores fp32 [N]"""
+    assert seqs.is_contiguous()
+    N, L = seqs.shape
+    assert given.dtype == torch.int32 and given.is_contiguous() and tuple(given.shape) == (N, L)
+    assert hold.dtype == torch.uint8 and hold.is_contiguous() and tuple(hold.shape) == (N, L)
+    assert held_scores.dtype == torch.float32 and held_scores.numel() == N
+    call("mst_token_step_held", dt(logits), N, V, i, L, ptr(logits), ld(logits), tau, top_k, top_p, ptr(seed_ptr), ptr(seqs), ptr(scores),
+         ptr(word), ptr(active), ptr(kept_out), eos, pad, ptr(given), ptr(hold), ptr(held_scores), stream())
+
+
 def beam_gather(cache_in, cache_out, src, n_rows, skip_cols=None):
     """cache_out[j, :n_rows] = cache_in[src[j], :n_rows] for [N, t_max, width] caches (mst_beam_gather);
     skip_cols = (first, count): those columns of every row are left alone (mst_beam_gather_cols)"""

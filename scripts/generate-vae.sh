@@ -1,6 +1,7 @@
 #!/bin/bash
 # Generate .mid files from the latent space of a model trained by scripts/train-vae.sh: every melody of the first batch in every
-# class, from one encode. Other modes: --mode prior|posterior|interpolate|blend (python -m ...generate --help); whatever the caller
+# class, from one encode. Other modes: --mode prior|posterior|interpolate|blend, and on an existing piece --mode continue --prime N
+# [--n K] | repaint [--keep-time A B] [--keep-pitch LO HI] | score (python -m ...generate --help); whatever the caller
 # passes in "$@" is appended (e.g. --mode interpolate --pair 0 3 --steps 9 --decoder greedy). The draw of --decoder sampling is the raw
 # softmax as set below; flags in "$@" come later and win, e.g. scripts/generate-vae.sh --sample-temperature 0.9 --top-k 40 --top-p 0.9.
 # --ema (also through "$@") decodes with the checkpoint's averaged weights, for a model trained with --ema-decay.

@@ -11,7 +11,11 @@
      mst_sample_step per position) against decode.TokenSampling (one graph replay per position: the decode step and mst_token_step)
      with the filters off and with top_k 40, top_p 0.9 — per decoded position, row 0 given.
 
-    python tools/bench_generate.py [--case all|pianoroll|token] [--reps 3] [--out FILE]
+  4. (--case held, and part of --case pianoroll) constrained decoding: decode.FrameSampling's loop with HALF the cells held (a random
+     mask and piece; every position's graph ends in mst_frame_step_held, which reads two more bytes per cell) beside the
+     unconstrained loop of the same sampler — per decoded position, row 0 given, the two alternating.
+
+    python tools/bench_generate.py [--case all|pianoroll|token|held] [--reps 3] [--out FILE]
 
 Every timed window ends in a device synchronise; the two forms of each pair alternate inside the process; the first pass of
 every shape (lazy module loads, plan construction, graph capture) is outside the timed windows. Prints one JSON line."""
@@ -78,7 +82,7 @@ def token_case(args):
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--case", default="all", choices=("all", "pianoroll", "token"))
+    ap.add_argument("--case", default="all", choices=("all", "pianoroll", "token", "held"))
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--frames", type=int, default=256)
     ap.add_argument("--out", default=None)
@@ -90,6 +94,8 @@ def main(argv=None):
         res.update(pianoroll_case(args))
     if args.case in ("all", "token"):
         res.update(token_case(args))
+    if args.case == "held":
+        res.update(held_case(args))
     line = json.dumps(res)
     print(line)
     if args.out:
@@ -99,10 +105,9 @@ def main(argv=None):
     return res
 
 
-def pianoroll_case(args):
-    import torch
-    from musicstyletransfer_amd import generate as G
-    from musicstyletransfer_amd.VarAutoEncoder import model, sampler as S
+def _pianoroll_setup(args):
+    """the configs[1] piano-roll model, one batch of it and the number of decoded positions of one sample() call (sampler.py:163)"""
+    from musicstyletransfer_amd.VarAutoEncoder import model
     from musicstyletransfer_amd.VarAutoEncoder.data import Batch
     from musicstyletransfer_amd.VarAutoEncoder.transformer import TransformerConfig
     from musicstyletransfer_amd.VarAutoEncoder.utils import gpu
@@ -116,7 +121,62 @@ def pianoroll_case(args):
     x[:, 0] = 0
     x[:, 0, 0] = 1
     batch = Batch([x, np.full(B, T, np.int64), rng.integers(0, 2, B)], [])
-    positions = 2 * T - 1  # decoded positions of one sample() call (sampler.py:163)
+    return m, batch, B, T, P, 2 * T - 1
+
+
+def held_case(args, setup=None):
+    """-> FrameSampling's time per position, unconstrained and with half the cells held (medians over max(reps, 7) alternated windows;
+    `unconstrained_only`: a sampler without run(given, hold) — an older tree timed by the same tool — reports the first figure alone)"""
+    import inspect
+    import torch
+    m, batch, B, T, P, positions = setup or _pianoroll_setup(args)
+    fs = m.frame_sampling_plan(B, 2 * T)
+    row0 = m.decoder.initial_rows(*batch.data)
+    rng = np.random.default_rng(1)
+    given = (rng.random((B, positions, P)) < 0.04).astype(np.uint8)
+    hold = (rng.random((B, positions, P)) < 0.5).astype(np.uint8)
+    forms = {"free": lambda: fs.run(row0, seed=3)}
+    if "given" in inspect.signature(fs.run).parameters:
+        forms["half_held"] = lambda: fs.run(row0, seed=3, given=given, hold=hold)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    def upload():  # what a constrained run does once, in front of its first position: the piece and the mask to the device
+        with fs.plan._enter():
+            fs._load_constraint(given, hold)
+        fs.plan._leave()
+
+    for fn in forms.values():  # module loads, graph capture, then one replay
+        fn()
+        fn()
+    per = {k: [] for k in forms}
+    t_up = []
+    for _ in range(max(args.reps, 7)):
+        for k, fn in forms.items():
+            per[k].append(timed(fn) / positions * 1e6)
+        if "half_held" in forms:
+            t_up.append(timed(upload) * 1e3)
+    res = dict(held_B=B, held_P=P, held_positions=positions, held_graphs_captured=len(fs._graphs))
+    if t_up:
+        res.update(constraint_upload_ms_per_run=float(np.median(t_up)), constraint_upload_all_ms=t_up)
+    for k, v in per.items():
+        res["frame_sampling_" + k + "_us_per_position"] = float(np.median(v))
+        res["frame_sampling_" + k + "_all_us"] = v
+    return res
+
+
+def pianoroll_case(args):
+    import torch
+    from musicstyletransfer_amd import generate as G
+    from musicstyletransfer_amd.VarAutoEncoder import sampler as S
+
+    setup = _pianoroll_setup(args)
+    m, batch, B, T, P, positions = setup
 
     host = S.Sampling(seed=1)
     host.update_parameters(m)
@@ -170,6 +230,7 @@ def pianoroll_case(args):
                restyle_two_forwards_ms=med(t_two) * 1e3, restyle_two_forwards_all_ms=[t * 1e3 for t in t_two],
                restyle_one_encode_ms=med(t_one) * 1e3, restyle_one_encode_all_ms=[t * 1e3 for t in t_one],
                graphs_captured=len(fs._graphs))
+    res.update(held_case(args, setup))
     return res
 
 
