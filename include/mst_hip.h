@@ -387,20 +387,24 @@ int mst_gemm_wgrad_plan(const mst_wgrad_args* list, int n, int64_t scratch_bytes
  * (model.py:86-91, transformer.py:270; decoder: model.py:241-245 with cls = NULL, s_off = 1).
  * Also emits keymask[b, s_off + t] = (tok != 0) if keymask != NULL (model.py:81-83).
  * table, cls, pos fp32; tokens/classes int32; out act dtype [B, S_out, ld].
+ * keep (uint8 [B * T] or NULL; ABI 118): the decoder-input dropout mask of mst_step_begin_args.in_keep. Position (b, t) with
+ * keep[b * T + t] == 0 takes a zero row in place of table[tok] (the table row is not read): out = alpha*(0 + cls) + pos. keymask is
+ * emitted from the token as before. NULL: the launch as it was.
  * ------------------------------------------------------------------------ */
 int mst_embed_fwd(int dtype, int64_t B, int64_t T, int64_t D,
                   const int32_t* tokens, const float* table, int64_t ldt,
                   const int32_t* classes, const float* cls_table, int64_t ldc,
                   const float* pos, int64_t ldp, float alpha,
                   void* out, int64_t ld_out, int64_t S_out, int64_t s_off,
-                  uint8_t* keymask, mst_stream_t stream);
+                  uint8_t* keymask, const uint8_t* keep, mst_stream_t stream);
 
-/* scatter-add of alpha*dX rows into dtable (fp32, accumulated) and dcls (fp32, accumulated) */
+/* scatter-add of alpha*dX rows into dtable (fp32, accumulated) and dcls (fp32, accumulated). keep (as above, or NULL): a dropped
+ * position adds nothing to dtable; dcls gets every row either way. */
 int mst_embed_bwd(int dtype, int64_t B, int64_t T, int64_t D,
                   const int32_t* tokens, float* dtable, int64_t ldt,
                   const int32_t* classes, float* dcls, int64_t ldc, float alpha,
                   const void* dX, int64_t ld_dx, int64_t S_out, int64_t s_off,
-                  mst_stream_t stream);
+                  const uint8_t* keep, mst_stream_t stream);
 
 /* dst[idx[b], :] += alpha * sum_{t<T} X[b, s_off+t, :]  (fp32 dst, accumulated): gradient of the class
  * embedding that the piano-roll input GEMM's epilogue added to every frame (model.py:89-91) */
@@ -1068,7 +1072,8 @@ int mst_segment_sumsq(const float* x, const int64_t* ranges, int64_t n_segments,
 /* fp32 -> act dtype cast of a flat range (initial shadow fill) */
 int mst_cast_f32_to_act(int dtype, int64_t n, const float* src, void* dst, mst_stream_t stream);
 
-/* counter-based dropout keep-mask materialisation (for the oracle comparison): keep[i] in {0,1} */
+/* counter-based dropout keep-mask materialisation (for the oracle comparison): keep[i] in {0,1}; 0 <= p <= 1 (p = 1 keeps nothing: the
+ * layer dropouts stay below 1, the decoder-input dropout of mst_step_begin_args.in_* may reach it) */
 int mst_dropout_mask(int64_t n, float p, uint64_t seed, uint32_t site, uint8_t* keep, mst_stream_t stream);
 
 /* stream-ordered memset to zero (gradient bucket, metric sums) */
@@ -1105,11 +1110,38 @@ typedef struct mst_step_begin_args {
    * step the optimizer's guards take back (mst_step_metrics) takes the schedule back with the count.
    * Lengths and free bits must be >= 0; a cycle needs 0 < sched_kl_warmup <= sched_kl_cycle. */
   float* sched; float sched_kl_weight, sched_kl_free_bits; int32_t sched_kl_warmup, sched_kl_cycle, sched_lr_warmup;
+  /* Optional decoder-input dropout (ABI 118; in_keep == NULL: none, the launch is exactly the one without these fields; needs
+   * rng_state). "Word dropout" for the teacher-forced decoder: with probability p = in_p (0 <= p <= 1) the decoder does not see a
+   * previous frame / token and has to predict the next one through the latent. THE SEMANTICS, stated here once:
+   *   - Decoder input position k (k = 0..T-1) of sample b is the input of decoder row k + 1; r = b * T + k indexes in_keep, in_n = B * T.
+   *   - in_keep[r] = dropout_keep(s, in_site, in_index0 + r, in_p) (the function of the layer dropouts and of mst_dropout_mask), s
+   *     being this step's NEW seed — the value eps is drawn from, rng_state[0] after the launch. 1: kept, 0: dropped. The realised
+   *     keep probability is (65536 - floor(65536 p)) / 65536 as for the other masks; p = 1 drops every position.
+   *   - in_index0 = (the plan's first GLOBAL sample index) * T, as eps_index0, and in_site is ONE constant for all data-parallel ranks
+   *     (not offset per rank): a shard draws exactly what a single process draws for those samples.
+   *   - A dropped position contributes a ZERO EMBEDDING: its decoder input row is sqrt(D) * 0 + pos[k + 1], rounded to the activation
+   *     type. Piano-roll ends: the frame is all zeros (in_src / in_dst below). Token ends: no table row is gathered (mst_embed_fwd's
+   *     keep). No rescaling by 1 / (1 - p) — word dropout has none — and no UNK symbol: a zero row is the same thing for both kinds.
+   *   - Backward is the autograd of exactly that: a dropped position adds nothing to the decoder embedding's weight gradient (the
+   *     weight-gradient problem reads in_dst; mst_embed_bwd's keep); every other gradient follows from the changed forward values.
+   *   - Not affected: the encoder (it sees the intact piece), labels, loss, key masks, decoder row 0 (the latent block's). The draw
+   *     does not look at the sequence lengths: padded positions are drawn like any other and are masked as before.
+   *   - Inference passes carry no job: they are the launches, and the bits, of a step without these fields.
+   * With in_src (optional; in_src and in_dst come together) the bookkeeping workgroups also write the masked copy of the uint8 frames:
+   *   in_dst[r, 0..in_row_bytes) = in_keep[r] ? in_src[r, 0..in_row_bytes) : 0    (leading dimensions in_ld_src / in_ld_dst, in bytes)
+   * and touch no byte of a dst row beyond in_row_bytes. in_row_bytes and both leading dimensions are multiples of 8, the leading
+   * dimensions >= in_row_bytes, both pointers 8-byte aligned. in_n > 0, in_index0 >= 0, in_index0 + in_n < 2^31. */
+  uint8_t* in_keep; int64_t in_n; float in_p; uint32_t in_site; int64_t in_index0;
+  const uint8_t* in_src; int64_t in_ld_src; uint8_t* in_dst; int64_t in_ld_dst; int64_t in_row_bytes;
 } mst_step_begin_args;
 int mst_step_begin(const mst_step_begin_args* args, mst_stream_t stream);
 /* mst_step_begin and mst_gemm_nt_pair in ONE launch: nothing in the piano-roll ends' embedding GEMMs (the first arithmetic of the
  * step) reads what the bookkeeping writes, so its workgroups ride in front of the tiles of that launch. Where mst_gemm_nt_pair
- * would fall back to two launches this is exactly mst_step_begin(begin) followed by mst_gemm_nt_pair(args0, args1). */
+ * would fall back to two launches this is exactly mst_step_begin(begin) followed by mst_gemm_nt_pair(args0, args1).
+ * When `begin` carries a decoder-input dropout job (in_keep != NULL) the decoder's problem reads what the bookkeeping writes (in_dst),
+ * so the call is ALWAYS mst_step_begin(begin) followed by mst_gemm_nt_pair(args0, args1): the bookkeeping is a launch of its own in
+ * front (a requested shadow refresh stays behind the tiles of the GEMM launch, which neither reads nor writes what it touches). The
+ * rule lives here, in the library: the race cannot be constructed from outside. */
 int mst_gemm_nt_pair_begin(const mst_gemm_args* args0, const mst_gemm_args* args1, const mst_step_begin_args* begin,
                            mst_stream_t stream);
 /* eps ~ N(0,1) (replaces mx.nd.random_normal, model.py:292): Box-Muller over the counter hash;

@@ -3,7 +3,7 @@
 The flag set is the reference's, name for name and default for default (config.py:19-70), because
 scripts/train-vae.sh passes them; unknown flags are ignored as there (parse_known_args, :73-75). The flags
 are declared as a table. The additions (group MI355X) are all off by default: --pianoroll (attach the piano-roll ends), --dtype,
---d-causal, the training schedules, --clip-global-norm and --ema-decay."""
+--d-causal, the training schedules, --clip-global-norm, --ema-decay and --d-input-dropout."""
 import argparse
 import copy
 import inspect
@@ -74,6 +74,10 @@ _FLAGS = [
     # decay of an exponential moving average of the weights, kept by the optimizer launch inside the captured step (engine.ema_update);
     # validation, early stopping and the periodic samples then use the averaged weights, and generate.py --ema loads them. 0: off.
     ("MI355X", ("--ema-decay",), dict(type=float, default=0.0)),
+    # probability that a training step hides a decoder input position (the previous frame / token) from the teacher-forced decoder, drawn
+    # on the device inside the captured step (include/mst_hip.h: mst_step_begin_args.in_*): the decoder has to go through the latent —
+    # the third remedy for posterior collapse beside the KL warm-up and free bits. In [0, 1]; 0: off. Validation and sampling never drop.
+    ("MI355X", ("--d-input-dropout",), dict(type=float, default=0.0)),
 ]
 
 

@@ -25,7 +25,8 @@ def create_toy_model_config(data):
 
 
 def create_toy_train_config(max_steps=0, **schedule):
-    """main.py:41-55; schedule: the training-schedule fields of TrainConfig (the --kl-warmup-steps ... flags), clip_global_norm and ema_decay"""
+    """main.py:41-55; schedule: the training-schedule fields of TrainConfig (the --kl-warmup-steps ... flags), clip_global_norm, ema_decay and
+    d_input_dropout"""
     return trainer.TrainConfig(batch_size=1, sampling_frequency=500, checkpoint_frequency=1000, num_checkpoints_not_improved=-1,
                                kl_loss=1.0, optimizer=trainer.OptimizerConfig(learning_rate=1e-3, optimizer="adam",
                                                                               optimizer_params="clip_gradient:1.0"),
@@ -40,8 +41,10 @@ def main_toy(context, args):
     create_directory_if_not_present(model_folder)
     config.save(os.path.join(model_folder, "config"))
     schedule = {k: getattr(args, k) for k in ("kl_warmup_steps", "kl_cycle_steps", "kl_free_bits", "lr_warmup_steps", "clip_global_norm",
-                                              "ema_decay")}
-    t = trainer.Trainer(config=create_toy_train_config(args.max_steps, **schedule), context=context, model=m, sampler=None)
+                                              "ema_decay", "d_input_dropout")}
+    train_config = create_toy_train_config(args.max_steps, **schedule)
+    train_config.save(os.path.join(model_folder, "train_config"))
+    t = trainer.Trainer(config=train_config, context=context, model=m, sampler=None)
     t.fit(dataset=dataset, validation_dataset=dataset, model_folder=model_folder, epochs=20000 if not args.max_steps else args.max_steps)
     return t
 
@@ -57,7 +60,8 @@ def create_train_config(args):
                                verbose=args.verbose, dtype=args.dtype, max_steps=args.max_steps,
                                kl_warmup_steps=args.kl_warmup_steps, kl_cycle_steps=args.kl_cycle_steps,
                                kl_free_bits=args.kl_free_bits, lr_warmup_steps=args.lr_warmup_steps,
-                               clip_global_norm=args.clip_global_norm, ema_decay=args.ema_decay)
+                               clip_global_norm=args.clip_global_norm, ema_decay=args.ema_decay,
+                               d_input_dropout=args.d_input_dropout)
 
 
 def create_model_config(args, dataset):
@@ -96,7 +100,9 @@ def main(argv=None):
     log_config(config)
     m = model.Model(config=config)
     sampler = get_sampler("sampling", args.model_output, context, None, args)
-    t = trainer.Trainer(config=create_train_config(args), context=context, model=m, sampler=sampler)
+    train_config = create_train_config(args)
+    train_config.save(os.path.join(args.model_output, "train_config"))
+    t = trainer.Trainer(config=train_config, context=context, model=m, sampler=sampler)
     t.fit(dataset=train_dataset, validation_dataset=valid_dataset, model_folder=args.model_output, epochs=args.epochs)
     print("Training finished.")
     return t

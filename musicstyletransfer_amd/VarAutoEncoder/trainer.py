@@ -18,7 +18,7 @@ import torch
 from . import utils
 from .config import Config
 from .. import parallel
-from ..engine import check_clip, check_ema, check_schedule, roll_scores
+from ..engine import check_clip, check_ema, check_input_dropout, check_schedule, roll_scores
 from ..pianoroll import PinnedBatchPipeline
 
 
@@ -42,18 +42,23 @@ class TrainConfig(Config):
     their defaults. clip_global_norm: bound on the global L2 norm of the gradient, applied inside the step (engine.clip_scale); 0: off.
     ema_decay: decay of the exponential moving average of the weights the step keeps (engine.ema_update), which validation, early
     stopping and the periodic samples then use; 0: off.
+    d_input_dropout: probability that a training step hides a decoder input position from the teacher-forced decoder
+    (engine.check_input_dropout; include/mst_hip.h: mst_step_begin_args.in_*), in [0, 1]; 0: off. Validation never drops.
     YAML-serialisable (Config): a file written before a field existed loads with that field's default."""
 
     def __init__(self, batch_size: int, sampling_frequency: int, checkpoint_frequency: int, num_checkpoints_not_improved: int,
                  optimizer: OptimizerConfig, kl_loss: float, label_smoothing: float, negative_label_downscaling: bool,
                  verbose: bool, dtype: str = "bf16", max_steps: int = 0, kl_warmup_steps: int = 0, kl_cycle_steps: int = 0,
-                 kl_free_bits: float = 0.0, lr_warmup_steps: int = 0, clip_global_norm: float = 0.0, ema_decay: float = 0.0):
+                 kl_free_bits: float = 0.0, lr_warmup_steps: int = 0, clip_global_norm: float = 0.0, ema_decay: float = 0.0,
+                 d_input_dropout: float = 0.0):
         super().__init__()
         check_schedule(kl_warmup_steps, kl_cycle_steps, kl_free_bits, lr_warmup_steps)
         check_clip(clip_global_norm)
         self.clip_global_norm = clip_global_norm
         check_ema(ema_decay)
         self.ema_decay = ema_decay
+        check_input_dropout(d_input_dropout)
+        self.d_input_dropout = d_input_dropout
         self.kl_warmup_steps, self.kl_cycle_steps = kl_warmup_steps, kl_cycle_steps
         self.kl_free_bits, self.lr_warmup_steps = kl_free_bits, lr_warmup_steps
         self.batch_size = batch_size
@@ -148,6 +153,14 @@ class Trainer:
         check_ema(self.ema_decay)
         if self.ema_decay > 0:
             self.hyper["ema_decay"] = self.ema_decay
+        # ... and decoder-input dropout
+        self.d_input_dropout = float(getattr(self.config, "d_input_dropout", 0.0))
+        check_input_dropout(self.d_input_dropout)
+        if self.d_input_dropout > 0:
+            self.hyper["d_input_dropout"] = self.d_input_dropout
+            if self.rank == 0:
+                print("Decoder-input dropout: a training step hides each decoder input position with probability {}".format(
+                    self.d_input_dropout))
         self.opt_extra = {k: v for k, v in extra.items() if k in ("beta1", "beta2", "epsilon", "wd")}
 
     # ------------------------------------------------------------------ the hot loop

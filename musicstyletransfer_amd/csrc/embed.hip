@@ -1,10 +1,11 @@
 // embed.hip — token-path input ends and padding masks.
 //
-//   mst_embed_fwd : out[b, s_off+t, :] = alpha*(table[tok[b,t]] + cls[c_b]) + pos[s_off+t]
+//   mst_embed_fwd : out[b, s_off+t, :] = alpha*(table[tok[b,t]] + cls[c_b]) + pos[s_off+t]; with a keep mask (decoder-input dropout,
+//                   include/mst_hip.h: mst_step_begin_args.in_*) a dropped position takes a zero row in place of its table row
 //                   (gluon Embedding + broadcast_add + sqrt(D)*x + pos: model.py:86-91,241-245,
 //                   transformer.py:237,270) and keymask = (tok != 0) (model.py:81-83)
 //   mst_embed_bwd : scatter-add of alpha*dX into the table gradient, per-sample column sums into the
-//                   class-embedding gradient (autograd of the above)
+//                   class-embedding gradient (autograd of the above: a dropped position adds nothing to the table gradient)
 //   mst_group_colsum : dst[idx[b], :] += alpha * sum_t X[b, s_off+t, :]   (class-embedding gradient of
 //                   the piano-roll input GEMM, whose epilogue added cls[c_b] to every frame)
 //   mst_mask_from_lengths : SequenceMask(ones, seq_len + add) (model.py:246-247)
@@ -22,7 +23,8 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(int64_t BT, int64_t T_le
                                                         const float* __restrict__ cls_table, int64_t ldc,
                                                         const float* __restrict__ pos, int64_t ldp, float alpha,
                                                         T* __restrict__ out, int64_t ld_out, int64_t S_out,
-                                                        int64_t s_off, uint8_t* __restrict__ keymask) {
+                                                        int64_t s_off, uint8_t* __restrict__ keymask,
+                                                        const uint8_t* __restrict__ keep) {
   // one wave per (b,t) row, lanes over D in float4 chunks
   const int lane = threadIdx.x & 63;
   const int64_t wave_global = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -34,8 +36,10 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(int64_t BT, int64_t T_le
     const float* crow = cls_table ? cls_table + (int64_t)classes[b] * ldc : nullptr;
     const float* prow = pos + (s_off + t) * ldp;
     T* orow = out + (b * S_out + s_off + t) * ld_out;
+    const bool kept = !keep || keep[r];  // (dropped: the table row is not read)
     for (int d = lane * 4; d < D; d += 256) {
-      f32x4 e = *reinterpret_cast<const f32x4*>(trow + d);
+      f32x4 e = {0.f, 0.f, 0.f, 0.f};
+      if (kept) e = *reinterpret_cast<const f32x4*>(trow + d);
       f32x4 p = *reinterpret_cast<const f32x4*>(prow + d);
       f32x4 c = {0.f, 0.f, 0.f, 0.f};
       if (crow) c = *reinterpret_cast<const f32x4*>(crow + d);
@@ -52,11 +56,12 @@ template <typename T>
 __global__ __launch_bounds__(256) void embed_scatter_kernel(int64_t BT, int64_t T_len, int D, const int32_t* __restrict__ tokens,
                                                             float* __restrict__ dtable, int64_t ldt, float alpha,
                                                             const T* __restrict__ dX, int64_t ld_dx, int64_t S_out,
-                                                            int64_t s_off) {
+                                                            int64_t s_off, const uint8_t* __restrict__ keep) {
   const int lane = threadIdx.x & 63;
   const int64_t wave_global = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)gridDim.x * 4;
   for (int64_t r = wave_global; r < BT; r += nwaves) {
+    if (keep && !keep[r]) continue;  // a dropped position's input was a zero row, not table[tok]
     const int64_t b = r / T_len, t = r % T_len;
     const int tok = tokens[r];
     const T* grow = dX + (b * S_out + s_off + t) * ld_dx;
@@ -118,7 +123,7 @@ using namespace mst;
 extern "C" int mst_embed_fwd(int dtype, int64_t B, int64_t T, int64_t D, const int32_t* tokens, const float* table,
                              int64_t ldt, const int32_t* classes, const float* cls_table, int64_t ldc,
                              const float* pos, int64_t ldp, float alpha, void* out, int64_t ld_out, int64_t S_out,
-                             int64_t s_off, uint8_t* keymask, mst_stream_t stream) {
+                             int64_t s_off, uint8_t* keymask, const uint8_t* keep, mst_stream_t stream) {
   MST_CHECK_ARG(B > 0 && T > 0 && D > 0 && D % 4 == 0, "mst_embed_fwd: B,T,D must be positive and D a multiple of 4");
   MST_CHECK_ARG(tokens && table && pos && out, "mst_embed_fwd: null pointer");
   MST_CHECK_ARG(!cls_table || classes, "mst_embed_fwd: cls_table needs classes");
@@ -129,7 +134,7 @@ extern "C" int mst_embed_fwd(int dtype, int64_t B, int64_t T, int64_t D, const i
   return dispatch_act(dtype, [&](auto tag) -> int {
     typedef decltype(tag) TT;
     hipLaunchKernelGGL((embed_fwd_kernel<TT>), dim3(grid), dim3(256), 0, (hipStream_t)stream, BT, T, (int)D, tokens, table,
-                       ldt, classes, cls_table, ldc, pos, ldp, alpha, (TT*)out, ld_out, S_out, s_off, keymask);
+                       ldt, classes, cls_table, ldc, pos, ldp, alpha, (TT*)out, ld_out, S_out, s_off, keymask, keep);
     MST_CHECK_LAUNCH("embed_fwd_kernel");
     return MST_OK;
   });
@@ -154,7 +159,8 @@ extern "C" int mst_group_colsum(int dtype, int64_t B, int64_t T, int64_t D, cons
 
 extern "C" int mst_embed_bwd(int dtype, int64_t B, int64_t T, int64_t D, const int32_t* tokens, float* dtable,
                              int64_t ldt, const int32_t* classes, float* dcls, int64_t ldc, float alpha,
-                             const void* dX, int64_t ld_dx, int64_t S_out, int64_t s_off, mst_stream_t stream) {
+                             const void* dX, int64_t ld_dx, int64_t S_out, int64_t s_off, const uint8_t* keep,
+                             mst_stream_t stream) {
   MST_CHECK_ARG(B > 0 && T > 0 && D > 0, "mst_embed_bwd: B,T,D must be positive");
   MST_CHECK_ARG(tokens && dtable && dX, "mst_embed_bwd: null pointer");
   MST_CHECK_ARG(!dcls || classes, "mst_embed_bwd: dcls needs classes");
@@ -163,7 +169,7 @@ extern "C" int mst_embed_bwd(int dtype, int64_t B, int64_t T, int64_t D, const i
   int rc = dispatch_act(dtype, [&](auto tag) -> int {
     typedef decltype(tag) TT;
     hipLaunchKernelGGL((embed_scatter_kernel<TT>), dim3(grid), dim3(256), 0, (hipStream_t)stream, BT, T, (int)D, tokens,
-                       dtable, ldt, alpha, (const TT*)dX, ld_dx, S_out, s_off);
+                       dtable, ldt, alpha, (const TT*)dX, ld_dx, S_out, s_off, keep);
     MST_CHECK_LAUNCH("embed_scatter_kernel");
     return MST_OK;
   });

@@ -250,9 +250,21 @@ extern "C" int mst_gemm_nt_pair_begin(const mst_gemm_args* args0, const mst_gemm
   int n_begin = 0;
   if (begin) {
     int64_t grid = 0;
-    const int rc = pack_step_begin(*begin, sb, &grid);
+    int rc = pack_step_begin(*begin, sb, &grid);
     if (rc) return rc;
-    n_begin = (int)((grid + 7) / 8 * 8);
+    if (begin->in_keep) {
+      // a decoder-input dropout job: the decoder's problem reads the masked frames the bookkeeping writes, so the bookkeeping is a
+      // launch of its own in front of this one (mst_step_begin(begin), then mst_gemm_nt_pair(args0, args1)) — whatever the caller
+      // asked for. A shadow refresh stays behind this launch's tiles: nothing here reads or writes what it touches.
+      mst_step_begin_args own = *begin;
+      own.sh_w = nullptr;
+      if ((rc = mst_step_begin(&own, stream)) != MST_OK) return rc;
+      StepBegin sh = {};
+      sh.sh_w = sb.sh_w; sh.sh_wt16 = sb.sh_wt16; sh.sh_desc = sb.sh_desc; sh.sh_prefix = sb.sh_prefix; sh.sh_n_mat = sb.sh_n_mat; sh.sh_tiles = sb.sh_tiles;
+      sb = sh;
+    } else {
+      n_begin = (int)((grid + 7) / 8 * 8);
+    }
   }
   hipStream_t s = (hipStream_t)stream;
   return dispatch_act(a0.dtype, [&](auto tag) -> int {

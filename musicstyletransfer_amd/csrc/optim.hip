@@ -567,7 +567,7 @@ extern "C" int mst_add_act(int dtype, int64_t n, const void* a, const void* b, v
 }
 
 extern "C" int mst_dropout_mask(int64_t n, float p, uint64_t seed, uint32_t site, uint8_t* keep, mst_stream_t stream) {
-  MST_CHECK_ARG(n > 0 && keep && p >= 0.f && p < 1.f, "mst_dropout_mask: bad argument");
+  MST_CHECK_ARG(n > 0 && keep && p >= 0.f && p <= 1.f, "mst_dropout_mask: bad argument");
   hipLaunchKernelGGL(dropout_mask_kernel, dim3(grid_for(n, 4)), dim3(256), 0, (hipStream_t)stream, n, p, seed, site, keep);
   MST_CHECK_LAUNCH("dropout_mask_kernel");
   return MST_OK;

@@ -27,6 +27,9 @@ struct StepBegin {  // mst_step_begin_args with the zero lists in 16-byte units 
   const float* sh_w; void* sh_wt16; const int64_t* sh_desc; const int64_t* sh_prefix; int sh_n_mat; int64_t sh_tiles;
   // optional training schedules (mst_step_begin_args.sched*; sched == nullptr: none)
   float* sched; float kl_weight, kl_free_bits; int32_t kl_warmup, kl_cycle, lr_warmup;
+  // optional decoder-input dropout (mst_step_begin_args.in_*; in_keep == nullptr: none) — only step_begin_wg<NT, true> reads these
+  uint8_t* in_keep; int64_t in_n; float in_p; uint32_t in_site; int64_t in_index0;
+  const uint8_t* in_src; int64_t in_ld_src; uint8_t* in_dst; int64_t in_ld_dst; int64_t in_chunks;  // (8-byte chunks of a row)
 };
 
 // The training schedules, pure functions of Adam's step count t (1-based), in double: the learning-rate warm-up factor f_lr and the
@@ -43,7 +46,10 @@ __host__ __device__ inline double sched_kl_ramp(int t, int W_b, int C) {
 // state is written back by the workgroup that ARRIVES LAST at rng_state[3], i.e. after every other workgroup has read the old
 // counter. Workgroups [0, n_state) do the bookkeeping (and take part in the arrival count); the rest only help clearing the two
 // buffers — the gradient bucket is most of the bytes and has no business waiting on 64 workgroups' worth of store bandwidth.
-template <int NT>
+// IN: the launch carries a decoder-input dropout job (q.in_*; include/mst_hip.h). Its draw needs the new seed, so it is work of the
+// bookkeeping workgroups; the flag keeps its code out of every launch that cannot carry one (gemm_nt_pair_kernel: the decoder's tiles
+// of that launch would read the masked frames while these workgroups write them).
+template <int NT, bool IN = false>
 __device__ __forceinline__ void step_begin_wg(const StepBegin& q, int wg, int nwg) {
   const u32x4 z4 = {0u, 0u, 0u, 0u};
   {
@@ -100,6 +106,23 @@ __device__ __forceinline__ void step_begin_wg(const StepBegin& q, int wg, int nw
       const uint32_t b = (uint32_t)i / (uint32_t)q.Sd, r = (uint32_t)i - b * (uint32_t)q.Sd;
       q.mask_d[i] = ((int64_t)r < (int64_t)q.lens[b] + q.add_d) ? 1 : 0;
     }
+  if constexpr (IN) {
+    // keep[r] = dropout_keep(seed of this step, site, index0 + r, p): one byte per decoder input position ...
+    for (int64_t r = gid; r < q.in_n; r += gsz) q.in_keep[r] = dropout_keep(s, q.in_site, (uint64_t)(q.in_index0 + r), q.in_p) ? 1 : 0;
+    if (q.in_src) {
+      // ... and the frames with the dropped rows zeroed, 8 bytes per thread (every thread draws for its own row again: the byte
+      // above may be another workgroup's). Two divisions per thread: the (row, chunk) pair advances by a constant.
+      const int64_t cpr = q.in_chunks, dr = gsz / cpr, dc = gsz - dr * cpr;
+      int64_t r = gid / cpr, c = gid - r * cpr;
+      while (r < q.in_n) {
+        u32x2 v = {0u, 0u};
+        if (dropout_keep(s, q.in_site, (uint64_t)(q.in_index0 + r), q.in_p)) v = *reinterpret_cast<const u32x2*>(q.in_src + r * q.in_ld_src + c * 8);
+        *reinterpret_cast<u32x2*>(q.in_dst + r * q.in_ld_dst + c * 8) = v;
+        r += dr; c += dc;
+        if (c >= cpr) { c -= cpr; ++r; }
+      }
+    }
+  }
   if (q.rng_state) {
     __syncthreads();  // every thread of this workgroup has read the old counter
     if (threadIdx.x == 0) {
@@ -125,7 +148,26 @@ static inline int pack_step_begin(const mst_step_begin_args& a, StepBegin& q, in
   MST_CHECK_ARG((!a.mask_e && !a.mask_d) || (a.lens && a.B > 0), "mst_step_begin: masks need the lengths");
   MST_CHECK_ARG((!a.mask_e || (a.Se > 0 && a.B * a.Se < (1ll << 31))) && (!a.mask_d || (a.Sd > 0 && a.B * a.Sd < (1ll << 31))),
                 "mst_step_begin: B * S must stay below 2^31");
+  int64_t in_chunks = 0;
+  if (a.in_keep) {  // decoder-input dropout (the semantics: include/mst_hip.h)
+    MST_CHECK_ARG(a.rng_state, "mst_step_begin: input dropout needs the rng state");
+    MST_CHECK_ARG(a.in_p >= 0.f && a.in_p <= 1.f, "mst_step_begin: in_p must lie in [0, 1]");
+    MST_CHECK_ARG(a.in_n > 0 && a.in_n < (1ll << 31), "mst_step_begin: in_n must be positive (and below 2^31)");
+    MST_CHECK_ARG(a.in_index0 >= 0 && a.in_index0 < (1ll << 31) && a.in_index0 + a.in_n < (1ll << 31),
+                  "mst_step_begin: in_index0 must not be negative and in_index0 + in_n must stay below 2^31");
+    MST_CHECK_ARG(!a.in_src == !a.in_dst, "mst_step_begin: in_src and in_dst come together");
+    if (a.in_src) {
+      MST_CHECK_ARG(a.in_row_bytes > 0 && a.in_row_bytes % 8 == 0 && a.in_ld_src % 8 == 0 && a.in_ld_dst % 8 == 0,
+                    "mst_step_begin: in_row_bytes, in_ld_src and in_ld_dst must be (positive) multiples of 8");
+      MST_CHECK_ARG(a.in_ld_src >= a.in_row_bytes && a.in_ld_dst >= a.in_row_bytes,
+                    "mst_step_begin: in_ld_src and in_ld_dst must be at least in_row_bytes");
+      MST_CHECK_ARG((uintptr_t)a.in_src % 8 == 0 && (uintptr_t)a.in_dst % 8 == 0, "mst_step_begin: in_src and in_dst must be 8-byte aligned");
+      in_chunks = a.in_row_bytes / 8;
+    }
+  }
   int64_t work = a.n_eps / 2;
+  if (a.in_keep && a.in_n > work) work = a.in_n;
+  if (in_chunks > 0 && (a.in_n * in_chunks) / 2 > work) work = (a.in_n * in_chunks) / 2;  // (16 bytes of the copy weigh like one mask byte)
   if (a.mask_e && a.B * a.Se > work) work = a.B * a.Se;
   if (a.mask_d && a.B * a.Sd > work) work = a.B * a.Sd;
   const int64_t n16_a = a.zero_a ? a.zero_a_bytes / 16 : 0, n16_b = a.zero_b ? a.zero_b_bytes / 16 : 0;
@@ -142,7 +184,12 @@ static inline int pack_step_begin(const mst_step_begin_args& a, StepBegin& q, in
   *grid = g;
   q = StepBegin{a.rng_state, a.adam_state, a.lr, a.beta1, a.beta2, a.eps_out, a.n_eps, a.eps_site, a.eps_index0, a.lens, a.B,
                 a.mask_e, a.Se, a.add_e, a.mask_d, a.Sd, a.add_d, (u32x4*)a.zero_a, n16_a, (u32x4*)a.zero_b, n16_b, (int)n_state,
-                nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 0.f, 0.f, 0, 0, 0};
+                nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 0.f, 0.f, 0, 0, 0,
+                nullptr, 0, 0.f, 0u, 0, nullptr, 0, nullptr, 0, 0};
+  if (a.in_keep) {
+    q.in_keep = a.in_keep; q.in_n = a.in_n; q.in_p = a.in_p; q.in_site = a.in_site; q.in_index0 = a.in_index0;
+    if (in_chunks > 0) { q.in_src = a.in_src; q.in_ld_src = a.in_ld_src; q.in_dst = a.in_dst; q.in_ld_dst = a.in_ld_dst; q.in_chunks = in_chunks; }
+  }
   if (a.sched) {
     MST_CHECK_ARG(a.adam_state, "mst_step_begin: the schedule block is a function of Adam's step count (adam_state)");
     MST_CHECK_ARG(a.sched_kl_warmup >= 0 && a.sched_kl_cycle >= 0 && a.sched_lr_warmup >= 0 && a.sched_kl_free_bits >= 0.f,

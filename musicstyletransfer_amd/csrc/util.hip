@@ -39,7 +39,9 @@ __global__ __launch_bounds__(256) void randn_kernel(int64_t n, float* __restrict
   }
 }
 
-__global__ __launch_bounds__(SB_THREADS) void step_begin_kernel(StepBegin q) { step_begin_wg<SB_THREADS>(q, (int)blockIdx.x, (int)gridDim.x); }
+// IN: with a decoder-input dropout job (mst_step_begin_args.in_*); without one the launch is the kernel it always was
+template <bool IN>
+__global__ __launch_bounds__(SB_THREADS) void step_begin_kernel(StepBegin q) { step_begin_wg<SB_THREADS, IN>(q, (int)blockIdx.x, (int)gridDim.x); }
 
 __global__ __launch_bounds__(256) void partial_sums_kernel(PartialSumBatch b) {
   __shared__ f32x4 red[16][16];
@@ -56,7 +58,10 @@ extern "C" int mst_step_begin(const mst_step_begin_args* args, mst_stream_t stre
   int64_t grid = 0;
   int rc = pack_step_begin(*args, q, &grid);
   if (rc) return rc;
-  hipLaunchKernelGGL(step_begin_kernel, dim3((unsigned)grid), dim3(SB_THREADS), 0, (hipStream_t)stream, q);
+  if (q.in_keep)
+    hipLaunchKernelGGL(step_begin_kernel<true>, dim3((unsigned)grid), dim3(SB_THREADS), 0, (hipStream_t)stream, q);
+  else
+    hipLaunchKernelGGL(step_begin_kernel<false>, dim3((unsigned)grid), dim3(SB_THREADS), 0, (hipStream_t)stream, q);
   MST_CHECK_LAUNCH("step_begin_kernel");
   // (as a launch of its own the bookkeeping hosts nothing: a requested shadow refresh is the separate launch it always was)
   if (args->sh_w)

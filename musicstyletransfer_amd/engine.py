@@ -772,7 +772,7 @@ def row_tail_selfcheck(store, B=64, S=2):
 # kqv_head_e — the K | Q | V input gradient of an encoder layer above another one is formed inside that layer's feed-forward backward launch
 # (mst_kqv_ffn_ln_bwd), in front of the leading LayerNorm backward, instead of by a GEMM launch that writes the gradient.
 Forms = namedtuple("Forms", "tails riders shadows fuse_bce bce_dgrad skip_row0 cls_fold ffn_e ffn_d ln_bwd_e ln_bwd_d sched dec_tail gnorm ema "
-                            "attn_proj_e attn_proj_d kqv_head_e")
+                            "attn_proj_e attn_proj_d kqv_head_e in_drop")
 
 
 def roll_scores(tp, pred, pos, cells):
@@ -801,6 +801,13 @@ def check_clip(clip_global_norm=0.0):
     """clip_global_norm: 0 (off) or a positive finite bound on the gradient's global L2 norm; raises ValueError otherwise"""
     if not (0 <= clip_global_norm < float("inf")):
         raise ValueError(f"clip_global_norm must be 0 (off) or a positive finite norm, not {clip_global_norm!r}")
+
+
+def check_input_dropout(d_input_dropout=0.0):
+    """d_input_dropout: probability in [0, 1] that a decoder input position is dropped in a training step (0: off, 1: every position);
+    raises ValueError otherwise (a NaN too)"""
+    if not (0 <= d_input_dropout <= 1):
+        raise ValueError(f"d_input_dropout must lie in [0, 1], not {d_input_dropout!r}")
 
 
 def clip_scale(norm, max_norm):
@@ -854,15 +861,19 @@ class StepPlan:
     def __init__(self, store, B, T, lr=3e-4, clip_gradient=1.0, kl_weight=1.0, label_smoothing=0.0,
                  negative_label_downscaling=False, global_batch=None, gscale=None, want_probs=False, seed=0,
                  internal_eps=False, optimizer_params=None, sample_offset=0, site_base=0,
-                 kl_warmup_steps=0, kl_cycle_steps=0, kl_free_bits=0.0, lr_warmup_steps=0, clip_global_norm=0.0, ema_decay=0.0):
+                 kl_warmup_steps=0, kl_cycle_steps=0, kl_free_bits=0.0, lr_warmup_steps=0, clip_global_norm=0.0, ema_decay=0.0,
+                 d_input_dropout=0.0):
         """kl_warmup_steps / kl_cycle_steps / kl_free_bits / lr_warmup_steps: the training schedules (schedule_values),
         evaluated on the device from Adam's step count. All zero (the default): the plain launches with their constants.
         clip_global_norm: bound on the global L2 norm of the batch-mean gradient, applied on the device ahead of Adam (clip_scale;
         DESIGN §12); a step whose norm is not finite is skipped. 0 (the default): off, the optimizer launches as they were.
         ema_decay: decay of an exponential moving average of the weights kept by the Adam launch(es) themselves in store.ema (ema_decay_at,
         ema_update). 0 (the default): off, the optimizer launches as they were.
-        sample_offset: index of this plan's first sample in the global batch (data parallel: rank * B) — the in-graph eps
-        is drawn per GLOBAL sample index, so the result does not depend on the sharding.
+        d_input_dropout: probability that a training step hides a decoder input position (the previous frame / token) from the
+        teacher-forced decoder, drawn on the device by the step's bookkeeping launch (include/mst_hip.h: mst_step_begin_args.in_*;
+        DESIGN §16). 0 (the default): off, the launches as they were. Inference passes and validation steps never drop.
+        sample_offset: index of this plan's first sample in the global batch (data parallel: rank * B) — the in-graph eps and the
+        decoder-input dropout mask are drawn per GLOBAL sample index, so the result does not depend on the sharding.
         site_base: added to every dropout site id (data parallel: a different value per rank gives every rank its own
         masks under the common step seed)."""
         cfg = store.cfg
@@ -880,6 +891,9 @@ class StepPlan:
         self.ema_decay = float(ema_decay)
         if self.ema_decay > 0:
             store.enable_ema()  # (a copy of w, made here, never inside a capture)
+        check_input_dropout(d_input_dropout)
+        self.d_input_dropout = float(d_input_dropout)
+        self._infer = self._tick_adam = False  # (set by forward() / the step; _resolve_forms below reads them)
         self.ls, self.nld = label_smoothing, negative_label_downscaling
         self.global_batch = global_batch or B
         self.sample_offset, self.site_base = int(sample_offset), int(site_base)
@@ -941,6 +955,14 @@ class StepPlan:
             off = roundup(off + nbytes, 16)
         self.own_inbuf = torch.zeros(off, dtype=torch.uint8, device=dev)
         self.bind_inputs(self.own_inbuf)
+        # decoder-input dropout (allocated here, never inside a capture): the step's keep mask, one byte per decoder input position, and
+        # on the piano-roll ends the frames with the dropped rows zeroed — the A operand of the decoder's embedding GEMM and of its
+        # weight gradient in place of `roll` (rows as wide as that view, with a leading dimension of their own)
+        self.in_keep = self.roll_d = None
+        if self.d_input_dropout > 0:
+            self.in_keep = torch.zeros(B * T, dtype=torch.uint8, device=dev)
+            if cfg.kind != "token":
+                self.roll_d = torch.zeros(B * T, roundup(cfg.in_dim, 8), dtype=torch.uint8, device=dev)
         self.eps = torch.zeros(B, Z, **f32)
         self.rng_state = store.rng_state(seed)
         self._outers = []
@@ -1108,7 +1130,11 @@ class StepPlan:
             # the K | Q | V input gradient of an encoder layer as the head of the one-launch backward block below it (which then starts
             # with its leading LayerNorm backward: row_block_bwd 'fused' with a lead), where the library takes the shape that way
             kqv_head_e=bool(self.kqv_head and cfg.e_layers >= 2 and o.ffn_fusion_pays(De, 4 * De) and not o.ln_bwd_fusion_pays(De) and
-                            o.kqv_head_pays(self.adt, B * T, De)))
+                            o.kqv_head_pays(self.adt, B * T, De)),
+            # decoder-input dropout: the bookkeeping draws the keep mask (and writes the masked frames), the decoder's embedding and
+            # its gradient read them. Training steps only: an inference pass and a validation step (is_train False) see every input —
+            # their objective must not move with the option, and they are the launches of a plan without it
+            in_drop=self.d_input_dropout > 0 and self._tick_adam and not self._infer)
 
     def _attn_proj(self, S, H, D):
         return bool(o.attn_bwd_form(self.adt, self.B, S, H, D // H, 0, D, 2 * D, 3 * D, D, 3 * D, proj=True)["proj"])
@@ -1311,7 +1337,7 @@ class StepPlan:
         sq_e, sq_d = math.sqrt(float(De)), math.sqrt(float(Dd))
         self._wgrads, self._psums, self._outers, self._cls_job = [], [], [], None  # deferred gradient work of this step
         # one bookkeeping launch: RNG seed of this step, Adam's step count / lr_t, eps, both padding masks
-        need_rng = self.e_p > 0 or self.d_p > 0 or self.internal_eps
+        need_rng = self.e_p > 0 or self.d_p > 0 or self.internal_eps or F.in_drop
         rng = st.rng_state_inference() if self._infer else self.rng_state
         tick = self._tick_adam and not self._infer
         begin = dict(rng_state=rng if need_rng else None,
@@ -1324,6 +1350,15 @@ class StepPlan:
             begin["shadows"] = self._late_shadows()
         if F.sched and tick:  # the thread that ticks Adam writes this step's schedule block
             begin["schedule"] = dict(block=st.sched, kl_weight=self.kl_weight, **self.schedule)
+        roll_d = keep_d = None  # what the decoder's embedding reads in place of `roll` / besides the tokens
+        if F.in_drop:
+            # position k of sample b (the input of decoder row k + 1) is draw number (sample_offset + b) * T + k of the step's stream:
+            # per GLOBAL sample index, like eps (mst_step_begin_args.in_*)
+            begin["input_drop"] = dict(keep=self.in_keep, p=self.d_input_dropout, index0=self.sample_offset * T)
+            keep_d = self.in_keep
+            if cfg.kind != "token":
+                roll_d = self.roll_d
+                begin["input_drop"].update(src=self.roll, dst=roll_d)  # (the bound blob's frames: bind_inputs)
         # (piano-roll ends: nothing in the embedding GEMMs reads what the bookkeeping writes — it rides on their launch)
         ride = cfg.kind != "token"
         if not ride:
@@ -1336,7 +1371,8 @@ class StepPlan:
             # both ends' embedding GEMMs read the same frames: one launch (the decoder's rows 1..T; its row 0 is latent_fwd's)
             o.gemm_nt_pair(dict(A=self.roll, B=st.t("encoder.embedding.weight"), C_out=self.x0_e, N=De, alpha=sq_e,
                                 grpadd=st.p("encoder.class2hid.weight"), grp_index=self.classes, rowadd=self.pos_e, rowadd_period=T),
-                           dict(A=self.roll, B=st.t("decoder.embedding.weight"), C_out=self.x0_d, M=B * T, N=Dd, alpha=sq_d,
+                           dict(A=roll_d if F.in_drop else self.roll, B=st.t("decoder.embedding.weight"), C_out=self.x0_d, M=B * T, N=Dd,
+                                alpha=sq_d,
                                 rowadd=self.pos_d[1:], rowadd_period=T, c_remap=(T, Sd, 1)),
                            begin=begin if ride else None)
         x = self.x0_e
@@ -1359,7 +1395,7 @@ class StepPlan:
             return
         # ---- decoder positions 1..T (model.py:241-245, transformer.py:237)
         if cfg.kind == "token":
-            o.embed_fwd(self.tokens, st.p("decoder.embedding.weight"), self.pos_d, self.x0_d.view(B, Sd, -1), 1, sq_d)
+            o.embed_fwd(self.tokens, st.p("decoder.embedding.weight"), self.pos_d, self.x0_d.view(B, Sd, -1), 1, sq_d, keep=keep_d)
         x = self.x0_d
         site_d = self._site_d(0)
         for i, L in enumerate(self.dec):
@@ -1574,10 +1610,11 @@ class StepPlan:
         rider, dx0 = handed or (None, None)
         # ---- decoder input: rows 1..T -> embedding, row 0 -> latent block
         if cfg.kind == "token":
-            o.embed_bwd(self.tokens, st.grad("decoder.embedding.weight"), d_x0_d.view(B, Sd, -1), 1, sq_d)
-        else:
-            self._wgrads.append(o.wgrad_problem(self.roll, d_x0_d, st.grad("decoder.embedding.weight"), M=B * T, N=cfg.out_dim,
-                                                K=Dd, scale=sq_d, b_remap=(T, Sd, 1)))
+            o.embed_bwd(self.tokens, st.grad("decoder.embedding.weight"), d_x0_d.view(B, Sd, -1), 1, sq_d,
+                        keep=self.in_keep if F.in_drop else None)
+        else:  # (Forms.in_drop: the frames the forward pass read, dropped rows zeroed)
+            self._wgrads.append(o.wgrad_problem(self.roll_d if F.in_drop else self.roll, d_x0_d, st.grad("decoder.embedding.weight"),
+                                                M=B * T, N=cfg.out_dim, K=Dd, scale=sq_d, b_remap=(T, Sd, 1)))
         # gradient w.r.t. the encoder output: zero except position 0 of every sample
         d_enc = self.d_enc_out
         # nothing but the optimizer reads the latent block's parameter gradients: they ride on the weight-gradient flush (extra

@@ -775,20 +775,22 @@ def layernorm_bwd(x, gamma, mean, rstd, dy, dx, dgamma, dbeta, D=None, dx_masked
 
 
 # --------------------------------------------------------------------------- embedding / masks
-def embed_fwd(tokens, table, pos, out3, s_off, alpha, classes=None, cls_table=None, keymask=None):
-    """out3: [B, S_out, ld] activation buffer; tokens int32 [B, T]."""
+def embed_fwd(tokens, table, pos, out3, s_off, alpha, classes=None, cls_table=None, keymask=None, keep=None):
+    """out3: [B, S_out, ld] activation buffer; tokens int32 [B, T]. keep: uint8 [B * T] decoder-input dropout mask (step_begin's
+    input_drop) — a dropped position takes a zero row in place of its table row"""
     B, T = tokens.shape
     D = table.shape[1]
     call("mst_embed_fwd", dt(out3), B, T, D, ptr(tokens), ptr(table), table.stride(0), ptr(classes), ptr(cls_table),
          (cls_table.stride(0) if cls_table is not None else 0), ptr(pos), pos.stride(0), alpha, ptr(out3),
-         out3.stride(1), out3.shape[1], s_off, ptr(keymask), stream())
+         out3.stride(1), out3.shape[1], s_off, ptr(keymask), ptr(keep), stream())
 
 
-def embed_bwd(tokens, dtable, dX3, s_off, alpha, classes=None, dcls=None):
+def embed_bwd(tokens, dtable, dX3, s_off, alpha, classes=None, dcls=None, keep=None):
+    """keep: the mask embed_fwd ran with — a dropped position adds nothing to dtable (dcls gets every row)"""
     B, T = tokens.shape
     D = dtable.shape[1]
     call("mst_embed_bwd", dt(dX3), B, T, D, ptr(tokens), ptr(dtable), dtable.stride(0), ptr(classes), ptr(dcls),
-         (dcls.stride(0) if dcls is not None else 0), alpha, ptr(dX3), dX3.stride(1), dX3.shape[1], s_off, stream())
+         (dcls.stride(0) if dcls is not None else 0), alpha, ptr(dX3), dX3.stride(1), dX3.shape[1], s_off, ptr(keep), stream())
 
 
 def group_colsum(X3, T, D, s_off, idx, dst, alpha):
@@ -1081,12 +1083,19 @@ def randn(out, seed=0, seed_ptr=None, site=0):
     call("mst_randn", out.numel(), ptr(out), seed, ptr(seed_ptr), site, stream())
 
 
+IN_SITE = 0x7FFF0001  # site of the decoder-input dropout draw: one constant for every rank, next to eps' 0x7FFF0000
+
+
 def _step_begin_args(rng_state=None, adam_state=None, lr=0.0, beta1=0.9, beta2=0.999, eps_out=None, eps_site=0x7FFF0000, eps_index0=0,
-                     lens=None, mask_e=None, add_e=0, mask_d=None, add_d=1, zero_a=None, zero_b=None, shadows=None, schedule=None):
+                     lens=None, mask_e=None, add_e=0, mask_d=None, add_d=1, zero_a=None, zero_b=None, shadows=None, schedule=None,
+                     input_drop=None):
     """shadows: dict(w, wt16, desc, prefix, n_mat, tiles) — a transposed-shadow refresh (transpose_shadows' arguments) hosted by the
     launch that carries the bookkeeping.
     schedule: dict(block, kl_weight, kl_warmup_steps, kl_cycle_steps, kl_free_bits, lr_warmup_steps) — the thread that advances Adam's
-    step count also writes the fp32 schedule block {beta_t, tau, f_lr, t} and puts the warm-up factor into lr_t (mst_step_begin_args.sched*)"""
+    step count also writes the fp32 schedule block {beta_t, tau, f_lr, t} and puts the warm-up factor into lr_t (mst_step_begin_args.sched*)
+    input_drop: dict(keep, p, index0=0, site=IN_SITE, src=None, dst=None, row_bytes=None) — decoder-input dropout (mst_step_begin_args.in_*,
+    where the semantics are stated): keep uint8 [n] gets the step's draw; with src / dst (uint8 [n, >= row_bytes] views, any row stride)
+    dst's rows are src's with the dropped ones zeroed"""
     q = StepBeginArgs()
     nbytes = lambda t: t.numel() * t.element_size() if t is not None else 0
     q.rng_state, q.adam_state, q.lr, q.beta1, q.beta2 = ptr(rng_state), ptr(adam_state), lr, beta1, beta2
@@ -1104,6 +1113,16 @@ def _step_begin_args(rng_state=None, adam_state=None, lr=0.0, beta1=0.9, beta2=0
         q.sched, q.sched_kl_weight, q.sched_kl_free_bits = ptr(block), schedule["kl_weight"], schedule.get("kl_free_bits", 0.0)
         q.sched_kl_warmup, q.sched_kl_cycle = int(schedule.get("kl_warmup_steps", 0)), int(schedule.get("kl_cycle_steps", 0))
         q.sched_lr_warmup = int(schedule.get("lr_warmup_steps", 0))
+    if input_drop:
+        keep, src, dst = input_drop["keep"], input_drop.get("src"), input_drop.get("dst")
+        assert keep.dtype == torch.uint8 and keep.is_contiguous()
+        q.in_keep, q.in_n, q.in_p = ptr(keep), keep.numel(), input_drop["p"]
+        q.in_site, q.in_index0 = input_drop.get("site", IN_SITE), input_drop.get("index0", 0)
+        if src is not None or dst is not None:
+            row_bytes = input_drop.get("row_bytes")
+            q.in_src, q.in_ld_src = ptr(src), (src.stride(0) if src is not None else 0)
+            q.in_dst, q.in_ld_dst = ptr(dst), (dst.stride(0) if dst is not None else 0)
+            q.in_row_bytes = (src if src is not None else dst).shape[1] if row_bytes is None else row_bytes
     return q
 
 

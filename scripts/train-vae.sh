@@ -3,6 +3,8 @@
 # differ per machine): the module path, every flag and every value are the reference's. Two flags are appended
 # for this implementation: --gpu (the step has no CPU path) and, optionally, whatever the caller passes in "$@"
 # (e.g. --pianoroll, --max-steps 200, --dtype fp16).
+#   --d-input-dropout P   hide each decoder input position (the previous frame / token) with probability P in training steps, so the
+#                         decoder has to use the latent (against posterior collapse, beside --kl-warmup-steps / --kl-free-bits); 0: off
 cd "$(dirname "$0")/.." || exit 1
 
 python -m music_style_transfer.VarAutoEncoder.main \
