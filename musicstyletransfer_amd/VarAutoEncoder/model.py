@@ -209,72 +209,48 @@ class Model:
 
     DECODE_PLAN_MAX = 8
 
+    def _decode_cached(self, kind, key, make, reset=False):
+        """the decode-side object of this kind and key (its shape and the RESOLVED attention mode), built by make(*key) at first use:
+        per kind the DECODE_PLAN_MAX most recently used are kept, and all are dropped when the model gets a new store"""
+        if getattr(self, "_decode_cache_store", None) is not self.store:
+            self._decode_caches, self._decode_cache_store = {}, self.store
+        cache = self._decode_caches.setdefault(kind, OrderedDict())
+        obj = cache.pop(key, None)
+        if obj is None:
+            obj = make(*key)
+            while len(cache) >= self.DECODE_PLAN_MAX:
+                torch.cuda.synchronize(self.store.device)  # nothing in flight may still read its buffers / graphs
+                cache.popitem(last=False)  # least recently used first
+        if reset:
+            obj.reset()
+        cache[key] = obj  # most recently used last
+        return obj
+
     def decode_plan(self, n_hyp, t_max, attention=None):
         """the DecodePlan (caches + one captured graph per position) of this many hypotheses / positions, kept across
         batches: a sampler that decodes batch after batch of one shape captures its graphs once"""
         from .. import decode
-        attention = resolve_attention(self.engine_config, attention)
-        if not hasattr(self, "_decode_plans") or getattr(self, "_decode_store", None) is not self.store:
-            self._decode_plans, self._decode_store = OrderedDict(), self.store
-        key = (n_hyp, t_max, attention)
-        plan = self._decode_plans.pop(key, None)
-        if plan is None:
-            plan = decode.DecodePlan(self.store, n_hyp, t_max, attention=attention)
-            while len(self._decode_plans) >= self.DECODE_PLAN_MAX:
-                torch.cuda.synchronize(self.store.device)
-                self._decode_plans.popitem(last=False)
-        plan.reset()
-        self._decode_plans[key] = plan
-        return plan
+        return self._decode_cached("plan", (n_hyp, t_max, resolve_attention(self.engine_config, attention)),
+                                   lambda B, t, att: decode.DecodePlan(self.store, B, t, attention=att), reset=True)
 
     def beam_search_plan(self, B, K, i_max, attention=None):
         """decode.BeamSearch of this shape (caches, token rows, one captured graph per position), kept across batches"""
         from .. import decode
-        attention = resolve_attention(self.engine_config, attention)
-        if not hasattr(self, "_beam_plans") or getattr(self, "_beam_store", None) is not self.store:
-            self._beam_plans, self._beam_store = OrderedDict(), self.store
-        key = (B, K, i_max, attention)
-        bs = self._beam_plans.pop(key, None)
-        if bs is None:
-            bs = decode.BeamSearch(self.store, B, K, i_max, attention=attention)
-            while len(self._beam_plans) >= self.DECODE_PLAN_MAX:
-                torch.cuda.synchronize(self.store.device)
-                self._beam_plans.popitem(last=False)
-        self._beam_plans[key] = bs
-        return bs
+        return self._decode_cached("beam", (B, K, i_max, resolve_attention(self.engine_config, attention)),
+                                   lambda B, K, i, att: decode.BeamSearch(self.store, B, K, i, attention=att))
 
     def frame_sampling_plan(self, N, L, attention=None, keep_probs=False):
         """decode.FrameSampling of this shape (piano-roll ends: caches, the roll, one captured graph per position), kept across batches"""
         from .. import decode
-        attention = resolve_attention(self.engine_config, attention)
-        if not hasattr(self, "_frame_plans") or getattr(self, "_frame_store", None) is not self.store:
-            self._frame_plans, self._frame_store = OrderedDict(), self.store
-        key = (N, L, attention, bool(keep_probs))
-        fs = self._frame_plans.pop(key, None)
-        if fs is None:
-            fs = decode.FrameSampling(self.store, N, L, attention=attention, keep_probs=keep_probs)
-            while len(self._frame_plans) >= self.DECODE_PLAN_MAX:
-                torch.cuda.synchronize(self.store.device)
-                self._frame_plans.popitem(last=False)
-        self._frame_plans[key] = fs
-        return fs
+        return self._decode_cached("frame", (N, L, resolve_attention(self.engine_config, attention), bool(keep_probs)),
+                                   lambda N, L, att, keep: decode.FrameSampling(self.store, N, L, attention=att, keep_probs=keep))
 
     def token_sampling_plan(self, N, L, attention=None, keep_logits=False):
         """decode.TokenSampling of this shape (token ends: caches, token rows, one captured graph per position and filter setting), kept
         across batches"""
         from .. import decode
-        attention = resolve_attention(self.engine_config, attention)
-        if not hasattr(self, "_token_plans") or getattr(self, "_token_store", None) is not self.store:
-            self._token_plans, self._token_store = OrderedDict(), self.store
-        key = (N, L, attention, bool(keep_logits))
-        ts = self._token_plans.pop(key, None)
-        if ts is None:
-            ts = decode.TokenSampling(self.store, N, L, attention=attention, keep_logits=keep_logits)
-            while len(self._token_plans) >= self.DECODE_PLAN_MAX:
-                torch.cuda.synchronize(self.store.device)
-                self._token_plans.popitem(last=False)
-        self._token_plans[key] = ts
-        return ts
+        return self._decode_cached("token", (N, L, resolve_attention(self.engine_config, attention), bool(keep_logits)),
+                                   lambda N, L, att, keep: decode.TokenSampling(self.store, N, L, attention=att, keep_logits=keep))
 
     def on_plan_evicted(self, callback):
         """callback(plan) when the cache drops a plan (holders of per-plan state — graphs, input rings — forget it)"""

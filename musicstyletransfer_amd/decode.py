@@ -18,8 +18,9 @@ oracle/vae_oracle.py::decode_incremental and implemented here on the same kernel
 Everything is one row per sample: the GEMMs are launch-bound M = B problems of the same mst_gemm_nt used in training, so a
 position is ~8 launches per layer of a few microseconds each. Every position is therefore captured ONCE as a hipGraph (its
 kernel arguments — the cache row written, the number of keys attended to, the positional row — are host scalars that differ
-per position, hence one graph per position, captured the first time a plan reaches it) and replayed from then on; plans are
+per position, hence one graph per position, captured by PositionGraphs.run — the one place) and replayed from then on; plans are
 kept per (hypotheses, positions, attention mode) by the model, so beam search over many batches captures nothing twice."""
+import contextlib
 import math
 import os
 
@@ -27,7 +28,35 @@ import numpy as np
 import torch
 
 from . import ops as o
+from .MIDIUtil.defaults import EOS_ID, PAD_ID, SOS_ID
 from .engine import ALL_ROWS, NO_DROPOUT, positional_table, roundup, row_block_fwd
+
+
+class PositionGraphs:
+    """A position's kernel sequence, eager once, then a captured graph: the key -> ops.Graph dict and the warm state of ONE owner
+    (DecodePlan, BeamSearch, FrameSampling and TokenSampling each hold their own). A key is captured once its lane is warm, i.e. once a
+    sequence of that lane has run eagerly here: HIP modules load lazily and cannot be loaded inside a capture. capture_behind: the
+    eager position is captured right behind its eager run (not launched), so the next run replays it too; otherwise it is captured
+    when a later run reaches it. `plan.use_graphs` is read at every position (off: eager launches, no key ever)."""
+
+    def __init__(self, plan, capture_behind=False):
+        self.plan, self.capture_behind = plan, capture_behind
+        self.graphs, self.warm = {}, set()
+
+    def run(self, key, fn, lane=False, warms=True):
+        """warms=False: this eager run does not touch every kernel of the lane's later keys"""
+        use = self.plan.use_graphs
+        g = self.graphs.get(key) if use else None
+        if g is None:
+            if not (use and lane in self.warm):
+                fn()
+                if warms:
+                    self.warm.add(lane)
+                if use and self.capture_behind:
+                    self.graphs[key] = o.Graph().capture(fn)
+                return
+            g = self.graphs[key] = o.Graph().capture(fn)
+        g.launch()  # (all a captured position costs the host: one lookup, one launch)
 
 
 class DecodePlan:
@@ -76,8 +105,8 @@ class DecodePlan:
         # one captured graph per position (MST_DECODE_GRAPHS=0: eager launches); capture needs a stream of its own
         self.use_graphs = os.environ.get("MST_DECODE_GRAPHS", "1") != "0"
         self.stream = torch.cuda.Stream(device=dev)
-        self._graphs = {}
-        self._warm = False
+        self._runner = PositionGraphs(self)
+        self._graphs = self._runner.graphs  # position -> ops.Graph
 
     # ------------------------------------------------------------------ one position through the decoder layers
     def _layers(self, x, t):
@@ -145,16 +174,9 @@ class DecodePlan:
             o.sigmoid_bce(self.logits, self.zero_labels, self.loss, B, 1, cfg.out_dim, npos=self.npos, probs=self.probs, pre_zeroed=True)
 
     def _run_position(self, t):
-        """replay position t's graph (captured at first use; the very first position of a plan runs eagerly: HIP modules
-        load lazily and cannot be loaded inside a capture)"""
-        if not self.use_graphs or not self._warm:
-            self._position(t)
-            self._warm = self._warm or t >= 1  # (position 1 has touched every kernel of a later position)
-            return
-        g = self._graphs.get(t)
-        if g is None:
-            g = self._graphs[t] = o.Graph().capture(lambda: self._position(t))
-        g.launch()
+        """replay position t's graph (captured at first use once the plan has run a position >= 1 eagerly: position 1 has
+        touched every kernel of a later position, position 0 has not)"""
+        self._runner.run(t, lambda: self._position(t), warms=t >= 1)
 
     def step(self, prev):
         """position t = previous + 1: `prev` is the token fed at this position ([B] ids, token ends) or the frame ([B, P]
@@ -187,16 +209,73 @@ class DecodePlan:
         self._leave()
 
 
-class BeamSearch:
+class _Sampler:
+    """What the runs of the device samplers below share. Every sampler has a DecodePlan of its own (`plan`) of which only position 0
+    goes through _run_position: that plan never warms, so position 0 stays eager. The positions >= 1 go through the sampler's own
+    PositionGraphs (AncestralSampling: eager launches)."""
+
+    eos, pad, sos = EOS_ID, PAD_ID, SOS_ID
+
+    def _seed_words(self, dev):
+        """the draw's seed as a device word, which the host rewrites before a run through its pinned twin"""
+        self.seed_word = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._seed_host = torch.zeros(1, dtype=torch.int64).pin_memory()
+
+    def _run_length(self, length):
+        length = self.L if length is None else int(length)
+        if not 2 <= length <= self.L:
+            raise ValueError(f"length {length} outside [2, {self.L}]")
+        return length
+
+    @contextlib.contextmanager
+    def _started(self, row0, seed=None):
+        """the frame of a run, as `with self._started(row0) as p:` — on the plan's stream: the seed word rewritten (samplers that have
+        one), row0 fed, position 0 run; the body issues the later positions and copies its results back, then the caller's stream
+        waits for the plan's"""
+        p = self.plan
+        p.reset()
+        with p._enter():
+            if seed is not None:
+                seed &= 0xFFFFFFFFFFFFFFFF
+                self._seed_host[0] = seed - (1 << 64) if seed >= (1 << 63) else seed  # (an int64 word: two's complement)
+                self.seed_word.copy_(self._seed_host, non_blocking=True)
+            p.x.copy_(row0[:, : p.x.shape[1]])
+            p._run_position(0)
+            p.t = 0
+            yield p
+        p._leave()
+
+    def _sos_rows(self, seqs, scores, first=None):
+        """the token samplers' rows before position 1: SOS, then PAD; the scores at `first` (None: zero)"""
+        seqs.fill_(self.pad)
+        seqs[:, 0] = self.sos
+        if first is None:
+            o.zero(scores)
+        else:
+            scores.copy_(first)
+
+    def _load_held(self, given, hold):
+        """the piece and the mask of a constrained run, as _constraint returned them, into the sampler's device buffers (allocated
+        by the first such run), and held_dev zeroed. Called on the plan's stream."""
+        if self.given is None:
+            self.given, self.hold = self._held_buffers()
+            self.held_dev = torch.zeros_like(self.scores)
+        self._load_constraint(given, hold)
+        o.zero(self.held_dev)
+
+    def _read_held(self, held):
+        if held:
+            self.held_scores = self.held_dev.cpu().numpy()
+
+
+class BeamSearch(_Sampler):
     """Beam search with everything of a position on the device (reference sampler.py:198-257): the decode step of the B x K
     hypotheses, their re-ranking (mst_beam_step: scores, token rows, the words fed next) and the gather of the layers' cache
     rows (mst_beam_gather) are ONE captured graph per position; the host launches graphs and looks at a device counter of
     running hypotheses every few positions. Token rows, scores and caches alternate between two buffers by position parity."""
 
     def __init__(self, store, B, K, i_max, attention="query"):
-        from .MIDIUtil.defaults import EOS_ID, PAD_ID, SOS_ID
         self.B, self.K, self.i_max = B, K, i_max
-        self.eos, self.pad, self.sos = EOS_ID, PAD_ID, SOS_ID
         self.plan = DecodePlan(store, B * K, i_max + 1, attention=attention, pingpong=True)
         dev, N = store.device, B * K
         self.seqs = [torch.zeros(N, i_max, dtype=torch.int32, device=dev) for _ in range(2)]
@@ -207,7 +286,8 @@ class BeamSearch:
         first = torch.full((B, K), float("inf"))
         first[:, 0] = 0.0  # the K copies of a sample start identical: only the first one may expand
         self.first_scores = first.reshape(-1).to(dev)
-        self._graphs, self._warm = {}, False
+        self._runner = PositionGraphs(self.plan)
+        self._graphs = self._runner.graphs  # position -> ops.Graph
         self.positions = 0
 
     def _position(self, i):
@@ -223,29 +303,15 @@ class BeamSearch:
     def run(self, row0, check_every=8):
         """row0: [B * K, >= D] initial decoder rows (every sample's row repeated K times). Returns (token rows [B*K, n] int32,
         scores [B*K] fp32) as host arrays, hypotheses of a sample best first."""
-        p = self.plan
-        p.reset()
-        with p._enter():
-            p.x.copy_(row0[:, : p.x.shape[1]])
-            p._run_position(0)                      # cache set 0, row 0 ...
+        with self._started(row0) as p:              # position 0 fills cache set 0, row 0 ...
             for cin, cout in zip(p.cache_sets[0], p.cache_sets[1]):
                 o.beam_gather(cin, cout, self.ident, 1)  # ... which position 1 expects in set 1
-            p.t = 0
-            self.seqs[1].fill_(self.pad)
-            self.seqs[1][:, 0] = self.sos
-            self.scores[1].copy_(self.first_scores)
+            self._sos_rows(self.seqs[1], self.scores[1], self.first_scores)
             p.tokens.fill_(self.sos)
             o.zero(self.active)
             last = 0
             for i in range(1, self.i_max):
-                if not p.use_graphs or not self._warm:
-                    self._position(i)               # (the first position ever runs eagerly: lazy HIP module loads)
-                    self._warm = True
-                else:
-                    g = self._graphs.get(i)
-                    if g is None:
-                        g = self._graphs[i] = o.Graph().capture(lambda: self._position(i))
-                    g.launch()
+                self._runner.run(i, lambda: self._position(i))
                 p.t = last = i
                 if i % check_every == 0 and int(self.active[i].item()) == 0:
                     break                            # every hypothesis has ended (sampler.py: the loop's exit test)
@@ -253,7 +319,6 @@ class BeamSearch:
             got = self.seqs[res][:, : last + 1].cpu().numpy()
             scores = self.scores[res].cpu().numpy()
             live = self.active[: last + 1].cpu().numpy()
-        p._leave()
         # rows of width i_max like the host loop's (sampler.py:203): PAD behind the last decoded position
         seqs = np.full((got.shape[0], self.i_max), self.pad, got.dtype)
         seqs[:, : last + 1] = got
@@ -264,15 +329,13 @@ class BeamSearch:
         return seqs, scores
 
 
-class AncestralSampling:
+class AncestralSampling(_Sampler):
     """Ancestral sampling (sampler.py:155-190, token ends) with the draw on the device (mst_sample_step): the host neither
     sees the distributions nor feeds the tokens — it launches a position's kernels and polls a device counter of running
     sequences every few positions."""
 
     def __init__(self, store, B, i_max, attention="query", seed=0):
-        from .MIDIUtil.defaults import EOS_ID, PAD_ID, SOS_ID
         self.B, self.i_max = B, i_max
-        self.eos, self.pad, self.sos = EOS_ID, PAD_ID, SOS_ID
         self.plan = DecodePlan(store, B, i_max + 1, attention=attention)
         dev = store.device
         self.seqs = torch.zeros(B, i_max, dtype=torch.int32, device=dev)
@@ -284,17 +347,10 @@ class AncestralSampling:
     def run(self, row0, check_every=8):
         """-> (token rows [B, n] int32, scores [B]) as host arrays. (Eager launches: the draw's seed changes from run to run and
         is a kernel argument; a position is the decode step's ~10 launches + one draw, with no host round trip in between.)"""
-        p = self.plan
-        p.reset()
         self.runs += 1
         seed = (self.seed * 0x9E3779B97F4A7C15 + self.runs) & 0xFFFFFFFFFFFFFFFF
-        with p._enter():
-            p.x.copy_(row0[:, : p.x.shape[1]])
-            p._position(0)
-            p.t = 0
-            self.seqs.fill_(self.pad)
-            self.seqs[:, 0] = self.sos
-            o.zero(self.scores)
+        with self._started(row0) as p:
+            self._sos_rows(self.seqs, self.scores)
             o.zero(self.active)
             p.tokens.fill_(self.sos)
             last = 0
@@ -306,12 +362,11 @@ class AncestralSampling:
                     break
             seqs = self.seqs[:, : last + 1].cpu().numpy()
             scores = self.scores.cpu().numpy()
-        p._leave()
         self.positions = last
         return seqs, scores
 
 
-class FrameSampling:
+class FrameSampling(_Sampler):
     """Sampling for the piano-roll ends with the whole position on the device (sampler.py:155-190 with a Bernoulli draw per pitch):
     the decode step of position i and mst_frame_step — which reads the position's logits, writes the frame where the next position's
     embedding GEMM reads it and into the roll, and adds the frame's -log p to the scores — are ONE captured graph per position. The
@@ -340,12 +395,11 @@ class FrameSampling:
         self.roll = torch.zeros(N, L, roundup(self.P, 8), dtype=torch.uint8, device=dev)
         self.scores = torch.zeros(N, dtype=torch.float32, device=dev)
         self.probs = torch.zeros(N, L, self.P, dtype=torch.float32, device=dev) if keep_probs else None
-        self.seed_word = torch.zeros(1, dtype=torch.int64, device=dev)
-        self._seed_host = torch.zeros(1, dtype=torch.int64).pin_memory()
-        self._graphs, self._warm = {}, False
+        self._seed_words(dev)
+        self._runner = PositionGraphs(self.plan, capture_behind=True)
+        self._graphs = self._runner.graphs  # (position, tau, mode, thr[, True: constrained]) -> ops.Graph
         self.given = self.hold = self.held_dev = None  # device buffers of constrained runs, allocated by the first one
         self.held_scores = None                        # host fp32 [N] of the latest constrained run
-        self._warm_held = False
 
     def _position(self, i, tau, mode, thr, held=False):
         p = self.plan
@@ -368,15 +422,13 @@ class FrameSampling:
             raise ValueError(f"{given.shape[1]} constrained frames for a run of {length - 1}")
         return given, hold
 
+    def _held_buffers(self):
+        self._given_host, self._hold_host = (torch.zeros(self.roll.shape, dtype=torch.uint8).pin_memory() for _ in range(2))
+        return torch.zeros_like(self.roll), torch.zeros_like(self.roll)
+
     def _load_constraint(self, given, hold):
-        """the piece and the mask into the sampler's device buffers (allocated here at first use), through pinned copies of the
-        buffers' own layout: one contiguous transfer each. A cell is set where the byte is non-zero (the kernel's rule), so byte
-        arrays go in as they are. held_scores is zeroed. Called on the plan's stream."""
-        if self.given is None:
-            self.given, self.hold = torch.zeros_like(self.roll), torch.zeros_like(self.roll)
-            self.held_dev = torch.zeros_like(self.scores)
-            self._given_host, self._hold_host = torch.zeros(self.roll.shape, dtype=torch.uint8).pin_memory(), \
-                torch.zeros(self.roll.shape, dtype=torch.uint8).pin_memory()
+        """_load_held's copies: through pinned twins of the buffers' own layout, one contiguous transfer each. A cell is set where
+        the byte is non-zero (the kernel's rule), so byte arrays go in as they are."""
         T = given.shape[1]
         for src, host, dev in ((given, self._given_host, self.given), (hold, self._hold_host, self.hold)):
             view = host.numpy()
@@ -386,7 +438,6 @@ class FrameSampling:
             else:
                 np.not_equal(src, 0, out=view[:, :T, : self.P])
             dev.copy_(host, non_blocking=True)
-        o.zero(self.held_dev)
 
     def run(self, row0, length=None, tau=1.0, mode="draw", thr=0.5, seed=0, given=None, hold=None):
         """row0: [N, >= D] initial decoder rows. Decodes positions 1 .. length - 1 (default: all L - 1) and returns
@@ -394,54 +445,29 @@ class FrameSampling:
         given, hold: host arrays [N, T <= length - 1, P] in the returned roll's indexing: cell [n, k, j] of the roll is given[n, k, j]
         != 0 where hold[n, k, j] != 0 and drawn (or thresholded) elsewhere; the scores then sum the free cells only, and the held
         cells' cost is left in self.held_scores."""
-        p = self.plan
-        length = self.L if length is None else int(length)
-        if not 2 <= length <= self.L:
-            raise ValueError(f"length {length} outside [2, {self.L}]")
+        length = self._run_length(length)
         tau, thr = float(tau), float(thr)
         held = given is not None or hold is not None
         if held:
             given, hold = self._constraint(given, hold, length)
-        p.reset()
-        seed &= 0xFFFFFFFFFFFFFFFF
-        self._seed_host[0] = seed - (1 << 64) if seed >= (1 << 63) else seed
-        with p._enter():
-            self.seed_word.copy_(self._seed_host, non_blocking=True)
-            p.x.copy_(row0[:, : p.x.shape[1]])
-            p._run_position(0)
-            p.t = 0
+        with self._started(row0, seed) as p:
             o.zero(self.scores)
             o.zero(p.frames)
             p.frames[:, 0] = 1  # the start row (pianoroll.pianoroll_arrays)
             if held:
-                self._load_constraint(given, hold)
+                self._load_held(given, hold)
             for i in range(1, length):
-                key = (i, tau, mode, thr, True) if held else (i, tau, mode, thr)
-                warm = self._warm_held if held else self._warm
-                g = self._graphs.get(key) if p.use_graphs else None
-                if g is None and p.use_graphs and warm:
-                    g = self._graphs[key] = o.Graph().capture(lambda: self._position(i, tau, mode, thr, held))
-                if g is not None:
-                    g.launch()
-                else:
-                    self._position(i, tau, mode, thr, held)  # (the first position ever runs eagerly: lazy HIP module loads ...
-                    if held:
-                        self._warm_held = True
-                    else:
-                        self._warm = True
-                    if p.use_graphs:                   # ... and is captured behind that, so the next run replays it too)
-                        self._graphs[key] = o.Graph().capture(lambda: self._position(i, tau, mode, thr, held))
+                self._runner.run((i, tau, mode, thr, True) if held else (i, tau, mode, thr),
+                                 lambda: self._position(i, tau, mode, thr, held), lane=held)
                 p.t = i
             roll = self.roll[:, : length - 1, : self.P].cpu().numpy()
             scores = self.scores.cpu().numpy()
-            if held:
-                self.held_scores = self.held_dev.cpu().numpy()
-        p._leave()
+            self._read_held(held)
         self.positions = length - 1
         return roll, scores
 
 
-class TokenSampling:
+class TokenSampling(_Sampler):
     """Sampling for the token ends with a temperature, a top-k and a nucleus cut, the whole position on the device: the decode step of
     position i up to its logits and mst_token_step — which cuts, draws, writes the token where the next position's embedding reads it
     and keeps the sampler's books (finished sequences, scores, the `active` counter) — are ONE captured graph per position. The draw's
@@ -456,27 +482,24 @@ class TokenSampling:
     def __init__(self, store, N, L, attention="query", keep_logits=False):
         """L positions: the start row + up to L - 1 tokens. keep_logits: every position's logits stay in self.logits (fp32 [N, L, V],
         row i = what position i's draw read; tests and diagnostics)"""
-        from .MIDIUtil.defaults import EOS_ID, PAD_ID, SOS_ID
         cfg = store.cfg
         if cfg.kind != "token":
             raise ValueError("TokenSampling draws tokens; the piano-roll ends have FrameSampling")
         if L < 2:
             raise ValueError("TokenSampling needs at least two positions")
         self.N, self.L, self.V = N, L, cfg.out_dim
-        self.eos, self.pad, self.sos = EOS_ID, PAD_ID, SOS_ID
         self.plan = DecodePlan(store, N, L, attention=attention)
         dev = store.device
         self.seqs = torch.zeros(N, L, dtype=torch.int32, device=dev)
         self.scores = torch.zeros(N, dtype=torch.float32, device=dev)
         self.active = torch.zeros(L + 1, dtype=torch.int32, device=dev)
         self.logits = torch.zeros(N, L, self.V, dtype=torch.float32, device=dev) if keep_logits else None
-        self.seed_word = torch.zeros(1, dtype=torch.int64, device=dev)
-        self._seed_host = torch.zeros(1, dtype=torch.int64).pin_memory()
-        self._graphs, self._warm = {}, False
+        self._seed_words(dev)
+        self._runner = PositionGraphs(self.plan, capture_behind=True)
+        self._graphs = self._runner.graphs  # (position, tau, top_k, top_p[, True: constrained]) -> ops.Graph
         self.positions = 0
         self.given = self.hold = self.held_dev = None  # device buffers of constrained runs, allocated by the first one
         self.held_scores = None                        # host fp32 [N] of the latest constrained run
-        self._warm_held = False
 
     def _position(self, i, tau, top_k, top_p, held=False):
         p = self.plan
@@ -506,16 +529,22 @@ class TokenSampling:
             raise ValueError(f"a held token outside [0, {self.V}): {np.asarray(given)[bad][:8].tolist()}")
         return np.where(hold != 0, given, self.pad).astype(np.int32), hold
 
+    def _held_buffers(self):
+        return torch.zeros_like(self.seqs), torch.zeros(self.N, self.L, dtype=torch.uint8, device=self.seqs.device)
+
+    def _load_constraint(self, given, hold):
+        T = given.shape[1]
+        o.zero(self.hold)  # (positions behind T hold nothing)
+        self.given[:, :T].copy_(torch.from_numpy(given))
+        self.hold[:, :T].copy_(torch.from_numpy(hold))
+
     def run(self, row0, length=None, tau=1.0, top_k=0, top_p=1.0, seed=0, check_every=8, given=None, hold=None):
         """row0: [N, >= D] initial decoder rows. Decodes positions 1 .. length - 1 (default: all L - 1), stopping early once every
         sequence has ended (looked at every check_every positions), and returns (token rows [N, n] int32, scores [N]) as host arrays.
         given, hold: host arrays [N, T <= length] in the returned rows' indexing: token [n, i] is given[n, i] where hold[n, i] != 0
         (i >= 1) and drawn elsewhere; the scores then sum the drawn tokens only, and the held tokens' cost is left in
         self.held_scores. A run does not stop before its last held position."""
-        p = self.plan
-        length = self.L if length is None else int(length)
-        if not 2 <= length <= self.L:
-            raise ValueError(f"length {length} outside [2, {self.L}]")
+        length = self._run_length(length)
         tau, top_k, top_p = float(tau), int(top_k), float(top_p)
         if not (0.0 < tau < float("inf")) or top_k < 0 or not 0.0 < top_p <= 1.0:
             raise ValueError(f"tau > 0 finite, top_k >= 0 and 0 < top_p <= 1 wanted, got {tau}, {top_k}, {top_p}")
@@ -524,53 +553,21 @@ class TokenSampling:
             given, hold = self._constraint(given, hold, length)
             cols = np.nonzero(hold.any(0))[0]
             last_held = int(cols[-1]) if cols.size else 0
-        p.reset()
-        seed &= 0xFFFFFFFFFFFFFFFF
-        self._seed_host[0] = seed - (1 << 64) if seed >= (1 << 63) else seed
-        with p._enter():
-            self.seed_word.copy_(self._seed_host, non_blocking=True)
-            p.x.copy_(row0[:, : p.x.shape[1]])
-            p._run_position(0)
-            p.t = 0
-            self.seqs.fill_(self.pad)
-            self.seqs[:, 0] = self.sos
-            o.zero(self.scores)
+        with self._started(row0, seed) as p:
+            self._sos_rows(self.seqs, self.scores)
             o.zero(self.active)
             p.tokens.fill_(self.sos)
             if held:
-                if self.given is None:
-                    self.given = torch.zeros_like(self.seqs)
-                    self.hold = torch.zeros(self.N, self.L, dtype=torch.uint8, device=self.seqs.device)
-                    self.held_dev = torch.zeros_like(self.scores)
-                T = given.shape[1]
-                o.zero(self.hold)  # (positions behind T hold nothing)
-                self.given[:, :T].copy_(torch.from_numpy(given))
-                self.hold[:, :T].copy_(torch.from_numpy(hold))
-                o.zero(self.held_dev)
+                self._load_held(given, hold)
             last = 0
             for i in range(1, length):
-                key = (i, tau, top_k, top_p, True) if held else (i, tau, top_k, top_p)
-                warm = self._warm_held if held else self._warm
-                g = self._graphs.get(key) if p.use_graphs else None
-                if g is None and p.use_graphs and warm:
-                    g = self._graphs[key] = o.Graph().capture(lambda: self._position(i, tau, top_k, top_p, held))
-                if g is not None:
-                    g.launch()
-                else:
-                    self._position(i, tau, top_k, top_p, held)  # (the first position ever runs eagerly: lazy HIP module loads ...
-                    if held:
-                        self._warm_held = True
-                    else:
-                        self._warm = True
-                    if p.use_graphs:                      # ... and is captured behind that, so the next run replays it too)
-                        self._graphs[key] = o.Graph().capture(lambda: self._position(i, tau, top_k, top_p, held))
+                self._runner.run((i, tau, top_k, top_p, True) if held else (i, tau, top_k, top_p),
+                                 lambda: self._position(i, tau, top_k, top_p, held), lane=held)
                 p.t = last = i
                 if i % check_every == 0 and i >= last_held and int(self.active[i].item()) == 0:
                     break
             seqs = self.seqs[:, : last + 1].cpu().numpy()
             scores = self.scores.cpu().numpy()
-            if held:
-                self.held_scores = self.held_dev.cpu().numpy()
-        p._leave()
+            self._read_held(held)
         self.positions = last
         return seqs, scores

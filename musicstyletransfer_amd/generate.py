@@ -423,15 +423,19 @@ class LatentGenerator:
             return (roll, scores, (fs.probs[:, : length - 1].cpu().numpy() if self.keep_probs else None),
                     fs.held_scores if given is not None else None)
         from .MIDIUtil.defaults import PAD_ID
+
+        def padded(got):  # the rows a run returned (it may have stopped early), PAD up to `length`
+            seqs = np.full((n, length), PAD_ID, np.int64)
+            seqs[:, : got.shape[1]] = got
+            return seqs
+
         if given is not None or (self.decoder == "sampling" and (self.sample_temperature != 1.0 or self.top_k != 0 or self.top_p != 1.0)):
             # (a constrained piece always decodes here; 'greedy' is then the draw among the single most likely token)
             greedy = self.decoder != "sampling"
             ts = self.last_sampler = m.token_sampling_plan(n, length, attention)
             got, scores = ts.run(row0, length, tau=1.0 if greedy else self.sample_temperature, top_k=1 if greedy else self.top_k,
                                  top_p=1.0 if greedy else self.top_p, seed=seed, given=given, hold=hold)
-            seqs = np.full((n, length), PAD_ID, np.int64)
-            seqs[:, : got.shape[1]] = got
-            return seqs, scores, None, (ts.held_scores if given is not None else None)
+            return padded(got), scores, None, (ts.held_scores if given is not None else None)
         if self.decoder == "sampling":
             key = (n, length, attention, id(m.store))
             smp = self._samplers.get(key)
@@ -441,9 +445,7 @@ class LatentGenerator:
                 smp = self._samplers[key] = decode.AncestralSampling(m.store, n, length, attention, seed=seed)
             self.last_sampler = smp
             got, scores = smp.run(row0)
-            seqs = np.full((n, length), PAD_ID, np.int64)
-            seqs[:, : got.shape[1]] = got
-            return seqs, scores, None, None
+            return padded(got), scores, None, None
         K = self.beam_size if self.decoder == "beam" else 1  # (one beam is greedy decoding)
         bs = self.last_sampler = m.beam_search_plan(n, K, length, attention)
         seqs, scores = bs.run(row0.repeat_interleave(K, dim=0).contiguous() if K > 1 else row0)

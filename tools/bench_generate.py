@@ -148,7 +148,7 @@ def held_case(args, setup=None):
 
     def upload():  # what a constrained run does once, in front of its first position: the piece and the mask to the device
         with fs.plan._enter():
-            fs._load_constraint(given, hold)
+            fs._load_held(given, hold)
         fs.plan._leave()
 
     for fn in forms.values():  # module loads, graph capture, then one replay
