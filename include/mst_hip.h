@@ -939,10 +939,8 @@ int mst_loss_combine(int64_t B, const float* recon, const float* kl, float kl_we
  *   that reason: 1 - 0.999f is already 1.3e-5 off); t lives in step_state[0] on the device and is advanced by a
  *   1-thread kernel issued ahead of the update in the same stream, so a captured graph replays
  *   with the right bias correction.
- * Also refreshes the 16-bit shadow copy w16 (act dtype, same offsets).
- * metrics (optional): the end-of-step bookkeeping of mst_loss_combine (total[b] = recon[b] + kl_weight * kl[b] and the
- * running metric sums; trainer.py:107-120,172,181-186) done by the first workgroup of this launch instead of a launch of
- * its own.
+ * Also refreshes the 16-bit shadow copy w16 (act dtype, same offsets; may be NULL).
+ * ONE entry point, mst_adam_flat, over ONE argument block, mst_adam_args (below, where every optional group is stated).
  * ------------------------------------------------------------------------ */
 typedef struct mst_step_metrics {
   int64_t B; const float* recon; const float* kl; float kl_weight; float* total; float* metric;
@@ -964,75 +962,49 @@ typedef struct mst_step_metrics {
 #define MST_TAIL_SPIN_FWD 1u     /* a grid barrier of mst_row_tail_fwd gave up waiting */
 #define MST_TAIL_SPIN_BWD 2u     /* ... of mst_row_tail_bwd */
 #define MST_STEP_INCOMPLETE 16u  /* an expect_ptr of the step guard did not hold its value at the end of the step */
-int mst_adam_flat(int dtype, int64_t n, float* w, const float* grad, float* m, float* v,
-                  void* w16, double lr, double beta1, double beta2, float eps, float wd,
-                  float rescale, float clip, int32_t* step_state /* device int32[2]: {t, bits(lr_t)} */,
-                  int advance_step /* 0: reuse the lr_t of the previous launch (second range of one step) */,
-                  const mst_step_metrics* metrics, mst_stream_t stream);
-/* mst_loss_combine with the step guard of mst_step_metrics (validation steps: a step whose position-0 tail failed adds
- * nothing to the running sums) */
-int mst_loss_combine_v(const mst_step_metrics* metrics, mst_stream_t stream);
-
-/* mst_adam_flat that also keeps the transposed 16-bit shadow of up to two matrices current (the piano-roll embedding tables,
- * which the step's first launch reads): for an element of matrix j — emb[4j..4j+3] = {source offset in the flat bucket, offset
- * in wt16, rows, cols}, host array — the new weight is also stored at wt16[dst + c * roundup8(rows) + r]. `base` is the flat
- * offset of `w` itself (a launch over a sub-range of the bucket). Everything else as mst_adam_flat with advance_step = 0. */
-int mst_adam_flat_emb(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
-                      double beta2, float eps, float wd, float rescale, float clip, int32_t* step_state,
-                      const mst_step_metrics* metrics, int64_t base, const int64_t* emb, int64_t n_emb, void* wt16, mst_stream_t stream);
-
-/* The scheduled forms of mst_adam_flat (with advance_step = 0: the schedule block exists only behind an mst_step_begin of the same
- * step) and of mst_adam_flat_emb. The end-of-step bookkeeping reads the device schedule block `sched` of mst_step_begin instead of
- * metrics->kl_weight, which is ignored:  total[b] = recon[b] + sched[0] * max(kl[b] - sched[1], 0)   (the KL charged beyond the
- * free bits, at this step's weight); metric[0] += sum_b kl[b] — the RAW KL, comparable across schedules —, metric[1] += sum_b total,
- * metric[2] += B. The step guard and the non-finite guard (on the raw per-sample losses) are those of the unscheduled launches; a
- * step they skip takes the step count back, and the schedule — a function of that count alone — with it. lr_t is read from
- * step_state as always: the learning-rate warm-up is already in it. */
-int mst_adam_flat_sched(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
-                        double beta2, float eps, float wd, float rescale, float clip, int32_t* step_state,
-                        const mst_step_metrics* metrics, const float* sched, mst_stream_t stream);
-int mst_adam_flat_emb_sched(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
-                            double beta2, float eps, float wd, float rescale, float clip, int32_t* step_state,
-                            const mst_step_metrics* metrics, const float* sched, int64_t base, const int64_t* emb, int64_t n_emb,
-                            void* wt16, mst_stream_t stream);
-
-/* Clipping by the global L2 norm (gluon.utils.clip_global_norm's rule), inside the step: two entry points.
+/* The argument block of mst_adam_flat: ONE launch over w[0..n), behind — with advance_step — the 1-thread launch that advances
+ * the step count. The first three lines of fields state the update rule above; each optional group below is off while its
+ * pointer is NULL, and the launch is then exactly the one without the group. Every check named here is made before any HIP call.
  *
- * mst_grad_sumsq: ONE launch of mst_grad_sumsq_parts() workgroups (a fixed count, <= 256) over the flat fp32 gradient bucket
- * grad[0..n) (16-byte aligned). Element i is multiplied by rescale_lo if i < cut, else by rescale_hi (0 <= cut <= n, any residue
- * mod 4: the two loss-scale ranges of an fp16 step), and squared; workgroup j stores the sum over its elements at parts[j].
- * Order: per thread an fp32 chain over its grid-stride 4-vectors (the up-to-three tail elements on the last workgroup), a DPP
- * wave sum, the four waves through LDS in wave order. No atomics: the same data gives the same bits in every launch. A NaN or
- * inf in the bucket — or an element whose square overflows fp32, |g r| > 1.8e19 — makes a part non-finite.
+ * dtype is the act dtype of w16 and wt16. w, grad, m, v: fp32, n > 0 elements, 16-byte aligned. step_state: device int32[2] =
+ * {t, bits(lr_t)}. advance_step = 1 (standalone use): t and lr_t are advanced here from lr, beta1, beta2; 0: the launch reuses
+ * the lr_t that mst_step_begin, or the previous launch of the step (a second range of one step), left there. advance_step = 1
+ * goes with none of sched, emb, parts and ema, whose step count is mst_step_begin's.
  *
- * mst_adam_flat_gnorm: mst_adam_flat_emb_sched in which `sched` may be NULL and n_emb may be 0 (both are then ignored: one entry
- * point for the four forms; advance_step = 0 as there), with the gradient clipped by the norm the parts state:
+ * metrics: the end-of-step bookkeeping of mst_loss_combine (total[b] = recon[b] + kl_weight * kl[b] and the running metric
+ * sums; trainer.py:107-120,172,181-186) done by the first workgroup of this launch instead of a launch of its own, and the two
+ * guards of mst_step_metrics. The launch given `recon` carries the step's bookkeeping; a second range of the step gets the guards'
+ * fields alone.
+ *
+ * sched: the bookkeeping reads the device schedule block of mst_step_begin (which exists only behind an mst_step_begin of the
+ * same step) instead of metrics->kl_weight, which is ignored:  total[b] = recon[b] + sched[0] * max(kl[b] - sched[1], 0)  (the KL
+ * charged beyond the free bits, at this step's weight); metric[0] += sum_b kl[b] — the RAW KL, comparable across schedules —,
+ * metric[1] += sum_b total, metric[2] += B. The guards work on the raw per-sample losses as without a schedule; a step they skip
+ * takes the step count back, and the schedule — a function of that count alone — with it. lr_t is read from step_state as
+ * always: the learning-rate warm-up is already in it.
+ *
+ * base, emb, n_emb, wt16: the launch also keeps the transposed 16-bit shadow of n_emb = 0..2 matrices current (the piano-roll
+ * embedding tables, which the step's first launch reads). emb is a HOST array, emb[4j..4j+3] = {source offset in the flat bucket,
+ * offset in wt16, rows, cols} (rows, cols > 0, rows * cols < 2^31, the offset in wt16 >= 0); for an element of matrix j the new weight is
+ * also stored at wt16[dst + c * roundup8(rows) + r]. base >= 0 is the flat offset of `w` itself (a launch over a sub-range of the
+ * bucket); a matrix outside [base, base + n) simply never matches. n_emb = 0: emb and wt16 are ignored.
+ *
+ * parts, n_parts, max_norm, gstat: the gradient is clipped by its global L2 norm (gluon.utils.clip_global_norm's rule), which the
+ * per-workgroup sums of squares that mst_grad_sumsq left in parts state:
  *   S    = sum of parts[0..n_parts) in double, formed by every wave alike: lane l adds parts[4l..4l+3] as (p0 + p1) + (p2 + p3),
  *          then six pairwise levels across the 64 lanes (partners 1 and 2 apart, mirrored within 8 and within 16, 16 and 32
  *          apart; each level the commutative sum of two lanes' values) — the same instructions on the same words in every wave
  *          of every launch of the step, so all of them apply the same factor
  *   norm = sqrtf((float)S);  c = max_norm / (norm + 1e-8f) in fp32, and c = 1 unless c < 1
- *   g    = grad * fl32(rescale * c) + wd * w, then the per-element clip and the update of mst_adam_flat
+ *   g    = grad * fl32(rescale * c) + wd * w, then the per-element clip and the update as above
  * The norm is that of the batch-mean, loss-scale-free gradient, before weight decay: pass mst_grad_sumsq the rescales of the
- * Adam launches. A step whose norm is not finite is SKIPPED by every launch handed these parts: parameters, moments, shadows and
- * the metric sums stay as they were; the launch with `gstat` (the one that carries the step's bookkeeping; NULL on the others)
- * takes the step count back and, if metrics->status is given, increments status[2] — once per step, for any number of ranks.
- * This guard comes after the two of mst_step_metrics, which count their own skips. On a step that counts, that launch writes
+ * Adam launches. gstat (NULL on every launch but the one that carries the step's bookkeeping) receives, on a step that counts,
  * gstat[0..6) = {norm, c, running sum of norms, largest norm, steps, steps with c < 1}; the host clears the running fields.
- * parts non-NULL and 16-byte aligned, n_parts == mst_grad_sumsq_parts() and 0 < max_norm < inf are checked before any HIP call. */
-int64_t mst_grad_sumsq_parts(void);
-int mst_grad_sumsq(int64_t n, const float* grad, int64_t cut, float rescale_lo, float rescale_hi, float* parts, mst_stream_t stream);
-int mst_adam_flat_gnorm(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
-                        double beta2, float eps, float wd, float rescale, float clip, int32_t* step_state,
-                        const mst_step_metrics* metrics, const float* sched, int64_t base, const int64_t* emb, int64_t n_emb,
-                        void* wt16, const float* parts, int64_t n_parts, float max_norm, float* gstat, mst_stream_t stream);
-
-/* An exponential moving average of the weights, kept by the Adam launch itself: two entry points.
+ * Checked: parts 16-byte aligned, n_parts == mst_grad_sumsq_parts(), 0 < max_norm < inf; and with parts NULL, that n_parts,
+ * max_norm and gstat are 0 / NULL too.
  *
- * mst_adam_flat_ema: mst_adam_flat_gnorm in which `parts` may be NULL too (no clipping: n_parts, max_norm and gstat are then
- * ignored; given, they are checked as there) — with `sched` and n_emb optional as there, ONE entry point for every form of the Adam
- * launch, advance_step = 0 — whose threads also fold each weight they have just written into ema[0..n) (fp32, 16-byte aligned,
- * the flat offsets of `w`):
+ * ema, decay: the averaging form. Every thread also folds each weight it has just written into ema[0..n) (fp32, 16-byte aligned,
+ * the flat offsets of `w`), an exponential moving average of the weights:
  *   t    = step_state[0], Adam's step count after the step's increment (1-based)
  *   d_t  = fminf(decay, (1.f + t) / (10.f + t))      fp32, t converted to fp32 first, a correctly rounded division: the usual
  *          warm-up, so the first steps do not average in the initial weights
@@ -1040,22 +1012,52 @@ int mst_adam_flat_gnorm(int dtype, int64_t n, float* w, const float* grad, float
  *   e_i <- fl(fl(d_t * e_i) + fl(omd * w_i'))        w_i' the fp32 weight this thread stores: two rounded products and one
  *          rounded sum, in this order, never contracted into an FMA (engine.ema_decay_at / engine.ema_update state the same in
  *          np.float32; the result is theirs bit for bit)
- * w, m, v, w16 and the transposed shadows are exactly what the launch without `ema` writes. The average follows the launch's own
- * skip predicate: on a step the step guard, the non-finite guard or the non-finite-norm guard skips, ema stays as it was, like
- * w, m and v. Reading t is race-free: in this launch only the bookkeeping thread ever writes step_state, and only to take the
- * count back on a skipped step, where every thread returns before the read; on a step that counts nobody writes it (the
- * increment is mst_step_begin's, earlier in the stream). Both ranges of a two-range fp16 step read the same t, hence the same d_t.
- * ema non-NULL and 16-byte aligned and 0 < decay < 1 are checked before any HIP call.
+ * w, m, v, w16 and the transposed shadows are exactly what the launch without `ema` writes. Reading t is race-free: in this
+ * launch only the bookkeeping thread ever writes step_state, and only to take the count back on a skipped step, where every
+ * thread returns before the read; on a step that counts nobody writes it (the increment is mst_step_begin's, earlier in the
+ * stream). Both ranges of a two-range fp16 step read the same t, hence the same d_t. Checked: ema 16-byte aligned and
+ * 0 < decay < 1 (a NaN fails); and with ema NULL, that decay is 0.
  *
- * mst_ema_swap: ONE launch that exchanges w[i] <-> ema[i] over the bucket (16-byte loads and stores, a grid-stride loop, the
- * up-to-three tail elements on the last workgroup) and writes w16[i] (may be NULL) from the new w[i], the cast the Adam launch
- * writes. Contents move, pointers do not: captured graphs stay valid. Exact: two calls restore every bit of w and ema. The
- * transposed shadows are the caller's to refresh (mst_transpose_shadows). */
-int mst_adam_flat_ema(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
-                      double beta2, float eps, float wd, float rescale, float clip, int32_t* step_state,
-                      const mst_step_metrics* metrics, const float* sched, int64_t base, const int64_t* emb, int64_t n_emb,
-                      void* wt16, const float* parts, int64_t n_parts, float max_norm, float* gstat, float* ema, float decay,
-                      mst_stream_t stream);
+ * Skipped steps. Three guards, asked in this order, each uniform over the launch and over the launches of a step: the step guard
+ * and the non-finite guard of mst_step_metrics, then — with parts — a norm that is not finite (a NaN or inf somewhere in the
+ * bucket). A launch that a guard skips leaves parameters, moments, w16, the transposed shadows, ema and the metric sums as they
+ * were. The launch that carries the step's bookkeeping (metrics->recon for the first two guards, gstat for the third) takes the
+ * step count back — once per step, for any number of ranges and ranks — and counts the skip: the step guard in metrics->status[0]
+ * and [1] as stated at mst_step_metrics, either non-finite guard by incrementing status[2] (the third only if metrics->status is
+ * given). gstat is not written on a skipped step. */
+typedef struct mst_adam_args {
+  int32_t dtype; int64_t n; float* w; const float* grad; float* m; float* v; void* w16;
+  double lr, beta1, beta2; float eps, wd, rescale, clip;
+  int32_t* step_state; int32_t advance_step;
+  const mst_step_metrics* metrics;
+  const float* sched;
+  int64_t base; const int64_t* emb; int64_t n_emb; void* wt16;
+  const float* parts; int64_t n_parts; float max_norm; float* gstat;
+  float* ema; float decay;
+} mst_adam_args;
+int mst_adam_flat(const mst_adam_args* args, mst_stream_t stream);
+/* What mst_adam_flat launches for a block: no HIP call, no device pointer followed, the launch's own checks with its status and
+ * message. form[0..5) = {scheduled bookkeeping, clipping, averaging (each 0/1: the three switches of the kernel), transposed
+ * shadows kept (0..2), the step-count launch ahead (0/1)}. */
+int mst_adam_flat_form(const mst_adam_args* args, int64_t* form);
+/* mst_loss_combine with the step guard of mst_step_metrics (validation steps: a step whose position-0 tail failed adds
+ * nothing to the running sums) */
+int mst_loss_combine_v(const mst_step_metrics* metrics, mst_stream_t stream);
+
+/* mst_grad_sumsq, for the clipping group of mst_adam_args: ONE launch of mst_grad_sumsq_parts() workgroups (a fixed count,
+ * <= 256) over the flat fp32 gradient bucket grad[0..n) (16-byte aligned). Element i is multiplied by rescale_lo if i < cut, else
+ * by rescale_hi (0 <= cut <= n, any residue mod 4: the two loss-scale ranges of an fp16 step), and squared; workgroup j stores the
+ * sum over its elements at parts[j]. Order: per thread an fp32 chain over its grid-stride 4-vectors (the up-to-three tail
+ * elements on the last workgroup), a DPP wave sum, the four waves through LDS in wave order. No atomics: the same data gives the
+ * same bits in every launch. A NaN or inf in the bucket — or an element whose square overflows fp32, |g r| > 1.8e19 — makes a
+ * part non-finite. */
+int64_t mst_grad_sumsq_parts(void);
+int mst_grad_sumsq(int64_t n, const float* grad, int64_t cut, float rescale_lo, float rescale_hi, float* parts, mst_stream_t stream);
+
+/* mst_ema_swap, for the averaging group of mst_adam_args: ONE launch that exchanges w[i] <-> ema[i] over the bucket (16-byte loads
+ * and stores, a grid-stride loop, the up-to-three tail elements on the last workgroup) and writes w16[i] (may be NULL) from the
+ * new w[i], the cast the Adam launch writes. Contents move, pointers do not: captured graphs stay valid. Exact: two calls restore
+ * every bit of w and ema. The transposed shadows are the caller's to refresh (mst_transpose_shadows). */
 int mst_ema_swap(int dtype, int64_t n, float* w, float* ema, void* w16, mst_stream_t stream);
 
 /* 16-bit shadow + transposed shadow refresh for a list of matrices.
@@ -1097,7 +1099,7 @@ typedef struct mst_step_begin_args {
   /* Optional transposed-shadow refresh riding on the same launch (mst_transpose_shadows' arguments; sh_w == NULL: none): the
    * 16-bit transposed copies of matrices that only the BACKWARD pass reads can be rebuilt from the fp32 weights at the start
    * of the next step instead of in a launch of their own behind the optimizer. Matrices the launch itself reads (the
-   * piano-roll embedding tables of mst_gemm_nt_pair_begin) must not be listed: mst_adam_flat_emb keeps those current. */
+   * piano-roll embedding tables of mst_gemm_nt_pair_begin) must not be listed: mst_adam_flat keeps those current (mst_adam_args.emb). */
   int32_t sh_dtype; const float* sh_w; void* sh_wt16; const int64_t* sh_desc; const int64_t* sh_prefix; int64_t sh_n_mat, sh_tiles;
   /* Optional training schedules (sched == NULL: none, the launch is exactly the one without these fields; needs adam_state). With t =
    * adam_state[0] AFTER this launch's increment (1-based) and all arithmetic in double:
@@ -1105,7 +1107,7 @@ typedef struct mst_step_begin_args {
    *   u      = sched_kl_cycle > 0 ? ((t - 1) mod sched_kl_cycle) + 1 : t;  ramp = sched_kl_warmup > 0 ? min(1, u / sched_kl_warmup) : 1
    *   beta_t = (float)((double)sched_kl_weight * ramp)
    * and the thread that advances Adam's step count writes the fp32 schedule block sched[0..3] = {beta_t, sched_kl_free_bits, f_lr, t},
-   * which the scheduled launches of the same step read (mst_latent_bwd_vec_sched, mst_adam_flat_sched). A pure function of the step
+   * which the scheduled launches of the same step read (mst_latent_bwd_vec_sched, mst_adam_flat with mst_adam_args.sched). A pure function of the step
    * count: it replays inside a captured graph, resumes with the optimizer state and is the same on every data-parallel rank; a
    * step the optimizer's guards take back (mst_step_metrics) takes the schedule back with the count.
    * Lengths and free bits must be >= 0; a cycle needs 0 < sched_kl_warmup <= sched_kl_cycle. */

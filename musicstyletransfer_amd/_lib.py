@@ -26,7 +26,7 @@ _SCALARS = {"int": C.c_int, "int32_t": c_i32, "int64_t": c_i64, "uint8_t": C.c_u
 _STRUCT_NAMES = {"mst_gemm_args": "GemmArgs", "mst_bce_args": "BceArgs", "mst_row_tail_args": "RowTailArgs",
                  "mst_row_tail_bwd_args": "RowTailBwdArgs", "mst_ln_args": "LnArgs", "mst_ln_bwd_in": "LnBwdIn",
                  "mst_step_metrics": "StepMetrics", "mst_partial_sum": "PartialSum", "mst_step_begin_args": "StepBeginArgs",
-                 "mst_outer_job": "OuterJob", "mst_wgrad_args": "WgradArgs"}
+                 "mst_outer_job": "OuterJob", "mst_wgrad_args": "WgradArgs", "mst_adam_args": "AdamArgs"}
 
 # one top-level declaration: a struct typedef, an enum, the stream typedef, or (anything else up to its ';') a prototype
 _DECL = re.compile(r"\s*(?:typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*(\w+)\s*;|enum\s+\w+\s*\{([^{}]*)\}\s*;"

@@ -7,7 +7,7 @@
 //   m   = b1*m + (1-b1)*g ;  v = b2*v + (1-b2)*g*g
 //   w  -= lr * sqrt(1-b2^t)/(1-b1^t) * m / (sqrt(v) + eps)
 // HBM-bound: 16 B/param read (w,g,m,v) + 12 B/param written (w,m,v) + 2 B/param 16-bit shadow; in the averaging form
-// (mst_adam_flat_ema) 4 + 4 B/param more for the exponential moving average of the weights, which the same thread keeps.
+// (mst_adam_args.ema) 4 + 4 B/param more for the exponential moving average of the weights, which the same thread keeps.
 // The step counter lives on the device and is advanced by a 1-thread kernel in the same stream,
 // so a captured graph replays with the right bias correction.
 #include <math.h>
@@ -26,7 +26,7 @@ __global__ void adam_tick_kernel(int32_t* state, double lr, double beta1, double
   reinterpret_cast<float*>(state)[1] = (float)(lr * sqrt(c2) / c1);
 }
 
-// transposed shadows kept current by the optimizer itself (mst_adam_flat_emb): up to two matrices, flat offsets relative to the
+// transposed shadows kept current by the optimizer itself (mst_adam_args.emb): up to two matrices, flat offsets relative to the
 // launch's own `w`
 struct AdamEmb {
   int n;
@@ -49,7 +49,7 @@ __device__ __forceinline__ void adam_emb_store(const AdamEmb& e, int64_t i, floa
 // workgroups of mst_grad_sumsq = rows of its `parts` (mst_grad_sumsq_parts): one per compute unit of an MI355X
 constexpr int kGnormParts = 256;
 
-// global-norm clipping (mst_adam_flat_gnorm): the per-workgroup sums of squares of mst_grad_sumsq, the bound, the statistics block
+// global-norm clipping (mst_adam_args.parts): the per-workgroup sums of squares of mst_grad_sumsq, the bound, the statistics block
 struct AdamGnorm {
   const float* parts;
   float max_norm;
@@ -92,7 +92,7 @@ __device__ __forceinline__ float gnorm_clip_scale(float norm, float max_norm) {
   return c < 1.f ? c : 1.f;
 }
 
-// the average of mst_adam_flat_ema: the shadow bucket and the configured decay (ema == nullptr in every other form)
+// the average of mst_adam_args.ema: the shadow bucket and the configured decay (ema == nullptr in every other form)
 struct AdamEma {
   float* ema;
   float decay;
@@ -129,9 +129,9 @@ __device__ __forceinline__ void adam_elem(float& w, float grad, float& m, float&
   w = w - (lr_t * m) / (sqrtf(v) + eps);
 }
 
-// SCHED (mst_adam_flat_sched): the bookkeeping takes the KL weight and the free bits from the device schedule block
-// GNORM (mst_adam_flat_gnorm): the gradient is clipped by its global L2 norm, and a step whose norm is not finite is skipped
-// EMA (mst_adam_flat_ema): every thread folds the weight it has just written into the exponential moving average em.ema. t is read
+// SCHED (mst_adam_args.sched): the bookkeeping takes the KL weight and the free bits from the device schedule block
+// GNORM (mst_adam_args.parts): the gradient is clipped by its global L2 norm, and a step whose norm is not finite is skipped
+// EMA (mst_adam_args.ema): every thread folds the weight it has just written into the exponential moving average em.ema. t is read
 // from state[0] behind the guards: only the bookkeeping thread of this launch ever writes that word, and only on a step the guards
 // skip — where every thread has returned before this read — so on a step that counts nobody writes it while it is read
 template <typename T, bool SCHED, bool GNORM, bool EMA = false>
@@ -290,139 +290,94 @@ static unsigned grid_for(int64_t n, int per_thread) {
   return (unsigned)g;
 }
 
-static int adam_flat_impl(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr,
-                          double beta1, double beta2, float eps, float wd, float rescale, float clip,
-                          int32_t* step_state, int advance_step, const mst_step_metrics* metrics, const AdamEmb& emb, const float* sched,
-                          mst_stream_t stream, const AdamGnorm* gnorm = nullptr, const AdamEma* ema = nullptr) {
-  MST_CHECK_ARG(n > 0 && w && grad && m && v && step_state, "mst_adam_flat: bad argument");
-  mst_step_metrics mt = {};
-  if (metrics) {
-    MST_CHECK_ARG(metrics->recon == nullptr || (metrics->B > 0 && metrics->kl), "mst_adam_flat: metrics need B, recon and kl");
-    MST_CHECK_ARG(metrics->status || (!metrics->expect_ptr0 && !metrics->expect_ptr1), "mst_adam_flat: expectations need the status words");
-    mt = *metrics;
+// One Adam launch as the host has decided it: the kernel's by-value blocks and the three switches that choose its instantiation.
+struct AdamPlan {
+  mst_step_metrics mt;
+  AdamEmb emb;
+  AdamGnorm gn;
+  AdamEma em;
+  bool sched, gnorm, ema, tick;
+};
+
+// Every check of mst_adam_flat, in the header's order, before any HIP call: mst_adam_flat launches what this leaves in `p`,
+// mst_adam_flat_form reports it.
+static int adam_plan(const mst_adam_args* args, AdamPlan& p) {
+  MST_CHECK_ARG(args != nullptr, "mst_adam_flat: null args");
+  const mst_adam_args& a = *args;
+  p = AdamPlan{};
+  MST_CHECK_ARG(a.ema != nullptr || a.decay == 0.f, "mst_adam_flat: decay without ema (the averaging form takes both)");
+  if (a.ema) {
+    MST_CHECK_ARG((uintptr_t)a.ema % 16 == 0, "mst_adam_flat: ema must be 16-byte aligned");
+    MST_CHECK_ARG(a.decay > 0.f && a.decay < 1.f, "mst_adam_flat: decay must lie in (0, 1)");
+    p.em = {a.ema, a.decay};
   }
-  MST_CHECK_ARG(((uintptr_t)w % 16 == 0) && ((uintptr_t)grad % 16 == 0) && ((uintptr_t)m % 16 == 0) && ((uintptr_t)v % 16 == 0),
+  MST_CHECK_ARG(a.parts != nullptr || (a.n_parts == 0 && a.max_norm == 0.f && a.gstat == nullptr),
+                "mst_adam_flat: n_parts, max_norm or gstat without parts (mst_grad_sumsq writes them)");
+  if (a.parts) {
+    MST_CHECK_ARG((uintptr_t)a.parts % 16 == 0, "mst_adam_flat: parts must be 16-byte aligned");
+    MST_CHECK_ARG(a.n_parts == kGnormParts, "mst_adam_flat: n_parts must be mst_grad_sumsq_parts() = %d", kGnormParts);
+    MST_CHECK_ARG(a.max_norm > 0.f && a.max_norm <= 3.0e38f, "mst_adam_flat: max_norm must be positive and finite");
+    p.gn = {a.parts, a.max_norm, a.gstat};
+  }
+  MST_CHECK_ARG(a.n_emb >= 0 && a.n_emb <= 2 && (a.n_emb == 0 || (a.emb && a.wt16)) && a.base >= 0,
+                "mst_adam_flat: up to two matrices, with their table and wt16");
+  for (int j = 0; j < (int)a.n_emb; ++j) {
+    const int64_t so = a.emb[4 * j], dst = a.emb[4 * j + 1], rows = a.emb[4 * j + 2], cols = a.emb[4 * j + 3];
+    MST_CHECK_ARG(rows > 0 && cols > 0 && rows * cols < (1ll << 31) && dst >= 0, "mst_adam_flat: bad matrix %d", j);
+    // (a matrix outside this launch's range [base, base + n) simply never matches)
+    AdamEmb& e = p.emb;
+    e.lo[e.n] = so - a.base; e.hi[e.n] = so - a.base + rows * cols; e.dst[e.n] = dst; e.rows[e.n] = (int32_t)rows; e.cols[e.n] = (int32_t)cols;
+    ++e.n;
+  }
+  p.emb.wt16 = a.wt16;
+  MST_CHECK_ARG(!a.advance_step || (!a.sched && !a.emb && !a.parts && !a.ema),
+                "mst_adam_flat: advance_step goes with none of sched, emb, parts and ema (their step count is mst_step_begin's)");
+  MST_CHECK_ARG(a.n > 0 && a.w && a.grad && a.m && a.v && a.step_state, "mst_adam_flat: bad argument");
+  if (a.metrics) {
+    MST_CHECK_ARG(a.metrics->recon == nullptr || (a.metrics->B > 0 && a.metrics->kl), "mst_adam_flat: metrics need B, recon and kl");
+    MST_CHECK_ARG(a.metrics->status || (!a.metrics->expect_ptr0 && !a.metrics->expect_ptr1), "mst_adam_flat: expectations need the status words");
+    p.mt = *a.metrics;
+  }
+  MST_CHECK_ARG(((uintptr_t)a.w % 16 == 0) && ((uintptr_t)a.grad % 16 == 0) && ((uintptr_t)a.m % 16 == 0) && ((uintptr_t)a.v % 16 == 0),
                 "mst_adam_flat: buffers must be 16-byte aligned");
+  p.sched = a.sched != nullptr; p.gnorm = a.parts != nullptr; p.ema = a.ema != nullptr; p.tick = a.advance_step != 0;
+  return dispatch_act(a.dtype, [](auto) -> int { return MST_OK; });
+}
+
+// the eight instantiations of one activation type, indexed [EMA][GNORM][SCHED]
+template <typename T> using AdamKernel = decltype(&adam_flat_kernel<T, false, false, false>);
+template <typename T>
+static constexpr AdamKernel<T> kAdamKernels[2][2][2] = {
+    {{adam_flat_kernel<T, false, false, false>, adam_flat_kernel<T, true, false, false>},
+     {adam_flat_kernel<T, false, true, false>, adam_flat_kernel<T, true, true, false>}},
+    {{adam_flat_kernel<T, false, false, true>, adam_flat_kernel<T, true, false, true>},
+     {adam_flat_kernel<T, false, true, true>, adam_flat_kernel<T, true, true, true>}}};
+
+extern "C" int mst_adam_flat_form(const mst_adam_args* args, int64_t* form) {
+  MST_CHECK_ARG(form != nullptr, "mst_adam_flat_form: null form");
+  AdamPlan p;
+  if (const int rc = adam_plan(args, p)) return rc;
+  form[0] = p.sched; form[1] = p.gnorm; form[2] = p.ema; form[3] = p.emb.n; form[4] = p.tick;
+  return MST_OK;
+}
+
+extern "C" int mst_adam_flat(const mst_adam_args* args, mst_stream_t stream) {
+  AdamPlan p;
+  if (const int rc = adam_plan(args, p)) return rc;
+  const mst_adam_args& a = *args;
   hipStream_t s = (hipStream_t)stream;
-  if (advance_step) {  // a second launch over another range of the same step passes 0
-    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, s, step_state, lr, beta1, beta2);
+  if (p.tick) {  // a launch behind mst_step_begin, or over a second range of the same step, passes 0
+    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, s, a.step_state, a.lr, a.beta1, a.beta2);
     MST_CHECK_LAUNCH("adam_tick_kernel");
   }
-  return dispatch_act(dtype, [&](auto tag) -> int {
+  return dispatch_act(a.dtype, [&](auto tag) -> int {
     typedef decltype(tag) T;
-    const AdamGnorm gn = gnorm ? *gnorm : AdamGnorm{};
-    const AdamEma em = ema ? *ema : AdamEma{};
-    if (ema) {  // (the averaging form: the same four, with the fourth switch)
-      const dim3 grid(grid_for(n, 4));
-      if (gnorm && sched)
-        hipLaunchKernelGGL((adam_flat_kernel<T, true, true, true>), grid, dim3(256), 0, s, n, w, grad, m, v, (T*)w16, step_state,
-                           (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, sched, gn, em);
-      else if (gnorm)
-        hipLaunchKernelGGL((adam_flat_kernel<T, false, true, true>), grid, dim3(256), 0, s, n, w, grad, m, v, (T*)w16, step_state,
-                           (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, (const float*)nullptr, gn, em);
-      else if (sched)
-        hipLaunchKernelGGL((adam_flat_kernel<T, true, false, true>), grid, dim3(256), 0, s, n, w, grad, m, v, (T*)w16, step_state,
-                           (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, sched, gn, em);
-      else
-        hipLaunchKernelGGL((adam_flat_kernel<T, false, false, true>), grid, dim3(256), 0, s, n, w, grad, m, v, (T*)w16, step_state,
-                           (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, (const float*)nullptr, gn, em);
-    } else if (gnorm && sched)
-      hipLaunchKernelGGL((adam_flat_kernel<T, true, true>), dim3(grid_for(n, 4)), dim3(256), 0, s, n, w, grad, m, v, (T*)w16, step_state,
-                         (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, sched, gn, em);
-    else if (gnorm)
-      hipLaunchKernelGGL((adam_flat_kernel<T, false, true>), dim3(grid_for(n, 4)), dim3(256), 0, s, n, w, grad, m, v, (T*)w16, step_state,
-                         (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, (const float*)nullptr, gn, em);
-    else if (sched)
-      hipLaunchKernelGGL((adam_flat_kernel<T, true, false>), dim3(grid_for(n, 4)), dim3(256), 0, s, n, w, grad, m, v, (T*)w16, step_state,
-                         (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, sched, gn, em);
-    else
-      hipLaunchKernelGGL((adam_flat_kernel<T, false, false>), dim3(grid_for(n, 4)), dim3(256), 0, s, n, w, grad, m, v, (T*)w16, step_state,
-                         (float)beta1, (float)beta2, eps, wd, rescale, clip, mt, step_state, emb, (const float*)nullptr, gn, em);
+    hipLaunchKernelGGL(kAdamKernels<T>[p.ema][p.gnorm][p.sched], dim3(grid_for(a.n, 4)), dim3(256), 0, s, a.n, a.w, a.grad, a.m, a.v,
+                       (T*)a.w16, a.step_state, (float)a.beta1, (float)a.beta2, a.eps, a.wd, a.rescale, a.clip, p.mt, a.step_state, p.emb,
+                       a.sched, p.gn, p.em);
     MST_CHECK_LAUNCH("adam_flat_kernel");
     return MST_OK;
   });
-}
-
-extern "C" int mst_adam_flat(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr,
-                             double beta1, double beta2, float eps, float wd, float rescale, float clip,
-                             int32_t* step_state, int advance_step, const mst_step_metrics* metrics, mst_stream_t stream) {
-  AdamEmb none = {};
-  return adam_flat_impl(dtype, n, w, grad, m, v, w16, lr, beta1, beta2, eps, wd, rescale, clip, step_state, advance_step, metrics, none, nullptr,
-                        stream);
-}
-
-extern "C" int mst_adam_flat_sched(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
-                                   double beta2, float eps, float wd, float rescale, float clip, int32_t* step_state,
-                                   const mst_step_metrics* metrics, const float* sched, mst_stream_t stream) {
-  MST_CHECK_ARG(sched != nullptr, "mst_adam_flat_sched: null schedule block");
-  AdamEmb none = {};
-  return adam_flat_impl(dtype, n, w, grad, m, v, w16, lr, beta1, beta2, eps, wd, rescale, clip, step_state, 0, metrics, none, sched, stream);
-}
-
-static int adam_flat_emb_impl(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
-                              double beta2, float eps, float wd, float rescale, float clip, int32_t* step_state,
-                              const mst_step_metrics* metrics, const float* sched, int64_t base, const int64_t* emb, int64_t n_emb,
-                              void* wt16, mst_stream_t stream, const AdamGnorm* gnorm = nullptr, const AdamEma* ema = nullptr) {
-  MST_CHECK_ARG(n_emb >= 0 && n_emb <= 2 && (n_emb == 0 || (emb && wt16)) && base >= 0, "mst_adam_flat_emb: up to two matrices, with their table and wt16");
-  AdamEmb e = {};
-  for (int j = 0; j < (int)n_emb; ++j) {
-    const int64_t so = emb[4 * j], dst = emb[4 * j + 1], rows = emb[4 * j + 2], cols = emb[4 * j + 3];
-    MST_CHECK_ARG(rows > 0 && cols > 0 && rows * cols < (1ll << 31) && dst >= 0, "mst_adam_flat_emb: bad matrix %d", j);
-    // (a matrix outside this launch's range [base, base + n) simply never matches)
-    e.lo[e.n] = so - base; e.hi[e.n] = so - base + rows * cols; e.dst[e.n] = dst; e.rows[e.n] = (int32_t)rows; e.cols[e.n] = (int32_t)cols;
-    ++e.n;
-  }
-  e.wt16 = wt16;
-  return adam_flat_impl(dtype, n, w, grad, m, v, w16, lr, beta1, beta2, eps, wd, rescale, clip, step_state, 0, metrics, e, sched, stream, gnorm, ema);
-}
-
-extern "C" int mst_adam_flat_emb(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
-                                 double beta2, float eps, float wd, float rescale, float clip, int32_t* step_state,
-                                 const mst_step_metrics* metrics, int64_t base, const int64_t* emb, int64_t n_emb, void* wt16,
-                                 mst_stream_t stream) {
-  return adam_flat_emb_impl(dtype, n, w, grad, m, v, w16, lr, beta1, beta2, eps, wd, rescale, clip, step_state, metrics, nullptr, base, emb, n_emb,
-                            wt16, stream);
-}
-
-extern "C" int mst_adam_flat_emb_sched(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
-                                       double beta2, float eps, float wd, float rescale, float clip, int32_t* step_state,
-                                       const mst_step_metrics* metrics, const float* sched, int64_t base, const int64_t* emb, int64_t n_emb,
-                                       void* wt16, mst_stream_t stream) {
-  MST_CHECK_ARG(sched != nullptr, "mst_adam_flat_emb_sched: null schedule block");
-  return adam_flat_emb_impl(dtype, n, w, grad, m, v, w16, lr, beta1, beta2, eps, wd, rescale, clip, step_state, metrics, sched, base, emb, n_emb,
-                            wt16, stream);
-}
-
-extern "C" int mst_adam_flat_gnorm(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
-                                   double beta2, float eps, float wd, float rescale, float clip, int32_t* step_state,
-                                   const mst_step_metrics* metrics, const float* sched, int64_t base, const int64_t* emb, int64_t n_emb,
-                                   void* wt16, const float* parts, int64_t n_parts, float max_norm, float* gstat, mst_stream_t stream) {
-  MST_CHECK_ARG(parts != nullptr, "mst_adam_flat_gnorm: null parts (mst_grad_sumsq writes them)");
-  MST_CHECK_ARG((uintptr_t)parts % 16 == 0, "mst_adam_flat_gnorm: parts must be 16-byte aligned");
-  MST_CHECK_ARG(n_parts == kGnormParts, "mst_adam_flat_gnorm: n_parts must be mst_grad_sumsq_parts() = %d", kGnormParts);
-  MST_CHECK_ARG(max_norm > 0.f && max_norm <= 3.0e38f, "mst_adam_flat_gnorm: max_norm must be positive and finite");
-  const AdamGnorm gn = {parts, max_norm, gstat};
-  return adam_flat_emb_impl(dtype, n, w, grad, m, v, w16, lr, beta1, beta2, eps, wd, rescale, clip, step_state, metrics, sched, base, emb, n_emb,
-                            wt16, stream, &gn);
-}
-
-extern "C" int mst_adam_flat_ema(int dtype, int64_t n, float* w, const float* grad, float* m, float* v, void* w16, double lr, double beta1,
-                                 double beta2, float eps, float wd, float rescale, float clip, int32_t* step_state,
-                                 const mst_step_metrics* metrics, const float* sched, int64_t base, const int64_t* emb, int64_t n_emb,
-                                 void* wt16, const float* parts, int64_t n_parts, float max_norm, float* gstat, float* ema, float decay,
-                                 mst_stream_t stream) {
-  MST_CHECK_ARG(ema != nullptr && (uintptr_t)ema % 16 == 0, "mst_adam_flat_ema: ema must be given and 16-byte aligned");
-  MST_CHECK_ARG(decay > 0.f && decay < 1.f, "mst_adam_flat_ema: decay must lie in (0, 1)");
-  const AdamEma em = {ema, decay};
-  if (!parts)  // (no clipping: n_parts, max_norm and gstat are ignored)
-    return adam_flat_emb_impl(dtype, n, w, grad, m, v, w16, lr, beta1, beta2, eps, wd, rescale, clip, step_state, metrics, sched, base, emb,
-                              n_emb, wt16, stream, nullptr, &em);
-  MST_CHECK_ARG((uintptr_t)parts % 16 == 0, "mst_adam_flat_ema: parts must be 16-byte aligned");
-  MST_CHECK_ARG(n_parts == kGnormParts, "mst_adam_flat_ema: n_parts must be mst_grad_sumsq_parts() = %d", kGnormParts);
-  MST_CHECK_ARG(max_norm > 0.f && max_norm <= 3.0e38f, "mst_adam_flat_ema: max_norm must be positive and finite");
-  const AdamGnorm gn = {parts, max_norm, gstat};
-  return adam_flat_emb_impl(dtype, n, w, grad, m, v, w16, lr, beta1, beta2, eps, wd, rescale, clip, step_state, metrics, sched, base, emb, n_emb,
-                            wt16, stream, &gn, &em);
 }
 
 // w[i] <-> ema[i] over the flat bucket, w16[i] from the new w[i] (the cast the Adam launch writes): 16-byte loads and stores over a
@@ -465,7 +420,7 @@ extern "C" int mst_ema_swap(int dtype, int64_t n, float* w, float* ema, void* w1
   });
 }
 
-// sums of squares of the rescaled flat gradient for mst_adam_flat_gnorm: workgroup j leaves parts[j]. Per thread an fp32 chain over
+// sums of squares of the rescaled flat gradient for mst_adam_flat's clipping group: workgroup j leaves parts[j]. Per thread an fp32 chain over
 // its grid-stride elements, then wave_sum (DPP), then the four waves through LDS in wave order: no atomics, a fixed order
 __global__ __launch_bounds__(256) void grad_sumsq_kernel(int64_t n, const float* __restrict__ grad, int64_t cut, float rescale_lo,
                                                          float rescale_hi, float* __restrict__ parts) {

@@ -182,7 +182,7 @@ class ParamStore:
         # Deferred shadow refresh (piano-roll ends): the transposed shadows of the matrices only the BACKWARD pass reads are rebuilt by
         # extra workgroups of the NEXT step's first launch (mst_gemm_nt_pair_begin, sh_*) instead of a launch of their own behind the
         # optimizer; the two embedding tables, which that first launch itself reads, are kept current by the optimizer launch
-        # (mst_adam_flat_emb). Token ends keep the separate launch.
+        # (mst_adam_args.emb). Token ends keep the separate launch.
         emb_names = [n for n in ("encoder.embedding.weight", "decoder.embedding.weight") if n in self.t_specs]
         late = [n for n in self.t_specs if n not in emb_names]
         self.shadows_deferred = cfg.kind == "pianoroll" and len(emb_names) == 2 and len(late) > 0
@@ -212,7 +212,7 @@ class ParamStore:
         # sched = the fp32 schedule block {beta_t, tau, f_lr, t} the step's first launch writes for a plan with training schedules
         # (schedule_values; mst_step_begin_args.sched*), read by that step's scheduled launches — and here, with the metrics
         # gstat = the statistics block of global-norm clipping {norm, c, sum of norms, largest norm, steps, clipped steps}, written by
-        # the bookkeeping thread of every counted step of a plan with clip_global_norm (mst_adam_flat_gnorm), read with the metrics
+        # the bookkeeping thread of every counted step of a plan with clip_global_norm (mst_adam_args.gstat), read with the metrics
         self._metric_buf = torch.zeros(20, **f32)
         self.metric_acc = self._metric_buf[:3]
         self.step_status = self._metric_buf[4:7].view(torch.int32)
@@ -766,7 +766,7 @@ def row_tail_selfcheck(store, B=64, S=2):
 # sched — the latent block's backward launch and the step-closing bookkeeping in their scheduled forms (training schedules on).
 # dec_tail — the last decoder layer's row-wise block, the loss launch and the block's backward as ONE launch (a training step with gradient).
 # gnorm — the optimizer clips by the global gradient norm: one mst_grad_sumsq launch ahead of the Adam launches in their gnorm form.
-# ema — the Adam launches in their averaging form (mst_adam_flat_ema): the same launches in the same order, none added.
+# ema — the Adam launches in their averaging form (mst_adam_args.ema): the same launches in the same order, none added.
 # attn_proj_e / attn_proj_d — the W_proj input gradient of an encoder layer below the top one / of a (non-causal) decoder layer is formed
 # inside its attention-backward launch (mst_attn_proj_bwd) instead of by a GEMM launch that writes datt.
 # kqv_head_e — the K | Q | V input gradient of an encoder layer above another one is formed inside that layer's feed-forward backward launch
@@ -812,7 +812,7 @@ def check_input_dropout(d_input_dropout=0.0):
 
 def clip_scale(norm, max_norm):
     """the factor c global-norm clipping applies to a gradient of L2 norm `norm` — gluon.utils.clip_global_norm's rule as the device
-    evaluates it (mst_adam_flat_gnorm), stated once for the host in np.float32 arithmetic: c = max_norm / (norm + 1e-8), and 1 unless
+    evaluates it (mst_adam_flat's clipping group), stated once for the host in np.float32 arithmetic: c = max_norm / (norm + 1e-8), and 1 unless
     that is below 1"""
     c = np.float32(max_norm) / (np.float32(norm) + np.float32(1e-8))
     return c if c < np.float32(1) else np.float32(1)
@@ -826,7 +826,7 @@ def check_ema(ema_decay=0.0):
 
 def ema_decay_at(t, decay):
     """d_t, the decay the average applies at training step t (Adam's step count after the step's increment, 1-based) — the rule as the
-    device evaluates it (mst_adam_flat_ema), stated once for the host in np.float32 arithmetic: min(decay, (1 + t) / (10 + t)), the usual
+    device evaluates it (mst_adam_flat's averaging group), stated once for the host in np.float32 arithmetic: min(decay, (1 + t) / (10 + t)), the usual
     warm-up, so that the first steps do not average in the initial weights"""
     tf = np.float32(t)
     d = (np.float32(1) + tf) / (np.float32(10) + tf)
@@ -835,7 +835,7 @@ def ema_decay_at(t, decay):
 
 def ema_update(e, w_new, d):
     """the average after a step: fl(fl(d * e) + fl((1 - d) * w_new)) in np.float32 — two rounded products and one rounded sum, in this
-    order and never fused, which is what mst_adam_flat_ema computes (include/mst_hip.h) bit for bit. e, w_new: fp32 arrays (or scalars)"""
+    order and never fused, which is what mst_adam_flat computes for mst_adam_args.ema (include/mst_hip.h) bit for bit. e, w_new: fp32 arrays (or scalars)"""
     d = np.float32(d)
     omd = np.float32(1) - d
     a = d * np.asarray(e, np.float32)
@@ -1671,33 +1671,27 @@ class StepPlan:
         # end-of-step bookkeeping (total loss, running metric sums) on the first Adam launch: losses(combine=False)
         guard = self._guard()
         mt = dict(recon=self.recon, kl=self.kl, kl_weight=self.kl_weight, total=self.total, metric=self.metric_acc, **guard)
-        emb = (lambda base: dict(base=base, specs=st.emb_specs, wt16=st.wt16)) if deferred else (lambda base: None)
-        # clipping by the global norm: every Adam launch of the step reads the same sums of squares — taken here, behind the
-        # all-reduce, from the whole bucket at the launches' own rescales —; the launch with the bookkeeping keeps the statistics.
-        # Off: no extra keyword, the calls as they were
-        gn = ((lambda a: dict(gnorm=dict(parts=self.grad_parts, max_norm=self.clip_global_norm, gstat=st.gstat if a == 0 else None)))
-              if self.forms.gnorm else (lambda a: {}))
-        # the average: each Adam launch folds the weights of its own range into the same range of store.ema. Off: no extra keyword
-        av = (lambda a, b: dict(ema=dict(buf=st.ema[a:b], decay=self.ema_decay))) if self.forms.ema else (lambda a, b: {})
-        if self.gscale == self.gscale_enc:
-            r = 1.0 / (self.global_batch * self.gscale)
-            if self.forms.gnorm:
-                o.grad_sumsq(st.g, 0, r, r, self.grad_parts)
-            o.adam_flat(st.w, st.g, st.m, st.v, st.w16, st.step_state, lr=self.lr,
-                        rescale=r, clip=clip, advance_step=False, metrics=mt, emb=emb(0),
-                        sched=sched, **gn(0), **av(0, st.n), **self.opt)
-        else:
-            # encoder.* tensors come first in the flat buffers; everything from decoder.latent2hid on is decoder-side.
-            # NOTE the latent_proj gradients are produced by latent_bwd_vec at the encoder-side scale.
+        # one launch over the whole bucket, or — two loss scales — one per range: encoder.* tensors come first in the flat buffers,
+        # everything from decoder.latent2hid on is decoder-side. NOTE the latent_proj gradients are produced by latent_bwd_vec at the
+        # encoder-side scale.
+        ranges = [(0, st.n, self.gscale)]
+        if self.gscale != self.gscale_enc:
             cut = st.offsets["decoder.latent2hid.weight"]
-            rng = [(0, cut, self.gscale_enc, False), (cut, st.n, self.gscale, False)]
-            if self.forms.gnorm:
-                o.grad_sumsq(st.g, cut, 1.0 / (self.global_batch * self.gscale_enc), 1.0 / (self.global_batch * self.gscale), self.grad_parts)
-            for a, b, gs, adv in rng:
-                o.adam_flat(st.w[a:b], st.g[a:b], st.m[a:b], st.v[a:b], st.w16[a:b], st.step_state, lr=self.lr,
-                            rescale=1.0 / (self.global_batch * gs), clip=clip, advance_step=adv,
-                            metrics=mt if a == 0 else (guard or None), emb=emb(a), sched=sched if a == 0 else None, **gn(a),
-                            **av(a, b), **self.opt)
+            ranges = [(0, cut, self.gscale_enc), (cut, st.n, self.gscale)]
+        rescale = [1.0 / (self.global_batch * gs) for _, _, gs in ranges]
+        if self.forms.gnorm:
+            # clipping by the global norm: every Adam launch of the step reads the same sums of squares — taken here, behind the
+            # all-reduce, from the whole bucket at the launches' own rescales
+            o.grad_sumsq(st.g, ranges[-1][0], rescale[0], rescale[-1], self.grad_parts)
+        for (a, b, _), r in zip(ranges, rescale):
+            first = a == 0  # the launch that carries the bookkeeping: the metrics, the schedule block, the clipping statistics
+            o.adam_flat(st.w[a:b], st.g[a:b], st.m[a:b], st.v[a:b], st.w16[a:b], st.step_state, lr=self.lr, rescale=r, clip=clip,
+                        advance_step=False, metrics=mt if first else (guard or None), sched=sched if first else None,
+                        emb=dict(base=a, specs=st.emb_specs, wt16=st.wt16) if deferred else None,
+                        gnorm=dict(parts=self.grad_parts, max_norm=self.clip_global_norm, gstat=st.gstat if first else None)
+                        if self.forms.gnorm else None,
+                        # the average: each launch folds the weights of its own range into the same range of store.ema
+                        ema=dict(buf=st.ema[a:b], decay=self.ema_decay) if self.forms.ema else None, **self.opt)
         if not deferred:  # (deferred: the next step's first launch rebuilds them, forward())
             o.transpose_shadows(st.w, st.wt16, st.t_desc, st.t_prefix, len(st.t_specs), st.t_tiles)
 

@@ -980,56 +980,60 @@ def loss_combine(recon, kl, kl_weight, total=None, metric_acc=None, guard=None):
 
 
 # --------------------------------------------------------------------------- optimizer / shadows
-def adam_flat(w, grad, m, v, w16, step_state, lr, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.0, rescale=1.0, clip=-1.0,
-              advance_step=True, metrics=None, emb=None, sched=None, gnorm=None, ema=None):
-    """metrics: dict(recon, kl, kl_weight, total, metric) -> loss_combine's bookkeeping runs in this launch;
+def _adam_args(w, grad, m, v, w16, step_state, lr, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.0, rescale=1.0, clip=-1.0,
+               advance_step=True, metrics=None, emb=None, sched=None, gnorm=None, ema=None):
+    """-> AdamArgs, the block of mst_adam_flat (include/mst_hip.h states every group).
+    metrics: dict(recon, kl, kl_weight, total, metric) -> loss_combine's bookkeeping runs in this launch;
     + status / expect: the step guard (_step_metrics).
     sched: the device schedule block of step_begin {beta_t, tau, ...} — the bookkeeping charges total = recon + beta_t * max(kl - tau, 0)
-    instead of recon + kl_weight * kl (mst_adam_flat_sched / mst_adam_flat_emb_sched; the step count is step_begin's: no advance_step)
+    instead of recon + kl_weight * kl.
+    emb: dict(specs=[(source offset, offset in wt16, rows, cols), ...], wt16[, base]) — the launch keeps the transposed shadows of these
+    (up to two) matrices current.
     gnorm: dict(parts, max_norm[, gstat]) — clipping by the global norm grad_sumsq() left in `parts`, and the skip of a step whose norm
-    is not finite (mst_adam_flat_gnorm, which takes emb and sched or neither; gstat: on the launch that carries the bookkeeping)
-    ema: dict(buf, decay) — the launch in its averaging form (mst_adam_flat_ema, which takes emb, sched and gnorm or none of them): buf, the
-    fp32 average at w's offsets, takes in every weight the launch writes (engine.ema_update at engine.ema_decay_at of the step count)"""
-    mt = _step_metrics(metrics) if metrics is not None else None
+    is not finite (gstat: on the launch that carries the bookkeeping).
+    ema: dict(buf, decay) — the averaging form: buf, the fp32 average at w's offsets, takes in every weight the launch writes
+    (engine.ema_update at engine.ema_decay_at of the step count).
+    Every group is optional and goes with every other; advance_step with none of sched, emb, gnorm and ema (their step count is
+    step_begin's)."""
+    q = _lib.AdamArgs()
+    q.dtype, q.n, q.w, q.grad, q.m, q.v, q.w16 = dt(w16), w.numel(), ptr(w), ptr(grad), ptr(m), ptr(v), ptr(w16)
+    q.lr, q.beta1, q.beta2, q.eps, q.wd, q.rescale, q.clip = lr, beta1, beta2, eps, wd, rescale, clip
+    q.step_state, q.advance_step = ptr(step_state), 1 if advance_step else 0
+    if metrics is not None:
+        q.metrics = C.pointer(_step_metrics(metrics))
     if sched is not None:
         assert not advance_step and sched.dtype == torch.float32 and sched.numel() >= 4
-    block = () if sched is None else (ptr(sched),)
+        q.sched = ptr(sched)
+    if emb is not None:
+        assert not advance_step
+        flat = [int(x) for spec in emb["specs"] for x in spec]
+        q._emb = (_lib.c_i64 * len(flat))(*flat)  # (a host array: the block keeps it alive)
+        q.base, q.emb, q.n_emb, q.wt16 = emb.get("base", 0), C.addressof(q._emb), len(flat) // 4, ptr(emb["wt16"])
+    if gnorm is not None:
+        parts, gstat = gnorm["parts"], gnorm.get("gstat")
+        assert not advance_step and parts.dtype == torch.float32
+        assert gstat is None or (gstat.dtype == torch.float32 and gstat.numel() >= 6)
+        q.parts, q.n_parts, q.max_norm, q.gstat = ptr(parts), parts.numel(), gnorm["max_norm"], ptr(gstat)
     if ema is not None:
         buf = ema["buf"]
         assert not advance_step and buf.dtype == torch.float32 and buf.numel() == w.numel()
-        parts, gstat = (gnorm["parts"], gnorm.get("gstat")) if gnorm is not None else (None, None)
-        assert parts is None or parts.dtype == torch.float32
-        assert gstat is None or (gstat.dtype == torch.float32 and gstat.numel() >= 6)
-        flat = [int(x) for spec in emb["specs"] for x in spec] if emb is not None else []
-        call("mst_adam_flat_ema", dt(w16), w.numel(), ptr(w), ptr(grad), ptr(m), ptr(v), ptr(w16), lr, beta1, beta2, eps, wd, rescale, clip,
-             ptr(step_state), C.byref(mt) if mt is not None else None, ptr(sched), emb.get("base", 0) if emb is not None else 0,
-             (_lib.c_i64 * len(flat))(*flat) if flat else None, len(flat) // 4, ptr(emb["wt16"]) if emb is not None else None,
-             ptr(parts), parts.numel() if parts is not None else 0, gnorm["max_norm"] if gnorm is not None else 0.0, ptr(gstat),
-             ptr(buf), ema["decay"], stream())
-        return
-    if gnorm is not None:
-        assert not advance_step and gnorm["parts"].dtype == torch.float32
-        gstat = gnorm.get("gstat")
-        assert gstat is None or (gstat.dtype == torch.float32 and gstat.numel() >= 6)
-        flat = [int(x) for spec in emb["specs"] for x in spec] if emb is not None else []
-        call("mst_adam_flat_gnorm", dt(w16), w.numel(), ptr(w), ptr(grad), ptr(m), ptr(v), ptr(w16), lr, beta1, beta2, eps, wd, rescale, clip,
-             ptr(step_state), C.byref(mt) if mt is not None else None, ptr(sched), emb.get("base", 0) if emb is not None else 0,
-             (_lib.c_i64 * len(flat))(*flat) if flat else None, len(flat) // 4, ptr(emb["wt16"]) if emb is not None else None,
-             ptr(gnorm["parts"]), gnorm["parts"].numel(), gnorm["max_norm"], ptr(gstat), stream())
-        return
-    if emb is not None:  # (the optimizer keeps the transposed shadows of these matrices current: mst_adam_flat_emb)
-        assert not advance_step
-        flat = [int(x) for spec in emb["specs"] for x in spec]
-        call("mst_adam_flat_emb" + ("_sched" if sched is not None else ""), dt(w16), w.numel(), ptr(w), ptr(grad), ptr(m), ptr(v), ptr(w16),
-             lr, beta1, beta2, eps, wd, rescale, clip, ptr(step_state), C.byref(mt) if mt is not None else None, *block, emb.get("base", 0),
-             (_lib.c_i64 * len(flat))(*flat), len(emb["specs"]), ptr(emb["wt16"]), stream())
-        return
-    if sched is not None:
-        call("mst_adam_flat_sched", dt(w16), w.numel(), ptr(w), ptr(grad), ptr(m), ptr(v), ptr(w16), lr, beta1, beta2, eps, wd,
-             rescale, clip, ptr(step_state), C.byref(mt) if mt is not None else None, *block, stream())
-        return
-    call("mst_adam_flat", dt(w16), w.numel(), ptr(w), ptr(grad), ptr(m), ptr(v), ptr(w16), lr, beta1, beta2, eps, wd,
-         rescale, clip, ptr(step_state), 1 if advance_step else 0, C.byref(mt) if mt is not None else None, stream())
+        q.ema, q.decay = ptr(buf), ema["decay"]
+    return q
+
+
+def adam_flat(*a, **kw):
+    """mst_adam_flat (arguments: _adam_args)"""
+    call("mst_adam_flat", C.byref(_adam_args(*a, **kw)), stream())
+
+
+def adam_flat_form(block=None, **kw):
+    """what adam_flat launches for these arguments — or for `block`, an AdamArgs (or the byref of one) as adam_flat hands it to the
+    library — (mst_adam_flat_form in include/mst_hip.h); no launch.
+    -> dict(sched, gnorm, ema (the kernel's three switches, 0/1), emb (matrices kept, 0..2), tick (0/1))"""
+    q = _adam_args(**kw) if block is None else getattr(block, "_obj", block)
+    form = (C.c_int64 * 5)()
+    call("mst_adam_flat_form", C.byref(q), form)
+    return dict(zip(("sched", "gnorm", "ema", "emb", "tick"), form))
 
 
 def grad_sumsq_parts():

@@ -30,7 +30,8 @@ def test_header_symbols_are_exported(lib):
 
 
 REMOVED = ["mst_gemm_wgrad", "mst_gemm_wgrad_batch", "mst_gemm_wgrad_batch_ws", "mst_gemm_wgrad_batch_sums", "mst_step_begin_v",
-           "mst_device_count"]
+           "mst_device_count", "mst_adam_flat_emb", "mst_adam_flat_sched", "mst_adam_flat_emb_sched", "mst_adam_flat_gnorm",
+           "mst_adam_flat_ema"]
 
 
 def test_exports_are_exactly_the_declarations(lib):
@@ -57,7 +58,7 @@ def test_struct_layouts_match_c(lib):
     binding's parser, which only supplies the names to ask about)"""
     import ctypes, subprocess, tempfile
     from musicstyletransfer_amd import _lib
-    assert len(_lib.STRUCTS) == 11
+    assert len(_lib.STRUCTS) == 12
     lines = []
     for cname, cls in _lib.STRUCTS.items():
         lines.append(f'printf("%zu\\n", sizeof({cname}));')
@@ -79,7 +80,7 @@ def test_struct_layouts_match_c(lib):
     assert n_fields >= 240 and next(got, None) is None
     # Python names the package, the tests and tools/ use
     for py in ("GemmArgs BceArgs RowTailArgs RowTailBwdArgs LnArgs LnBwdIn StepMetrics PartialSum StepBeginArgs OuterJob "
-               "WgradArgs").split():
+               "WgradArgs AdamArgs").split():
         assert getattr(_lib, py) in _lib.STRUCTS.values()
 
 
@@ -95,7 +96,8 @@ def test_parser_known_answers():
         "mst_graph_end": (ci, [vp, P(vp)]),
         "mst_gemm_nt_ln_parts": (i64, [i64]),
         "mst_layernorm_bwd_parts": (i64, [i64, i64]),
-        "mst_adam_flat": (ci, [ci, i64, vp, vp, vp, vp, vp, f64, f64, f64, f32, f32, f32, f32, vp, ci, P(_lib.StepMetrics), vp]),
+        "mst_adam_flat": (ci, [P(_lib.AdamArgs), vp]),
+        "mst_adam_flat_form": (ci, [P(_lib.AdamArgs), vp]),
         "mst_latent_rows": (ci, [ci, i64, i64, i64, i64, vp, vp, vp, vp, vp, ci, f32, u64, vp, u32, i64, vp, vp,
                                  vp, vp, vp, vp, i64, i64, vp, f32, vp, vp, i64, vp]),
         "mst_attn_decode": (ci, [ci, i64, i64, i64, i64, i64, vp, i64, i64, i64, i64, ci, vp, i64, vp]),

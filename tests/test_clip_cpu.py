@@ -1,5 +1,5 @@
 """Clipping by the global gradient norm on the host side: engine.clip_scale — the one host statement of the factor the device applies
-(mst_adam_flat_gnorm) —, the refused values, the flag, TrainConfig's YAML round trip, and the argument checks of the two entry points,
+(the clipping group of mst_adam_args) —, the refused values, the flag, TrainConfig's YAML round trip, and the argument checks of the two entry points,
 which happen before any HIP call."""
 import os
 import sys
@@ -100,14 +100,23 @@ def test_entry_points_reject_bad_arguments_before_any_hip_call():
     assert b"mst_grad_sumsq" in lib.mst_last_error()
     assert lib.mst_grad_sumsq(8, 20, 4, 1.0, 1.0, one, None) == -1 and b"aligned" in lib.mst_last_error()
 
-    def gnorm(parts=one, n_parts=G, max_norm=1.0):
-        return lib.mst_adam_flat_gnorm(_lib.MST_BF16, 8, one, one, one, one, None, 1e-3, 0.9, 0.999, 1e-8, 0.0, 1.0, -1.0, None, None, None, 0, None, 0,
-                                       None, parts, n_parts, max_norm, None, None)
+    def gnorm(parts=one, n_parts=G, max_norm=1.0, **kw):
+        q = _lib.AdamArgs(dtype=_lib.MST_BF16, n=8, w=one, grad=one, m=one, v=one, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, rescale=1.0, clip=-1.0,
+                          parts=parts, n_parts=n_parts, max_norm=max_norm, **kw)
+        return lib.mst_adam_flat(q, None)
 
     assert gnorm(parts=None) == -1 and b"parts" in lib.mst_last_error()
+    # the other fields of the group without parts are refused too, not ignored
+    assert gnorm(parts=None, n_parts=0) == -1 and b"parts" in lib.mst_last_error()  # (max_norm alone)
+    assert gnorm(parts=None, max_norm=0.0) == -1 and b"parts" in lib.mst_last_error()  # (n_parts alone)
+    assert gnorm(parts=None, n_parts=0, max_norm=0.0, gstat=one) == -1 and b"parts" in lib.mst_last_error()
     assert gnorm(n_parts=G - 1) == -1 and gnorm(n_parts=0) == -1 and b"mst_grad_sumsq_parts" in lib.mst_last_error()
     for bad in (0.0, -1.0, float("inf"), float("nan")):
         assert gnorm(max_norm=bad) == -1 and b"max_norm" in lib.mst_last_error(), bad
-    assert gnorm() == -1 and b"mst_adam_flat: bad argument" in lib.mst_last_error()  # (null step_state: the checks of mst_adam_flat follow)
+    assert gnorm(parts=20) == -1 and b"aligned" in lib.mst_last_error()
+    # the step count of a clipped launch is mst_step_begin's
+    assert gnorm(step_state=one, advance_step=1) == -1 and b"advance_step" in lib.mst_last_error()
+    assert gnorm() == -1 and b"mst_adam_flat: bad argument" in lib.mst_last_error()  # (null step_state: the launch's own checks follow)
+    assert lib.mst_adam_flat(None, None) == -1 and b"mst_adam_flat" in lib.mst_last_error()
     with pytest.raises(_lib.MstError):
         _lib.call("mst_grad_sumsq", 0, None, 0, 1.0, 1.0, None, None)

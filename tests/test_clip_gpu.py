@@ -93,7 +93,7 @@ def test_grad_sumsq_exact_and_repeatable(gpu):
 
 # ------------------------------------------------------------------------------------------ Adam launches: helpers
 LR, T0 = 1e-3, 5
-EMB = (64, 0, 10, 32)  # a [10, 32] matrix at flat offset 64 whose transposed shadow the launch keeps (mst_adam_flat_emb)
+EMB = (64, 0, 10, 32)  # a [10, 32] matrix at flat offset 64 whose transposed shadow the launch keeps (mst_adam_args.emb)
 
 
 def _problem(gpu, n, seed):
@@ -339,12 +339,12 @@ def test_whole_steps_off_path_call_list_nodes_and_replays(gpu, dtype):
     names = {k: _calls(o, lambda: p.step_kernels(True)) for k, p in (("off", p_off), ("zero", p_zero), ("on", p_on))}
     torch.cuda.synchronize()
     adam = [i for i, nm in enumerate(names["off"]) if nm.startswith("mst_adam_flat")]
-    assert names["off"] == names["zero"] and not any(nm in ("mst_grad_sumsq", "mst_adam_flat_gnorm") for nm in names["off"])
+    assert names["off"] == names["zero"] and not any(nm == "mst_grad_sumsq" or "+gnorm" in nm for nm in names["off"])
     assert len(adam) == (2 if two else 1) and adam == list(range(adam[0], adam[0] + len(adam)))
-    assert {names["off"][i] for i in adam} <= {"mst_adam_flat", "mst_adam_flat_emb"}
+    assert {names["off"][i] for i in adam} <= {"mst_adam_flat", "mst_adam_flat+emb"}
     want = list(names["off"])
     for i in adam:
-        want[i] = "mst_adam_flat_gnorm"
+        want[i] = names["off"][i] + "+gnorm"  # (the same launch otherwise: the matrices it keeps included)
     want.insert(adam[0], "mst_grad_sumsq")
     assert names["on"] == want
     assert "grad_norm" not in s_off.read_metrics(reset=False) and not s_off.gstat.any()

@@ -1,5 +1,5 @@
 """The exponential moving average of the weights on the host side: engine.ema_decay_at and engine.ema_update — the one host
-statement of what the Adam launch computes in its averaging form (mst_adam_flat_ema) —, the refused values, the flag, TrainConfig's YAML
+statement of what the Adam launch computes in its averaging form (mst_adam_args.ema) —, the refused values, the flag, TrainConfig's YAML
 round trip, the plan's hyper-parameters with the option off, and the argument checks of the two entry points, which happen before any
 HIP call."""
 import os
@@ -159,23 +159,27 @@ def test_off_leaves_the_plans_hyper_parameters_as_they_were():
 def test_entry_points_reject_bad_arguments_before_any_hip_call():
     from musicstyletransfer_amd import _lib
     lib = _lib.load()
-    assert lib.mst_version() >= 112  # 112: mst_adam_flat_ema, mst_ema_swap
+    assert lib.mst_version() >= 119  # 119: mst_adam_args; 112: mst_ema_swap
     G = lib.mst_grad_sumsq_parts()
     one = 16  # a non-NULL, 16-byte aligned stand-in: every call below is refused before anything is read
 
-    def adam(ema=one, decay=0.99, parts=None, n_parts=0, max_norm=0.0, state=None):
-        return lib.mst_adam_flat_ema(_lib.MST_BF16, 8, one, one, one, one, None, 1e-3, 0.9, 0.999, 1e-8, 0.0, 1.0, -1.0, state, None, None, 0, None,
-                                     0, None, parts, n_parts, max_norm, None, ema, decay, None)
+    def adam(ema=one, decay=0.99, parts=None, n_parts=0, max_norm=0.0, **kw):
+        q = _lib.AdamArgs(dtype=_lib.MST_BF16, n=8, w=one, grad=one, m=one, v=one, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, rescale=1.0, clip=-1.0,
+                          parts=parts, n_parts=n_parts, max_norm=max_norm, ema=ema, decay=decay, **kw)
+        return lib.mst_adam_flat(q, None)
 
     assert adam(ema=None) == -1 and b"ema" in lib.mst_last_error()
     assert adam(ema=20) == -1 and b"aligned" in lib.mst_last_error()
     for bad in (0.0, -0.5, 1.0, 2.0, float("inf"), float("nan")):
         assert adam(decay=bad) == -1 and b"decay" in lib.mst_last_error(), bad
-    # with parts, the checks of mst_adam_flat_gnorm; without, its three other arguments are ignored
+    assert adam(ema=None, decay=float("nan")) == -1 and b"ema" in lib.mst_last_error()
+    # with parts, the checks of the clipping group
     assert adam(parts=one, n_parts=G - 1, max_norm=1.0) == -1 and b"mst_grad_sumsq_parts" in lib.mst_last_error()
     assert adam(parts=one, n_parts=G, max_norm=0.0) == -1 and b"max_norm" in lib.mst_last_error()
     assert adam(parts=20, n_parts=G, max_norm=1.0) == -1 and b"aligned" in lib.mst_last_error()
-    assert adam() == -1 and b"mst_adam_flat: bad argument" in lib.mst_last_error()  # (null step_state: the checks of mst_adam_flat follow)
+    # the step count of an averaging launch is mst_step_begin's
+    assert adam(step_state=one, advance_step=1) == -1 and b"advance_step" in lib.mst_last_error()
+    assert adam() == -1 and b"mst_adam_flat: bad argument" in lib.mst_last_error()  # (null step_state: the launch's own checks follow)
     assert adam(parts=one, n_parts=G, max_norm=1.0) == -1 and b"mst_adam_flat: bad argument" in lib.mst_last_error()
 
     swap = lambda n=8, w=one, ema=32, w16=64: lib.mst_ema_swap(_lib.MST_BF16, n, w, ema, w16, None)

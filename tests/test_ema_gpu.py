@@ -26,7 +26,7 @@ SIZES = [1, 3, 1023, 256 * 1024 + 5, 2 ** 21 + 1027]
 DECAY = 0.99
 STEPS = (1, 7, 889, 890, 5000)  # t = 1, inside the warm-up, the last step below the crossing of 0.99, the crossing, far beyond
 LR, R = 1e-3, 1 / 32
-EMB = (64, 0, 10, 32)  # a [10, 32] matrix at flat offset 64 whose transposed shadow the launch keeps (mst_adam_flat_emb)
+EMB = (64, 0, 10, 32)  # a [10, 32] matrix at flat offset 64 whose transposed shadow the launch keeps (mst_adam_args.emb)
 FORMS = ("plain", "sched", "gnorm", "emb", "emb_sched_gnorm")
 
 
@@ -109,11 +109,9 @@ def test_adam_ema_is_the_existing_launch_plus_the_host_rule(gpu, n, dtype):
     p = _problem(gpu, n, 100 + n % 1000)
     parts, max_norm = _parts(o, p, gpu)
     e0 = p["ema"].cpu().numpy()
-    names = []
-    real = o.call
-    o.call = lambda name, *a: (names.append(name), real(name, *a))[1]
-    try:
-        steps = STEPS if n < 2 ** 20 else (1, 890)  # (the largest size is there for the second round, not for the rule)
+    steps = STEPS if n < 2 ** 20 else (1, 890)  # (the largest size is there for the second round, not for the rule)
+
+    def run():
         for form in FORMS:
             for t in steps:
                 a = _launch(o, p, _fresh(gpu, p, dtype, t), form, True, parts, max_norm)
@@ -128,11 +126,15 @@ def test_adam_ema_is_the_existing_launch_plus_the_host_rule(gpu, n, dtype):
                 assert (got != e0).any()
                 if "gnorm" in form:
                     assert 0.49 < a["gstat"][1].item() < 0.51  # (clipped: the factor went into the update on both sides)
-    finally:
-        o.call = real
-    # the comparison was between the new entry point and, per form, the existing one
-    assert set(names) == {"mst_adam_flat_ema", "mst_adam_flat", "mst_adam_flat_sched", "mst_adam_flat_gnorm", "mst_adam_flat_emb"}
-    assert names.count("mst_adam_flat_ema") == len(FORMS) * len(steps)
+
+    names = _calls(o, run)
+    # the comparison was, per form, between the launch with the average and the same launch without: the five of FORMS, each as often
+    labels = {"plain": "mst_adam_flat", "sched": "mst_adam_flat+sched", "gnorm": "mst_adam_flat+gnorm", "emb": "mst_adam_flat+emb",
+              "emb_sched_gnorm": "mst_adam_flat+emb+sched+gnorm"}
+    assert [nm for nm in names if nm.startswith("mst_adam_flat")] == [
+        labels[form] + tail for form in FORMS for t in steps for tail in ("+ema", "")]
+    assert {nm for nm in names if "+ema" not in nm} == {labels[form] for form in FORMS}
+    assert sum("+ema" in nm for nm in names) == len(FORMS) * len(steps)
     assert float(E.ema_decay_at(889, DECAY)) < float(E.ema_decay_at(890, DECAY)) == float(np.float32(DECAY))
 
 
@@ -278,12 +280,15 @@ def test_whole_steps_training_untouched_recurrence_eager_and_nodes(gpu, dtype, e
     names = {k: _calls(o, lambda: p.step_kernels(True)) for k, p in (("off", p_off), ("zero", p_zero), ("on", p_on))}
     torch.cuda.synchronize()
     adam = [i for i, nm in enumerate(names["off"]) if nm.startswith("mst_adam_flat")]
-    assert names["off"] == names["zero"] and not any(nm in ("mst_adam_flat_ema", "mst_ema_swap") for nm in names["off"])
+    assert names["off"] == names["zero"] and not any("+ema" in nm or nm == "mst_ema_swap" for nm in names["off"])
     assert len(adam) == (2 if two else 1) and adam == list(range(adam[0], adam[0] + len(adam)))
-    assert {names["off"][i] for i in adam} <= ({"mst_adam_flat_gnorm"} if extra else {"mst_adam_flat", "mst_adam_flat_emb"})
+    if extra:  # clipped in every range, scheduled where the bookkeeping is: the first
+        assert [names["off"][i].replace("+emb", "") for i in adam] == ["mst_adam_flat+sched+gnorm", "mst_adam_flat+gnorm"][: len(adam)]
+    else:
+        assert {names["off"][i] for i in adam} <= {"mst_adam_flat", "mst_adam_flat+emb"}
     want = list(names["off"])
     for i in adam:
-        want[i] = "mst_adam_flat_ema"
+        want[i] = names["off"][i] + "+ema"  # (the same launch otherwise)
     assert names["on"] == want
     assert set(p_off.metrics(reset=False)) == set(p_on.metrics(reset=False))
     for s, was in saved:

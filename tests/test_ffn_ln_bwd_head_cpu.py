@@ -63,7 +63,7 @@ def test_abi_116_exports_the_launch_and_its_form_query(lib):
     g, q, l = (C.POINTER(_lib.STRUCTS[n]) for n in ("mst_gemm_args", "mst_ln_bwd_in", "mst_ln_args"))
     assert _lib.SIGNATURES["mst_kqv_ffn_ln_bwd"] == (C.c_int, [g, q, g, g, l, C.c_void_p])
     assert _lib.SIGNATURES["mst_kqv_ffn_ln_bwd_form"] == (C.c_int, [g, g, g, C.c_void_p])
-    assert len(_lib.STRUCTS) == 11  # (the head is an mst_gemm_args: no new struct)
+    assert len(_lib.STRUCTS) == 12  # (the head is an mst_gemm_args: no new struct; the twelfth is ABI 119's mst_adam_args)
 
 
 def _mut(**fields):

@@ -52,10 +52,24 @@ def _restore(store, saved):
         t.copy_(s)
 
 
+def _label(o, name, args):
+    """an entry point as the call lists name it: mst_adam_flat with what the block it was handed switches on (ops.adam_flat_form)"""
+    if name != "mst_adam_flat":
+        return name
+    form = o.adam_flat_form(args[0])
+    return name + "".join("+" + k for k in ("emb", "sched", "gnorm", "ema") if form[k])
+
+
 def _calls(o, fn):
-    """names of the C-ABI entry points fn() goes through, in order"""
+    """names of the C-ABI entry points fn() goes through, in order (_label)"""
     names, real = [], o.call
-    o.call = lambda name, *a: (names.append(name), real(name, *a))[1]
+
+    def call(name, *a):
+        if name != "mst_adam_flat_form":  # (_label's own question)
+            names.append(_label(o, name, a))
+        return real(name, *a)
+
+    o.call = call
     try:
         fn()
     finally:
@@ -352,15 +366,19 @@ def test_defaults_resolve_to_the_plain_launches(gpu):
         plan.step_kernels(True)
         torch.cuda.synchronize()
     assert torch.equal(sa.w, sb.w) and torch.equal(sa.m, sb.m) and torch.equal(sa.v, sb.v) and torch.equal(pa.kl, pb.kl)
-    assert names["a"] == names["b"] and not any(n.endswith("_sched") for n in names["a"])
+    scheduled = lambda n: n.endswith("_sched") or "+sched" in n  # (the latent backward by its name, Adam by its label)
+    plain = lambda n: n[: -len("_sched")] if n.endswith("_sched") else n.replace("+sched", "")
+    assert names["a"] == names["b"] and not any(scheduled(n) for n in names["a"])
     assert not sb.sched.any() and "kl_weight" not in sb.read_metrics(reset=False)  # nothing wrote the block
     assert pb.metrics(reset=False)["kl_weight"] == 0.5 and pb.metrics(reset=False)["lr_scale"] == 1.0
     # the scheduled step adds no launch: the same entry points in the same order, two of them in their scheduled form (each issues
     # the launches of its unscheduled sibling)
-    plain = [n[: -len("_sched")] if n.endswith("_sched") else n for n in names["c"]]
-    assert plain == names["a"] and sorted(n for n in names["c"] if n.endswith("_sched")) == sorted(
-        n + "_sched" for n in names["a"] if n.startswith("mst_latent_bwd_vec") or n.startswith("mst_adam_flat"))
-    assert len([n for n in names["c"] if n.endswith("_sched")]) == 2
+    assert [plain(n) for n in names["c"]] == names["a"]
+    assert [plain(n) for n in names["c"] if scheduled(n)] == [
+        n for n in names["a"] if n.startswith("mst_latent_bwd_vec") or n.startswith("mst_adam_flat")]
+    two = [n for n in names["c"] if scheduled(n)]
+    assert len(two) == 2 and two[0].startswith("mst_latent_bwd_vec") and two[0].endswith("_sched")
+    assert two[1].startswith("mst_adam_flat+") and two[1].endswith("+sched") and sum(n.startswith("mst_adam_flat") for n in names["c"]) == 1
     # ... and the captured graphs say the same of the launches themselves: as many nodes, as many kernel launches among them
     torch.cuda.synchronize()
     with torch.cuda.stream(torch.cuda.Stream()):  # (the legacy default stream cannot be captured)

@@ -647,7 +647,7 @@ def test_a_step_with_a_non_finite_loss_leaves_the_model_alone(gpu):
 
 
 def test_deferred_shadow_refresh_matches_the_separate_launch(gpu):
-    """Piano-roll ends: the optimizer launch keeps the two embedding tables' transposed shadows current (mst_adam_flat_emb) and the NEXT
+    """Piano-roll ends: the optimizer launch keeps the two embedding tables' transposed shadows current (mst_adam_args.emb) and the NEXT
     step's first launch rebuilds the backward-only ones (mst_gemm_nt_pair_begin, sh_*): after the optimizer the embedding shadows
     equal the weights, after the next forward pass all of them do — and the run equals one with the separate refresh launch."""
     O, E, ocfg, ecfg, params, batch, eps = _setup("pianoroll", (48, 48, 2, 16, 64, 2, 2, 32, 1, 2), 4, 16, 61)

@@ -4,7 +4,7 @@ alternating the two in rounds, HIP events around every replay. Prints one JSON l
     python tools/bench_ema.py [--config 1] [--steps 200] [--warmup 20] [--rounds 4] [--decay 0.999]
 
 Same inputs, weights, dropout and step options as bench.py's resident-data run of that config. "on" issues the same launches in the same
-order, with the optimizer launch(es) in the averaging form (mst_adam_flat_ema: one more fp32 read and one more fp32 write of the bucket;
+order, with the optimizer launch(es) in the averaging form (mst_adam_args.ema: one more fp32 read and one more fp32 write of the bucket;
 DESIGN §13). For a kernel timeline of either step run one mode alone under a kernel trace (--modes on --rounds 1) and read it with
 tools/step_timeline.py."""
 import argparse
