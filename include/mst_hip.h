@@ -662,6 +662,21 @@ int mst_latent_bwd_vec_proj_sched(int dtype, int64_t B, int64_t De, int64_t Z, i
  * projection of a width the backward one does not take: form[5] stays as the caller left it). */
 int mst_latent_form(int64_t De, int64_t Z, int64_t Dd, int64_t nq, const void* Wl, int64_t* form);
 
+/* Per-dimension statistics of the posterior (ABI 120): what the logs need to tell "a few dimensions carry everything" from "every
+ * dimension carries a little", and whether z separates the classes. mu, sigma: fp32 [B, ld >= Z] as mst_latent_fwd leaves them;
+ * classes int32 [B]; acc: double [C][5][Z], ADDED to by every launch. Plane k of class c, dimension d, over the counted samples b
+ * with classes[b] == c:
+ *   0: n (the number of terms)   1: sum mu   2: sum mu^2   3: sum sigma^2   4: sum kl_d, kl_d = 0.5 * (sigma^2 + mu^2 - 1 - log(sigma^2))
+ * fp64 arithmetic on the fp32 values widened (loss.py:8-12 per element, no epsilon). A (sample, dimension) term whose mu or sigma is
+ * not finite, or whose sigma == 0, is in none of the five planes; neither is a sample whose class is outside [0, C) (the class is
+ * compared, never used as an index). Every cell of acc is owned by one thread — (class, plane, dimension), consecutive threads on
+ * consecutive dimensions — which adds its column's terms in ascending batch order from zero, then adds that sum to the cell: no
+ * atomics, nothing summed across threads, so launches ordered on one stream give the same bits every time. (The terms themselves, an
+ * fp64 logarithm each, are evaluated by the whole workgroup, 64 rows x 16 dimensions at a time through LDS.) Classes go four at a
+ * time; C > 4 takes more passes over the batch. Grid cdiv(Z, 16), 1024 threads. */
+int mst_latent_dim_stats(int64_t B, int64_t Z, int64_t C, const float* mu, int64_t ld_mu, const float* sigma, int64_t ld_sigma,
+                         const int32_t* classes, double* acc, mst_stream_t stream);
+
 /* standalone reparameterisation + KL (loss.VariationalKLLoss, loss.py:4-12; model.py:292) */
 int mst_reparam_kl_fwd(int64_t B, int64_t Z, const float* mu, const float* sigma, const float* eps,
                        float* z, float* kl, mst_stream_t stream);

@@ -3,7 +3,7 @@
 The flag set is the reference's, name for name and default for default (config.py:19-70), because
 scripts/train-vae.sh passes them; unknown flags are ignored as there (parse_known_args, :73-75). The flags
 are declared as a table. The additions (group MI355X) are all off by default: --pianoroll (attach the piano-roll ends), --dtype,
---d-causal, the training schedules, --clip-global-norm, --ema-decay and --d-input-dropout."""
+--d-causal, the training schedules, --clip-global-norm, --ema-decay, --d-input-dropout and --latent-stats."""
 import argparse
 import copy
 import inspect
@@ -78,6 +78,10 @@ _FLAGS = [
     # on the device inside the captured step (include/mst_hip.h: mst_step_begin_args.in_*): the decoder has to go through the latent —
     # the third remedy for posterior collapse beside the KL warm-up and free bits. In [0, 1]; 0: off. Validation and sampling never drop.
     ("MI355X", ("--d-input-dropout",), dict(type=float, default=0.0)),
+    # per-dimension statistics of the posterior, summed on the device by one more launch of the captured step (include/mst_hip.h:
+    # mst_latent_dim_stats) and read with the other running sums: the log lines, the scalar log and the validation line gain
+    # active_units, kl_dims_used, kl_dim_max, sigma_rms and class_leak (engine.latent_scores). Off: the step and its metrics as before.
+    ("MI355X", ("--latent-stats",), dict(action="store_true")),
 ]
 
 

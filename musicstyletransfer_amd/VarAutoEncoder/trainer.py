@@ -18,7 +18,7 @@ import torch
 from . import utils
 from .config import Config
 from .. import parallel
-from ..engine import check_clip, check_ema, check_input_dropout, check_schedule, roll_scores
+from ..engine import check_clip, check_ema, check_input_dropout, check_schedule, latent_scores, roll_scores
 from ..pianoroll import PinnedBatchPipeline
 
 
@@ -44,13 +44,15 @@ class TrainConfig(Config):
     stopping and the periodic samples then use; 0: off.
     d_input_dropout: probability that a training step hides a decoder input position from the teacher-forced decoder
     (engine.check_input_dropout; include/mst_hip.h: mst_step_begin_args.in_*), in [0, 1]; 0: off. Validation never drops.
+    latent_stats: the steps keep per-class, per-dimension sums of the posterior's mu, sigma and KL on the device, and the metrics gain
+    active_units, kl_dims_used, kl_dim_max, sigma_rms and class_leak (engine.latent_scores); False: off.
     YAML-serialisable (Config): a file written before a field existed loads with that field's default."""
 
     def __init__(self, batch_size: int, sampling_frequency: int, checkpoint_frequency: int, num_checkpoints_not_improved: int,
                  optimizer: OptimizerConfig, kl_loss: float, label_smoothing: float, negative_label_downscaling: bool,
                  verbose: bool, dtype: str = "bf16", max_steps: int = 0, kl_warmup_steps: int = 0, kl_cycle_steps: int = 0,
                  kl_free_bits: float = 0.0, lr_warmup_steps: int = 0, clip_global_norm: float = 0.0, ema_decay: float = 0.0,
-                 d_input_dropout: float = 0.0):
+                 d_input_dropout: float = 0.0, latent_stats: bool = False):
         super().__init__()
         check_schedule(kl_warmup_steps, kl_cycle_steps, kl_free_bits, lr_warmup_steps)
         check_clip(clip_global_norm)
@@ -59,6 +61,7 @@ class TrainConfig(Config):
         self.ema_decay = ema_decay
         check_input_dropout(d_input_dropout)
         self.d_input_dropout = d_input_dropout
+        self.latent_stats = bool(latent_stats)
         self.kl_warmup_steps, self.kl_cycle_steps = kl_warmup_steps, kl_cycle_steps
         self.kl_free_bits, self.lr_warmup_steps = kl_free_bits, lr_warmup_steps
         self.batch_size = batch_size
@@ -161,6 +164,9 @@ class Trainer:
             if self.rank == 0:
                 print("Decoder-input dropout: a training step hides each decoder input position with probability {}".format(
                     self.d_input_dropout))
+        # ... and the per-dimension latent statistics (not a hyper-parameter: a flag of the plan, set in _plan)
+        self.latent_stats = bool(getattr(self.config, "latent_stats", False))
+        self.last_latent_stats = None  # engine.latent_scores of the latest collect_metrics()
         self.opt_extra = {k: v for k, v in extra.items() if k in ("beta1", "beta2", "epsilon", "wd")}
 
     # ------------------------------------------------------------------ the hot loop
@@ -176,6 +182,7 @@ class Trainer:
                     plan.opt[dst] = self.opt_extra[src]
             plan.track_token_metrics = plan.cfg.kind == "token"  # ppl / acc / topk sums ride on the CE launch
             plan.track_roll_metrics = plan.cfg.kind == "pianoroll"  # tp / pred / pos / cells counts ride on the BCE launch
+            plan.track_latent_stats = self.latent_stats  # per-dimension sums of mu / sigma / KL: one launch behind the latent block's
             plan._trainer_set = True
         return plan
 
@@ -289,7 +296,9 @@ class Trainer:
         of the last training step, from the device schedule block in the same read (the configured constants without schedules;
         computed per rank from the same step count, so there is nothing to reduce). With clip_global_norm on, also grad_norm (the mean
         gradient norm before clipping over those steps), grad_norm_max and clip_frac: taken from the all-reduced bucket, the same on
-        every rank, so nothing to reduce either."""
+        every rank, so nothing to reduce either. With latent_stats on, also active_units, kl_dims_used, kl_dim_max, sigma_rms and
+        class_leak (engine.latent_scores of the per-class, per-dimension sums the steps keep, summed over the ranks with the rest);
+        the whole dict of that read, the per-dimension KL included, stays in last_latent_stats."""
         failure = None
         with torch.cuda.stream(self.stream):  # ordered behind every step launched so far
             try:
@@ -304,15 +313,19 @@ class Trainer:
         gnorm = {k: m[k] for k in ("grad_norm", "grad_norm_max", "clip_frac") if k in m} if self.clip_global_norm > 0 else {}
         keys = [k for k in ("kl_sum", "total_sum", "count", "nll_sum", "acc_hits", "topk_hits", "n_tokens", "roll_tp", "roll_pred", "roll_pos",
                             "roll_cells") if k in m]  # (the counts: float64 is exact far beyond any run's)
+        lat = m["lat_stats"] if self.latent_stats else None  # fp64 [classes, 5, Z] sums: they add over the ranks like the rest
         if self.dist is not None:
             with torch.cuda.stream(self.stream):
-                t = torch.tensor([m[k] for k in keys] + [1.0 if failure is not None else 0.0], dtype=torch.float64,
-                                 device=self.model.store.device)
+                t = torch.tensor([m[k] for k in keys] + [1.0 if failure is not None else 0.0] + (lat.ravel().tolist() if lat is not None else []),
+                                 dtype=torch.float64, device=self.model.store.device)
                 self.dist.all_reduce(t)
                 vals = t.tolist()
-                m = dict(zip(keys, vals[:-1]))
-            if vals[-1] > 0:
-                raise RuntimeError(f"{int(vals[-1])} rank(s) skipped optimizer steps after a failed position-0 tail; the replicas "
+                m = dict(zip(keys, vals))
+                failed = vals[len(keys)]
+                if lat is not None:
+                    lat = np.asarray(vals[len(keys) + 1:], np.float64).reshape(lat.shape)
+            if failed > 0:
+                raise RuntimeError(f"{int(failed)} rank(s) skipped optimizer steps after a failed position-0 tail; the replicas "
                                    "are no longer identical — restart from the last checkpoint with MST_ROW_TAIL=0"
                                    + (f" (this rank: {failure})" if failure is not None else ""))
         out = {}
@@ -328,6 +341,9 @@ class Trainer:
         out["total_loss"] = m["total_sum"] / n
         out["kl_weight"], out["lr_scale"] = kl_weight, lr_scale
         out.update(gnorm)
+        if lat is not None:
+            self.last_latent_stats = latent_scores(lat)
+            out.update({k: self.last_latent_stats[k] for k in ("active_units", "kl_dims_used", "kl_dim_max", "sigma_rms", "class_leak")})
         return out
 
     def _metric_to_string_output(self, n_batches):

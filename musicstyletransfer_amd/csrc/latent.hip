@@ -315,6 +315,86 @@ __global__ __launch_bounds__(256) void class_table_grad_kernel(int64_t B, int Dd
   class_table_block((int)blockIdx.x, threadIdx.x, B, Dd, tvec, classes, dcls, ld_cls);
 }
 
+// Per-dimension statistics of the posterior (mst_latent_dim_stats): acc[c][k][d] += over the samples b of class c of
+// {1, mu, mu^2, sigma^2, kl_d}[k] at dimension d, fp64 on the fp32 values widened. Every cell of acc is OWNED by one thread, which
+// adds its column's terms in ascending batch order from zero and then adds that sum to the cell: nothing is summed across threads
+// and there is no atomic, so the same inputs give the same bits. A workgroup holds LS_DIMS dimensions. Its owners are waves 0..4,
+// one plane each (the plane is wave-uniform: one LDS array per wave), a lane being (class slot lane / 16, dimension lane % 16): the
+// classes go LS_CLS at a time, selected by compare (x + 0 is exact), never used as an index; more classes take more passes.
+// The TERMS are everybody's work: an fp64 log is ~100 instructions at half rate, and with one thread per dimension doing all of it
+// the launch was one wave issuing for 35 us at configs[1] (B = 64, Z = 64, C = 2). So a tile of LS_TILE rows x LS_DIMS
+// dimensions is evaluated one term per thread into LDS (mu, sigma, kl_d; NaN for a term that does not count), then the owners add
+// it row by row. The next tile's loads are requested before the current tile is added.
+constexpr int LS_DIMS = 16, LS_TILE = 64, LS_THREADS = LS_DIMS * LS_TILE, LS_CLS = 4, LS_PLANES = 5;
+static_assert(LS_CLS * LS_DIMS == 64 && LS_THREADS >= 64 * LS_PLANES, "an owner wave is LS_CLS class slots x LS_DIMS dimensions");
+__global__ __launch_bounds__(LS_THREADS) void latent_dim_stats_kernel(int64_t B, int Z, int C, const float* __restrict__ mu, int64_t ld_mu,
+                                                                      const float* __restrict__ sigma, int64_t ld_sigma,
+                                                                      const int32_t* __restrict__ classes, double* __restrict__ acc) {
+  __shared__ double s_kl[LS_TILE][LS_DIMS];
+  __shared__ float s_mu[LS_TILE][LS_DIMS], s_sg[LS_TILE][LS_DIMS];
+  __shared__ int s_cl[LS_TILE];
+  const int tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // both roles of a thread see the same dimension: tid % 16 (term: row tid / 16 of the tile; owner: class slot (tid % 64) / 16)
+  const int dl = tid & (LS_DIMS - 1), d = blockIdx.x * LS_DIMS + dl, tr = tid / LS_DIMS, q = (tid & 63) / LS_DIMS;
+  const bool col = d < Z;
+  const float fnan = __builtin_nanf("");
+  float pm, ps;
+  int pc;
+  // (a row past the batch, or a column past Z: NaN, never loaded)
+  auto load = [&](int64_t t0) {
+    const int64_t b = t0 + tr;
+    const bool in = b < B;
+    pm = in && col ? mu[b * ld_mu + d] : fnan;
+    ps = in && col ? sigma[b * ld_sigma + d] : fnan;
+    pc = in ? classes[b] : -1;
+  };
+  for (int c0 = 0; c0 < C; c0 += LS_CLS) {
+    const int c = c0 + q;  // the owner's class (>= 0; a sample's class is compared with it)
+    const bool owner = w < LS_PLANES && col && c < C;
+    double* cell = acc + ((int64_t)c * LS_PLANES + w) * Z + d;
+    const double old = owner ? *cell : 0.0;  // (read now, written once at the end)
+    double sum = 0.0;
+    load(0);
+    for (int64_t t0 = 0; t0 < B; t0 += LS_TILE) {
+      {
+        // a term with a non-finite mu or sigma or sigma == 0 is in none of the five sums: NaN in all three arrays
+        const bool ok = isfinite(pm) && isfinite(ps) && ps != 0.f;
+        const double m = (double)pm, s = (double)ps;
+        const double s2 = s * s;                                // (exact: 24-bit factors)
+        const double kl = 0.5 * (s2 + m * m - 1.0 - log(s2));  // loss.py:8-12 per element
+        s_mu[tr][dl] = ok ? pm : fnan;
+        s_sg[tr][dl] = ok ? ps : fnan;
+        s_kl[tr][dl] = ok ? kl : (double)fnan;
+        if (dl == 0) s_cl[tr] = pc;
+      }
+      if (t0 + LS_TILE < B) load(t0 + LS_TILE);
+      __syncthreads();
+      if (w < LS_PLANES) {
+        auto add = [&](auto plane) {
+          constexpr int K = decltype(plane)::value;
+#pragma unroll 8
+          for (int r = 0; r < LS_TILE; ++r) {  // rows in batch order
+            double v;
+            if constexpr (K == 4) v = s_kl[r][dl];
+            else if constexpr (K == 3) { const double s = (double)s_sg[r][dl]; v = s * s; }
+            else { const double m = (double)s_mu[r][dl]; v = K == 2 ? m * m : m; }
+            const bool on = v == v && s_cl[r] == c;  // (a class outside [0, C) meets no owner that writes)
+            if constexpr (K == 0) v = 1.0;
+            sum += on ? v : 0.0;
+          }
+        };
+        if (w == 0) add(std::integral_constant<int, 0>{});
+        else if (w == 1) add(std::integral_constant<int, 1>{});
+        else if (w == 2) add(std::integral_constant<int, 2>{});
+        else if (w == 3) add(std::integral_constant<int, 3>{});
+        else add(std::integral_constant<int, 4>{});
+      }
+      __syncthreads();
+    }
+    if (owner) *cell = old + sum;
+  }
+}
+
 }  // namespace mst
 
 using namespace mst;
@@ -492,6 +572,18 @@ extern "C" int mst_class_table_grad(const int32_t* classes, const float* tvec, f
   hipLaunchKernelGGL(class_table_grad_kernel, dim3((unsigned)c.wgs), dim3(256), 0, (hipStream_t)stream, c.B, c.Dd, c.tvec, c.classes, c.dcls,
                      c.ld_cls);
   MST_CHECK_LAUNCH("class_table_grad_kernel");
+  return MST_OK;
+}
+
+extern "C" int mst_latent_dim_stats(int64_t B, int64_t Z, int64_t C, const float* mu, int64_t ld_mu, const float* sigma, int64_t ld_sigma,
+                                    const int32_t* classes, double* acc, mst_stream_t stream) {
+  MST_CHECK_ARG(B > 0 && Z > 0 && C > 0 && Z < (1ll << 30) && C < (1ll << 30),
+                "mst_latent_dim_stats: B, Z and C must be positive (Z and C below 2^30)");
+  MST_CHECK_ARG(ld_mu >= Z && ld_sigma >= Z, "mst_latent_dim_stats: ld_mu / ld_sigma < Z");
+  MST_CHECK_ARG(mu && sigma && classes && acc, "mst_latent_dim_stats: null pointer");
+  hipLaunchKernelGGL(latent_dim_stats_kernel, dim3((unsigned)cdiv(Z, LS_DIMS)), dim3(LS_THREADS), 0, (hipStream_t)stream, B, (int)Z, (int)C, mu,
+                     ld_mu, sigma, ld_sigma, classes, acc);
+  MST_CHECK_LAUNCH("latent_dim_stats_kernel");
   return MST_OK;
 }
 

@@ -233,6 +233,8 @@ class ParamStore:
         self.tok_parts = torch.zeros(CE_MAX_WORKGROUPS, 4, **f32) if cfg.kind == "token" else None
         # roll_counts = the piano-roll ends' slots of {tp, pred, pos, cells} the BCE launches add to (mst_bce_args.counts)
         self.roll_counts = torch.zeros(ROLL_SLOTS, 4, dtype=torch.int64, device=device) if cfg.kind == "pianoroll" else None
+        # lat_stats = per class and latent dimension {n, sum mu, sum mu^2, sum sigma^2, sum kl_d} (mst_latent_dim_stats; latent_scores)
+        self.lat_stats = torch.zeros(cfg.num_classes, 5, cfg.latent_dim, dtype=torch.float64, device=device)
         if params_np is None:
             params_np = xavier_init(cfg, np.random.default_rng(seed))
         self.load_numpy(params_np)
@@ -380,7 +382,9 @@ class ParamStore:
         if self.roll_counts is not None:
             c = self.roll_counts.cpu().sum(0).tolist()
             out.update(roll_tp=int(c[0]), roll_pred=int(c[1]), roll_pos=int(c[2]), roll_cells=int(c[3]))
+        out["lat_stats"] = self.lat_stats.cpu().numpy()  # (all zero unless a plan with track_latent_stats ran; latent_scores)
         if reset:
+            o.zero(self.lat_stats)
             o.zero(self.metric_acc)
             if g_steps > 0:
                 o.zero(self.gstat[2:6])
@@ -784,6 +788,41 @@ def roll_scores(tp, pred, pos, cells):
                 cell_acc=(cells - pred - pos + 2 * tp) / cells if cells else nan)
 
 
+def latent_scores(acc, threshold=0.01):
+    """the per-class, per-dimension sums of ParamStore.read_metrics' 'lat_stats' (fp64 [C, 5, Z], planes {n, sum mu, sum mu^2,
+    sum sigma^2, sum kl_d}: mst_latent_dim_stats) as scores. Per dimension d, pooled over the classes: n, m = sum mu / n,
+    V = sum mu^2 / n - m^2 (the variance of the posterior mean over the data).
+      active_units  number of dimensions with V > threshold (Burda et al.'s 0.01)
+      kl_dims       [Z] mean KL of each dimension, sum kl_d / n
+      kl_dim_max    the largest of kl_dims
+      kl_dims_used  number of dimensions with mean KL > threshold
+      sigma_rms     sqrt(mean over d of sum sigma^2 / n)
+      class_leak    max over the active dimensions of eta^2_d = sum_c (n_c / n) (m_cd - m_d)^2 / V_d, the share of a dimension's variance
+                    that lies BETWEEN the classes (0: z says nothing about the class; 1: the class alone decides mu_d). NaN without an
+                    active dimension, or when fewer than two classes have samples.
+    A dimension with n == 0 has NaN entries and is not active (kl_dim_max and sigma_rms are taken over the dimensions with samples)."""
+    acc = np.asarray(acc, np.float64)
+    if acc.ndim != 3 or acc.shape[1] != 5:
+        raise ValueError(f"latent_scores takes [C, 5, Z] sums, not {acc.shape}")
+    nan = float("nan")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        n_c = acc[:, 0]                                   # [C, Z]
+        n, s_mu, s_mu2, s_s2, s_kl = acc.sum(0)           # [Z] each
+        m = s_mu / n
+        var = s_mu2 / n - m * m
+        kl_dims = s_kl / n
+        active = var > threshold                          # (NaN compares false)
+        m_c = acc[:, 1] / n_c                             # [C, Z]; NaN for a class without samples: its weight below is 0
+        between = np.where(n_c > 0, n_c / n * (m_c - m) ** 2, 0.0).sum(0)
+        eta2 = np.minimum(between / var, 1.0)             # (between <= V; the two are rounded apart)
+    seen = n > 0
+    classes_seen = int((n_c.sum(1) > 0).sum())
+    leak = float(eta2[active].max()) if active.any() and classes_seen >= 2 else nan
+    return dict(active_units=int(active.sum()), kl_dims=kl_dims, kl_dim_max=float(kl_dims[seen].max()) if seen.any() else nan,
+                kl_dims_used=int((kl_dims > threshold).sum()),
+                sigma_rms=float(np.sqrt((s_s2[seen] / n[seen]).mean())) if seen.any() else nan, class_leak=leak)
+
+
 def check_schedule(kl_warmup_steps=0, kl_cycle_steps=0, kl_free_bits=0.0, lr_warmup_steps=0):
     """the combinations of training-schedule settings that mean something; raises ValueError otherwise"""
     for name, val in (("kl_warmup_steps", kl_warmup_steps), ("kl_cycle_steps", kl_cycle_steps), ("lr_warmup_steps", lr_warmup_steps)):
@@ -1003,7 +1042,10 @@ class StepPlan:
         self.metric_acc = store.metric_acc  # [sum kl, sum total, count]  (trainer.py:115-116)
         self.track_token_metrics = False  # Trainer: accumulate ppl / acc / topk sums on the device in the CE launch
         self.track_roll_metrics = False   # Trainer: count tp / pred / pos / cells on the device in whichever launch computes the BCE
-        self.logits = None if self.forms.fuse_bce else act(B * T, cfg.out_dim)  # (fused: the logits never reach HBM)
+        # Trainer: one launch behind the latent block's adds the batch's per-class, per-dimension sums of mu, mu^2, sigma^2 and kl_d to
+        # store.lat_stats (training steps and validation forwards, never inference; not undone by the step guards, as roll_counts)
+        self.track_latent_stats = False
+        self.logits =None if self.forms.fuse_bce else act(B * T, cfg.out_dim)  # (fused: the logits never reach HBM)
         self.dlogits = act(B * T, cfg.out_dim)
         if cfg.kind == "token":
             self.probs = torch.zeros(B * T, cfg.out_dim, **f32) if want_probs else None
@@ -1391,6 +1433,8 @@ class StepPlan:
             Pd = st.layer("decoder", 0)
             proj0 = (Pd.kqv.w, Pd.kqv.b, self.dec[0].qkv.view(B, Sd, -1))
         o.latent_fwd(*lat, proj=proj0)
+        if self.track_latent_stats and not self._infer:
+            o.latent_dim_stats(self.mu, self.sigma, self.classes, st.lat_stats)
         if upto == "latent":
             return
         # ---- decoder positions 1..T (model.py:241-245, transformer.py:237)

@@ -834,6 +834,18 @@ def latent_form(De, Z, Dd, nq=0, Wl=0, part=None):
     return dict(zip(names[5:], form[5:8])) if part == "bwd" else dict(zip(names, form))
 
 
+LAT_STAT_PLANES = ("n", "mu", "mu2", "sigma2", "kl")  # planes of latent_dim_stats' accumulator, in order
+
+
+def latent_dim_stats(mu, sigma, classes, acc):
+    """acc (fp64 [C, 5, Z], contiguous) += per class and dimension {n, sum mu, sum mu^2, sum sigma^2, sum kl_d} of this batch
+    (mst_latent_dim_stats): mu, sigma fp32 [B, Z] views (rows may be padded), classes int32 [B]"""
+    B, Z = mu.shape
+    assert mu.dtype == sigma.dtype == torch.float32 and sigma.shape == mu.shape and classes.dtype == torch.int32 and classes.numel() == B
+    assert acc.dtype == torch.float64 and acc.is_contiguous() and acc.dim() == 3 and acc.shape[1:] == (len(LAT_STAT_PLANES), Z)
+    call("mst_latent_dim_stats", B, Z, acc.shape[0], ptr(mu), ld(mu), ptr(sigma), ld(sigma), ptr(classes), ptr(acc), stream())
+
+
 LATENT_ROWS_SITE = 0x7FFE0000  # the generator's eps stream (the training step's eps site is 0x7FFF0000)
 INTERP = {"lerp": 0, "slerp": 1}
 

@@ -5,6 +5,8 @@
 # (e.g. --pianoroll, --max-steps 200, --dtype fp16).
 #   --d-input-dropout P   hide each decoder input position (the previous frame / token) with probability P in training steps, so the
 #                         decoder has to use the latent (against posterior collapse, beside --kl-warmup-steps / --kl-free-bits); 0: off
+#   --latent-stats        log per-dimension statistics of the posterior, summed on the device inside the step: active_units,
+#                         kl_dims_used, kl_dim_max, sigma_rms and class_leak (how much of z's variation is between the classes)
 cd "$(dirname "$0")/.." || exit 1
 
 python -m music_style_transfer.VarAutoEncoder.main \
