@@ -399,7 +399,9 @@ int mst_embed_fwd(int dtype, int64_t B, int64_t T, int64_t D,
                   uint8_t* keymask, const uint8_t* keep, mst_stream_t stream);
 
 /* scatter-add of alpha*dX rows into dtable (fp32, accumulated) and dcls (fp32, accumulated). keep (as above, or NULL): a dropped
- * position adds nothing to dtable; dcls gets every row either way. */
+ * position adds nothing to dtable; dcls gets every row either way. With dcls the column sums are mst_group_colsum's, and its
+ * checks (D a multiple of 8, ...) are made with this call's own before the first launch: a refused call adds nothing anywhere.
+ * The sums are fp32 atomics in no fixed order: equal calls may differ in the last bits. */
 int mst_embed_bwd(int dtype, int64_t B, int64_t T, int64_t D,
                   const int32_t* tokens, float* dtable, int64_t ldt,
                   const int32_t* classes, float* dcls, int64_t ldc, float alpha,
@@ -411,6 +413,14 @@ int mst_embed_bwd(int dtype, int64_t B, int64_t T, int64_t D,
 int mst_group_colsum(int dtype, int64_t B, int64_t T, int64_t D, const void* X, int64_t ldx,
                      int64_t S_out, int64_t s_off, const int32_t* idx, float* dst, int64_t ldd,
                      float alpha, mst_stream_t stream);
+
+/* The thread map and launch of mst_group_colsum for T frames of width D (ABI 121; also mst_embed_bwd's dcls part): no launch, no
+ * HIP call, `form` is 4 int64. A workgroup of 256 threads takes 64 frames of one sample; a thread owns one 16-byte chunk (8 columns)
+ * of every RG-th frame.
+ *   form[0]  cpr = D / 8: chunks per row        form[1]  RG = 256 / cpr: row groups (threads cpr * RG .. 255 idle)
+ *   form[2]  grid.x = ceil(T / 64) (grid.y = B)  form[3]  dynamic LDS bytes, 4 * RG * D
+ * Returns 0; T, D refused as mst_group_colsum refuses them (MST_ERR_INVALID, same message). */
+int mst_group_colsum_form(int64_t T, int64_t D, int64_t* form);
 
 /* key-validity mask from lengths: keymask[b,s] = s < lens[b] + add (model.py:246-247 SequenceMask) */
 int mst_mask_from_lengths(int64_t B, int64_t S, const int32_t* lens, int32_t add,
@@ -554,6 +564,18 @@ int mst_layernorm_bwd(int dtype, int64_t M, int64_t D, const void* x, int64_t ld
                                          with mst_partial_sums */,
                       mst_stream_t stream);
 int64_t mst_layernorm_bwd_parts(int64_t M, int64_t D);
+
+/* What mst_layernorm_fwd (backward = 0) or mst_layernorm_bwd (backward != 0) instantiates and launches for M rows of width D
+ * (ABI 121): no launch, no HIP call, no pointer followed but `form` (5 int64). The launch and this query share one host function, so
+ * they cannot disagree.
+ *   form[0]  NV: 64-lane groups of 4 elements per row: 1 for D <= 256, 2 for D <= 512, 4 for D <= 1024
+ *   form[1]  R: rows a wave has in flight. Forward: 2 when M > 4 grid.x (grid.x is capped at 2048, so M > 8192), else 1.
+ *            Backward: 2 when NV = 1 and ceil(M / (grid.x * waves)) > 1, else 1
+ *   form[2]  grid.x (backward: the rows of `partials`, what mst_layernorm_bwd_parts returns)
+ *   form[3]  waves per workgroup (forward: 4; backward: min(16, 4096 / D), at least 1)
+ *   form[4]  dynamic LDS bytes (forward: 0; backward: 8 * waves * D)
+ * Returns 0; M, D refused as the launches refuse them (MST_ERR_INVALID, same message), MST_ERR_UNSUPPORTED for the dtype. */
+int mst_layernorm_form(int backward, int dtype, int64_t M, int64_t D, int64_t* form);
 
 /* ------------------------------------------------------------------------
  * K8/K9/K10 latent block (model.py:97-103,292,229-232; loss.py:8-12), fp32 math:

@@ -140,20 +140,58 @@ extern "C" int mst_embed_fwd(int dtype, int64_t B, int64_t T, int64_t D, const i
   });
 }
 
+// Every check of mst_group_colsum and its launch geometry, before any HIP call: mst_group_colsum launches what this leaves,
+// mst_group_colsum_form reports it, and mst_embed_bwd asks it BEFORE its scatter launch when it is given dcls (a refused call
+// leaves dtable as it was).
+struct ColsumPlan {
+  int cpr, rg;
+  unsigned grid;
+  size_t lds;
+};
+
+static int colsum_shape(int64_t T, int64_t D, ColsumPlan& p) {
+  MST_CHECK_ARG(T > 0 && D > 0, "mst_group_colsum: bad argument");
+  MST_CHECK_ARG(D % 8 == 0 && D <= 2048, "mst_group_colsum: D must be a multiple of 8 (<= 2048), rows 16-byte aligned");
+  p.cpr = (int)(D / 8);
+  p.rg = 256 / p.cpr;
+  p.grid = (unsigned)cdiv(T, GC_ROWS);
+  p.lds = sizeof(float) * (size_t)p.rg * (size_t)D;
+  return MST_OK;
+}
+
+static int colsum_plan(int64_t B, int64_t T, int64_t D, const void* X, int64_t ldx, const int32_t* idx, const float* dst,
+                       ColsumPlan& p) {
+  MST_CHECK_ARG(B > 0 && X && idx && dst, "mst_group_colsum: bad argument");
+  MST_CHECK_ARG(B <= 65535, "mst_group_colsum: B too large for grid.y");
+  if (const int rc = colsum_shape(T, D, p)) return rc;
+  MST_CHECK_ARG(ldx % 8 == 0 && ((uintptr_t)X % 16 == 0), "mst_group_colsum: D must be a multiple of 8 (<= 2048), rows 16-byte aligned");
+  return MST_OK;
+}
+
+template <typename TT>
+static int colsum_launch(const ColsumPlan& p, int64_t B, int64_t T, int64_t D, const void* X, int64_t ldx, int64_t S_out,
+                         int64_t s_off, const int32_t* idx, float* dst, int64_t ldd, float alpha, mst_stream_t stream) {
+  hipLaunchKernelGGL((group_colsum_kernel<TT>), dim3(p.grid, (unsigned)B), dim3(256), p.lds, (hipStream_t)stream, T,
+                     (int)D, (const TT*)X, ldx, S_out, s_off, idx, dst, ldd, alpha);
+  MST_CHECK_LAUNCH("group_colsum_kernel");
+  return MST_OK;
+}
+
+extern "C" int mst_group_colsum_form(int64_t T, int64_t D, int64_t* form) {
+  MST_CHECK_ARG(form != nullptr, "mst_group_colsum_form: null form");
+  ColsumPlan p;
+  if (const int rc = colsum_shape(T, D, p)) return rc;
+  form[0] = p.cpr; form[1] = p.rg; form[2] = p.grid; form[3] = (int64_t)p.lds;
+  return MST_OK;
+}
+
 extern "C" int mst_group_colsum(int dtype, int64_t B, int64_t T, int64_t D, const void* X, int64_t ldx, int64_t S_out,
                                 int64_t s_off, const int32_t* idx, float* dst, int64_t ldd, float alpha,
                                 mst_stream_t stream) {
-  MST_CHECK_ARG(B > 0 && T > 0 && D > 0 && X && idx && dst, "mst_group_colsum: bad argument");
-  MST_CHECK_ARG(B <= 65535, "mst_group_colsum: B too large for grid.y");
-  MST_CHECK_ARG(D % 8 == 0 && D <= 2048 && ldx % 8 == 0 && ((uintptr_t)X % 16 == 0),
-                "mst_group_colsum: D must be a multiple of 8 (<= 2048), rows 16-byte aligned");
-  const size_t lds = sizeof(float) * (size_t)(256 / (D / 8)) * (size_t)D;
+  ColsumPlan p;
+  if (const int rc = colsum_plan(B, T, D, X, ldx, idx, dst, p)) return rc;
   return dispatch_act(dtype, [&](auto tag) -> int {
-    typedef decltype(tag) TT;
-    hipLaunchKernelGGL((group_colsum_kernel<TT>), dim3((unsigned)cdiv(T, GC_ROWS), (unsigned)B), dim3(256), lds, (hipStream_t)stream, T,
-                       (int)D, (const TT*)X, ldx, S_out, s_off, idx, dst, ldd, alpha);
-    MST_CHECK_LAUNCH("group_colsum_kernel");
-    return MST_OK;
+    return colsum_launch<decltype(tag)>(p, B, T, D, X, ldx, S_out, s_off, idx, dst, ldd, alpha, stream);
   });
 }
 
@@ -164,18 +202,19 @@ extern "C" int mst_embed_bwd(int dtype, int64_t B, int64_t T, int64_t D, const i
   MST_CHECK_ARG(B > 0 && T > 0 && D > 0, "mst_embed_bwd: B,T,D must be positive");
   MST_CHECK_ARG(tokens && dtable && dX, "mst_embed_bwd: null pointer");
   MST_CHECK_ARG(!dcls || classes, "mst_embed_bwd: dcls needs classes");
+  ColsumPlan p{};
+  if (dcls)  // the column sums' own checks come before the first launch
+    if (const int rc = colsum_plan(B, T, D, dX, ld_dx, classes, dcls, p)) return rc;
   const int64_t BT = B * T;
   const unsigned grid = (unsigned)(cdiv(BT, 4) < 4096 ? cdiv(BT, 4) : 4096);
-  int rc = dispatch_act(dtype, [&](auto tag) -> int {
+  return dispatch_act(dtype, [&](auto tag) -> int {
     typedef decltype(tag) TT;
     hipLaunchKernelGGL((embed_scatter_kernel<TT>), dim3(grid), dim3(256), 0, (hipStream_t)stream, BT, T, (int)D, tokens,
                        dtable, ldt, alpha, (const TT*)dX, ld_dx, S_out, s_off, keep);
     MST_CHECK_LAUNCH("embed_scatter_kernel");
+    if (dcls) return colsum_launch<TT>(p, B, T, D, dX, ld_dx, S_out, s_off, classes, dcls, ldc, alpha, stream);
     return MST_OK;
   });
-  if (rc) return rc;
-  if (dcls) return mst_group_colsum(dtype, B, T, D, dX, ld_dx, S_out, s_off, classes, dcls, ldc, alpha, stream);
-  return MST_OK;
 }
 
 extern "C" int mst_mask_from_lengths(int64_t B, int64_t S, const int32_t* lens, int32_t add, uint8_t* keymask,

@@ -264,33 +264,66 @@ static unsigned ln_bwd_grid(int64_t M, int64_t D, int& nw) {
   return (unsigned)(wgs < 256 ? wgs : 256);
 }
 
+// What a launch instantiates and how it is laid out, from the shape alone, with the shape's checks: mst_layernorm_fwd / _bwd
+// launch what this leaves, mst_layernorm_form reports it (no HIP call here).
+struct LnPlan {
+  int nv, r, nw;
+  unsigned grid;
+  size_t lds;
+};
+
+static int ln_plan(bool backward, int64_t M, int64_t D, LnPlan& p) {
+  MST_CHECK_ARG(M > 0 && D > 0, "layernorm: M and D must be positive");
+  MST_CHECK_ARG(D % 4 == 0 && D <= 4 * 64 * LN_MAXV, "layernorm: D must be a multiple of 4 and <= %d (got %lld)",
+                4 * 64 * LN_MAXV, (long long)D);
+  p.nv = ln_dispatch_nv(D, [](auto nv) -> int { return decltype(nv)::value; });
+  if (backward) {
+    p.grid = ln_bwd_grid(M, D, p.nw);
+    p.lds = (size_t)2 * p.nw * D * sizeof(float);
+    // rows in flight per wave, bounded by the 128 registers of a 1024-thread block: two only at NV = 1
+    p.r = (p.nv == 1 && cdiv(M, (int64_t)p.grid * p.nw) > 1) ? 2 : 1;
+  } else {
+    p.nw = 4;
+    p.grid = (unsigned)(cdiv(M, 4) < 2048 ? cdiv(M, 4) : 2048);
+    p.lds = 0;
+    p.r = M > (int64_t)p.grid * 4 ? 2 : 1;  // more than one row per wave: work on two at a time
+  }
+  return MST_OK;
+}
+
+static int ln_check_ld(int64_t D, int64_t ldx, int64_t ldy) {
+  MST_CHECK_ARG(ldx % 4 == 0 && ldy % 4 == 0 && ldx >= D && ldy >= D, "layernorm: leading dims must be multiples of 4 and >= D");
+  return MST_OK;
+}
+
+extern "C" int mst_layernorm_form(int backward, int dtype, int64_t M, int64_t D, int64_t* form) {
+  MST_CHECK_ARG(form != nullptr, "mst_layernorm_form: null form");
+  LnPlan p;
+  if (const int rc = ln_plan(backward != 0, M, D, p)) return rc;
+  if (const int rc = dispatch_act(dtype, [](auto) -> int { return MST_OK; })) return rc;
+  form[0] = p.nv; form[1] = p.r; form[2] = p.grid; form[3] = p.nw; form[4] = (int64_t)p.lds;
+  return MST_OK;
+}
+
 extern "C" int64_t mst_layernorm_bwd_parts(int64_t M, int64_t D) {
   if (M <= 0 || D <= 0) return 0;
   int nw;
   return (int64_t)ln_bwd_grid(M, D, nw);
 }
 
-static int ln_check(int64_t M, int64_t D, int64_t ldx, int64_t ldy) {
-  MST_CHECK_ARG(M > 0 && D > 0, "layernorm: M and D must be positive");
-  MST_CHECK_ARG(D % 4 == 0 && D <= 4 * 64 * LN_MAXV, "layernorm: D must be a multiple of 4 and <= %d (got %lld)",
-                4 * 64 * LN_MAXV, (long long)D);
-  MST_CHECK_ARG(ldx % 4 == 0 && ldy % 4 == 0 && ldx >= D && ldy >= D, "layernorm: leading dims must be multiples of 4 and >= D");
-  return MST_OK;
-}
-
 extern "C" int mst_layernorm_fwd(int dtype, int64_t M, int64_t D, const void* x, int64_t ldx, const float* gamma,
                                  const float* beta, float eps, void* y, int64_t ldy, float* mean, float* rstd,
                                  int64_t row_id_stride, mst_stream_t stream) {
-  int rc = ln_check(M, D, ldx, ldy);
-  if (rc) return rc;
+  LnPlan p;
+  if (const int rc = ln_plan(false, M, D, p)) return rc;
+  if (const int rc = ln_check_ld(D, ldx, ldy)) return rc;
   MST_CHECK_ARG(x && gamma && beta && y && mean && rstd, "mst_layernorm_fwd: null pointer");
-  const unsigned grid = (unsigned)(cdiv(M, 4) < 2048 ? cdiv(M, 4) : 2048);
-  const bool multi = M > (int64_t)grid * 4;  // more than one row per wave: work on two at a time
+  const unsigned grid = p.grid;
   return dispatch_act(dtype, [&](auto tag) -> int {
     typedef decltype(tag) T;
     return ln_dispatch_nv(D, [&](auto nv) -> int {
       constexpr int NV = decltype(nv)::value;
-      if (multi)
+      if (p.r == 2)
         hipLaunchKernelGGL((layernorm_fwd_kernel<T, NV, 2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, M, (int)D,
                            (const T*)x, ldx, gamma, beta, eps, (T*)y, ldy, mean, rstd, row_id_stride > 0 ? row_id_stride : 1);
       else
@@ -308,24 +341,24 @@ extern "C" int mst_layernorm_bwd(int dtype, int64_t M, int64_t D, const void* x,
                                  int mask_mode, float dropout_p, uint64_t dropout_seed, uint32_t dropout_site,
                                  const uint64_t* dropout_seed_ptr, int64_t row_id_stride, float* partials,
                                  mst_stream_t stream) {
-  int rc = ln_check(M, D, ldx, ldy);
-  if (rc) return rc;
+  LnPlan p;
+  if (const int rc = ln_plan(true, M, D, p)) return rc;
+  if (const int rc = ln_check_ld(D, ldx, ldy)) return rc;
   MST_CHECK_ARG(x && gamma && mean && rstd && dy && dx && (partials || (dgamma && dbeta)), "mst_layernorm_bwd: null pointer");
   MST_CHECK_ARG(ld_dx % 4 == 0 && ld_dx >= D, "mst_layernorm_bwd: bad ld_dx");
   MST_CHECK_ARG(mask_mode >= 0 && mask_mode <= 2, "mst_layernorm_bwd: mask_mode must be 0,1,2");
   MST_CHECK_ARG(mask_mode != 1 || (dx_masked && ld_dxm % 4 == 0 && ld_dxm >= D), "mst_layernorm_bwd: mask_mode 1 needs dx_masked");
   MST_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "mst_layernorm_bwd: dropout_p must be in [0,1)");
   MST_CHECK_ARG(!partials || (uintptr_t)partials % 16 == 0, "mst_layernorm_bwd: partials must be 16-byte aligned");
-  int nw;
-  const unsigned grid = ln_bwd_grid(M, D, nw);
-  const size_t lds = (size_t)2 * nw * D * sizeof(float);
-  const int64_t rows_per_wave = cdiv(M, (int64_t)grid * nw);
+  const unsigned grid = p.grid;
+  const int nw = p.nw;
+  const size_t lds = p.lds;
   return dispatch_act(dtype, [&](auto tag) -> int {
     typedef decltype(tag) T;
     return ln_dispatch_nv(D, [&](auto nv) -> int {
       constexpr int NV = decltype(nv)::value;
-      constexpr int RB = NV == 1 ? 2 : 1;  // rows in flight per wave, bounded by the 128 registers of a 1024-thread block
-      if (rows_per_wave > 1 && RB > 1)
+      constexpr int RB = NV == 1 ? 2 : 1;  // the only R > 1 instantiated: ln_plan leaves r = 2 at NV = 1 alone
+      if (p.r == 2 && RB > 1)
         hipLaunchKernelGGL((layernorm_bwd_kernel<T, NV, RB>), dim3(grid), dim3(64 * nw), lds, (hipStream_t)stream, M, (int)D,
                            (const T*)x, ldx, gamma, mean, rstd, (const T*)dy, ldy, (T*)dx, ld_dx, (T*)dx_masked, ld_dxm,
                            dgamma, dbeta, mask_mode, dropout_p, dropout_seed, dropout_site, dropout_seed_ptr,

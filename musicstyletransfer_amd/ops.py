@@ -490,6 +490,14 @@ def layernorm_bwd_parts(M, D):
     return int(_lib.load().mst_layernorm_bwd_parts(M, D))
 
 
+def layernorm_form(backward, dtype, M, D):
+    """what layernorm_fwd (backward false) or layernorm_bwd launches for M rows of width D (mst_layernorm_form in include/mst_hip.h);
+    no launch, no device. -> dict(nv, r, grid, waves, lds)"""
+    form = (C.c_int64 * 5)()
+    call("mst_layernorm_form", 1 if backward else 0, dt(dtype), M, D, form)
+    return dict(nv=form[0], r=form[1], grid=form[2], waves=form[3], lds=form[4])
+
+
 PARTIAL_SUM_MAX_JOBS = 20
 
 
@@ -797,6 +805,14 @@ def group_colsum(X3, T, D, s_off, idx, dst, alpha):
     B = X3.shape[0]
     call("mst_group_colsum", dt(X3), B, T, D, ptr(X3), X3.stride(1), X3.shape[1], s_off, ptr(idx), ptr(dst),
          dst.stride(0), alpha, stream())
+
+
+def group_colsum_form(T, D):
+    """the thread map and launch of group_colsum (and of embed_bwd's dcls part) for T frames of width D (mst_group_colsum_form);
+    no launch, no device. -> dict(cpr, rg, grid, lds)"""
+    form = (C.c_int64 * 4)()
+    call("mst_group_colsum_form", T, D, form)
+    return dict(cpr=form[0], rg=form[1], grid=form[2], lds=form[3])
 
 
 def mask_from_lengths(lens, add, keymask):

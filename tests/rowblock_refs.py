@@ -41,6 +41,9 @@ subnormal: + 2^-25):
   dgamma   terms dy xh (16-bit-exact dy times fp32 xh: 4 u each for xh's error and the product), summed over M rows by 8 or 16 row
            groups of a workgroup, through LDS, then by atomics or partial rows:  2 (M + 16) u (sum|dy xh| + |initial|) + 4 u sum|dy xh|
            (+ sum e |xh| where dy carries e);  dbeta: 2 (M + 16) u (sum|dy| + |initial|) (+ sum e)
+           The stand-alone kernel at M = 16389 needs no wider term: counted off layernorm_bwd_kernel, a column's M terms are added
+           per wave in row order (5 at most there), then over the 16 waves of a workgroup through LDS, then over 256 workgroups by
+           atomics or partial rows: every path is a sum of the same M terms in SOME order, which (M + 16) u already covers.
 No constant above was chosen after looking at a GPU result.
 
 The dropout keep decision is imported from gemm_refs (checked there against csrc/common.hpp), not restated.
@@ -96,6 +99,7 @@ class Case:
     lead: int = -1         # ffn_bwd: the leading LayerNorm backward's mask mode (-1: none)
     bias: bool = True
     tag: str = ""
+    form: tuple = None     # ln: the instantiations the case is in the table for, (NV, R forward, R backward); asked of the library where it is run
 
     @property
     def id(self):
@@ -107,6 +111,12 @@ class Case:
 M_WHOLE, M_GUARDED = 1600, 1637    # 25 whole tiles: all four chunk rotations (blockIdx.x / 8) % 4; 26 tiles, the last ragged, grid % 8 != 0
 RG = (64, 65, 1)                   # rows 1..T of every T + 1, T = 64
 M_RG = 26 * 64                     # B = 26: 1664 logical rows, 1690 physical
+
+
+# (M, D) -> (NV, R of the forward, R of the backward) the new stand-alone LayerNorm shapes are meant to reach
+LN_FORMS = {(8197, 32): (1, 2, 2), (8197, 260): (2, 2, 1), (8197, 772): (4, 2, 1), (77, 512): (2, 1, 1), (1000, 512): (2, 1, 1),
+            (1025, 128): (1, 1, 2), (1029, 128): (1, 1, 2), (1025, 256): (1, 1, 2), (1029, 256): (1, 1, 2), (16389, 32): (1, 2, 2),
+            (8192, 32): (1, 1, 2), (8193, 32): (1, 2, 2)}
 
 
 def _cases():
@@ -168,8 +178,17 @@ def _cases():
         for D, M, stride, mode, parts in ((32, 16, 1, 0, False), (40, 77, 4, 1, True), (128, 1000, 1, 2, True), (256, 77, 1, 1, False),
                                           (1024, 16, 4, 2, False), (1024, 1000, 1, 1, True), (40, 1000, 1, 0, False), (256, 1000, 4, 2, True),
                                           (128, 16, 1, 1, True), (32, 77, 1, 2, False)):
-            C("ln", M, D, groups=(1, stride, 0), mode=mode, partials=parts, tag=f"m{mode}")
-        C("ln", 77, 128, groups=(1, 1, 0), mode=2, p=0.0, tag="m2-p0")
+            C("ln", M, D, groups=(1, stride, 0), mode=mode, partials=parts, tag=f"m{mode}", form=(1 if D <= 256 else 4, 1, 1))
+        C("ln", 77, 128, groups=(1, 1, 0), mode=2, p=0.0, tag="m2-p0", form=(1, 1, 1))
+        # ---- ... in every instantiation <NV, R> (LN_FORMS below: what each shape is here for). Forward R = 2 from M = 8193
+        # (2048 workgroups of 4 waves); backward R = 2 at NV = 1 from M = 1025 (64 workgroups of 16 waves), its 256-workgroup cap
+        # from M = 16385. The last pair of a wave is ragged (first row live, second dead) for all but M - 8192 (forward), M - 1024
+        # (backward at M = 1025 / 1029) waves; M = 16389 gives the forward a second trip and the backward three, the last ragged
+        for M, D, stride, mode, parts in ((8197, 32, 1, 1, True), (8197, 260, 1, 0, False), (8197, 772, 1, 2, False),
+                                          (77, 512, 1, 1, True), (1000, 512, 1, 2, False),
+                                          (1025, 128, 4, 1, False), (1029, 128, 4, 2, True), (1025, 256, 4, 2, False), (1029, 256, 4, 1, True),
+                                          (16389, 32, 1, 0, False), (16389, 32, 1, 2, True), (8192, 32, 1, 0, False), (8193, 32, 1, 1, True)):
+            C("ln", M, D, groups=(1, stride, 0), mode=mode, partials=parts, tag=f"m{mode}", form=LN_FORMS[(M, D)])
         C("dec_tail", M_RG, 128, 512, groups=RG, mode=1, resid="self", partials=True)
     return tuple(out)
 
@@ -195,6 +214,20 @@ def ln_bwd_parts(M, D):
     if wgs < 64:
         wgs = min(cdiv(M, nw), 64)
     return min(wgs, 256)
+
+
+def ln_form(backward, M, D):
+    """mst_layernorm_form, restated from csrc/layernorm.hip (ln_plan) -> (NV, R, grid.x, waves per workgroup, LDS bytes). Used to lay
+    out the partial rows and the kernel-order emulation without the library; where the library is at hand (the GPU test, the CPU
+    completeness test) its query is asked and this restatement is only held against it"""
+    cdiv = lambda a, b: (a + b - 1) // b  # noqa: E731
+    nv = 1 if D <= 256 else (2 if D <= 512 else 4)
+    if backward:
+        nw = max(1, min(16, 32768 // (8 * D)))
+        grid = ln_bwd_parts(M, D)
+        return nv, (2 if nv == 1 and cdiv(M, grid * nw) > 1 else 1), grid, nw, 8 * nw * D
+    grid = min(cdiv(M, 4), 2048)
+    return nv, (2 if M > 4 * grid else 1), grid, 4, 0
 
 
 def n_parts(c):

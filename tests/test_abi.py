@@ -49,7 +49,7 @@ def test_exports_are_exactly_the_declarations(lib):
 
 
 def test_version_and_error_string(lib):
-    assert lib.mst_version() >= 111  # 111: mst_row_tail_form
+    assert lib.mst_version() >= 121  # 121: mst_layernorm_form, mst_group_colsum_form
     assert isinstance(lib.mst_last_error(), bytes)
 
 
@@ -96,6 +96,8 @@ def test_parser_known_answers():
         "mst_graph_end": (ci, [vp, P(vp)]),
         "mst_gemm_nt_ln_parts": (i64, [i64]),
         "mst_layernorm_bwd_parts": (i64, [i64, i64]),
+        "mst_layernorm_form": (ci, [ci, ci, i64, i64, vp]),
+        "mst_group_colsum_form": (ci, [i64, i64, vp]),
         "mst_adam_flat": (ci, [P(_lib.AdamArgs), vp]),
         "mst_adam_flat_form": (ci, [P(_lib.AdamArgs), vp]),
         "mst_latent_rows": (ci, [ci, i64, i64, i64, i64, vp, vp, vp, vp, vp, ci, f32, u64, vp, u32, i64, vp, vp,

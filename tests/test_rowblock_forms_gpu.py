@@ -110,8 +110,11 @@ def _run(o, c, ins, gpu):
     bufs, _ = R.plan(c)
     i = {k: t.to(gpu) for k, t in ins.items()}
     u = {k: t.to(gpu) for k, t in R.outputs(c).items()}
-    if c.kind == "ln":
-        assert o.layernorm_bwd_parts(c.M, c.D) == R.n_parts(c)
+    if c.kind == "ln":  # the instantiation the table claims is the one the library launches, forward and backward
+        fwd, bwd = o.layernorm_form(False, c.dtype, c.M, c.D), o.layernorm_form(True, c.dtype, c.M, c.D)
+        assert (fwd["nv"], fwd["r"], bwd["r"]) == c.form and bwd["nv"] == fwd["nv"], (c.id, fwd, bwd)
+        assert (fwd["waves"], fwd["lds"]) == (4, 0) and bwd["lds"] == 8 * bwd["waves"] * c.D
+        assert bwd["grid"] == R.n_parts(c) == o.layernorm_bwd_parts(c.M, c.D)
     elif c.kind != "gemm_ln_fwd" and c.kind != "ffn_fwd":
         assert o.gemm_nt_ln_parts(c.M) == R.n_parts(c)
     _launch(o, c, i, u)

@@ -383,7 +383,8 @@ def test_the_table_reaches_every_ffn_ln_kernel_and_every_chunk_rotation():
         g = [c for c in R.CASES if c.dtype == dtype and c.kind == "gemm_ln_bwd"]
         assert {c.mode for c in g} == {0, 1, 2} and {c.partials for c in g} == {True, False}
         ln = [c for c in R.CASES if c.dtype == dtype and c.kind == "ln"]
-        assert {c.D for c in ln} == {32, 40, 128, 256, 1024} and {c.M for c in ln} == {16, 77, 1000}
+        assert {c.D for c in ln} == {32, 40, 128, 256, 260, 512, 772, 1024}
+        assert {c.M for c in ln} == {16, 77, 1000, 1025, 1029, 8192, 8193, 8197, 16389}
         assert {c.groups[1] for c in ln} == {1, 4} and {c.mode for c in ln} == {0, 1, 2} and {c.partials for c in ln} == {True, False}
         assert sum(c.kind == "dec_tail" and c.dtype == dtype for c in R.CASES) == 1
     assert len(set(IDS)) == len(IDS)
@@ -423,10 +424,288 @@ def test_the_operands_are_hard(cid):
         elif b.rows in ("log", "phys", "w"):
             t = ins[n].float().numpy()
             own = R.owned(c, b)
-            assert np.isnan(t[~own]).all() and np.isfinite(t[own]).all() and t.shape[1] == b.width + 8 and ins[n].stride(0) % 8 == 0
+            assert np.isnan(t[~own]).all() and np.isfinite(t[own]).all() and t.shape[1] == b.width + 8
+            # (rows of 16 bytes for the GEMM launches; the stand-alone LayerNorm loads 8 bytes and takes any multiple of 4: D = 260)
+            assert ins[n].stride(0) % (4 if c.kind == "ln" else 8) == 0
             if c.groups is not None and b.rows == "phys" and c.kind != "ln":
                 assert (~own).any(1).all() and (~own).all(1).any(), f"{n}: rows outside the groups hold NaN"
         elif b.rows == "stat":
             t = ins[n].numpy()
             own = R.owned(c, b)
             assert np.isnan(t[~own]).all() and np.isfinite(t[own]).all()
+
+
+# ------------------------------------------------------------------------------------------ the stand-alone kernels, form by form
+LN = [c for c in R.CASES if c.kind == "ln"]
+LN_NEW = [c for c in LN if (c.M, c.D) in R.LN_FORMS]
+
+
+@pytest.fixture(scope="module")
+def ops():
+    from musicstyletransfer_amd import ops as o
+    o._lib.load()
+    return o
+
+
+def test_the_ln_cases_reach_every_instantiation_the_dispatcher_has(ops):
+    """asked of the library (mst_layernorm_form: no HIP call): each case runs the <NV, R> it claims, the restated ln_form agrees with
+    the query field by field, and between them the cases leave no (NV, R) pair of either direction unclaimed"""
+    for dtype in R.DTYPES:
+        fwd, bwd = set(), set()
+        for c in (c for c in LN if c.dtype == dtype):
+            f, b = ops.layernorm_form(False, c.dtype, c.M, c.D), ops.layernorm_form(True, c.dtype, c.M, c.D)
+            assert (f["nv"], f["r"], b["r"]) == c.form and b["nv"] == f["nv"], (c.id, f, b)
+            for back, q in ((False, f), (True, b)):
+                assert R.ln_form(back, c.M, c.D) == (q["nv"], q["r"], q["grid"], q["waves"], q["lds"]), c.id
+            assert b["grid"] == R.n_parts(c) == ops.layernorm_bwd_parts(c.M, c.D)
+            fwd.add((f["nv"], f["r"])), bwd.add((b["nv"], b["r"]))
+        # what the dispatcher can produce at all: every (NV, R) the query returns over a sweep of shapes around every threshold
+        can_f, can_b = set(), set()
+        for D in (4, 32, 256, 260, 512, 516, 1024):
+            for M in (1, 16, 1024, 1025, 4096, 8192, 8193, 16384, 16385, 70000):
+                f, b = ops.layernorm_form(False, dtype, M, D), ops.layernorm_form(True, dtype, M, D)
+                can_f.add((f["nv"], f["r"])), can_b.add((b["nv"], b["r"]))
+        assert can_f == {(nv, r) for nv in (1, 2, 4) for r in (1, 2)} and can_b == {(1, 1), (1, 2), (2, 1), (4, 1)}
+        assert fwd == can_f and bwd == can_b
+        new = [c for c in LN_NEW if c.dtype == dtype]
+        # the boundary, the 256-workgroup cap with an odd number of trips, a partly empty last lane group at NV = 2 and 4
+        assert {ops.layernorm_form(False, dtype, M, 32)["r"] for M in (8192,)} == {1} and R.ln_form(False, 8193, 32)[1] == 2
+        assert any(R.ln_form(True, c.M, c.D)[2] == 256 and -(-c.M // (256 * 16 * 2)) % 2 == 1 and not c.partials for c in new)
+        assert any(R.ln_form(True, c.M, c.D)[2] == 256 and c.partials for c in new)
+        assert {nv for c in new for nv in [R.ln_form(False, c.M, c.D)[0]] if (c.D // 4) % 64} >= {1, 2, 4}
+        assert any(c.groups[1] > 1 and c.mode == m and c.p > 0 and c.form[2] == 2 for c in new for m in (1,)) \
+            and any(c.groups[1] > 1 and c.mode == 2 and c.p > 0 and c.form[2] == 2 for c in new)
+    with pytest.raises(ops._lib.MstError, match="multiple of 4"):
+        ops.layernorm_form(False, torch.bfloat16, 8, 6)
+    with pytest.raises(ops._lib.MstError, match="must be positive"):
+        ops.layernorm_form(True, torch.bfloat16, 0, 8)
+    with pytest.raises(ops._lib.MstError, match="<= 1024"):
+        ops.layernorm_form(True, torch.float16, 8, 1028)
+
+
+def _tree64(x):
+    """the sum over the 64 lanes (last axis) as a butterfly: 32 + 32, 16 + 16, ..."""
+    while x.shape[-1] > 1:
+        h = x.shape[-1] // 2
+        x = x[..., :h] + x[..., h:]
+    return x[..., 0]
+
+
+def _lanes(t, nv):
+    """[M, D] -> [M, NV, 64, 4]: element 4 (64 i + lane) + e at [i, lane, e], zeros behind D as the kernel's registers hold them"""
+    M, D = t.shape
+    out = torch.zeros((M, nv * 256), dtype=torch.float32)
+    out[:, :D] = t
+    return out.view(M, nv, 64, 4)
+
+
+def emulate_ln(c, ins, wrong=None):
+    """the two stand-alone launches of an "ln" case in torch fp32, in the kernels' order: a row's elements dealt to 64 lanes in NV groups
+    of 4, per-lane sums in the kernel's association, a butterfly over the lanes, two-pass variance over the live lane groups only; rows
+    dealt to waves as `for m0 = wave; m0 < M; m0 += nwaves * R` with rows m0 and m0 + nwaves in flight; the parameter gradients summed
+    per wave in row order, over the waves of a workgroup in index order, then per workgroup (a partial row each, or added to the
+    initial value in index order). wrong: one mistake a kernel of this shape can make (the list is the issue's). -> the output buffers"""
+    f32 = torch.float32
+    bufs, _ = R.plan(c)
+    outs = R.outputs(c)
+    M, D, stride = c.M, c.D, c.groups[1]
+    T = lambda name: torch.from_numpy(R.gather(c, bufs[name], ins[name])).to(f32)  # noqa: E731
+    x, dy, gamma, beta = T("x"), T("dy"), T("gamma"), T("beta")
+    n_live = D // 4
+    sentinel = torch.tensor(R.SENTINEL, dtype=f32)
+
+    def pairs(back):
+        """-> (second-row flag of every row, index of its pair partner or -1)"""
+        nv, r, grid, nw, _ = R.ln_form(back, M, D)
+        nwaves = grid * nw
+        m = np.arange(M)
+        if r == 1:
+            return nv, nwaves, np.zeros(M, dtype=bool), np.full(M, -1)
+        second = (m // nwaves) % 2 == 1
+        partner = np.where(second, m - nwaves, m + nwaves)
+        return nv, nwaves, second, np.where(partner < M, partner, -1)
+
+    # ---------------- forward
+    nv, nwaves, second, partner = pairs(False)
+    v = _lanes(x, nv)
+    s = torch.zeros((M, 64), dtype=f32)
+    for i in range(nv):
+        s = s + ((v[:, i, :, 0] + v[:, i, :, 1]) + (v[:, i, :, 2] + v[:, i, :, 3]))
+    inv_d = torch.tensor(1.0, dtype=f32) / torch.tensor(float(D), dtype=f32)
+    mean = _tree64(s) * inv_d
+    live = (torch.arange(nv * 64).view(nv, 64) < n_live)  # [NV, 64]
+    ss = torch.zeros((M, 64), dtype=f32)
+    for i in range(nv):
+        for e in range(4):
+            d = v[:, i, :, e] - mean[:, None]
+            sq = d * d
+            ss = ss + (sq if wrong == "empty_group_counted" else torch.where(live[i][None, :], sq, torch.zeros((), dtype=f32)))
+    var = _tree64(ss) * (torch.tensor(1.0, dtype=f32) / torch.tensor(float(D - 1), dtype=f32) if wrong == "unbiased_var" else inv_d)
+    eps = torch.tensor(1e-5, dtype=f32)
+    rstd = 1.0 / (torch.sqrt(var) + eps) if wrong == "eps_outside_root" else 1.0 / torch.sqrt(var + eps)
+    if wrong == "pair_stats_swapped":
+        both = torch.from_numpy(partner >= 0)
+        idx = torch.from_numpy(np.where(partner >= 0, partner, np.arange(M)))
+        mean, rstd = torch.where(both, mean[idx], mean), torch.where(both, rstd[idx], rstd)
+    y = (x - mean[:, None]) * rstd[:, None] * gamma + beta
+    done = np.ones(M, dtype=bool)
+    if wrong == "pair_second_dropped":   # the second row's liveness tested as m + 1 < M
+        done = ~(second & (np.arange(M) == M - 1))
+    dn = torch.from_numpy(done)
+    R.scatter(c, bufs["y"], outs["y"], torch.where(dn[:, None], y.to(c.dtype).float(), sentinel).numpy())
+    if wrong == "stats_at_m":            # statistics stored at m, not m * row_id_stride
+        outs["mean"][:M], outs["rstd"][:M] = mean, rstd
+    else:
+        R.scatter(c, bufs["mean"], outs["mean"], torch.where(dn, mean, sentinel).numpy())
+        R.scatter(c, bufs["rstd"], outs["rstd"], torch.where(dn, rstd, sentinel).numpy())
+    # ---------------- backward, on the statistics the forward stored
+    mean = torch.from_numpy(R.gather(c, bufs["mean"], outs["mean"])).to(f32)
+    rstd = torch.from_numpy(R.gather(c, bufs["rstd"], outs["rstd"])).to(f32)
+    nv, nwaves, second, partner = pairs(True)
+    _, _, grid, nw, _ = R.ln_form(True, M, D)
+    xh = (x - mean[:, None]) * rstd[:, None]
+    g = dy * gamma
+    gl, gxl = _lanes(g, nv), _lanes(g * xh, nv)
+    s1, s2 = torch.zeros((M, 64), dtype=f32), torch.zeros((M, 64), dtype=f32)
+    for i in range(nv):
+        for e in range(4):
+            s1, s2 = s1 + gl[:, i, :, e], s2 + gxl[:, i, :, e]
+    s1, s2 = _tree64(s1) * inv_d, _tree64(s2) * inv_d
+    dx = rstd[:, None] * (g - s1[:, None] - xh * s2[:, None])
+    p = c.p if c.mode else 0.0
+    if p > 0:
+        counter = np.arange(M) if wrong == "counter_from_m" else R.rows(c)[0]
+        idx = counter.astype(np.uint64)[:, None] * np.uint64(D) + np.arange(D, dtype=np.uint64)[None, :]
+        keep, scale = R.keep_mask(R.SEED if wrong == "seed_ignored" else R.SEED ^ R.SEED_WORD, R.SITE_LN, idx, p)
+        k = torch.from_numpy(keep * scale).to(f32)
+    else:
+        k = torch.ones((M, D), dtype=f32)
+    done = np.ones(M, dtype=bool)
+    if wrong == "pair_second_dropped":
+        done = ~(second & (np.arange(M) == M - 1))
+    dn = torch.from_numpy(done)[:, None]
+    main = dx * (1.0 + k) if c.mode == 2 else dx
+    R.scatter(c, bufs["dx"], outs["dx"], torch.where(dn, main.to(c.dtype).float(), sentinel).numpy())
+    if c.mode == 1:
+        R.scatter(c, bufs["dxm"], outs["dxm"], torch.where(dn, (dx * k).to(c.dtype).float(), sentinel).numpy())
+    acc = torch.zeros((nwaves, 2 * D), dtype=f32)
+    terms = torch.cat([dy * xh, dy], 1) * torch.from_numpy(done)[:, None]
+    for j in range(-(-M // nwaves)):
+        rows_ = terms[j * nwaves:(j + 1) * nwaves]
+        acc[:rows_.shape[0]] += rows_
+    wg = torch.zeros((grid, 2 * D), dtype=f32)
+    for w in range(nw):
+        wg += acc.view(grid, nw, 2 * D)[:, w]
+    tot = torch.full((2 * D,), R.INIT, dtype=f32)
+    for b in range(grid):
+        tot = tot + wg[b]
+    if c.partials:
+        outs["parts"][:grid] = wg
+    R.scatter(c, bufs["dgamma"], outs["dgamma"], tot[:D].numpy()), R.scatter(c, bufs["dbeta"], outs["dbeta"], tot[D:].numpy())
+    return outs
+
+
+_LN_CACHE = {}
+
+
+def _ln_eval(c):
+    if c.id not in _LN_CACHE:
+        ins = R.operands(c)
+        _LN_CACHE[c.id] = (ins, emulate_ln(c, ins))
+    return _LN_CACHE[c.id]
+
+
+@pytest.mark.parametrize("c", LN_NEW, ids=lambda c: c.id)
+def test_the_bounds_take_the_kernels_own_order(c):
+    ins, outs = _ln_eval(c)
+    results = R.check(c, ins, outs)
+    print(f"\n{c.id}: worst fp32 (kernel order) error / bound " + ", ".join(f"{r.name} {r.ratio:.3f}" for r in results))
+    for r in results:
+        assert not r.bad.any(), R.describe(c, r)
+    assert R.intact(c, outs) == []
+
+
+def _ln_share(c, wrong, name, sel):
+    ins, _ = _ln_eval(c)
+    r = [x for x in R.check(c, ins, emulate_ln(c, ins, wrong)) if x.name == name]
+    assert len(r) == 1
+    sel = sel(r[0]) if callable(sel) else sel
+    assert sel.any(), (c.id, wrong, name)
+    share = float(r[0].bad[sel].mean())
+    print(f"{c.id}: {wrong}: {name}: {share:.3f} of {int(sel.sum())} affected elements outside the bound")
+    return share
+
+
+@pytest.mark.parametrize("c", LN_NEW, ids=lambda c: c.id)
+def test_the_bounds_refuse_what_a_wrong_pair_kernel_stores(c):
+    """every mistake in every case suited to it (a case is suited where the mistake changes what is stored)"""
+    M, D, stride = c.M, c.D, c.groups[1]
+    m = np.arange(M)
+    const = _rows_mask(c, [R.CONST_ROW])
+    tried = set()
+    for back, names in ((False, ("y", "mean", "rstd")), (True, ("dx",))):
+        nv, r, grid, nw, _ = R.ln_form(back, M, D)
+        nwaves = grid * nw
+        if r == 2:
+            second = (m // nwaves) % 2 == 1
+            if second[M - 1]:   # the row is never stored: the sentinel stays, in every element
+                for name in names:
+                    sel = (m == M - 1) if name in ("mean", "rstd") else np.broadcast_to((m == M - 1)[:, None], (M, D))
+                    # (an element of y or dx may itself lie at the sentinel, 7: gamma reaches 4)
+                    assert _ln_share(c, "pair_second_dropped", name, sel) >= (1.0 if name in ("mean", "rstd") else 0.95)
+                tried.add("pair_second_dropped")
+            if not back:
+                partner = np.where(second, m - nwaves, m + nwaves)
+                both = partner < M
+                # two rows' means differ by far more than (n + 16) u mean|h| unless both are offset rows (8 + sixteenths: their means
+                # are 0.1 apart at most) or chance has it
+                assert _ln_share(c, "pair_stats_swapped", "mean", both) >= 0.95
+                tried.add("pair_stats_swapped")
+    if stride > 1:
+        # index m holds row m's statistics, index m * stride is read: another row's (or the sentinel)
+        assert _ln_share(c, "stats_at_m", "mean", m > 0) >= 0.95
+        tried.add("stats_at_m")
+        if c.mode and c.p > 0:
+            name = "dxm" if c.mode == 1 else "dx"
+            differ = R.keep_scale(c, D, c.p, R.SITE_LN) != R.keep_scale(c, D, c.p, R.SITE_LN, m)
+            assert 0.25 < differ[1:].mean() < 0.4   # 2 p (1 - p) = 0.32 (row 0: the same counter either way)
+            # a decision the other way moves the element by its own size (mode 1: dx / 0.8 against 0; mode 2: dx against 2.25 dx)
+            assert _ln_share(c, "counter_from_m", name, lambda r: differ & (np.abs(r.ref) + np.abs(r.got) > 0)) >= 0.95
+            tried.add("counter_from_m")
+    if c.mode and c.p > 0:
+        name = "dxm" if c.mode == 1 else "dx"
+        idx = R.rows(c)[0].astype(np.uint64)[:, None] * np.uint64(D) + np.arange(D, dtype=np.uint64)[None, :]
+        differ = R.keep_mask(R.SEED, R.SITE_LN, idx, c.p)[0] != R.keep_mask(R.SEED ^ R.SEED_WORD, R.SITE_LN, idx, c.p)[0]
+        assert 0.25 < differ.mean() < 0.4
+        assert _ln_share(c, "seed_ignored", name, lambda r: differ & (np.abs(r.ref) + np.abs(r.got) > 0)) >= 0.95
+        tried.add("seed_ignored")
+    if (D // 4) % 64:
+        # e = 256 NV - D zeros, each counted as mean^2: the variance grows by mean^2 e / D. A unit-scale row has mean = z / sqrt(D) with z
+        # a standard normal deviate, so rstd moves by z^2 e / (2 D^2) of itself against a bound of about (D + 20) u / 2: refused where
+        # z^2 > (D + 20) u D^2 / e, a share of erfc(sqrt(that / 2)) of the rows (0.95 at D = 260, 0.74 at D = 772); the constant row
+        # (variance 0, mean 3) and the offset rows (mean 8) by orders of magnitude
+        e = 256 * R.ln_form(False, M, D)[0] - D
+        expect = math.erfc(math.sqrt((D + 20) * R.U * D * D / e / 2))
+        assert _ln_share(c, "empty_group_counted", "rstd", np.ones(M, dtype=bool)) >= expect - 0.05, expect
+        assert _ln_share(c, "empty_group_counted", "rstd", const | (m % 8 == R.OFFSET_ROW)) == 1.0
+        tried.add("empty_group_counted")
+    # n / (n - 1) under the root: 1 / (2 n) of rstd in every row that has a variance, against (n + 20) u / 2
+    assert _ln_share(c, "unbiased_var", "rstd", ~const) >= 0.99
+    # eps decides rstd alone on the constant row; on the offset rows (var about 0.008) it moves it by 6e-4 against a bound of 5e-6
+    assert _ln_share(c, "eps_outside_root", "rstd", const | (m % 8 == R.OFFSET_ROW)) == 1.0
+    want = {"unbiased_var", "eps_outside_root"} | tried
+    print(f"{c.id}: refused {sorted(want)}")
+
+
+def test_every_pair_mistake_has_a_case():
+    """the mistakes that need a shape of their own are each refused in at least one case per type (which: the test above prints)"""
+    for dtype in R.DTYPES:
+        new = [c for c in LN_NEW if c.dtype == dtype]
+        f = lambda c, back: R.ln_form(back, c.M, c.D)  # noqa: E731
+        def second_last(c, back):
+            nv, r, grid, nw, _ = f(c, back)
+            return r == 2 and ((c.M - 1) // (grid * nw)) % 2 == 1
+        assert any(second_last(c, False) for c in new) and any(second_last(c, True) for c in new)
+        assert any(c.groups[1] > 1 and f(c, True)[1] == 2 and c.mode == 1 for c in new)
+        assert any(c.groups[1] > 1 and f(c, True)[1] == 2 and c.mode == 2 for c in new)
+        assert {f(c, False)[0] for c in new if (c.D // 4) % 64 and f(c, False)[1] == 2} == {1, 2, 4}
