@@ -699,6 +699,38 @@ int mst_latent_form(int64_t De, int64_t Z, int64_t Dd, int64_t nq, const void* W
 int mst_latent_dim_stats(int64_t B, int64_t Z, int64_t C, const float* mu, int64_t ld_mu, const float* sigma, int64_t ld_sigma,
                          const int32_t* classes, double* acc, mst_stream_t stream);
 
+/* The importance-weighted bound on log p(x) from K posterior draws (ABI 122; Burda et al.):
+ *   log p(x) ~= log (1/K) sum_k p(x | z_k) p(z_k) / q(z_k | x)
+ * folded one draw at a time on the device, so that K decoder passes and a whole validation set need one read at the end.
+ *
+ * mst_iw_fold — one draw. eps, sigma, z: fp32 [B, ld >= Z] as mst_step_begin / mst_latent_fwd leave them; recon: the fp32 [B] the loss
+ * launch leaves (the project's MEAN reconstruction loss of sample b); recon_scale turns that mean back into nats: T * P for the
+ * piano-roll ends (padded frames count as the loss counts them), T for the token ends. state: double [B][6] =
+ * {m, s, s2, sum_lw, n, n_bad}, zeroed by the caller before the first draw. The log-weight of sample b in this draw, in fp64 on the
+ * fp32 inputs widened:
+ *   lw = -recon_scale * recon[b] + sum_d (0.5 eps_d^2 - 0.5 z_d^2 + log|sigma_d|)
+ * (log p(z) - log q(z | x) written through eps: z = mu + eps sigma, so (z - mu) / sigma = eps and the 2 pi terms cancel; sigma is a raw
+ * linear output and may be negative, hence |sigma|). The sum over d: lane l of the sample's wave adds its terms d = l, l + 64, ... in
+ * ascending order from zero, then the 64 partial sums go through xor butterflies of 32, 16, 8, 4, 2, 1 lanes — a fixed order.
+ * Each sample is one wave, a workgroup holds four samples; lane 0 then does the online update of its sample's six cells:
+ *   lw not finite (a non-finite input, sigma_d == 0, an infinite recon): a BAD draw — n_bad += 1 and no other cell changes
+ *   n == 0:   m = lw, s = s2 = 1
+ *   lw > m:   s = s * exp(m - lw) + 1, s2 = s2 * exp(2 (m - lw)) + 1, m = lw
+ *   else:     r = exp(lw - m), s += r, s2 += r * r
+ *   then      sum_lw += lw, n += 1
+ * so that s = sum_k exp(lw_k - m) and s2 = sum_k exp(2 (lw_k - m)) with m the largest log-weight so far. No atomics; every cell of
+ * state is owned by one lane: launches ordered on a stream give the same bits each time.
+ * Checked before any HIP call: null pointers; B, Z > 0; leading dimensions >= Z; state 16-byte aligned; recon_scale finite and > 0. */
+int mst_iw_fold(int64_t B, int64_t Z, const float* eps, int64_t ld_eps, const float* sigma, int64_t ld_sigma, const float* z, int64_t ld_z,
+                const float* recon, double recon_scale, double* state, mst_stream_t stream);
+/* mst_iw_finish — the bound from the folded state. out: double [B][4] =
+ *   {log_px = m + log(s) - log(n),  elbo = sum_lw / n,  ess = s^2 / s2,  n}
+ * A sample with n == 0 or n_bad > 0 is INVALID: its out row is NaN except the n entry. acc: double [6], ADDED to —
+ *   {sum log_px, sum elbo, sum ess, sum n, pieces counted, pieces invalid}
+ * over the valid samples (an invalid one adds 1 to acc[5] only), in ascending sample order, by one thread: a validation set
+ * accumulates on the device and is read once. One workgroup; plain stores. log_px >= elbo (Jensen) and 1 <= ess <= n up to rounding. */
+int mst_iw_finish(int64_t B, const double* state, double* out, double* acc, mst_stream_t stream);
+
 /* standalone reparameterisation + KL (loss.VariationalKLLoss, loss.py:4-12; model.py:292) */
 int mst_reparam_kl_fwd(int64_t B, int64_t Z, const float* mu, const float* sigma, const float* eps,
                        float* z, float* kl, mst_stream_t stream);

@@ -3,7 +3,7 @@
 The flag set is the reference's, name for name and default for default (config.py:19-70), because
 scripts/train-vae.sh passes them; unknown flags are ignored as there (parse_known_args, :73-75). The flags
 are declared as a table. The additions (group MI355X) are all off by default: --pianoroll (attach the piano-roll ends), --dtype,
---d-causal, the training schedules, --clip-global-norm, --ema-decay, --d-input-dropout and --latent-stats."""
+--d-causal, the training schedules, --clip-global-norm, --ema-decay, --d-input-dropout, --latent-stats and --iw-samples."""
 import argparse
 import copy
 import inspect
@@ -82,6 +82,11 @@ _FLAGS = [
     # mst_latent_dim_stats) and read with the other running sums: the log lines, the scalar log and the validation line gain
     # active_units, kl_dims_used, kl_dim_max, sigma_rms and class_leak (engine.latent_scores). Off: the step and its metrics as before.
     ("MI355X", ("--latent-stats",), dict(action="store_true")),
+    # K of the importance-weighted bound on log p(x) (engine.IWBound; include/mst_hip.h: mst_iw_fold): after the validation pass of a
+    # checkpoint the trainer scores the same batches from K posterior draws each — one full inference forward and K - 1 replays of a
+    # captured decoder-only pass — and the validation line, last_validation and the scalar log gain iw_nll, iw_elbo_nll, iw_gap, iw_ess,
+    # iw_bits_per_cell and iw_invalid (engine.iw_scores). Early stopping still compares total_loss. 0: off, validation as before.
+    ("MI355X", ("--iw-samples",), dict(type=int, default=0)),
 ]
 
 

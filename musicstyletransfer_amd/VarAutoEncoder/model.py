@@ -289,6 +289,34 @@ class Model:
         plan.forward(inference=True, upto="latent")
         return plan.mu.clone(), plan.sigma.clone()
 
+    def iw_runner(self, plan, acc=None):
+        """the engine.IWBound of a plan of this model, made at first use and kept with the plan (its captured draw pass with it)"""
+        iw = plan.__dict__.get("_iw")
+        if iw is None:
+            iw = plan._iw = E.IWBound(plan, acc=acc)
+        elif acc is not None:
+            iw.acc = acc
+        return iw
+
+    def iw_bound(self, tokens, seq_lens, classes, labels, samples=1, keep_draws=False):
+        """the importance-weighted bound on log p(labels | class) of every piece of the batch from `samples` posterior draws
+        (engine.IWBound), in inference mode and with the plain likelihood. Returns host arrays per piece — log_px, elbo, ess,
+        n, valid — plus acc (the batch's six sums, engine.iw_scores' input) and cells (cells per piece); with keep_draws also draws, the
+        [K, ...] device buffers of every draw's eps, sigma, z, recon and seed."""
+        if self.store is None:
+            raise RuntimeError("call initialize(ctx) first")
+        E.check_iw(samples)
+        x = np.asarray(tokens.cpu() if torch.is_tensor(tokens) else tokens)
+        B, T = x.shape[0], x.shape[1]
+        plan = self.plan(B, T, want_probs=False, internal_eps=True)
+        plan.load_batch(x, seq_lens, classes, labels)
+        iw = self.iw_runner(plan).run(samples, keep_draws=keep_draws, reset_acc=True)
+        res = iw.results()
+        res.update(acc=iw.read_acc(reset=True), cells=iw.cells)
+        if keep_draws:
+            res["draws"] = iw.draws
+        return res
+
     # -- checkpoints (utils.save_model / load_model_parameters)
     def save_parameters(self, fname):
         np.savez(fname if fname.endswith(".npz") else fname + ".npz", **self.store.to_numpy("w"))

@@ -18,7 +18,7 @@ import torch
 from . import utils
 from .config import Config
 from .. import parallel
-from ..engine import check_clip, check_ema, check_input_dropout, check_schedule, latent_scores, roll_scores
+from ..engine import check_clip, check_ema, check_input_dropout, check_iw, check_schedule, iw_scores, latent_scores, roll_scores
 from ..pianoroll import PinnedBatchPipeline
 
 
@@ -46,14 +46,19 @@ class TrainConfig(Config):
     (engine.check_input_dropout; include/mst_hip.h: mst_step_begin_args.in_*), in [0, 1]; 0: off. Validation never drops.
     latent_stats: the steps keep per-class, per-dimension sums of the posterior's mu, sigma and KL on the device, and the metrics gain
     active_units, kl_dims_used, kl_dim_max, sigma_rms and class_leak (engine.latent_scores); False: off.
+    iw_samples: K of the importance-weighted bound on log p(x) the trainer computes over the validation set after each checkpoint's
+    validation pass (engine.IWBound, engine.iw_scores), an integer >= 1; 0: off. Early stopping still compares total_loss.
     YAML-serialisable (Config): a file written before a field existed loads with that field's default."""
 
     def __init__(self, batch_size: int, sampling_frequency: int, checkpoint_frequency: int, num_checkpoints_not_improved: int,
                  optimizer: OptimizerConfig, kl_loss: float, label_smoothing: float, negative_label_downscaling: bool,
                  verbose: bool, dtype: str = "bf16", max_steps: int = 0, kl_warmup_steps: int = 0, kl_cycle_steps: int = 0,
                  kl_free_bits: float = 0.0, lr_warmup_steps: int = 0, clip_global_norm: float = 0.0, ema_decay: float = 0.0,
-                 d_input_dropout: float = 0.0, latent_stats: bool = False):
+                 d_input_dropout: float = 0.0, latent_stats: bool = False, iw_samples: int = 0):
         super().__init__()
+        if iw_samples != 0:
+            check_iw(iw_samples)
+        self.iw_samples = iw_samples
         check_schedule(kl_warmup_steps, kl_cycle_steps, kl_free_bits, lr_warmup_steps)
         check_clip(clip_global_norm)
         self.clip_global_norm = clip_global_norm
@@ -167,6 +172,11 @@ class Trainer:
         # ... and the per-dimension latent statistics (not a hyper-parameter: a flag of the plan, set in _plan)
         self.latent_stats = bool(getattr(self.config, "latent_stats", False))
         self.last_latent_stats = None  # engine.latent_scores of the latest collect_metrics()
+        # ... and the importance-weighted bound over the validation set (not a hyper-parameter either: _iw_validation)
+        self.iw_samples = getattr(self.config, "iw_samples", 0)
+        if self.iw_samples != 0:
+            check_iw(self.iw_samples)
+        self._iw_acc = None  # the six fp64 sums every IWBound of a validation adds to, made at first use
         self.opt_extra = {k: v for k, v in extra.items() if k in ("beta1", "beta2", "epsilon", "wd")}
 
     # ------------------------------------------------------------------ the hot loop
@@ -390,6 +400,42 @@ class Trainer:
         self.summary_writer.add_scalar(tag="global_grad", value=sum(norms.values()) / max(1, len(norms)),
                                        global_step=self.train_state.n_batches)
 
+    def _iw_validation(self, validation_dataset):
+        """The importance-weighted bound on log p(x) over the validation set from iw_samples draws per piece (engine.IWBound): called
+        inside the validation's own context — the trainer's stream, the averaged weights where the run keeps them. Every batch's
+        runner adds to the same six device sums, which are read once; data parallel: each rank scores its shard (eps per global sample
+        index, plan.sample_offset) and the sums — with the cell and piece counts, in the same tensor — are all-reduced once, by every
+        rank unconditionally. Inference passes on the store's inference RNG stream: the training steps after it are what they would
+        have been. Returns engine.iw_scores' dict (cells per piece: the mean over the pieces scored); the figures also go to the scalar log."""
+        st = self.model.store
+        if self._iw_acc is None:
+            self._iw_acc = torch.zeros(6, dtype=torch.float64, device=st.device)
+        acc = self._iw_acc
+        acc.zero_()
+        cells = pieces = 0
+        for batch in validation_dataset:
+            tokens, seq_lens, classes = batch.data
+            labels = batch.label[0]
+            shard = self._shard(batch)
+            if shard is not None:
+                lo, hi = shard
+                tokens, seq_lens, classes, labels = tokens[lo:hi], seq_lens[lo:hi], classes[lo:hi], labels[lo:hi]
+            plan = self._plan(tokens.shape[0], tokens.shape[1])
+            plan.bind_inputs(plan.own_inbuf)
+            plan.load_batch(tokens, seq_lens, classes, labels)
+            iw = self.model.iw_runner(plan, acc=acc).run(self.iw_samples)
+            cells += plan.B * iw.cells
+            pieces += plan.B
+        t = torch.cat([acc, torch.tensor([cells, pieces], dtype=torch.float64, device=st.device)])
+        if self.dist is not None:
+            self.dist.all_reduce(t)
+        sums = t.tolist()
+        scores = iw_scores(sums[:6], sums[6] / sums[7] if sums[7] else 1.0)
+        if self.summary_writer is not None:
+            for name, val in scores.items():
+                self.summary_writer.add_scalar(tag=name, value=val, global_step=self.train_state.n_batches)
+        return scores
+
     # ------------------------------------------------------------------ checkpoint / resume (trainer.py:188-233)
     def _load_latest_checkpoint(self, model_folder):
         print("Looking into folder {} for a valid training.".format(model_folder))
@@ -438,6 +484,8 @@ class Trainer:
             for batch in validation_dataset:
                 self._step(batch, is_train=False)
             vals = self.collect_metrics(reset=True)
+            if self.iw_samples > 0:
+                vals.update(self._iw_validation(validation_dataset))
         loss = vals["total_loss"]
         if loss < self.train_state.best_resconstruction_loss:
             print("Loss improved from {} to {}.".format(self.train_state.best_resconstruction_loss, loss))

@@ -823,6 +823,36 @@ def latent_scores(acc, threshold=0.01):
                 sigma_rms=float(np.sqrt((s_s2[seen] / n[seen]).mean())) if seen.any() else nan, class_leak=leak)
 
 
+def iw_scores(acc, cells):
+    """the six running sums of IWBound (ops.IW_ACC: sum log_px, sum elbo, sum ess, sum n, pieces counted, pieces invalid — mst_iw_finish)
+    as the reported figures, stated once. cells: cells per piece (T * P for a piano-roll, T for a token sequence). Nats per piece:
+      iw_nll            -sum log_px / pieces     the importance-weighted bound on -log p(x)
+      iw_elbo_nll       -sum elbo / pieces       the same draws' mean log-weight: the ELBO in nats
+      iw_gap            iw_elbo_nll - iw_nll     >= 0 (Jensen); near 0: the posterior is tight, or the decoder ignores z
+      iw_ess            sum ess / pieces         effective sample size of the weights, between 1 and K
+      iw_bits_per_cell  iw_nll / (cells ln 2)
+      iw_invalid        pieces with a draw that was not finite (in none of the sums)
+    NaN where no piece was counted."""
+    acc = np.asarray(acc, np.float64).reshape(-1)
+    if acc.size != 6:
+        raise ValueError(f"iw_scores takes the six sums of mst_iw_finish, not {acc.size} values")
+    if not cells > 0:
+        raise ValueError(f"cells per piece must be positive, not {cells!r}")
+    pieces, nan = acc[4], float("nan")
+    nll = -acc[0] / pieces if pieces > 0 else nan
+    elbo_nll = -acc[1] / pieces if pieces > 0 else nan
+    return dict(iw_nll=float(nll), iw_elbo_nll=float(elbo_nll), iw_gap=float(elbo_nll - nll),
+                iw_ess=float(acc[2] / pieces) if pieces > 0 else nan, iw_bits_per_cell=float(nll / (cells * math.log(2.0))),
+                iw_invalid=int(acc[5]))
+
+
+def check_iw(samples):
+    """samples: K of the importance-weighted bound, an integer >= 1 (1: the one-sample ELBO); raises ValueError otherwise (a NaN, a
+    bool and a fraction too)"""
+    if isinstance(samples, bool) or not isinstance(samples, (int, np.integer)) or samples < 1:
+        raise ValueError(f"iw_samples must be an integer >= 1, not {samples!r}")
+
+
 def check_schedule(kl_warmup_steps=0, kl_cycle_steps=0, kl_free_bits=0.0, lr_warmup_steps=0):
     """the combinations of training-schedule settings that mean something; raises ValueError otherwise"""
     for name, val in (("kl_warmup_steps", kl_warmup_steps), ("kl_cycle_steps", kl_cycle_steps), ("lr_warmup_steps", lr_warmup_steps)):
@@ -1356,16 +1386,25 @@ class StepPlan:
             return (self.T, self.T + 1, 1)
         return None
 
-    def forward(self, inference=False, upto=None, with_grad=False):
+    def forward(self, inference=False, upto=None, with_grad=False, start=None):
         """inference=True: the forward pass as the reference runs it OUTSIDE autograd.record() (Model(...) called directly, the
         samplers: sampler.py:146-148) — every Dropout is the identity and the training RNG stream is left alone (an eps the
         caller did not supply is drawn from the store's inference stream).
         upto="latent" (inference only): stop behind the latent launch — mu, sigma, z and decoder row 0 are there, no decoder layer,
         output layer or loss launch is issued (Model.encode).
         with_grad=True (fwd_bwd_kernels, a training step): the caller issues losses(with_grad=True) next — where Forms.dec_tail holds,
-        the last decoder layer's row-wise block is left to that launch and dec_out is filled by it, not by forward()."""
-        if with_grad and (inference or upto):
+        the last decoder layer's row-wise block is left to that launch and dec_out is filled by it, not by forward().
+        start="latent" (inference only): a DRAW PASS — the decoder half alone, on the encoder output the preceding full inference forward
+        of this plan left (IWBound). One bookkeeping launch of its own (a new seed and eps from the store's inference stream for a plan
+        with internal_eps, the recon buffer cleared), the latent launch, the decoder layers and the output layer: no encoder launch.
+        Rows 1..T of the decoder input do not depend on z and no decoder launch writes them, so they are reused, as is — where the
+        forward tail's riders made it — the first K | Q | V projection of those rows. start=None issues the launches it always did."""
+        if with_grad and (inference or upto or start):
             raise ValueError("forward(with_grad=True) is the forward pass of a training step")
+        if start not in (None, "latent") or (start and (not inference or upto)):
+            raise ValueError("forward(start=...) takes 'latent', in inference mode and without upto")
+        if start and getattr(self, "enc_out", None) is None:
+            raise RuntimeError("forward(start='latent') needs the encoder output of a preceding full forward(inference=True) of this plan")
         if upto not in (None, "latent") or (upto and not inference):
             raise ValueError("forward(upto=...) takes 'latent', in inference mode only")
         cfg, st, B, T = self.cfg, self.store, self.B, self.T
@@ -1402,11 +1441,15 @@ class StepPlan:
                 roll_d = self.roll_d
                 begin["input_drop"].update(src=self.roll, dst=roll_d)  # (the bound blob's frames: bind_inputs)
         # (piano-roll ends: nothing in the embedding GEMMs reads what the bookkeeping writes — it rides on their launch)
-        ride = cfg.kind != "token"
-        if not ride:
+        ride = cfg.kind != "token" and not start
+        if start:  # the draw pass's own bookkeeping: seed + eps, the recon buffer; masks and decoder rows 1..T stand as they are
+            o.step_begin(rng_state=begin["rng_state"], eps_out=begin["eps_out"], eps_index0=begin["eps_index0"], zero_a=self._recon_buf)
+        elif not ride:
             o.step_begin(**begin)
         # ---- encoder input (model.py:81-91, transformer.py:270)
-        if cfg.kind == "token":
+        if start:
+            pass
+        elif cfg.kind == "token":
             o.embed_fwd(self.tokens, st.p("encoder.embedding.weight"), self.pos_e, self.x0_e.view(B, Se, -1), 0, sq_e,
                         classes=self.classes, cls_table=st.p("encoder.class2hid.weight"), keymask=self.keymask_e)
         else:
@@ -1417,8 +1460,8 @@ class StepPlan:
                                 alpha=sq_d,
                                 rowadd=self.pos_d[1:], rowadd_period=T, c_remap=(T, Sd, 1)),
                            begin=begin if ride else None)
-        x = self.x0_e
-        for i, L in enumerate(self.enc):
+        x = self.enc_out if start else self.x0_e
+        for i, L in enumerate(() if start else self.enc):
             x = self._layer_fwd("encoder", i, L, x, self.keymask_e, De, cfg.e_heads, Se, self.e_p, self._site_e(i))
         self.enc_out = x
         # ---- latent block + decoder position 0 (model.py:97-103,292,229-232)
@@ -1438,7 +1481,7 @@ class StepPlan:
         if upto == "latent":
             return
         # ---- decoder positions 1..T (model.py:241-245, transformer.py:237)
-        if cfg.kind == "token":
+        if cfg.kind == "token" and not start:
             o.embed_fwd(self.tokens, st.p("decoder.embedding.weight"), self.pos_d, self.x0_d.view(B, Sd, -1), 1, sq_d, keep=keep_d)
         x = self.x0_d
         site_d = self._site_d(0)
@@ -1451,15 +1494,20 @@ class StepPlan:
             o.gemm_nt(x, st.h("decoder.output_layer.weight"), self.logits, M=B * T, K=Dd, bias=st.p("decoder.output_layer.bias"),
                       a_remap=(T, Sd, 1))
 
-    def losses(self, with_grad=True, combine=True):
-        """combine=False: the total loss / running metric sums are left to optimizer() (they ride on the Adam launch)"""
+    def losses(self, with_grad=True, combine=True, plain=False):
+        """combine=False: the total loss / running metric sums are left to optimizer() (they ride on the Adam launch).
+        plain=True (without gradient: IWBound): the plain likelihood whatever the training configuration says — label smoothing 0,
+        down-weighting off — and nothing added to the trainer's token / piano-roll metric sums"""
         cfg, B, T, F = self.cfg, self.B, self.T, self.forms
+        if plain and with_grad:
+            raise ValueError("losses(plain=True) is a likelihood, not a training loss: with_grad=False")
+        ls, nld = (0.0, False) if plain else (self.ls, self.nld)
         dl = self.dlogits if with_grad else None
-        counts = self.store.roll_counts if self.track_roll_metrics else None
+        counts = self.store.roll_counts if self.track_roll_metrics and not plain else None
         if cfg.kind == "token":
             o.softmax_ce(self.logits, self.labels, self.recon, B, T, cfg.out_dim, probs=self.probs, dlogits=dl,
                          gscale=self.gscale, pre_zeroed=True,
-                         tok_parts=self.store.tok_parts if self.track_token_metrics else None)
+                         tok_parts=self.store.tok_parts if self.track_token_metrics and not plain else None)
         elif F.fuse_bce:
             dgrad = None
             if F.dec_tail and not with_grad:
@@ -1473,7 +1521,7 @@ class StepPlan:
                              **self._out_ln_bwd("decoder", last, self.dec[last], cfg.d_dropout, self._site_d(0) + 3 * last,
                                                 self.bd_l[last], B * T))
             loss = dict(A=self.dec_out, B=self.store.h("decoder.output_layer.weight"), labels=self.labels, loss=self.recon, T=T,
-                        dlogits=dl, probs=self.probs, label_smoothing=self.ls, downweight=self.nld, gscale=self.gscale, M=B * T,
+                        dlogits=dl, probs=self.probs, label_smoothing=ls, downweight=nld, gscale=self.gscale, M=B * T,
                         K=cfg.d_model, bias=self.store.p("decoder.output_layer.bias"), a_remap=(T, T + 1, 1), counts=counts)
             if F.dec_tail:
                 # ... and around it, in the same workgroups again, the last decoder layer's row-wise block (forward() left it out) and
@@ -1486,8 +1534,8 @@ class StepPlan:
             else:
                 o.gemm_sigmoid_bce(dgrad=dgrad, **loss)
         else:
-            o.sigmoid_bce(self.logits, self.labels, self.recon, B, T, cfg.out_dim, label_smoothing=self.ls,
-                          downweight=self.nld, npos=self.npos, probs=self.probs, dlogits=dl, gscale=self.gscale,
+            o.sigmoid_bce(self.logits, self.labels, self.recon, B, T, cfg.out_dim, label_smoothing=ls,
+                          downweight=nld, npos=self.npos, probs=self.probs, dlogits=dl, gscale=self.gscale,
                           pre_zeroed=True, counts=counts)
         if combine:
             o.loss_combine(self.recon, self.kl, self.kl_weight, self.total, self.metric_acc, guard=self._guard())
@@ -1827,3 +1875,110 @@ class StepPlan:
                 "kl_weight": m.get("kl_weight", self.kl_weight) if self.scheduled else self.kl_weight,
                 "lr_scale": m.get("lr_scale", 1.0) if self.scheduled else 1.0,
                 **{k: m[k] for k in ("grad_norm", "grad_norm_max", "clip_frac") if k in m}}
+
+
+class IWBound:
+    """The importance-weighted bound on log p(x) of the batch in `plan`'s input buffers from K posterior draws (Burda et al.):
+    log p(x) ~= log (1/K) sum_k p(x | z_k) p(z_k) / q(z_k | x), folded on the device (mst_iw_fold / mst_iw_finish).
+
+    run(K): state is zeroed; ONE full inference forward encodes the batch and is draw 1; draws 2..K are draw passes
+    (StepPlan.forward(inference=True, start="latent")): the decoder half alone, from one captured graph that is replayed — the draws
+    differ between replays because the seed lives on the device (the store's INFERENCE stream: the training stream is left alone).
+    Every draw is scored with the plain likelihood (StepPlan.losses(plain=True)) and folded; mst_iw_finish then writes the per-piece
+    rows into `out` and ADDS the batch's sums to `acc`, which several runners may share (the trainer's validation set: one read).
+
+    plan: a StepPlan with internal_eps (eps is drawn per global sample index, plan.sample_offset: a data-parallel shard draws what
+    the whole batch draws for its samples). The first draw pass of a runner is issued eagerly (HIP modules load lazily and are not
+    capturable), the graph is captured once and kept while the plan's launch forms and bound input blob stay what they were.
+    keep_draws=True (tests, small shapes): every draw's eps, sigma, z, recon and seed are copied to [K, ...] buffers (self.draws);
+    that path issues every draw eagerly."""
+
+    def __init__(self, plan, acc=None):
+        if not plan.internal_eps:
+            raise ValueError("IWBound needs a plan that draws its own eps (StepPlan(internal_eps=True))")
+        cfg, dev = plan.cfg, plan.dev
+        self.plan = plan
+        self.cells = plan.T * (cfg.out_dim if cfg.kind == "pianoroll" else 1)  # what the mean reconstruction loss was taken over
+        self.recon_scale = float(self.cells)
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.state = torch.zeros(plan.B, len(o.IW_STATE), **f64)
+        self.out = torch.zeros(plan.B, len(o.IW_OUT), **f64)
+        self.acc = acc if acc is not None else torch.zeros(len(o.IW_ACC), **f64)
+        self.graph, self._graph_key = None, None
+        self.captures = 0       # graphs captured so far (one, unless the plan's forms or input blob changed)
+        self._warm = False      # an eager draw pass has run
+        self.draws = None
+        self.stream = torch.cuda.Stream(device=dev)  # capture needs a stream of its own
+
+    def _score(self):
+        """the plain likelihood of the pass just issued, folded into state"""
+        p = self.plan
+        p.losses(with_grad=False, combine=False, plain=True)
+        o.iw_fold(p.eps, p.sigma, p.z, p.recon, self.recon_scale, self.state)
+
+    def draw_pass(self):
+        """one draw: the decoder half on a new eps, its likelihood, the fold (the kernel sequence of the captured graph)"""
+        self.plan.forward(inference=True, start="latent")
+        self._score()
+
+    def graph_nodes(self):
+        """(nodes, kernel launches among them) of the captured draw pass"""
+        if self.graph is None:
+            raise RuntimeError("no draw pass has been captured yet (run() with samples >= 3)")
+        return self.graph.nodes, self.graph.kernel_nodes
+
+    def _record(self, k):
+        p, d = self.plan, self.draws
+        for name in ("eps", "sigma", "z", "recon"):
+            d[name][k].copy_(getattr(p, name))
+        d["seed"][k].copy_(p.store.rng_state_inference()[0])
+
+    def run(self, samples, keep_draws=False, reset_acc=False):
+        """the bound of the batch in the plan's input buffers from `samples` draws; results() reads it. reset_acc: acc is cleared first
+        (it then holds this batch's sums alone)"""
+        check_iw(samples)
+        p, K = self.plan, int(samples)
+        self.stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self.stream):
+            self.draws = None
+            if keep_draws:
+                f32 = dict(dtype=torch.float32, device=p.dev)
+                Z = p.cfg.latent_dim
+                self.draws = dict(eps=torch.zeros(K, p.B, Z, **f32), sigma=torch.zeros(K, p.B, Z, **f32), z=torch.zeros(K, p.B, Z, **f32),
+                                  recon=torch.zeros(K, p.B, **f32), seed=torch.zeros(K, dtype=torch.int64, device=p.dev))
+            o.zero(self.state)
+            if reset_acc:
+                o.zero(self.acc)
+            p.forward(inference=True)  # encodes, and is draw 1
+            self._score()
+            if keep_draws:
+                self._record(0)
+            key = (p.forms, p.inbuf.data_ptr())
+            for k in range(1, K):
+                if keep_draws or not self._warm:
+                    self.draw_pass()
+                    self._warm = True
+                    if keep_draws:
+                        self._record(k)
+                    continue
+                if self.graph is None or self._graph_key != key:
+                    self.graph, self._graph_key = o.Graph().capture(self.draw_pass), key
+                    self.captures += 1
+                self.graph.launch()
+            o.iw_finish(self.state, self.out, self.acc)
+        torch.cuda.current_stream().wait_stream(self.stream)  # the caller reads the results on its own stream
+        return self
+
+    def results(self):
+        """per piece, as host arrays: log_px, elbo, ess, n (draws folded) and valid (False: a draw was not finite; the three figures are NaN)"""
+        out = self.out.cpu().numpy()
+        res = {name: out[:, i].copy() for i, name in enumerate(o.IW_OUT)}
+        res["valid"] = ~np.isnan(out[:, 0])
+        return res
+
+    def read_acc(self, reset=True):
+        """the six running sums (ops.IW_ACC) as a host array: one device->host read; iw_scores turns them into the reported figures"""
+        acc = self.acc.cpu().numpy().copy()
+        if reset:
+            o.zero(self.acc)
+        return acc

@@ -19,6 +19,10 @@ label k):
   * token ends: the piece is the token row with its EOS, [B, T + 1]; position i emits the token at index i, index 0 is SOS and is
     never held, and the EOS of a row of seq_len tokens (SOS included) sits at index seq_len.
 
+likelihood is not generation at all: the importance-weighted bound on log p(piece | class) from K posterior draws per melody
+(Model.iw_bound: engine.IWBound), the teacher-forced likelihood of the training step under K latent vectors — where score
+decodes the piece under ONE z (the mean) through a graph per position. It prints one line per melody and writes no files.
+
     python -m music_style_transfer.VarAutoEncoder.generate --model-output DIR --mode transfer --data MIDI_DIR --out OUT_DIR
 """
 import argparse
@@ -27,7 +31,7 @@ import os
 
 import numpy as np
 
-MODES = ("prior", "posterior", "interpolate", "transfer", "blend", "continue", "repaint", "score")
+MODES = ("prior", "posterior", "interpolate", "transfer", "blend", "continue", "repaint", "score", "likelihood")
 DECODERS = ("sampling", "greedy", "beam")
 
 
@@ -495,6 +499,19 @@ class LatentGenerator:
                          held_scores=np.concatenate(held) if given is not None else None, hold=hold)
 
 
+def likelihood_lines(model, batch, samples):
+    """--mode likelihood: one line per melody of the batch — the importance-weighted bound on -log p (nats), the same draws' ELBO, the
+    effective sample size of the weights, bits per cell, and whether every draw was finite"""
+    if not batch.label:
+        raise ValueError("the likelihood of a piece is that of the batch's labels: the batch has no label")
+    tokens, seq_lens, classes = batch.data[:3]
+    res = model.iw_bound(tokens, seq_lens, classes, batch.label[0], samples=samples)
+    per_cell = res["cells"] * math.log(2.0)
+    return ["melody {} class {} nll {:.6f} elbo_nll {:.6f} ess {:.3f} bits_per_cell {:.6f} valid {}".format(
+        i, int(c), -res["log_px"][i], -res["elbo"][i], res["ess"][i], -res["log_px"][i] / per_cell, int(res["valid"][i]))
+        for i, c in enumerate(np.asarray(classes).reshape(-1))]
+
+
 # ---------------------------------------------------------------------- command line
 def build_parser():
     p = argparse.ArgumentParser(prog="python -m music_style_transfer.VarAutoEncoder.generate",
@@ -506,7 +523,9 @@ def build_parser():
     src = p.add_mutually_exclusive_group()
     src.add_argument("--data", default=None, help="MIDI folder (one sub-folder per class); the first batch is used")
     src.add_argument("--toy", action="store_true", help="the three toy sequences instead of --data")
-    p.add_argument("--out", default=None, help="folder the .mid files are written to (every mode but score, which prints)")
+    p.add_argument("--out", default=None, help="folder the .mid files are written to (every mode but score and likelihood, which print)")
+    p.add_argument("--iw-samples", type=int, default=16, metavar="K",
+                   help="likelihood: posterior draws per melody of the importance-weighted bound (>= 1; 1 is the one-sample ELBO)")
     p.add_argument("--n", type=int, default=4, help="prior: number of pieces; posterior: draws per melody; continue: continuations per melody")
     p.add_argument("--prime", type=int, default=None, metavar="N", help="continue: hold the first N frames / tokens of every melody")
     p.add_argument("--keep-time", type=int, nargs=2, default=None, metavar=("A", "B"),
@@ -550,7 +569,7 @@ def _first_batch(args, kind):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    if args.mode != "score" and args.out is None:
+    if args.mode not in ("score", "likelihood") and args.out is None:
         raise SystemExit("--mode {} needs --out DIR".format(args.mode))
     if args.mode == "continue" and args.prime is None:
         raise SystemExit("--mode continue needs --prime N")
@@ -584,6 +603,10 @@ def main(argv=None):
                 raise SystemExit("--keep-pitch names piano-roll pitches; a token model keeps --keep-time A B")
             keep = hold_mask(lens, piece.shape[1], None if token else piece.shape[2], time=args.keep_time, pitch=args.keep_pitch)
             out = gen.repaint(batch, keep, args.classes or None, length=args.length)
+        elif args.mode == "likelihood":
+            lines = likelihood_lines(model, batch, args.iw_samples)
+            print("\n".join(lines))
+            return lines
         elif args.mode == "score":
             out = gen.score(batch, args.classes or None)
             lines = ["melody {} class {} nll {:.6f}".format(r["melody"], r["cls"], float(s)) for r, s in zip(out.rows, out.held_scores)]

@@ -862,6 +862,31 @@ def latent_dim_stats(mu, sigma, classes, acc):
     call("mst_latent_dim_stats", B, Z, acc.shape[0], ptr(mu), ld(mu), ptr(sigma), ld(sigma), ptr(classes), ptr(acc), stream())
 
 
+IW_STATE = ("m", "s", "s2", "sum_lw", "n", "n_bad")  # cells of iw_fold's per-sample state, in order
+IW_OUT = ("log_px", "elbo", "ess", "n")              # columns of iw_finish's per-sample rows
+IW_ACC = ("log_px", "elbo", "ess", "n", "pieces", "invalid")  # iw_finish's running sums
+
+
+def iw_fold(eps, sigma, z, recon, recon_scale, state):
+    """one posterior draw folded into state (fp64 [B, 6], contiguous; mst_iw_fold): eps, sigma, z fp32 [B, Z] views (rows may be
+    padded), recon fp32 [B], recon_scale the number of cells the mean reconstruction loss was taken over"""
+    B, Z = eps.shape
+    for t in (eps, sigma, z):
+        assert t.dtype == torch.float32 and tuple(t.shape) == (B, Z)
+    assert recon.dtype == torch.float32 and recon.numel() == B and recon.is_contiguous()
+    assert state.dtype == torch.float64 and state.is_contiguous() and tuple(state.shape) == (B, len(IW_STATE))
+    call("mst_iw_fold", B, Z, ptr(eps), ld(eps), ptr(sigma), ld(sigma), ptr(z), ld(z), ptr(recon), float(recon_scale), ptr(state), stream())
+
+
+def iw_finish(state, out, acc):
+    """out (fp64 [B, 4]) = {log_px, elbo, ess, n} of every sample of state; acc (fp64 [6]) += their sums over the valid samples and the
+    two counts (mst_iw_finish)"""
+    B = state.shape[0]
+    assert state.dtype == out.dtype == acc.dtype == torch.float64 and state.is_contiguous() and out.is_contiguous() and acc.is_contiguous()
+    assert tuple(state.shape) == (B, len(IW_STATE)) and tuple(out.shape) == (B, len(IW_OUT)) and acc.numel() == len(IW_ACC)
+    call("mst_iw_finish", B, ptr(state), ptr(out), ptr(acc), stream())
+
+
 LATENT_ROWS_SITE = 0x7FFE0000  # the generator's eps stream (the training step's eps site is 0x7FFF0000)
 INTERP = {"lerp": 0, "slerp": 1}
 

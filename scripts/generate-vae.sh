@@ -4,6 +4,8 @@
 # [--n K] | repaint [--keep-time A B] [--keep-pitch LO HI] | score (python -m ...generate --help); whatever the caller
 # passes in "$@" is appended (e.g. --mode interpolate --pair 0 3 --steps 9 --decoder greedy). The draw of --decoder sampling is the raw
 # softmax as set below; flags in "$@" come later and win, e.g. scripts/generate-vae.sh --sample-temperature 0.9 --top-k 40 --top-p 0.9.
+# --mode likelihood --iw-samples K prints the importance-weighted bound on log p(x) of every melody from K posterior draws (nll, elbo_nll,
+# ess, bits per cell, valid), one line per melody, and writes no files.
 # --ema (also through "$@") decodes with the checkpoint's averaged weights, for a model trained with --ema-decay.
 cd "$(dirname "$0")/.." || exit 1
 

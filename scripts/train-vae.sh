@@ -7,6 +7,8 @@
 #                         decoder has to use the latent (against posterior collapse, beside --kl-warmup-steps / --kl-free-bits); 0: off
 #   --latent-stats        log per-dimension statistics of the posterior, summed on the device inside the step: active_units,
 #                         kl_dims_used, kl_dim_max, sigma_rms and class_leak (how much of z's variation is between the classes)
+#   --iw-samples K        after every checkpoint's validation pass, score the validation set with the importance-weighted bound on
+#                         log p(x) from K posterior draws per piece: iw_nll, iw_elbo_nll, iw_gap, iw_ess, iw_bits_per_cell; 0: off
 cd "$(dirname "$0")/.." || exit 1
 
 python -m music_style_transfer.VarAutoEncoder.main \
