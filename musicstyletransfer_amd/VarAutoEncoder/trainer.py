@@ -18,7 +18,7 @@ import torch
 from . import utils
 from .config import Config
 from .. import parallel
-from ..engine import check_clip, check_ema, check_input_dropout, check_iw, check_schedule, iw_scores, latent_scores, roll_scores
+from ..step_math import check_clip, check_ema, check_input_dropout, check_iw, check_schedule, iw_scores, latent_scores, roll_scores
 from ..pianoroll import PinnedBatchPipeline
 
 

@@ -29,7 +29,9 @@ import torch
 
 from . import ops as o
 from .MIDIUtil.defaults import EOS_ID, PAD_ID, SOS_ID
-from .engine import ALL_ROWS, NO_DROPOUT, positional_table, roundup, row_block_fwd
+from .layer_block import ALL_ROWS, NO_DROPOUT, row_block_fwd
+from .ops import roundup
+from .spec import positional_table
 
 
 class PositionGraphs:

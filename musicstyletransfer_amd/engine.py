@@ -15,754 +15,23 @@ Layout in HBM
 There is no torch autograd, no torch operator and no CPU fallback on this path: backward is written
 out by hand below, mirroring the forward line by line.
 """
-import contextlib
 import math
-import os
-import warnings
-from collections import OrderedDict, namedtuple
+from collections import namedtuple
 
 import numpy as np
 import torch
 
 from . import ops as o
-from ._lib import CE_MAX_WORKGROUPS, ROLL_SLOTS
+from ._lib import CE_MAX_WORKGROUPS, ROLL_SLOTS  # noqa: F401  (re-exported)
 from .ops import roundup
-
-
-class VAEConfig:
-    """Shape of the model: the union of ModelConfig/EncoderConfig/DecoderConfig/TransformerConfig
-    (model.py:22-54, transformer.py:8-21) flattened, plus which ends are attached:
-    kind='token' (Embedding in, softmax-CE out: the reference's executed path) or
-    kind='pianoroll' (multi-hot frame x table in, sigmoid + BinaryCrossEntropy out)."""
-
-    def __init__(self, kind, in_dim, out_dim, num_classes, latent_dim, e_model, e_layers, e_heads, d_model, d_layers,
-                 d_heads, e_dropout=0.0, d_dropout=0.0, d_causal=False):
-        assert kind in ("token", "pianoroll")
-        assert e_model % e_heads == 0 and d_model % d_heads == 0  # transformer.py:134,167
-        self.kind = kind
-        self.in_dim, self.out_dim = in_dim, out_dim
-        self.num_classes, self.latent_dim = num_classes, latent_dim
-        self.e_model, self.e_layers, self.e_heads = e_model, e_layers, e_heads
-        self.d_model, self.d_layers, self.d_heads = d_model, d_layers, d_heads
-        self.e_dropout, self.d_dropout = float(e_dropout), float(d_dropout)
-        # d_causal: the decoder's self-attention is causal with a softmax over the keys (mst_attn_causal_fwd/bwd), the model
-        # DecodePlan(attention="key") samples from. Off: the reference's non-causal query-axis softmax (transformer.py:174,100).
-        self.d_causal = bool(d_causal)
-
-    def as_dict(self):
-        return dict(self.__dict__)
-
-
-def positional_table(model_size, max_len):
-    """transformer.py:204-211: exponent 2*i/D for every column, sin on even / cos on odd columns,
-    float64 then cast (host-side constant, built once)."""
-    pos = np.arange(max_len).reshape((-1, 1)) / np.power(10000, (2.0 / model_size) * np.arange(model_size).reshape((1, -1)))
-    pos[:, 0::2] = np.sin(pos[:, 0::2])
-    pos[:, 1::2] = np.cos(pos[:, 1::2])
-    return pos.astype(np.float32)
-
-
-def logical_param_shapes(cfg):
-    """name -> shape in the reference's construction order (model.py:57-71,206-227;
-    transformer.py:24-46,49-68,129-149,162-182): 58 tensors at e_layers=2, d_layers=1."""
-    s = OrderedDict()
-    De, Dd, Z, C = cfg.e_model, cfg.d_model, cfg.latent_dim, cfg.num_classes
-
-    def layer(prefix, D, last_ln):
-        for w in ("W_k", "W_q", "W_v", "W_proj"):
-            s[f"{prefix}.att.{w}.weight"] = (D, D)
-            s[f"{prefix}.att.{w}.bias"] = (D,)
-        s[f"{prefix}.ln1.gamma"] = (D,)
-        s[f"{prefix}.ln1.beta"] = (D,)
-        s[f"{prefix}.ff1.weight"] = (4 * D, D)
-        s[f"{prefix}.ff1.bias"] = (4 * D,)
-        s[f"{prefix}.ff2.weight"] = (D, 4 * D)
-        s[f"{prefix}.ff2.bias"] = (D,)
-        s[f"{prefix}.{last_ln}.gamma"] = (D,)
-        s[f"{prefix}.{last_ln}.beta"] = (D,)
-
-    s["encoder.class2hid.weight"] = (C, De)
-    s["encoder.embedding.weight"] = (cfg.in_dim, De)
-    for i in range(cfg.e_layers):
-        layer(f"encoder.layer{i}", De, "ln2")
-    s["encoder.latent_proj.weight"] = (2 * Z, De)
-    s["encoder.latent_proj.bias"] = (2 * Z,)
-    s["decoder.latent2hid.weight"] = (Dd, Z)
-    s["decoder.latent2hid.bias"] = (Dd,)
-    s["decoder.class2hid.weight"] = (C, Dd)
-    s["decoder.embedding.weight"] = (cfg.out_dim, Dd)
-    for i in range(cfg.d_layers):
-        layer(f"decoder.layer{i}", Dd, "ln3")
-    s["decoder.output_layer.weight"] = (cfg.out_dim, Dd)
-    s["decoder.output_layer.bias"] = (cfg.out_dim,)
-    return s
-
-
-def xavier_init(cfg, rng):
-    """trainer.py:103-105 model.initialize(mx.init.Xavier()): uniform, factor 'avg', magnitude 3 for
-    every '*weight' (Embedding tables included); biases / beta 0; gamma 1."""
-    out = OrderedDict()
-    for name, shape in logical_param_shapes(cfg).items():
-        if name.endswith("weight"):
-            fan_out, fan_in = shape[0], int(np.prod(shape[1:]))
-            scale = math.sqrt(3.0 / ((fan_in + fan_out) / 2.0))
-            out[name] = rng.uniform(-scale, scale, size=shape).astype(np.float32)
-        elif name.endswith("gamma"):
-            out[name] = np.ones(shape, np.float32)
-        else:
-            out[name] = np.zeros(shape, np.float32)
-    return out
-
-
-class ParamStore:
-    """Flat parameter / gradient / Adam-state buffers and their 16-bit shadows."""
-
-    def __init__(self, cfg, device, act_dtype=torch.bfloat16, params_np=None, seed=1234):
-        self.cfg, self.device, self.act_dtype = cfg, device, act_dtype
-        shapes = logical_param_shapes(cfg)
-        # flat order: per attention block the three K,Q,V weights first (fused [3D,D] GEMM), then their biases
-        order = []
-        for name in shapes:
-            if ".att.W_q." in name or ".att.W_v." in name:
-                continue
-            if name.endswith(".att.W_k.weight"):
-                p = name[: -len("W_k.weight")]
-                order += [p + "W_k.weight", p + "W_q.weight", p + "W_v.weight"]
-            elif name.endswith(".att.W_k.bias"):
-                p = name[: -len("W_k.bias")]
-                order += [p + "W_k.bias", p + "W_q.bias", p + "W_v.bias"]
-            else:
-                order.append(name)
-        if cfg.kind == "pianoroll":
-            # the class table right behind the input embedding: [in_dim + C, De] is then ONE matrix, and the class-embedding
-            # gradient is the last C rows of the embedding's weight-gradient problem (Forms.cls_fold)
-            order.remove("encoder.class2hid.weight")
-            order.insert(order.index("encoder.embedding.weight") + 1, "encoder.class2hid.weight")
-        self.shapes, self.offsets = shapes, OrderedDict()
-        off = 0
-        for name in order:
-            fused_tail = (".att.W_q." in name) or (".att.W_v." in name)
-            if not fused_tail:
-                off = roundup(off, 8)
-            self.offsets[name] = off
-            off += int(np.prod(shapes[name]))
-        self.n = roundup(off, 8)
-        self.n_params = sum(int(np.prod(s)) for s in shapes.values())
-        f32 = dict(dtype=torch.float32, device=device)
-        self.w = torch.zeros(self.n, **f32)
-        self.g = torch.zeros(self.n, **f32)
-        self.m = torch.zeros(self.n, **f32)
-        self.v = torch.zeros(self.n, **f32)
-        self.w16 = torch.zeros(self.n, dtype=act_dtype, device=device)
-        self.step_state = torch.zeros(2, dtype=torch.int32, device=device)
-
-        # transposed shadows: (source offset, rows, cols) -> dst [cols, roundup8(rows)]
-        self.t_specs = OrderedDict()
-        for side, D, L in (("encoder", cfg.e_model, cfg.e_layers), ("decoder", cfg.d_model, cfg.d_layers)):
-            for i in range(L):
-                p = f"{side}.layer{i}"
-                self.t_specs[f"{p}.att.W_kqv"] = (self.offsets[f"{p}.att.W_k.weight"], 3 * D, D)
-                self.t_specs[f"{p}.att.W_proj.weight"] = (self.offsets[f"{p}.att.W_proj.weight"], D, D)
-                self.t_specs[f"{p}.ff1.weight"] = (self.offsets[f"{p}.ff1.weight"], 4 * D, D)
-                self.t_specs[f"{p}.ff2.weight"] = (self.offsets[f"{p}.ff2.weight"], D, 4 * D)
-        self.t_specs["decoder.output_layer.weight"] = (self.offsets["decoder.output_layer.weight"], cfg.out_dim, cfg.d_model)
-        if cfg.kind == "pianoroll":
-            self.t_specs["encoder.embedding.weight"] = (self.offsets["encoder.embedding.weight"], cfg.in_dim, cfg.e_model)
-            self.t_specs["decoder.embedding.weight"] = (self.offsets["decoder.embedding.weight"], cfg.out_dim, cfg.d_model)
-        desc, prefix, doff, self.t_off = [], [0], 0, OrderedDict()
-        for name, (so, r, c) in self.t_specs.items():
-            self.t_off[name] = doff
-            desc += [so, doff, r, c]
-            doff += c * roundup(r, 8)
-            prefix.append(prefix[-1] + ((r + 31) // 32) * ((c + 31) // 32))
-        self.wt16 = torch.zeros(max(doff, 8), dtype=act_dtype, device=device)
-        self.t_desc = torch.tensor(desc, dtype=torch.int64, device=device)
-        self.t_prefix = torch.tensor(prefix, dtype=torch.int64, device=device)
-        self.t_tiles = prefix[-1]
-        # Deferred shadow refresh (piano-roll ends): the transposed shadows of the matrices only the BACKWARD pass reads are rebuilt by
-        # extra workgroups of the NEXT step's first launch (mst_gemm_nt_pair_begin, sh_*) instead of a launch of their own behind the
-        # optimizer; the two embedding tables, which that first launch itself reads, are kept current by the optimizer launch
-        # (mst_adam_args.emb). Token ends keep the separate launch.
-        emb_names = [n for n in ("encoder.embedding.weight", "decoder.embedding.weight") if n in self.t_specs]
-        late = [n for n in self.t_specs if n not in emb_names]
-        self.shadows_deferred = cfg.kind == "pianoroll" and len(emb_names) == 2 and len(late) > 0
-        ldesc, lprefix = [], [0]
-        for name in late:
-            so, r, c = self.t_specs[name]
-            ldesc += [so, self.t_off[name], r, c]
-            lprefix.append(lprefix[-1] + ((r + 31) // 32) * ((c + 31) // 32))
-        self.t_desc_late = torch.tensor(ldesc or [0, 0, 1, 1], dtype=torch.int64, device=device)
-        self.t_prefix_late = torch.tensor(lprefix, dtype=torch.int64, device=device)
-        self.t_n_late, self.t_tiles_late = len(late), lprefix[-1]
-        self.emb_specs = [(self.t_specs[n][0], self.t_off[n], self.t_specs[n][1], self.t_specs[n][2]) for n in emb_names]
-        # the views of every layer's parameters, built once: the flat buffers never move (captured graphs rely on that)
-        self._layers = {(side, i): self._layer_params(side, i)
-                        for side, n_l in (("encoder", cfg.e_layers), ("decoder", cfg.d_layers)) for i in range(n_l)}
-
-        # shared by every StepPlan of this store (plans run one after the other on one stream): the per-step RNG state
-        # — ONE stream of seeds however many (B, T) shapes a run goes through — and the weight-gradient work buffer
-        self._rng_state = None
-        self._wgrad_scratch = []
-        # running metric sums of every step since the last read (trainer.py:107-120,181-186), whatever plan ran it:
-        #   metric_acc = [sum kl, sum total, count]; tok_parts = per-workgroup partial rows of the masked token metrics
-        #   {sum -log p[label], #arg-max hits, #top-k hits, #valid} accumulated by mst_softmax_ce (token ends)
-        # step_status = three int32 words of the step guard (mst_step_metrics), read with the metrics (same device->host copy):
-        # {flags, skipped steps} — sticky, set on the device when a one-launch position-0 tail (mst_row_tail_*) could not finish —
-        # and the number of steps the optimizer skipped because a loss was not finite (not sticky: the next batch is tried again)
-        # sched = the fp32 schedule block {beta_t, tau, f_lr, t} the step's first launch writes for a plan with training schedules
-        # (schedule_values; mst_step_begin_args.sched*), read by that step's scheduled launches — and here, with the metrics
-        # gstat = the statistics block of global-norm clipping {norm, c, sum of norms, largest norm, steps, clipped steps}, written by
-        # the bookkeeping thread of every counted step of a plan with clip_global_norm (mst_adam_args.gstat), read with the metrics
-        self._metric_buf = torch.zeros(20, **f32)
-        self.metric_acc = self._metric_buf[:3]
-        self.step_status = self._metric_buf[4:7].view(torch.int32)
-        self.sched = self._metric_buf[8:12]
-        self.gstat = self._metric_buf[12:20]
-        self._grad_parts = None
-        # the exponential moving average of the weights (enable_ema): a second fp32 bucket at w's offsets, kept by the Adam launches of
-        # a plan with ema_decay. None for a store that does not average: it allocates what it always did
-        self.ema = None
-        self.ema_swapped = False      # True while w holds the averaged weights (swap_ema / ema_weights)
-        self.nonfinite_steps = 0      # steps skipped for a non-finite loss since the store was made (read_metrics adds them up)
-        self.tail_fused = os.environ.get("MST_ROW_TAIL", "1") != "0"  # False: the five-launch form of the position-0 tails
-        self.tail_checked = False     # row_tail_selfcheck() ran for this store
-        self.tail_policy = os.environ.get("MST_TAIL_FAILURE", "fallback")  # or "raise"
-        self.tail_failures = []       # (flags, skipped steps) of every failure seen
-        self._tail_listeners = []
-        self._rng_state_infer = None
-        self.tok_parts = torch.zeros(CE_MAX_WORKGROUPS, 4, **f32) if cfg.kind == "token" else None
-        # roll_counts = the piano-roll ends' slots of {tp, pred, pos, cells} the BCE launches add to (mst_bce_args.counts)
-        self.roll_counts = torch.zeros(ROLL_SLOTS, 4, dtype=torch.int64, device=device) if cfg.kind == "pianoroll" else None
-        # lat_stats = per class and latent dimension {n, sum mu, sum mu^2, sum sigma^2, sum kl_d} (mst_latent_dim_stats; latent_scores)
-        self.lat_stats = torch.zeros(cfg.num_classes, 5, cfg.latent_dim, dtype=torch.float64, device=device)
-        if params_np is None:
-            params_np = xavier_init(cfg, np.random.default_rng(seed))
-        self.load_numpy(params_np)
-
-    def rng_state(self, seed=0):
-        """uint64[4] device state of mst_step_begin / mst_rng_advance, created with the first plan's seed"""
-        if self._rng_state is None:
-            self._rng_state = torch.tensor([0, 0, seed ^ 0x5DEECE66D, 0], dtype=torch.int64, device=self.device)
-        return self._rng_state
-
-    def grad_parts(self):
-        """the per-workgroup sums of squares a step's mst_grad_sumsq launch leaves for its Adam launches (global-norm clipping), made
-        for the first plan that asks — a store without such a plan allocates what it always did — and never freed: captured graphs
-        keep the pointer"""
-        if self._grad_parts is None:
-            self._grad_parts = torch.zeros(o.grad_sumsq_parts(), dtype=torch.float32, device=self.device)
-        return self._grad_parts
-
-    def enable_ema(self):
-        """the average, made for the first plan (or trainer) that asks: a copy of w as it is now — at allocation time, never inside a
-        capture — and never freed or moved: captured graphs keep the pointer"""
-        if self.ema is None:
-            self.ema = self.w.clone()
-        return self.ema
-
-    def swap_ema(self):
-        """exchange the contents of w and ema in one launch (mst_ema_swap, which also writes w16 from the new w), then the shadow
-        refresh, so that every kernel consumes what a store loaded with those weights would. Contents move, pointers do not: every
-        captured graph stays valid. Exact: a second call puts back every bit."""
-        if self.ema is None:
-            raise RuntimeError("this store keeps no average of its weights (StepPlan(ema_decay=...) / enable_ema())")
-        o.ema_swap(self.w, self.ema, self.w16)
-        self.refresh_shadows()
-        self.ema_swapped = not self.ema_swapped
-
-    @contextlib.contextmanager
-    def ema_weights(self):
-        """with store.ema_weights(): ... — the averaged weights swapped in for validation, sampling or a forward pass, and the raw
-        iterate back on exit (also after an exception). No training step may run inside: it would update the average as the weights."""
-        self.swap_ema()
-        try:
-            yield self
-        finally:
-            self.swap_ema()
-
-    def rng_state_inference(self):
-        """the RNG state inference-mode forward passes advance (eps of Model.__call__ when none is given): never the
-        training stream's, so that a sampling hook in the middle of training leaves the steps after it as they were"""
-        if self._rng_state_infer is None:
-            self._rng_state_infer = torch.tensor([0, 0, 0x1F123BB5 ^ 0x5DEECE66D, 0], dtype=torch.int64, device=self.device)
-        return self._rng_state_infer
-
-    def on_tail_failure(self, callback):
-        """callback() after a failed position-0 tail made this store fall back to the five-launch form: holders of captured
-        graphs must drop them (they were recorded with the one-launch kernels)"""
-        self._tail_listeners.append(callback)
-
-    def handle_step_status(self, flags, skipped):
-        """A one-launch position-0 tail could not do its work in `skipped` steps since the last read (flags: _lib.TAIL_* /
-        STEP_INCOMPLETE). The optimizer launches of those steps left the model untouched (step guard), so nothing wrong was
-        learned; from here on the five-launch form runs (policy 'fallback'), or the run stops (policy 'raise')."""
-        o.zero(self._metric_buf[4:6])
-        self.tail_failures.append((int(flags), int(skipped)))
-        self.tail_fused = False
-        msg = (f"the one-launch position-0 tail of the top encoder layer failed (status flags {int(flags):#x}: "
-               f"{'forward barrier timed out; ' if flags & 1 else ''}{'backward barrier timed out; ' if flags & 2 else ''}"
-               f"{'tail incomplete at the end of a step; ' if flags & 16 else ''}"
-               f"{int(skipped)} step(s) skipped without touching the model)")
-        if self.tail_policy == "raise":
-            raise RuntimeError(msg + " — MST_TAIL_FAILURE=raise")
-        warnings.warn(msg + "; falling back to the five-launch form for the rest of the run", RuntimeWarning)
-        for cb in self._tail_listeners:
-            cb()
-
-    def poll_status(self, reduce=None):
-        """Cheap, NON-BLOCKING look at the step guard's sticky words, for the training loop to call every few steps (the
-        words are otherwise read only with the metrics — at the periodic log — and after one failed tail every following
-        step is a skipped batch until then). Two halves per call, no synchronisation in either: (1) if the copy the previous
-        call started has arrived (event query), look at it: a set flag goes to handle_step_status() — fall back to the
-        five-launch form at once, or raise; (2) start the next asynchronous copy of the words into page-locked memory
-        behind everything launched so far on the current stream. reduce(tensor): data parallel — an in-place SUM over the
-        ranks applied to a float copy of the words first, so that every rank sees a failure of ANY rank at the same poll
-        and all of them stop together (handle_step_status raises there: a skipped update on one rank lets the replicas drift).
-        Returns True when a failure was handled."""
-        if getattr(self, "_poll_host", None) is None:
-            self._poll_host = torch.zeros(2, dtype=torch.float32).pin_memory()
-            self._poll_dev = torch.zeros(2, dtype=torch.float32, device=self.device)
-            self._poll_event = torch.cuda.Event()
-            self._poll_pending = False
-        handled = False
-        if self._poll_pending and self._poll_event.query():
-            self._poll_pending = False
-            flags, skipped = (int(v) for v in self._poll_host.tolist())
-            if flags or skipped:
-                if reduce is not None:  # (summed over the ranks: only "non-zero" means anything)
-                    self.tail_fused = False
-                    raise RuntimeError(f"a one-launch position-0 tail failed on at least one rank (status words summed over the ranks: "
-                                       f"{flags}, {skipped} skipped step(s)); the replicas are no longer identical — restart from the "
-                                       "last checkpoint with MST_ROW_TAIL=0")
-                cur = self.step_status[:2].tolist()  # (one small blocking read, on the failure path only: the words as they are NOW)
-                self.handle_step_status(cur[0] or flags, cur[1] or skipped)
-                handled = True
-        if not self._poll_pending:
-            self._poll_dev.copy_(self.step_status[:2])
-            if reduce is not None:
-                reduce(self._poll_dev)
-            self._poll_host.copy_(self._poll_dev, non_blocking=True)
-            self._poll_event.record()
-            self._poll_pending = True
-        return handled
-
-    def read_metrics(self, reset=True):
-        """one device->host read of the running sums: {'kl_sum', 'total_sum', 'count'} and, for the token ends,
-        {'nll_sum', 'acc_hits', 'topk_hits', 'n_tokens'}, for the piano-roll ends the counts {'roll_tp', 'roll_pred', 'roll_pos',
-        'roll_cells'} as ints (roll_scores turns them into precision / recall / F1) (the caller orders this after the steps it wants included).
-        The step-status words travel in the same copy: a set flag is handled here (handle_step_status). So does the schedule
-        block: once a plan with training schedules has run, 'kl_weight' (beta_t) and 'lr_scale' (f_lr) of the last such step.
-        (The last step that RAN: after a step the guards skipped, whose step count was taken back, the block still holds that
-        step's values until the next step's first launch writes it again from the count — training is unaffected.)
-        And the statistics of global-norm clipping: once a step of a plan with clip_global_norm has counted, 'grad_norm' (the mean
-        norm before clipping over the counted steps since the last reset), 'grad_norm_max' and 'clip_frac' (the share of them that
-        were clipped); reset clears these running fields with the sums."""
-        buf = self._metric_buf.cpu()
-        acc = buf[:3].tolist()
-        flags, skipped, nonfinite = buf[4:7].view(torch.int32).tolist()
-        if nonfinite:
-            # (the optimizer left the model alone in those steps: an overflowed activation or sigma = 0 would have made every
-            # gradient NaN — mst_step_metrics' non-finite guard)
-            self.nonfinite_steps += int(nonfinite)
-            o.zero(self._metric_buf[6:7])
-            warnings.warn(f"{int(nonfinite)} training step(s) skipped: a per-sample loss was not finite (an fp16 activation overflow or "
-                          "sigma = 0 under log(sigma^2)); parameters, moments and the step count were left as they were", RuntimeWarning)
-        if flags or skipped:
-            self.handle_step_status(flags, skipped)
-        out = {"kl_sum": acc[0], "total_sum": acc[1], "count": acc[2], "skipped_steps": skipped, "nonfinite_steps": int(nonfinite)}
-        beta_t, _, f_lr, sched_t = buf[8:12].tolist()
-        if sched_t > 0:  # (a scheduled step wrote the block)
-            out.update(kl_weight=beta_t, lr_scale=f_lr)
-        _, _, norm_sum, norm_max, g_steps, g_clipped = buf[12:18].tolist()
-        if g_steps > 0:  # (a step with global-norm clipping counted)
-            out.update(grad_norm=norm_sum / g_steps, grad_norm_max=norm_max, clip_frac=g_clipped / g_steps)
-        if self.tok_parts is not None:
-            t = self.tok_parts.cpu().double().sum(0).tolist()
-            out.update(nll_sum=t[0], acc_hits=t[1], topk_hits=t[2], n_tokens=t[3])
-        if self.roll_counts is not None:
-            c = self.roll_counts.cpu().sum(0).tolist()
-            out.update(roll_tp=int(c[0]), roll_pred=int(c[1]), roll_pos=int(c[2]), roll_cells=int(c[3]))
-        out["lat_stats"] = self.lat_stats.cpu().numpy()  # (all zero unless a plan with track_latent_stats ran; latent_scores)
-        if reset:
-            o.zero(self.lat_stats)
-            o.zero(self.metric_acc)
-            if g_steps > 0:
-                o.zero(self.gstat[2:6])
-            if self.tok_parts is not None:
-                o.zero(self.tok_parts)
-            if self.roll_counts is not None:
-                o.zero(self.roll_counts)
-        return out
-
-    def wgrad_scratch(self, n_floats=16 * 1024 * 1024 + 256 * 256):
-        """fp32 work buffer of the wgrad launch's two-pass reduction: one full resident round of 256 x 256 slab tiles
-        (256 work items x 256 KiB = 64 MiB) plus each item's 256 bias column sums (256 KiB) is all
-        mst_gemm_wgrad_batch_flush ever asks for. Buffers are never freed:
-        captured graphs keep the pointer they were recorded with."""
-        for t in self._wgrad_scratch:
-            if t.numel() >= n_floats:
-                return t
-        t = torch.empty(n_floats, dtype=torch.float32, device=self.device)
-        self._wgrad_scratch.append(t)
-        return t
-
-    # ---- views
-    def _view(self, flat, name):
-        shape = self.shapes[name]
-        off = self.offsets[name]
-        return flat[off: off + int(np.prod(shape))].view(*shape)
-
-    def p(self, name):
-        return self._view(self.w, name)
-
-    def grad(self, name):
-        return self._view(self.g, name)
-
-    def h(self, name):
-        return self._view(self.w16, name)
-
-    def fused(self, flat, prefix, what):
-        """[3D, D] weight or [3D] bias view of a layer's K,Q,V Dense layers (K rows first)"""
-        D = self.shapes[f"{prefix}.att.W_k.weight"][0]
-        off = self.offsets[f"{prefix}.att.W_k.{what}"]
-        return flat[off: off + 3 * D * D].view(3 * D, D) if what == "weight" else flat[off: off + 3 * D]
-
-    def t(self, name):
-        so, r, c = self.t_specs[name]
-        off = self.t_off[name]
-        return self.wt16[off: off + c * roundup(r, 8)].view(c, roundup(r, 8))
-
-    def _layer_params(self, side, i):
-        pre = f"{side}.layer{i}"
-
-        def dense(name):
-            w, b = f"{pre}.{name}.weight", f"{pre}.{name}.bias"
-            return Dense(self.h(w), self.p(b), self.t(w), self.grad(w), self.grad(b))
-
-        def norm(name):
-            g, b = f"{pre}.{name}.gamma", f"{pre}.{name}.beta"
-            return Norm(self.p(g), self.p(b), self.grad(g), self.grad(b), f"{pre}.{name}")
-
-        kqv = Dense(self.fused(self.w16, pre, "weight"), self.fused(self.w, pre, "bias"), self.t(f"{pre}.att.W_kqv"),
-                    self.fused(self.g, pre, "weight"), self.fused(self.g, pre, "bias"))
-        dec = side == "decoder"
-        return LayerParams(kqv, dense("att.W_proj"), dense("ff1"), dense("ff2"), norm("ln1"), norm("ln3" if dec else "ln2"),
-                           self_resid=dec, mask_mode=2 if dec else 1)
-
-    def layer(self, side, i):
-        """the LayerParams record of layer i of the 'encoder' / 'decoder' stack"""
-        return self._layers[side, i]
-
-    # ---- host <-> device
-    def load_numpy(self, params_np):
-        host = np.zeros(self.n, np.float32)
-        for name, shape in self.shapes.items():
-            a = np.asarray(params_np[name], np.float32)
-            assert tuple(a.shape) == tuple(shape), f"{name}: expected {shape}, got {a.shape}"
-            host[self.offsets[name]: self.offsets[name] + a.size] = a.reshape(-1)
-        self.w.copy_(torch.from_numpy(host))
-        self.refresh_shadows()
-
-    def to_numpy(self, which="w"):
-        """name -> host copy of the tensor's part of a flat fp32 bucket: 'w', 'g', 'm', 'v', or 'ema' (a store that averages)"""
-        if which == "ema" and self.ema is None:
-            raise RuntimeError("this store keeps no average of its weights (StepPlan(ema_decay=...) / enable_ema())")
-        host = getattr(self, which).detach().cpu().numpy()
-        return OrderedDict((n, host[self.offsets[n]: self.offsets[n] + int(np.prod(s))].reshape(s).copy())
-                           for n, s in self.shapes.items())
-
-    def shadowed_names(self):
-        """parameters the kernels consume through a 16-bit shadow (GEMM B operands); every other tensor — biases,
-        LayerNorm gamma / beta, class tables, the latent block, token embedding tables — is read in fp32"""
-        names = set()
-        for key in self.t_specs:
-            if key.endswith(".att.W_kqv"):
-                p = key[: -len("W_kqv")]
-                names.update({p + "W_k.weight", p + "W_q.weight", p + "W_v.weight"})
-            else:
-                names.add(key)
-        return names
-
-    def as_consumed_numpy(self):
-        """name -> the values the kernels actually read: the 16-bit shadow (widened to fp32) for shadowed_names(), the
-        fp32 master otherwise. Feeding these to a reference separates weight rounding from kernel error."""
-        w = self.to_numpy("w")
-        w16 = self.w16.detach().float().cpu().numpy()
-        for n in self.shadowed_names():
-            s = self.shapes[n]
-            w[n] = w16[self.offsets[n]: self.offsets[n] + int(np.prod(s))].reshape(s).copy()
-        return w
-
-    def load_ema_numpy(self, params_np=None):
-        """set the average from name -> array (a checkpoint's), or to a copy of w (None)"""
-        self.enable_ema()
-        if params_np is None:
-            self.ema.copy_(self.w)
-            return
-        host = np.zeros(self.n, np.float32)
-        for name, shape in self.shapes.items():
-            a = np.asarray(params_np[name], np.float32)
-            assert tuple(a.shape) == tuple(shape), f"{name}: expected {shape}, got {a.shape}"
-            host[self.offsets[name]: self.offsets[name] + a.size] = a.reshape(-1)
-        self.ema.copy_(torch.from_numpy(host))
-
-    def refresh_shadows(self):
-        o.cast_to_act(self.w, self.w16)
-        o.transpose_shadows(self.w, self.wt16, self.t_desc, self.t_prefix, len(self.t_specs), self.t_tiles)
-
-
-class _Layer:
-    pass
-
-
-# Parameter views of one transformer layer as the kernels take them (ParamStore.layer). Dense: w the 16-bit shadow (GEMM B operand), b the
-# fp32 bias, t the transposed 16-bit shadow (dgrad B operand), dw / db their views of the gradient bucket; kqv is the layer's K | Q | V
-# projection as ONE [3D, D] Dense. Norm: site is the LayerNorm's key in StepPlan._ln_part. What an encoder and a decoder layer differ in
-# is data here: ln2 is the layer's LAST LayerNorm (the decoder's ln3); self_resid: the second residual is the feed-forward output itself
-# (decoder, transformer.py:199-200: LN3(ff + dropout(ff))) instead of x1 (encoder: LN2(x1 + dropout(ff))); mask_mode: what the backward
-# of that last LayerNorm does with the dropout mask (1: a masked copy of dx next to dx, 2: dx * (1 + mask)).
-Dense = namedtuple("Dense", "w b t dw db")
-Norm = namedtuple("Norm", "gamma beta dgamma dbeta site")
-LayerParams = namedtuple("LayerParams", "kqv proj ff1 ff2 ln1 ln2 self_resid mask_mode")
-
-# Which rows of a layer's [M, ld] buffers a row-wise block works on. view(buf): the operand a launch reads, or a LayerNorm writes; a
-# GEMM writes the whole buffer through the output row remap c_remap; ln: the row arguments of the LayerNorm launches.
-Rows = namedtuple("Rows", "view c_remap ln")
-ALL_ROWS = Rows(lambda buf: buf, (0, 0, 0), {})
-
-
-def position0_rows(B, S):
-    """position 0 of every sample of a [B * S, ld] buffer: B rows, logical row b -> physical row b * S"""
-    return Rows(lambda buf: buf.view(B, S, -1)[:, 0, :], (1, S, 0), dict(M=B, row_id_stride=S))
-
-
-class Dropout(namedtuple("Dropout", "p seed_ptr site0")):
-    """dropout of a layer's row-wise block: probability, the device seed word (None at p = 0), the first of the block's three site ids
-    (attention output, FFN hidden, FFN output)"""
-
-    def at(self, k):
-        """gemm_nt / layernorm_bwd keywords of site k of the block"""
-        return dict(dropout_p=self.p, dropout_site=self.site0 + k, dropout_seed_ptr=self.seed_ptr) if self.p > 0 else {}
-
-
-NO_DROPOUT = Dropout(0.0, None, 0)
-
-
-def row_block_fwd(P, L, x_in, rows, drop, form, row_groups=None, tail=None, launch=True):
-    """The row-wise block of a transformer layer behind the attention mix: W_proj + residual -> LayerNorm-1 -> FF1 + ReLU -> FF2 +
-    residual -> LayerNorm-2/3, on `rows` of the layer's buffers L (att in; h1, x1, a, h2, x2, mean1/2, rstd1/2 out). form:
-      'launches'  the five launches (any rows: the recovery path of the position-0 tail, and every width without a fused kernel)
-      'fused'     one launch, mst_proj_ffn_ln_fwd (all rows; row_groups: ops.ffn_ln_fwd's, the last decoder layer without position 0)
-      'tail'      one launch, mst_row_tail_fwd (position-0 rows; tail: its sync / stat_stride / phys_stride / status / rider / queue /
-                  shadows keywords)
-    launch=False ('fused' only): nothing is launched; returns ops.ffn_ln_fwd's keyword arguments (StepPlan.losses: ops.dec_tail_step)"""
-    D, v = P.proj.w.shape[0], rows.view
-    if form == "tail":
-        o.row_tail_fwd(v(L.att), v(x_in), P.proj.w, P.proj.b, P.ln1.gamma, P.ln1.beta, P.ff1.w, P.ff1.b, P.ff2.w, P.ff2.b, P.ln2.gamma,
-                       P.ln2.beta, v(L.h1), v(L.x1), v(L.a), v(L.h2), v(L.x2), L.mean1, L.rstd1, L.mean2, L.rstd2, dropout_p=drop.p,
-                       dropout_seed_ptr=drop.seed_ptr, site0=drop.site0, **tail)
-        return L.x2
-    proj = dict(N=D, K=D, bias=P.proj.b, resid=v(x_in), **drop.at(0))
-    ff1 = dict(K=D, bias=P.ff1.b, act=o.ACT_RELU, **drop.at(1))
-    ff2 = dict(K=4 * D, bias=P.ff2.b, **drop.at(2))
-    ff2.update(dict(self_resid=True) if P.self_resid else dict(resid=v(L.x1)))
-    if form == "fused":  # (same results as the five launches, bit for bit in a / h2. The projection's dgrad behind the backward block
-        # measured +14 us and was removed.)
-        head = dict(att=L.att, W=P.proj.w, h1=L.h1, gamma=P.ln1.gamma, beta=P.ln1.beta, mean=L.mean1, rstd=L.rstd1, **proj)
-        kw = dict(x=L.x1, W1=P.ff1.w, a_out=L.a, W2=P.ff2.w, h_out=L.h2, gamma=P.ln2.gamma, beta=P.ln2.beta, y_out=L.x2, mean=L.mean2,
-                  rstd=L.rstd2, ff1=ff1, ff2=ff2, proj=head, row_groups=row_groups)
-        if not launch:
-            return kw
-        o.ffn_ln_fwd(**kw)
-        return L.x2
-    # (Dense + LayerNorm in one launch, ops.gemm_nt_ln_fwd, does not pay in the forward pass: graph-replay timings at
-    # M = 16384 are 17.8 vs 19.9 us for N 256 K 256 but 30.3 vs 30.2 for K 1024 and 16.6 vs 13.0 / 21.3 vs 16.5 for
-    # N 128, and nothing at step level — the forward LayerNorm is a 7 us launch and the full-row tile costs the GEMM
-    # as much. The backward forms, where the LayerNorm launch is 16 us, do pay: row_block_bwd.)
-    o.gemm_nt(v(L.att), P.proj.w, L.h1, c_remap=rows.c_remap, **proj)
-    o.layernorm_fwd(v(L.h1), P.ln1.gamma, P.ln1.beta, v(L.x1), L.mean1, L.rstd1, D=D, **rows.ln)
-    o.gemm_nt(v(L.x1), P.ff1.w, L.a, c_remap=rows.c_remap, **ff1)
-    o.gemm_nt(v(L.a), P.ff2.w, L.h2, c_remap=rows.c_remap, **ff2)
-    o.layernorm_fwd(v(L.h2), P.ln2.gamma, P.ln2.beta, v(L.x2), L.mean2, L.rstd2, D=D, **rows.ln)
-    return L.x2
-
-
-def _lead_mask(P, t, drop):
-    """mask keywords of the LayerNorm backward a layer's backward pass starts with (LN2 of an encoder layer, LN3 of a decoder layer)"""
-    if P.mask_mode == 2:
-        return dict(mask_mode=2, **drop.at(2))
-    return dict(mask_mode=1, dx_masked=t.dhm, **drop.at(2)) if drop.p > 0 else {}
-
-
-def no_partials(norm, parts):
-    """row_block_bwd's `partials` for a block of few rows: the LayerNorm parameter gradients go straight into the bucket (atomics)"""
-    return None
-
-
-def ffn_bwd_parts(L, row_groups=None):
-    """workgroups (rows of LayerNorm-1 partials) of a layer's one-launch backward block"""
-    M = L.h1.shape[0]
-    return o.gemm_nt_ln_parts(M if row_groups is None else M // row_groups[1] * row_groups[0])
-
-
-def ffn_bwd_kw(P, L, t, drop, partials_buf, row_groups=None):
-    """ops.ffn_ln_bwd's keyword arguments (all but lead=) for a layer's one-launch backward block: row_block_bwd 'fused', and
-    StepPlan.losses where the block is a phase of ops.dec_tail_step. partials_buf: LayerNorm-1's partials buffer, or None (atomics)."""
-    dff = t.dhm if (drop.p > 0 and not P.self_resid) else t.dh
-    ln1 = dict(dx_masked=t.dh1m, mask_mode=1, **drop.at(0)) if drop.p > 0 else {}
-    return dict(dff=dff, W2t=P.ff2.t, dpre_out=t.dpre, gate=L.a, W1t=P.ff1.t, dx_out=t.dh1, x=L.h1, gamma=P.ln1.gamma, mean=L.mean1,
-                rstd=L.rstd1, dgamma=P.ln1.dgamma, dbeta=P.ln1.dbeta, alpha=1.0 / (1.0 - drop.p) if drop.p > 0 else 1.0,
-                resid=None if P.self_resid else t.dh, partials=partials_buf, row_groups=row_groups, **ln1)
-
-
-def row_block_bwd(P, L, t, dy, rows, drop, form, partials, dy_done=False, row_groups=None, tail=None, launch=True, proj_dgrad=True,
-                  head=None):
-    """Backward of row_block_fwd on the same rows: LayerNorm-2/3 backward of dy, both FFN dgrads, LayerNorm-1 backward, the W_proj
-    dgrad. t: the layer's backward buffers — dh, dhm, dx1, dh1m, dpre indexed by the block's own rows, dh1 and datt by the layer's
-    (written through `rows`). partials(norm, n_workgroups) -> the partials buffer of one LayerNorm-backward launch, or None
-    (StepPlan._ln_partials). Returns (dff, dproj): the A operands of the FF2 and W_proj weight gradients. form:
-      'launches'  five launches
-      'ln_fused'  FF1 dgrad + LayerNorm-1 backward in one launch (mst_gemm_nt_ln; the gradient in between is never stored): four
-      'fused'     both dgrads + LayerNorm-1 backward in one launch (mst_ffn_ln_bwd); an encoder layer's LayerNorm-2 backward rides in
-                  its prologue (mst_ffn_ln_bwd_lead; the prologue has no mask_mode 2). row_groups as in row_block_fwd
-      'tail'      one launch, mst_row_tail_bwd (position-0 rows; tail: its keywords)
-    dy_done: the producer of dy already ran the leading LayerNorm backward (t.dh / t.dhm are filled; not with 'tail').
-    launch=False ('fused' with dy_done only): the one-launch block itself is not issued — it ran as a phase of ops.dec_tail_step, from
-    ffn_bwd_kw's arguments —; the partial-sum job is registered and the W_proj dgrad issued as always.
-    proj_dgrad=False (not with 'tail'): the W_proj dgrad is left to the caller's attention-backward launch (ops.attn_proj_bwd on dproj);
-    t.datt is not written.
-    head ('fused' with the leading LayerNorm backward in its prologue only; dy is then not read): dict(A, B, resid) — dy = A B^T + resid,
-    the K | Q | V input gradient of the layer above, is formed by the one launch itself (ops.ffn_ln_bwd head=)."""
-    D, v = P.proj.w.shape[0], rows.view
-    if form == "tail":
-        o.row_tail_bwd(v(dy), v(L.h2), v(L.h1), v(L.a), L.mean1, L.rstd1, L.mean2, L.rstd2, P.ln1.gamma, P.ln2.gamma, P.ff2.t, P.ff1.t,
-                       P.proj.t, t.dh, t.dhm, t.dx1, t.dh1m, t.dpre, v(t.dh1), v(t.datt), P.ln1.dgamma, P.ln1.dbeta, P.ln2.dgamma,
-                       P.ln2.dbeta, dropout_p=drop.p, dropout_seed_ptr=drop.seed_ptr, site0=drop.site0, **tail)
-        return t.dhm, t.dh1m  # (the launch writes the masked copies at p = 0 too)
-    M = L.h1.shape[0]
-    lead = None
-    if not dy_done and form == "fused" and P.mask_mode == 1:
-        lead = dict(dy=None if head is not None else dy, x=L.h2, gamma=P.ln2.gamma, mean=L.mean2, rstd=L.rstd2, dx=t.dh,
-                    dgamma=P.ln2.dgamma, dbeta=P.ln2.dbeta,
-                    partials=partials(P.ln2, o.gemm_nt_ln_parts(M)), **_lead_mask(P, t, drop))
-    elif not dy_done:
-        mask = _lead_mask(P, t, drop)
-        if P.mask_mode == 2:
-            mask["dropout_site"] = drop.site0 + 2  # (this launch has always been given the site id at p = 0 too, where nothing reads it)
-        o.layernorm_bwd(v(L.h2), P.ln2.gamma, L.mean2, L.rstd2, v(dy), t.dh, P.ln2.dgamma, P.ln2.dbeta, D=D,
-                        partials=partials(P.ln2, o.layernorm_bwd_parts(M, D)), **rows.ln, **mask)
-    # encoder: dx feeds the residual branch, its masked copy the feed-forward branch; decoder: one branch (mask_mode 2)
-    dff = t.dhm if (drop.p > 0 and not P.self_resid) else t.dh
-    resid_ff = None if P.self_resid else t.dh
-    # FFN: d(pre-relu) = (dff W2) * 1[a > 0] / (1-p)   (a is stored post-dropout, so a > 0 <=> relu on and kept)
-    inv_keep = 1.0 / (1.0 - drop.p) if drop.p > 0 else 1.0
-    ln1 = dict(dx_masked=t.dh1m, mask_mode=1, **drop.at(0)) if drop.p > 0 else {}
-    if form == "fused":
-        buf = partials(P.ln1, ffn_bwd_parts(L, row_groups))
-        if head is not None and (lead is None or not launch):
-            raise ValueError("row_block_bwd(head=) needs the one launch that starts with the leading LayerNorm backward")
-        if launch:
-            o.ffn_ln_bwd(lead=lead, head=head, **ffn_bwd_kw(P, L, t, drop, buf, row_groups))
-        elif lead is not None:
-            raise ValueError("row_block_bwd(launch=False) needs dy_done: the block that ran elsewhere has no leading LayerNorm backward")
-    else:
-        o.gemm_nt(dff, P.ff2.t, t.dpre, N=4 * D, K=D, gate=v(L.a), alpha=inv_keep)
-        if form == "ln_fused":
-            o.gemm_nt_ln_bwd(t.dpre, P.ff1.t, t.dh1, L.h1, P.ln1.gamma, L.mean1, L.rstd1, P.ln1.dgamma, P.ln1.dbeta, N=D, K=4 * D,
-                             resid=resid_ff, partials=partials(P.ln1, o.gemm_nt_ln_parts(M)), **ln1)
-        else:
-            o.gemm_nt(t.dpre, P.ff1.t, t.dx1, N=D, K=4 * D, resid=resid_ff)
-            o.layernorm_bwd(v(L.h1), P.ln1.gamma, L.mean1, L.rstd1, t.dx1, v(t.dh1), P.ln1.dgamma, P.ln1.dbeta, D=D,
-                            partials=partials(P.ln1, o.layernorm_bwd_parts(M, D)), **rows.ln, **ln1)
-    dproj = t.dh1m if drop.p > 0 else v(t.dh1)
-    if proj_dgrad:
-        o.gemm_nt(dproj, P.proj.t, t.datt, N=D, K=D, c_remap=rows.c_remap)
-    return dff, dproj
-
-
-def layer_wgrads(P, L, t, x_in, dff, dproj, rows):
-    """a layer's four weight-gradient problems (FF2, FF1, W_proj on `rows`; K | Q | V on every row), for the step's ONE wgrad launch"""
-    D, v = P.proj.w.shape[0], rows.view
-    return [o.wgrad_problem(dff, v(L.a), P.ff2.dw, P.ff2.db, N=D, K=4 * D),
-            o.wgrad_problem(t.dpre, v(L.x1), P.ff1.dw, P.ff1.db, N=4 * D, K=D),
-            o.wgrad_problem(dproj, v(L.att), P.proj.dw, P.proj.db, N=D, K=D),
-            o.wgrad_problem(t.dqkv, x_in, P.kqv.dw, P.kqv.db, N=3 * D, K=D)]
-
-
-def row_tail_selfcheck(store, B=64, S=2):
-    """One-time start-up check of the one-launch position-0 tails (mst_row_tail_fwd / _bwd) on THIS device, process and
-    partition mode: both are run against the five launches the engine falls back to — row_block_fwd / row_block_bwd in both forms —
-    on random rows and the store's own top-layer weights. Their grid barrier rests on properties no API guarantees (enough workgroups
-    of an oversubscribed launch landing on one XCD, L1 behaviour of write-through lines — csrc/row_tail.hip), so shape alone does not
-    decide whether the fused form is used: a mismatch, an unfinished barrier or a status flag pins the store to the five-launch form."""
-    store.tail_checked = True
-    cfg, dev, adt = store.cfg, store.device, store.act_dtype
-    D, F = cfg.e_model, 4 * cfg.e_model
-    if not (o.can_row_tail(B, D) and store.tail_fused and cfg.e_layers >= 1):
-        return True
-    f32 = dict(dtype=torch.float32, device=dev)
-    P = store.layer("encoder", cfg.e_layers - 1)
-    # (the check's LayerNorm parameter gradients go to scratch, not into the store's bucket)
-    scratch = lambda n: n._replace(dgamma=torch.zeros(D, **f32), dbeta=torch.zeros(D, **f32))
-    P = P._replace(ln1=scratch(P.ln1), ln2=scratch(P.ln2))
-
-    def rnd(n, width, site):
-        a = torch.zeros(n, width, **f32)
-        o.randn(a, seed=0x7A11, site=site)
-        t = torch.zeros(n, width, dtype=adt, device=dev)
-        o.cast_to_act(a, t)  # (values ~ N(0, 1): LayerNorm makes the chain scale-free)
-        return t
-
-    z = lambda n, w: torch.zeros(n, w, dtype=adt, device=dev)
-    att, xin = rnd(B * S, D, 1), rnd(B * S, D, 2)
-    status = torch.zeros(2, dtype=torch.int32, device=dev)
-    sync = torch.zeros(8, dtype=torch.int32, device=dev)
-    rows = position0_rows(B, S)
-
-    def fbufs():
-        L = _Layer()
-        L.att, L.h1, L.x1, L.a, L.h2, L.x2 = att, z(B * S, D), z(B * S, D), z(B * S, F), z(B * S, D), z(B * S, D)
-        L.mean1, L.rstd1, L.mean2, L.rstd2 = (torch.zeros(B * S, **f32) for _ in range(4))
-        return L
-
-    u, f = fbufs(), fbufs()
-    tail = dict(stat_stride=S, phys_stride=S, status=status[0:1])
-    row_block_fwd(P, u, xin, rows, NO_DROPOUT, "launches")
-    row_block_fwd(P, f, xin, rows, NO_DROPOUT, "tail", tail=dict(tail, sync=sync[0:3]))
-    # backward chain on the forward's own activations
-    dy = rnd(B * S, D, 3)
-
-    def bbufs():
-        t = _Layer()
-        t.dh, t.dhm, t.dx1, t.dh1m, t.dpre, t.dh1, t.datt = z(B, D), z(B, D), z(B, D), z(B, D), z(B, F), z(B * S, D), z(B * S, D)
-        return t
-
-    ub, fb = bbufs(), bbufs()
-    row_block_bwd(P, u, ub, dy, rows, NO_DROPOUT, "launches", no_partials)
-    row_block_bwd(P, u, fb, dy, rows, NO_DROPOUT, "tail", no_partials, tail=dict(tail, sync=sync[4:7]))
-    torch.cuda.current_stream().synchronize()
-    want_f, want_b = o.row_tail_barriers(D)
-    sy, stv = sync.cpu().tolist(), status.cpu().tolist()
-    why = []
-    if stv[0]:
-        why.append(f"status flags {stv[0]:#x}")
-    if sy[0] != want_f or sy[4] != want_b:
-        why.append(f"barrier counters {sy[0]} / {sy[4]} instead of {want_f} / {want_b}")
-    ulp = 2.0 ** -7 if adt == torch.bfloat16 else 2.0 ** -10
-    host = lambda t: t.float().cpu().numpy()
-    for k in ("h1", "x1", "a", "h2", "x2"):
-        a, b = host(rows.view(getattr(f, k))), host(rows.view(getattr(u, k)))
-        if not np.all(np.abs(a - b) <= 4 * ulp * np.maximum(np.abs(b), 1.0)):
-            why.append(f"forward {k}: max difference {np.abs(a - b).max():.3g}")
-    for k in ("dh", "dpre", "dx1", "dh1", "datt"):
-        a, b = host(getattr(fb, k)), host(getattr(ub, k))
-        if not np.abs(a - b).max() <= 4 * ulp * max(float(np.abs(b).max()), 1e-6) + 1e-6:
-            why.append(f"backward {k}: max difference {np.abs(a - b).max():.3g} (scale {np.abs(b).max():.3g})")
-    if why:
-        store.tail_fused = False
-        warnings.warn("the one-launch position-0 tail failed its start-up check on this device (" + "; ".join(why) +
-                      "): using the five-launch form", RuntimeWarning)
-    return not why
+# the engine's parts, re-exported under the names they have always had here
+from .spec import VAEConfig, logical_param_shapes, positional_table, xavier_init  # noqa: F401
+from .step_math import (check_clip, check_ema, check_input_dropout, check_iw, check_schedule, clip_scale, ema_decay_at,  # noqa: F401
+                        ema_update, iw_scores, latent_scores, roll_scores, schedule_values)
+from .params import Dense, LayerParams, Norm, ParamStore  # noqa: F401
+from .layer_block import (ALL_ROWS, NO_DROPOUT, Dropout, Rows, _Layer, _lead_mask, ffn_bwd_kw, ffn_bwd_parts, layer_wgrads,  # noqa: F401
+                          no_partials, position0_rows, row_block_bwd, row_block_fwd, row_tail_selfcheck)
+from .iw import IWBound  # noqa: F401
 
 
 # The launch forms of one issued kernel sequence (StepPlan._resolve_forms): tails — the position-0 tails as one launch; riders — GEMMs
@@ -777,151 +46,6 @@ def row_tail_selfcheck(store, B=64, S=2):
 # (mst_kqv_ffn_ln_bwd), in front of the leading LayerNorm backward, instead of by a GEMM launch that writes the gradient.
 Forms = namedtuple("Forms", "tails riders shadows fuse_bce bce_dgrad skip_row0 cls_fold ffn_e ffn_d ln_bwd_e ln_bwd_d sched dec_tail gnorm ema "
                             "attn_proj_e attn_proj_d kqv_head_e in_drop")
-
-
-def roll_scores(tp, pred, pos, cells):
-    """the piano-roll counts of ParamStore.read_metrics (a cell is predicted where its logit is > 0) as scores: precision = tp / pred,
-    recall = tp / pos, f1 = 2 tp / (pred + pos), cell_acc = (cells - pred - pos + 2 tp) / cells; NaN where a denominator is 0"""
-    nan = float("nan")
-    return dict(precision=tp / pred if pred else nan, recall=tp / pos if pos else nan,
-                f1=2 * tp / (pred + pos) if pred + pos else nan,
-                cell_acc=(cells - pred - pos + 2 * tp) / cells if cells else nan)
-
-
-def latent_scores(acc, threshold=0.01):
-    """the per-class, per-dimension sums of ParamStore.read_metrics' 'lat_stats' (fp64 [C, 5, Z], planes {n, sum mu, sum mu^2,
-    sum sigma^2, sum kl_d}: mst_latent_dim_stats) as scores. Per dimension d, pooled over the classes: n, m = sum mu / n,
-    V = sum mu^2 / n - m^2 (the variance of the posterior mean over the data).
-      active_units  number of dimensions with V > threshold (Burda et al.'s 0.01)
-      kl_dims       [Z] mean KL of each dimension, sum kl_d / n
-      kl_dim_max    the largest of kl_dims
-      kl_dims_used  number of dimensions with mean KL > threshold
-      sigma_rms     sqrt(mean over d of sum sigma^2 / n)
-      class_leak    max over the active dimensions of eta^2_d = sum_c (n_c / n) (m_cd - m_d)^2 / V_d, the share of a dimension's variance
-                    that lies BETWEEN the classes (0: z says nothing about the class; 1: the class alone decides mu_d). NaN without an
-                    active dimension, or when fewer than two classes have samples.
-    A dimension with n == 0 has NaN entries and is not active (kl_dim_max and sigma_rms are taken over the dimensions with samples)."""
-    acc = np.asarray(acc, np.float64)
-    if acc.ndim != 3 or acc.shape[1] != 5:
-        raise ValueError(f"latent_scores takes [C, 5, Z] sums, not {acc.shape}")
-    nan = float("nan")
-    with np.errstate(divide="ignore", invalid="ignore"):
-        n_c = acc[:, 0]                                   # [C, Z]
-        n, s_mu, s_mu2, s_s2, s_kl = acc.sum(0)           # [Z] each
-        m = s_mu / n
-        var = s_mu2 / n - m * m
-        kl_dims = s_kl / n
-        active = var > threshold                          # (NaN compares false)
-        m_c = acc[:, 1] / n_c                             # [C, Z]; NaN for a class without samples: its weight below is 0
-        between = np.where(n_c > 0, n_c / n * (m_c - m) ** 2, 0.0).sum(0)
-        eta2 = np.minimum(between / var, 1.0)             # (between <= V; the two are rounded apart)
-    seen = n > 0
-    classes_seen = int((n_c.sum(1) > 0).sum())
-    leak = float(eta2[active].max()) if active.any() and classes_seen >= 2 else nan
-    return dict(active_units=int(active.sum()), kl_dims=kl_dims, kl_dim_max=float(kl_dims[seen].max()) if seen.any() else nan,
-                kl_dims_used=int((kl_dims > threshold).sum()),
-                sigma_rms=float(np.sqrt((s_s2[seen] / n[seen]).mean())) if seen.any() else nan, class_leak=leak)
-
-
-def iw_scores(acc, cells):
-    """the six running sums of IWBound (ops.IW_ACC: sum log_px, sum elbo, sum ess, sum n, pieces counted, pieces invalid — mst_iw_finish)
-    as the reported figures, stated once. cells: cells per piece (T * P for a piano-roll, T for a token sequence). Nats per piece:
-      iw_nll            -sum log_px / pieces     the importance-weighted bound on -log p(x)
-      iw_elbo_nll       -sum elbo / pieces       the same draws' mean log-weight: the ELBO in nats
-      iw_gap            iw_elbo_nll - iw_nll     >= 0 (Jensen); near 0: the posterior is tight, or the decoder ignores z
-      iw_ess            sum ess / pieces         effective sample size of the weights, between 1 and K
-      iw_bits_per_cell  iw_nll / (cells ln 2)
-      iw_invalid        pieces with a draw that was not finite (in none of the sums)
-    NaN where no piece was counted."""
-    acc = np.asarray(acc, np.float64).reshape(-1)
-    if acc.size != 6:
-        raise ValueError(f"iw_scores takes the six sums of mst_iw_finish, not {acc.size} values")
-    if not cells > 0:
-        raise ValueError(f"cells per piece must be positive, not {cells!r}")
-    pieces, nan = acc[4], float("nan")
-    nll = -acc[0] / pieces if pieces > 0 else nan
-    elbo_nll = -acc[1] / pieces if pieces > 0 else nan
-    return dict(iw_nll=float(nll), iw_elbo_nll=float(elbo_nll), iw_gap=float(elbo_nll - nll),
-                iw_ess=float(acc[2] / pieces) if pieces > 0 else nan, iw_bits_per_cell=float(nll / (cells * math.log(2.0))),
-                iw_invalid=int(acc[5]))
-
-
-def check_iw(samples):
-    """samples: K of the importance-weighted bound, an integer >= 1 (1: the one-sample ELBO); raises ValueError otherwise (a NaN, a
-    bool and a fraction too)"""
-    if isinstance(samples, bool) or not isinstance(samples, (int, np.integer)) or samples < 1:
-        raise ValueError(f"iw_samples must be an integer >= 1, not {samples!r}")
-
-
-def check_schedule(kl_warmup_steps=0, kl_cycle_steps=0, kl_free_bits=0.0, lr_warmup_steps=0):
-    """the combinations of training-schedule settings that mean something; raises ValueError otherwise"""
-    for name, val in (("kl_warmup_steps", kl_warmup_steps), ("kl_cycle_steps", kl_cycle_steps), ("lr_warmup_steps", lr_warmup_steps)):
-        if int(val) != val or val < 0:
-            raise ValueError(f"{name} must be a non-negative integer, not {val!r}")
-    if not kl_free_bits >= 0:
-        raise ValueError(f"kl_free_bits must be >= 0 nats per sample, not {kl_free_bits!r}")
-    if kl_cycle_steps > 0 and kl_warmup_steps == 0:
-        raise ValueError("kl_cycle_steps restarts the KL warm-up: it needs kl_warmup_steps > 0")
-    if kl_cycle_steps > 0 and kl_warmup_steps > kl_cycle_steps:
-        raise ValueError(f"kl_warmup_steps ({kl_warmup_steps}) must not exceed kl_cycle_steps ({kl_cycle_steps})")
-
-
-def check_clip(clip_global_norm=0.0):
-    """clip_global_norm: 0 (off) or a positive finite bound on the gradient's global L2 norm; raises ValueError otherwise"""
-    if not (0 <= clip_global_norm < float("inf")):
-        raise ValueError(f"clip_global_norm must be 0 (off) or a positive finite norm, not {clip_global_norm!r}")
-
-
-def check_input_dropout(d_input_dropout=0.0):
-    """d_input_dropout: probability in [0, 1] that a decoder input position is dropped in a training step (0: off, 1: every position);
-    raises ValueError otherwise (a NaN too)"""
-    if not (0 <= d_input_dropout <= 1):
-        raise ValueError(f"d_input_dropout must lie in [0, 1], not {d_input_dropout!r}")
-
-
-def clip_scale(norm, max_norm):
-    """the factor c global-norm clipping applies to a gradient of L2 norm `norm` — gluon.utils.clip_global_norm's rule as the device
-    evaluates it (mst_adam_flat's clipping group), stated once for the host in np.float32 arithmetic: c = max_norm / (norm + 1e-8), and 1 unless
-    that is below 1"""
-    c = np.float32(max_norm) / (np.float32(norm) + np.float32(1e-8))
-    return c if c < np.float32(1) else np.float32(1)
-
-
-def check_ema(ema_decay=0.0):
-    """ema_decay: 0 (off) or the decay of the weights' exponential moving average, in (0, 1); raises ValueError otherwise (a NaN too)"""
-    if not (0 <= ema_decay < 1):
-        raise ValueError(f"ema_decay must be 0 (off) or lie in (0, 1), not {ema_decay!r}")
-
-
-def ema_decay_at(t, decay):
-    """d_t, the decay the average applies at training step t (Adam's step count after the step's increment, 1-based) — the rule as the
-    device evaluates it (mst_adam_flat's averaging group), stated once for the host in np.float32 arithmetic: min(decay, (1 + t) / (10 + t)), the usual
-    warm-up, so that the first steps do not average in the initial weights"""
-    tf = np.float32(t)
-    d = (np.float32(1) + tf) / (np.float32(10) + tf)
-    return min(np.float32(decay), d)
-
-
-def ema_update(e, w_new, d):
-    """the average after a step: fl(fl(d * e) + fl((1 - d) * w_new)) in np.float32 — two rounded products and one rounded sum, in this
-    order and never fused, which is what mst_adam_flat computes for mst_adam_args.ema (include/mst_hip.h) bit for bit. e, w_new: fp32 arrays (or scalars)"""
-    d = np.float32(d)
-    omd = np.float32(1) - d
-    a = d * np.asarray(e, np.float32)
-    b = omd * np.asarray(w_new, np.float32)
-    return a + b
-
-
-def schedule_values(t, kl_weight=1.0, kl_warmup_steps=0, kl_cycle_steps=0, lr_warmup_steps=0):
-    """(beta_t, f_lr) of training step t (Adam's step count after the step's increment, 1-based) — the formulas the device evaluates
-    (step_begin.hpp), stated once for the host. Double arithmetic; beta_t is rounded once, to fp32, and returned as that value:
-        f_lr   = min(1, t / W_lr) if W_lr > 0 else 1                 the step runs at lr * f_lr
-        u      = ((t - 1) mod C) + 1 if C > 0 else t                 position in the current KL cycle
-        beta_t = fp32(fp32(kl_weight) * (min(1, u / W_b) if W_b > 0 else 1))"""
-    f_lr = min(1.0, t / lr_warmup_steps) if lr_warmup_steps > 0 else 1.0
-    u = (t - 1) % kl_cycle_steps + 1 if kl_cycle_steps > 0 else t
-    ramp = min(1.0, u / kl_warmup_steps) if kl_warmup_steps > 0 else 1.0
-    return float(np.float32(float(np.float32(kl_weight)) * ramp)), f_lr
 
 
 class StepPlan:
@@ -1130,8 +254,6 @@ class StepPlan:
         self.graph = None
         self.graph_late = None
         self.graph_opt = None
-        self._tick_adam = False
-        self._infer = False
         self._tail_used = dict(fwd=False, bwd=False)  # which one-launch tails the kernel sequence issued last contains
         if o.can_row_tail(B, De) and store.tail_fused and not store.tail_checked:
             row_tail_selfcheck(store)
@@ -1574,6 +696,21 @@ class StepPlan:
         return dict(x=L.h2, gamma=P.ln2.gamma, mean=L.mean2, rstd=L.rstd2, dgamma=P.ln2.dgamma, dbeta=P.ln2.dbeta,
                     partials=self._ln_partials(P.ln2, o.gemm_nt_ln_parts(M)), **_lead_mask(P, t, self._dropout(p, site0)))
 
+    def _kqv_dgrad(self, P, t, dx_in, next_ln, hand_down):
+        """Who forms a layer's K | Q | V input gradient t.dqkv W_kqv + t.dh1 (t: the layer's backward buffers, or the top encoder
+        layer's position-0 set): with next_ln, the GEMM that runs the leading LayerNorm backward of the layer below in its epilogue
+        instead of writing dx_in; with hand_down (Forms.kqv_head_e), the one-launch block of the layer below, in front of its leading
+        LayerNorm backward — nothing is issued, the GEMM is returned for it; else the plain GEMM into dx_in. Returns None unless handed down."""
+        D = P.proj.w.shape[0]
+        if next_ln is not None:
+            kw, t_below = next_ln
+            o.gemm_nt_ln_bwd(t.dqkv, P.kqv.t, t_below.dh, N=D, K=3 * D, resid=t.dh1, **kw)
+        elif hand_down:
+            return dict(A=t.dqkv, B=P.kqv.t, resid=t.dh1, N=D, K=3 * D)
+        else:
+            o.gemm_nt(t.dqkv, P.kqv.t, dx_in, N=D, K=3 * D, resid=t.dh1)
+        return None
+
     def _layer_bwd(self, side, i, L, x_in, dy, dx_in, keymask, D, H, S, p, site0, t, dy_done=False, next_ln=None, ride=False, head=None):
         """dy: gradient w.r.t. the layer output x2; writes the gradient w.r.t. x_in into dx_in.
         dy_done: the producer of dy already ran this layer's leading LayerNorm backward (t.dh / t.dhm are filled).
@@ -1598,19 +735,13 @@ class StepPlan:
             o.attn_proj_bwd(L.qkv, keymask, L.lse, dproj, P.proj.t, t.dqkv, t.delta, self.B, S, H, D // H, 0, D, 2 * D)
         else:
             o.attn_bwd(L.qkv, keymask, L.lse, t.datt, t.dqkv, t.delta, self.B, S, H, D // H, 0, D, 2 * D)
-        handed = None
-        if next_ln is not None:  # the layer below starts its backward pass with a LayerNorm backward: run it here
-            kw, t_below = next_ln
-            o.gemm_nt_ln_bwd(t.dqkv, P.kqv.t, t_below.dh, N=D, K=3 * D, resid=t.dh1, **kw)
-        elif side == "encoder" and i > 0 and F.kqv_head_e:  # the layer below forms it in front of its leading LayerNorm backward
-            handed = dict(A=t.dqkv, B=P.kqv.t, resid=t.dh1, N=D, K=3 * D)
-        elif ride:
+        if ride:  # (decoder layer 0: no layer below it to take the gradient in either other way)
             T_ = self.T
             handed = (dict(A=t.dqkv, B=P.kqv.t, C_out=dx_in, M=self.B * T_, N=D, K=3 * D, resid=t.dh1, resid_phys=True,
                            a_remap=(T_, T_ + 1, 1), c_remap=(T_, T_ + 1, 1)),
                       (t.dqkv.view(self.B, S, -1), P.kqv.t, t.dh1.view(self.B, S, -1)))
         else:
-            o.gemm_nt(t.dqkv, P.kqv.t, dx_in, N=D, K=3 * D, resid=t.dh1)
+            handed = self._kqv_dgrad(P, t, dx_in, next_ln, side == "encoder" and i > 0 and F.kqv_head_e)
         # the layer's four weight gradients: deferred to the ONE wgrad launch at the end of backward() (their operands
         # live in this layer's own scratch `t` and in the forward activations, so nothing is overwritten meanwhile)
         self._wgrads += layer_wgrads(P, L, t, x_in, dff, dproj, ALL_ROWS)
@@ -1624,7 +755,6 @@ class StepPlan:
         for backward_late's first _layer_bwd (dx_in is not written)."""
         cfg, st, B, S, F = self.cfg, self.store, self.B, self.T, self.forms
         D, H = cfg.e_model, cfg.e_heads
-        self._kqv_head = None
         P, c, rows = st.layer("encoder", i), self.top, position0_rows(B, S)
         self._tail_used["bwd"] = F.tails
         tail = None
@@ -1635,13 +765,8 @@ class StepPlan:
                                    "tail" if F.tails else "launches", no_partials, tail=tail)
         # d(attention output): rows b*S of a buffer that is zero elsewhere
         o.attn_bwd(L.qkv, self.keymask_e, L.lse, c.datt, c.dqkv, c.delta, B, S, H, D // H, 0, D, 2 * D, q_limit=1)
-        if next_ln is not None:  # as in _layer_bwd: the layer below's LayerNorm-2 backward rides on this GEMM
-            kw, t_below = next_ln
-            o.gemm_nt_ln_bwd(c.dqkv, P.kqv.t, t_below.dh, N=D, K=3 * D, resid=c.dh1, **kw)
-        elif i > 0 and F.kqv_head_e:  # as in _layer_bwd: left to the one-launch block of the layer below (the first launch of backward_late)
-            self._kqv_head = dict(A=c.dqkv, B=P.kqv.t, resid=c.dh1, N=D, K=3 * D)
-        else:
-            o.gemm_nt(c.dqkv, P.kqv.t, dx_in, N=D, K=3 * D, resid=c.dh1)
+        # (handed down: to the one-launch block of the layer below, the first launch of backward_late)
+        self._kqv_head = self._kqv_dgrad(P, c, dx_in, next_ln, i > 0 and F.kqv_head_e)
         self._wgrads += layer_wgrads(P, L, c, x_in, dff, dproj, rows)
 
     def backward(self):
@@ -1841,31 +966,28 @@ class StepPlan:
         if self.graph is None:
             raise RuntimeError("call capture() first")
         self.graph.launch()
+        g = self.store.g
         if self.graph_late is not None:
-            g, cut = self.store.g, self.grad_cut()
+            cut = self.grad_cut()
             pending = [reducer.start(g[cut:])] if reducer is not None else []
             self.graph_late.launch()  # runs while the early part of the bucket is on the wire
-            if stamps is not None:
-                stamps[0].record()
-            if reducer is not None:
-                pending.append(reducer.start(g[:cut]))
-                reducer.finish(pending)
-            elif reduce_fn is not None:
-                reduce_fn(g)
-            if stamps is not None:
-                stamps[1].record()
-            self.graph_opt.launch()
-            return
-        if self.graph_opt is not None:
-            if stamps is not None:
-                stamps[0].record()
-            if reducer is not None:
-                reducer.finish([reducer.start(self.store.g)])
-            elif reduce_fn is not None:
-                reduce_fn(self.store.g)
-            if stamps is not None:
-                stamps[1].record()
-            self.graph_opt.launch()
+            self._exchange_and_step(g[:cut], pending, reduce_fn, reducer, stamps)
+        elif self.graph_opt is not None:
+            self._exchange_and_step(g, [], reduce_fn, reducer, stamps)
+
+    def _exchange_and_step(self, rest, pending, reduce_fn, reducer, stamps):
+        """run()'s part between the last backward graph and the optimizer graph: stamp 0, the exchange of the gradient bucket — the
+        reducer takes `rest`, the part not yet on the wire, and waits for it and for the `pending` ones; reduce_fn takes the whole
+        bucket —, stamp 1, the optimizer graph"""
+        if stamps is not None:
+            stamps[0].record()
+        if reducer is not None:
+            reducer.finish(pending + [reducer.start(rest)])
+        elif reduce_fn is not None:
+            reduce_fn(self.store.g)
+        if stamps is not None:
+            stamps[1].record()
+        self.graph_opt.launch()
 
     def metrics(self, reset=True):
         """(kl_loss, total_loss) batch means accumulated on the device (trainer.py:115-116,185-186); one sync."""
@@ -1875,110 +997,3 @@ class StepPlan:
                 "kl_weight": m.get("kl_weight", self.kl_weight) if self.scheduled else self.kl_weight,
                 "lr_scale": m.get("lr_scale", 1.0) if self.scheduled else 1.0,
                 **{k: m[k] for k in ("grad_norm", "grad_norm_max", "clip_frac") if k in m}}
-
-
-class IWBound:
-    """The importance-weighted bound on log p(x) of the batch in `plan`'s input buffers from K posterior draws (Burda et al.):
-    log p(x) ~= log (1/K) sum_k p(x | z_k) p(z_k) / q(z_k | x), folded on the device (mst_iw_fold / mst_iw_finish).
-
-    run(K): state is zeroed; ONE full inference forward encodes the batch and is draw 1; draws 2..K are draw passes
-    (StepPlan.forward(inference=True, start="latent")): the decoder half alone, from one captured graph that is replayed — the draws
-    differ between replays because the seed lives on the device (the store's INFERENCE stream: the training stream is left alone).
-    Every draw is scored with the plain likelihood (StepPlan.losses(plain=True)) and folded; mst_iw_finish then writes the per-piece
-    rows into `out` and ADDS the batch's sums to `acc`, which several runners may share (the trainer's validation set: one read).
-
-    plan: a StepPlan with internal_eps (eps is drawn per global sample index, plan.sample_offset: a data-parallel shard draws what
-    the whole batch draws for its samples). The first draw pass of a runner is issued eagerly (HIP modules load lazily and are not
-    capturable), the graph is captured once and kept while the plan's launch forms and bound input blob stay what they were.
-    keep_draws=True (tests, small shapes): every draw's eps, sigma, z, recon and seed are copied to [K, ...] buffers (self.draws);
-    that path issues every draw eagerly."""
-
-    def __init__(self, plan, acc=None):
-        if not plan.internal_eps:
-            raise ValueError("IWBound needs a plan that draws its own eps (StepPlan(internal_eps=True))")
-        cfg, dev = plan.cfg, plan.dev
-        self.plan = plan
-        self.cells = plan.T * (cfg.out_dim if cfg.kind == "pianoroll" else 1)  # what the mean reconstruction loss was taken over
-        self.recon_scale = float(self.cells)
-        f64 = dict(dtype=torch.float64, device=dev)
-        self.state = torch.zeros(plan.B, len(o.IW_STATE), **f64)
-        self.out = torch.zeros(plan.B, len(o.IW_OUT), **f64)
-        self.acc = acc if acc is not None else torch.zeros(len(o.IW_ACC), **f64)
-        self.graph, self._graph_key = None, None
-        self.captures = 0       # graphs captured so far (one, unless the plan's forms or input blob changed)
-        self._warm = False      # an eager draw pass has run
-        self.draws = None
-        self.stream = torch.cuda.Stream(device=dev)  # capture needs a stream of its own
-
-    def _score(self):
-        """the plain likelihood of the pass just issued, folded into state"""
-        p = self.plan
-        p.losses(with_grad=False, combine=False, plain=True)
-        o.iw_fold(p.eps, p.sigma, p.z, p.recon, self.recon_scale, self.state)
-
-    def draw_pass(self):
-        """one draw: the decoder half on a new eps, its likelihood, the fold (the kernel sequence of the captured graph)"""
-        self.plan.forward(inference=True, start="latent")
-        self._score()
-
-    def graph_nodes(self):
-        """(nodes, kernel launches among them) of the captured draw pass"""
-        if self.graph is None:
-            raise RuntimeError("no draw pass has been captured yet (run() with samples >= 3)")
-        return self.graph.nodes, self.graph.kernel_nodes
-
-    def _record(self, k):
-        p, d = self.plan, self.draws
-        for name in ("eps", "sigma", "z", "recon"):
-            d[name][k].copy_(getattr(p, name))
-        d["seed"][k].copy_(p.store.rng_state_inference()[0])
-
-    def run(self, samples, keep_draws=False, reset_acc=False):
-        """the bound of the batch in the plan's input buffers from `samples` draws; results() reads it. reset_acc: acc is cleared first
-        (it then holds this batch's sums alone)"""
-        check_iw(samples)
-        p, K = self.plan, int(samples)
-        self.stream.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(self.stream):
-            self.draws = None
-            if keep_draws:
-                f32 = dict(dtype=torch.float32, device=p.dev)
-                Z = p.cfg.latent_dim
-                self.draws = dict(eps=torch.zeros(K, p.B, Z, **f32), sigma=torch.zeros(K, p.B, Z, **f32), z=torch.zeros(K, p.B, Z, **f32),
-                                  recon=torch.zeros(K, p.B, **f32), seed=torch.zeros(K, dtype=torch.int64, device=p.dev))
-            o.zero(self.state)
-            if reset_acc:
-                o.zero(self.acc)
-            p.forward(inference=True)  # encodes, and is draw 1
-            self._score()
-            if keep_draws:
-                self._record(0)
-            key = (p.forms, p.inbuf.data_ptr())
-            for k in range(1, K):
-                if keep_draws or not self._warm:
-                    self.draw_pass()
-                    self._warm = True
-                    if keep_draws:
-                        self._record(k)
-                    continue
-                if self.graph is None or self._graph_key != key:
-                    self.graph, self._graph_key = o.Graph().capture(self.draw_pass), key
-                    self.captures += 1
-                self.graph.launch()
-            o.iw_finish(self.state, self.out, self.acc)
-        torch.cuda.current_stream().wait_stream(self.stream)  # the caller reads the results on its own stream
-        return self
-
-    def results(self):
-        """per piece, as host arrays: log_px, elbo, ess, n (draws folded) and valid (False: a draw was not finite; the three figures are NaN)"""
-        out = self.out.cpu().numpy()
-        res = {name: out[:, i].copy() for i, name in enumerate(o.IW_OUT)}
-        res["valid"] = ~np.isnan(out[:, 0])
-        return res
-
-    def read_acc(self, reset=True):
-        """the six running sums (ops.IW_ACC) as a host array: one device->host read; iw_scores turns them into the reported figures"""
-        acc = self.acc.cpu().numpy().copy()
-        if reset:
-            o.zero(self.acc)
-        return acc

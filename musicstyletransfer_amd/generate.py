@@ -31,6 +31,9 @@ import os
 
 import numpy as np
 
+from .ops import roundup
+from .spec import positional_table
+
 MODES = ("prior", "posterior", "interpolate", "transfer", "blend", "continue", "repaint", "score", "likelihood")
 DECODERS = ("sampling", "greedy", "beam")
 
@@ -459,7 +462,6 @@ class LatentGenerator:
         """rows [lo, hi) of a recipe through mst_latent_rows -> (z fp32 [n, Z], decoder start rows [n, >= Dd]) on the device"""
         import torch
         from . import ops as o
-        from .engine import positional_table, roundup
         st, cfg = self.model.store, self.model.engine_config
         dev, Dd, n = st.device, cfg.d_model, hi - lo
         if self._pos0 is None or self._pos0.device != dev:
