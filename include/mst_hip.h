@@ -699,6 +699,40 @@ int mst_latent_form(int64_t De, int64_t Z, int64_t Dd, int64_t nq, const void* W
 int mst_latent_dim_stats(int64_t B, int64_t Z, int64_t C, const float* mu, int64_t ld_mu, const float* sigma, int64_t ld_sigma,
                          const int32_t* classes, double* acc, mst_stream_t stream);
 
+/* The class-conditional MMD penalty on z and its gradient (ABI 123; the Variational Fair Autoencoder's remedy, Louizos et al.): pulls the
+ * distribution of z within every class onto the pooled one, so that z itself does not tell the class (what mst_latent_dim_stats'
+ * class_leak measures). For the n = B rows z_i = mu_i + eps_i * sigma_i (fp32 [B, ld_z >= Z] as mst_latent_fwd leaves them) with classes
+ * c_i (int32 [B]) and the kernel k_ij = exp(-|z_i - z_j|^2 / (2 s2)):
+ *   L = sum_c (n_c / n) * MMD^2(q_c, q_pooled) = sum_ij w_ij k_ij,     w_ij = [c_i == c_j] / (n * n_{c_i}) - 1 / n^2
+ * n_{c_i}: the number of rows with row i's class. Classes are compared, never used as an index: any int32 value is a class and no class
+ * count is needed. One class in the batch: every w_ij is exactly 0, so L and every gradient are exactly 0. (With the linear kernel
+ * z_i . z_j the same weights give sum_c (n_c / n) |m_c - m|^2, the numerator of class_leak's eta^2 summed over the dimensions.)
+ *   g_i = dL/dz_i = sum_j c_ij (z_j - z_i),   c_ij = 2 w_ij k_ij / s2;     dL/dmu_i = g_i,   dL/dsigma_i = g_i * eps_i
+ * Arithmetic: q_ij = |z_i - z_j|^2 in fp32 by fmaf in ascending d on the fp32 differences; k_ij the fp32 exponential of -q_ij / (2 s2),
+ * exactly 1 for i == j; the counts, w_ij, c_ij, the differences z_j - z_i and every sum over j in fp64, in ascending j.
+ * VALUE. rows[i] = L_i = sum_j w_ij k_ij (i < B, plain stores). acc: double [3], ADDED to: with L = sum_i L_i, added by one thread in
+ * ascending i (the same bits on every run), {L, 1, 0} when L is finite and {0, 0, 1} when it is not. A non-finite z is not
+ * special-cased: NaN in, NaN out, as in the latent backward; only acc sorts such a launch into its third cell.
+ * GRADIENT, when dlat is non-NULL (then Wl, d_enc_out and eps must be non-NULL too; all four NULL: the value alone). dlat: the fp32
+ * [B, 2Z] d[mu | sigma] block mst_latent_bwd_vec* leaves at scratch + B * Dd; Wl: the fp32 [2Z, De] latent projection; eps fp32
+ * [B, ld_eps >= Z]; d_enc_out: the 16-bit d(enc_out) of that launch, row i at d_enc_out + i * denc_sample_stride.
+ *   dlat[i, d] += add_i[d] = (float)(coef * g_i[d]);       dlat[i, Z + d] += add_i[Z + d] = (float)(coef * g_i[d] * eps[i, d])
+ *   d_enc_out[i * stride + e] = round_act(float(old) + sum_{j < 2Z} add_i[j] * Wl[j, e]),   e < De (fp32 fmaf, ascending j)
+ * The latent backward is linear in dlat, so this is its own result for the summed gradient up to one more rounding to the activation
+ * type; the outer-product jobs of the weight-gradient flush read dlat later and pick up dWl and dbl unchanged. coef carries the
+ * caller's scaling: the gradient bucket holds sums over samples that the optimizer rescales by 1 / (global_batch * gscale), so a step
+ * with objective mean_b(recon_b + beta kl_b) + lambda * L passes coef = lambda * B * gscale (the encoder-side scale).
+ * One wave per row, sixteen rows per workgroup, grid cdiv(B, 16); z goes through LDS in 64 x 64 tiles. ticket: one word, zero before
+ * the launch and left at zero: the workgroup that draws the last ticket adds the rows. Z at most 256 (a row's sums live in registers).
+ * Before any HIP call a status for: a null pointer; B, Z or De not positive; ld_z (ld_eps) < Z; s2 not finite or not > 0; coef not
+ * finite; an inconsistent NULL set among the four gradient pointers; dtype not bf16 / fp16 when the gradient runs (value only: dtype is
+ * not looked at). */
+int mst_class_mmd(int dtype, int64_t B, int64_t Z, int64_t De,
+                  const float* z, int64_t ld_z, const float* eps, int64_t ld_eps, const int32_t* classes,
+                  float s2, float coef,
+                  const float* Wl, float* dlat, void* d_enc_out, int64_t denc_sample_stride,
+                  double* rows, uint32_t* ticket, double* acc, mst_stream_t stream);
+
 /* The importance-weighted bound on log p(x) from K posterior draws (ABI 122; Burda et al.):
  *   log p(x) ~= log (1/K) sum_k p(x | z_k) p(z_k) / q(z_k | x)
  * folded one draw at a time on the device, so that K decoder passes and a whole validation set need one read at the end.

@@ -3,7 +3,7 @@
 The flag set is the reference's, name for name and default for default (config.py:19-70), because
 scripts/train-vae.sh passes them; unknown flags are ignored as there (parse_known_args, :73-75). The flags
 are declared as a table. The additions (group MI355X) are all off by default: --pianoroll (attach the piano-roll ends), --dtype,
---d-causal, the training schedules, --clip-global-norm, --ema-decay, --d-input-dropout, --latent-stats and --iw-samples."""
+--d-causal, the training schedules, --clip-global-norm, --ema-decay, --d-input-dropout, --latent-stats, --iw-samples and --class-mmd / --class-mmd-bandwidth."""
 import argparse
 import copy
 import inspect
@@ -87,6 +87,13 @@ _FLAGS = [
     # captured decoder-only pass — and the validation line, last_validation and the scalar log gain iw_nll, iw_elbo_nll, iw_gap, iw_ess,
     # iw_bits_per_cell and iw_invalid (engine.iw_scores). Early stopping still compares total_loss. 0: off, validation as before.
     ("MI355X", ("--iw-samples",), dict(type=int, default=0)),
+    # multiplier lambda of the class-conditional MMD penalty on z (include/mst_hip.h: mst_class_mmd): a training step adds
+    # lambda * sum_c (n_c / n) MMD^2(q(z | c), q(z)) of its batch to the objective — one more launch of the captured step, behind the
+    # latent block's backward — so that z does not tell the class (the remedy for a class_leak near 1). The metrics gain class_mmd.
+    # Of order 1e2 - 1e3 by the size of its gradient; untuned. 0: off, the step as before. --class-mmd-bandwidth: the RBF kernel's
+    # s2; 0: the latent width.
+    ("MI355X", ("--class-mmd",), dict(type=float, default=0.0)),
+    ("MI355X", ("--class-mmd-bandwidth",), dict(type=float, default=0.0)),
 ]
 
 

@@ -26,7 +26,7 @@ def create_toy_model_config(data):
 
 def create_toy_train_config(max_steps=0, **schedule):
     """main.py:41-55; schedule: the training-schedule fields of TrainConfig (the --kl-warmup-steps ... flags), clip_global_norm, ema_decay,
-    d_input_dropout, latent_stats and iw_samples"""
+    d_input_dropout, latent_stats, iw_samples, class_mmd and class_mmd_bandwidth"""
     return trainer.TrainConfig(batch_size=1, sampling_frequency=500, checkpoint_frequency=1000, num_checkpoints_not_improved=-1,
                                kl_loss=1.0, optimizer=trainer.OptimizerConfig(learning_rate=1e-3, optimizer="adam",
                                                                               optimizer_params="clip_gradient:1.0"),
@@ -41,7 +41,8 @@ def main_toy(context, args):
     create_directory_if_not_present(model_folder)
     config.save(os.path.join(model_folder, "config"))
     schedule = {k: getattr(args, k) for k in ("kl_warmup_steps", "kl_cycle_steps", "kl_free_bits", "lr_warmup_steps", "clip_global_norm",
-                                              "ema_decay", "d_input_dropout", "latent_stats", "iw_samples")}
+                                              "ema_decay", "d_input_dropout", "latent_stats", "iw_samples", "class_mmd",
+                                              "class_mmd_bandwidth")}
     train_config = create_toy_train_config(args.max_steps, **schedule)
     train_config.save(os.path.join(model_folder, "train_config"))
     t = trainer.Trainer(config=train_config, context=context, model=m, sampler=None)
@@ -62,7 +63,7 @@ def create_train_config(args):
                                kl_free_bits=args.kl_free_bits, lr_warmup_steps=args.lr_warmup_steps,
                                clip_global_norm=args.clip_global_norm, ema_decay=args.ema_decay,
                                d_input_dropout=args.d_input_dropout, latent_stats=args.latent_stats,
-                               iw_samples=args.iw_samples)
+                               iw_samples=args.iw_samples, class_mmd=args.class_mmd, class_mmd_bandwidth=args.class_mmd_bandwidth)
 
 
 def create_model_config(args, dataset):

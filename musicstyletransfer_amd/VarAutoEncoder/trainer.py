@@ -18,7 +18,8 @@ import torch
 from . import utils
 from .config import Config
 from .. import parallel
-from ..step_math import check_clip, check_ema, check_input_dropout, check_iw, check_schedule, iw_scores, latent_scores, roll_scores
+from ..step_math import (check_class_mmd, check_clip, check_ema, check_input_dropout, check_iw, check_schedule, class_mmd_score, iw_scores,
+                         latent_scores, roll_scores)
 from ..pianoroll import PinnedBatchPipeline
 
 
@@ -48,13 +49,17 @@ class TrainConfig(Config):
     active_units, kl_dims_used, kl_dim_max, sigma_rms and class_leak (engine.latent_scores); False: off.
     iw_samples: K of the importance-weighted bound on log p(x) the trainer computes over the validation set after each checkpoint's
     validation pass (engine.IWBound, engine.iw_scores), an integer >= 1; 0: off. Early stopping still compares total_loss.
+    class_mmd: multiplier lambda of the class-conditional MMD penalty on z the training steps add to their objective (include/mst_hip.h:
+    mst_class_mmd); the metrics gain class_mmd, the mean penalty per batch, which early stopping does not look at. 0: off.
+    class_mmd_bandwidth: the penalty kernel's bandwidth s2; 0: the latent width.
     YAML-serialisable (Config): a file written before a field existed loads with that field's default."""
 
     def __init__(self, batch_size: int, sampling_frequency: int, checkpoint_frequency: int, num_checkpoints_not_improved: int,
                  optimizer: OptimizerConfig, kl_loss: float, label_smoothing: float, negative_label_downscaling: bool,
                  verbose: bool, dtype: str = "bf16", max_steps: int = 0, kl_warmup_steps: int = 0, kl_cycle_steps: int = 0,
                  kl_free_bits: float = 0.0, lr_warmup_steps: int = 0, clip_global_norm: float = 0.0, ema_decay: float = 0.0,
-                 d_input_dropout: float = 0.0, latent_stats: bool = False, iw_samples: int = 0):
+                 d_input_dropout: float = 0.0, latent_stats: bool = False, iw_samples: int = 0, class_mmd: float = 0.0,
+                 class_mmd_bandwidth: float = 0.0):
         super().__init__()
         if iw_samples != 0:
             check_iw(iw_samples)
@@ -67,6 +72,8 @@ class TrainConfig(Config):
         check_input_dropout(d_input_dropout)
         self.d_input_dropout = d_input_dropout
         self.latent_stats = bool(latent_stats)
+        check_class_mmd(class_mmd, class_mmd_bandwidth)
+        self.class_mmd, self.class_mmd_bandwidth = float(class_mmd), float(class_mmd_bandwidth)
         self.kl_warmup_steps, self.kl_cycle_steps = kl_warmup_steps, kl_cycle_steps
         self.kl_free_bits, self.lr_warmup_steps = kl_free_bits, lr_warmup_steps
         self.batch_size = batch_size
@@ -172,6 +179,12 @@ class Trainer:
         # ... and the per-dimension latent statistics (not a hyper-parameter: a flag of the plan, set in _plan)
         self.latent_stats = bool(getattr(self.config, "latent_stats", False))
         self.last_latent_stats = None  # engine.latent_scores of the latest collect_metrics()
+        # ... and the class-conditional MMD penalty on z (two fields of the plan, set in _plan: no new buffer, no other launch form)
+        self.class_mmd = float(getattr(self.config, "class_mmd", 0.0))
+        self.class_mmd_bandwidth = float(getattr(self.config, "class_mmd_bandwidth", 0.0))
+        check_class_mmd(self.class_mmd, self.class_mmd_bandwidth)
+        if self.class_mmd > 0 and self.rank == 0:
+            print("Class MMD penalty on z: lambda {}, bandwidth {}".format(self.class_mmd, self.class_mmd_bandwidth or "Z"))
         # ... and the importance-weighted bound over the validation set (not a hyper-parameter either: _iw_validation)
         self.iw_samples = getattr(self.config, "iw_samples", 0)
         if self.iw_samples != 0:
@@ -193,6 +206,7 @@ class Trainer:
             plan.track_token_metrics = plan.cfg.kind == "token"  # ppl / acc / topk sums ride on the CE launch
             plan.track_roll_metrics = plan.cfg.kind == "pianoroll"  # tp / pred / pos / cells counts ride on the BCE launch
             plan.track_latent_stats = self.latent_stats  # per-dimension sums of mu / sigma / KL: one launch behind the latent block's
+            plan.class_mmd, plan.class_mmd_s2 = self.class_mmd, self.class_mmd_bandwidth or None  # lambda * L joins the training objective
             plan._trainer_set = True
         return plan
 
@@ -308,7 +322,9 @@ class Trainer:
         gradient norm before clipping over those steps), grad_norm_max and clip_frac: taken from the all-reduced bucket, the same on
         every rank, so nothing to reduce either. With latent_stats on, also active_units, kl_dims_used, kl_dim_max, sigma_rms and
         class_leak (engine.latent_scores of the per-class, per-dimension sums the steps keep, summed over the ranks with the rest);
-        the whole dict of that read, the per-dimension KL included, stays in last_latent_stats."""
+        the whole dict of that read, the per-dimension KL included, stays in last_latent_stats. With class_mmd on, also class_mmd (the
+        mean penalty L per counted batch; data parallel: over every rank's shards, each penalised on its own) and class_mmd_bad (batches
+        whose L was not finite): engine.class_mmd_score of three more sums in the same all-reduce. total_loss stays recon + beta * kl."""
         failure = None
         with torch.cuda.stream(self.stream):  # ordered behind every step launched so far
             try:
@@ -324,16 +340,20 @@ class Trainer:
         keys = [k for k in ("kl_sum", "total_sum", "count", "nll_sum", "acc_hits", "topk_hits", "n_tokens", "roll_tp", "roll_pred", "roll_pos",
                             "roll_cells") if k in m]  # (the counts: float64 is exact far beyond any run's)
         lat = m["lat_stats"] if self.latent_stats else None  # fp64 [classes, 5, Z] sums: they add over the ranks like the rest
+        mmd = np.asarray(m["class_mmd_acc"], np.float64) if self.class_mmd > 0 else None  # {sum L, batches, bad batches}
         if self.dist is not None:
             with torch.cuda.stream(self.stream):
-                t = torch.tensor([m[k] for k in keys] + [1.0 if failure is not None else 0.0] + (lat.ravel().tolist() if lat is not None else []),
-                                 dtype=torch.float64, device=self.model.store.device)
+                t = torch.tensor([m[k] for k in keys] + [1.0 if failure is not None else 0.0] + (mmd.tolist() if mmd is not None else [])
+                                 + (lat.ravel().tolist() if lat is not None else []), dtype=torch.float64, device=self.model.store.device)
                 self.dist.all_reduce(t)
                 vals = t.tolist()
                 m = dict(zip(keys, vals))
                 failed = vals[len(keys)]
+                at = len(keys) + 1
+                if mmd is not None:
+                    mmd, at = np.asarray(vals[at: at + 3], np.float64), at + 3
                 if lat is not None:
-                    lat = np.asarray(vals[len(keys) + 1:], np.float64).reshape(lat.shape)
+                    lat = np.asarray(vals[at:], np.float64).reshape(lat.shape)
             if failed > 0:
                 raise RuntimeError(f"{int(failed)} rank(s) skipped optimizer steps after a failed position-0 tail; the replicas "
                                    "are no longer identical — restart from the last checkpoint with MST_ROW_TAIL=0"
@@ -354,6 +374,8 @@ class Trainer:
         if lat is not None:
             self.last_latent_stats = latent_scores(lat)
             out.update({k: self.last_latent_stats[k] for k in ("active_units", "kl_dims_used", "kl_dim_max", "sigma_rms", "class_leak")})
+        if mmd is not None:
+            out.update(class_mmd_score(mmd))
         return out
 
     def _metric_to_string_output(self, n_batches):

@@ -16,7 +16,7 @@ void set_error(const char* fmt, ...) {
 
 using namespace mst;
 
-extern "C" int mst_version(void) { return 122; }
+extern "C" int mst_version(void) { return 123; }
 extern "C" const char* mst_last_error(void) { return g_err; }
 
 #define HIP_TRY(expr)                                             \

@@ -26,8 +26,8 @@ from ._lib import CE_MAX_WORKGROUPS, ROLL_SLOTS  # noqa: F401  (re-exported)
 from .ops import roundup
 # the engine's parts, re-exported under the names they have always had here
 from .spec import VAEConfig, logical_param_shapes, positional_table, xavier_init  # noqa: F401
-from .step_math import (check_clip, check_ema, check_input_dropout, check_iw, check_schedule, clip_scale, ema_decay_at,  # noqa: F401
-                        ema_update, iw_scores, latent_scores, roll_scores, schedule_values)
+from .step_math import (check_class_mmd, check_clip, check_ema, check_input_dropout, check_iw, check_schedule, class_mmd_score,  # noqa: F401
+                        clip_scale, ema_decay_at, ema_update, iw_scores, latent_scores, roll_scores, schedule_values)
 from .params import Dense, LayerParams, Norm, ParamStore  # noqa: F401
 from .layer_block import (ALL_ROWS, NO_DROPOUT, Dropout, Rows, _Layer, _lead_mask, ffn_bwd_kw, ffn_bwd_parts, layer_wgrads,  # noqa: F401
                           no_partials, position0_rows, row_block_bwd, row_block_fwd, row_tail_selfcheck)
@@ -199,6 +199,13 @@ class StepPlan:
         # Trainer: one launch behind the latent block's adds the batch's per-class, per-dimension sums of mu, mu^2, sigma^2 and kl_d to
         # store.lat_stats (training steps and validation forwards, never inference; not undone by the step guards, as roll_counts)
         self.track_latent_stats = False
+        # Trainer: the class-conditional MMD penalty on z, lambda and the kernel's bandwidth s2 (None: the latent width Z). With
+        # lambda > 0 a training step issues mst_class_mmd directly behind the latent block's backward launch, with the gradient pointers;
+        # a forward without gradient issues the value-only launch behind the latent block's (and the statistics'); inference issues
+        # nothing. 0 (the default): the launches as they were. store.class_mmd_acc is not undone by the step guards, as lat_stats.
+        self.class_mmd, self.class_mmd_s2 = 0.0, None
+        self.class_mmd_issued = None  # the form the sequence issued last took: None, 'value' or 'grad'
+        self.class_mmd_rows = store.class_mmd_rows(B)  # (allocated here, never inside a capture)
         self.logits =None if self.forms.fuse_bce else act(B * T, cfg.out_dim)  # (fused: the logits never reach HBM)
         self.dlogits = act(B * T, cfg.out_dim)
         if cfg.kind == "token":
@@ -329,6 +336,14 @@ class StepPlan:
             # its gradient read them. Training steps only: an inference pass and a validation step (is_train False) see every input —
             # their objective must not move with the option, and they are the launches of a plan without it
             in_drop=self.d_input_dropout > 0 and self._tick_adam and not self._infer)
+
+    def _class_mmd_on(self):
+        check_class_mmd(self.class_mmd, self.class_mmd_s2)
+        return self.class_mmd > 0
+
+    def _class_mmd_s2(self):
+        """the kernel's bandwidth: E|z_i - z_j|^2 = 2 Z under the prior, so s2 = Z unless the caller chose one"""
+        return float(self.class_mmd_s2) if self.class_mmd_s2 else float(self.cfg.latent_dim)
 
     def _attn_proj(self, S, H, D):
         return bool(o.attn_bwd_form(self.adt, self.B, S, H, D // H, 0, D, 2 * D, 3 * D, D, 3 * D, proj=True)["proj"])
@@ -535,6 +550,7 @@ class StepPlan:
         # optimizer() — also when captured as graphs of their own — read the record this forward leaves.)
         F = self.forms = self._resolve_forms(with_grad)
         self._tail_used = dict(fwd=False, bwd=False)
+        self.class_mmd_issued = None
         De, Dd = cfg.e_model, cfg.d_model
         Se, Sd = T, T + 1
         sq_e, sq_d = math.sqrt(float(De)), math.sqrt(float(Dd))
@@ -600,6 +616,9 @@ class StepPlan:
         o.latent_fwd(*lat, proj=proj0)
         if self.track_latent_stats and not self._infer:
             o.latent_dim_stats(self.mu, self.sigma, self.classes, st.lat_stats)
+        if self._class_mmd_on() and not self._infer and not with_grad:  # (a training step: behind the latent backward, backward_early)
+            o.class_mmd(self.z, self.classes, self._class_mmd_s2(), self.class_mmd_rows, st.class_mmd_ticket, st.class_mmd_acc)
+            self.class_mmd_issued = "value"
         if upto == "latent":
             return
         # ---- decoder positions 1..T (model.py:241-245, transformer.py:237)
@@ -841,6 +860,15 @@ class StepPlan:
                          self.sigma, d_x0_d.view(B, Sd, -1), sq_d, self.kl_weight, self.gscale_enc,
                          None, d_enc.view(B, Se, -1), self.lat_scratch,
                          enc_scale=self.gscale_enc / self.gscale, proj=dx0, sched=(st.sched, self.kl) if F.sched else None)
+        if self._class_mmd_on():
+            # lambda * L joins the objective: its gradient is added to d[mu | sigma] (which the flush's outer products read later) and,
+            # through Wl, to d(enc_out). The bucket holds sums over samples at the encoder-side scale, rescaled by
+            # 1 / (global_batch * gscale) at the optimizer: coef = lambda * B * gscale_enc (each rank penalises its own shard)
+            Z = cfg.latent_dim
+            o.class_mmd(self.z, self.classes, self._class_mmd_s2(), self.class_mmd_rows, st.class_mmd_ticket, st.class_mmd_acc,
+                        grad=dict(eps=self.eps, coef=float(self.class_mmd) * B * self.gscale_enc, Wl=st.p("encoder.latent_proj.weight"),
+                                  dlat=self.lat_scratch[B * Dd: B * (Dd + 2 * Z)].view(B, 2 * Z), d_enc_out3=d_enc.view(B, Se, -1)))
+            self.class_mmd_issued = "grad"
         self._cls_job = o.class_job(self.classes, self.lat_scratch, st.grad("decoder.class2hid.weight"), B, Dd)
         self._outers += o.latent_outer_jobs(self.lat_scratch, self.enc_out.view(B, Se, -1), self.z,
                                             st.grad("encoder.latent_proj.weight"), st.grad("encoder.latent_proj.bias"),

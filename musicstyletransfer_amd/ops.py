@@ -862,6 +862,32 @@ def latent_dim_stats(mu, sigma, classes, acc):
     call("mst_latent_dim_stats", B, Z, acc.shape[0], ptr(mu), ld(mu), ptr(sigma), ld(sigma), ptr(classes), ptr(acc), stream())
 
 
+CLASS_MMD_ACC = ("sum", "count", "bad")  # cells of class_mmd's accumulator, in order
+
+
+def class_mmd(z, classes, s2, rows, ticket, acc, grad=None):
+    """the class-conditional MMD penalty L = sum_ij w_ij k_ij of a batch's z (mst_class_mmd): z fp32 [B, Z] view (rows may be padded),
+    classes int32 [B], s2 the kernel's bandwidth; rows fp64 [>= B] receives the per-row terms, acc (fp64 [3]) += {L, 1, 0} or {0, 0, 1}
+    (L not finite), ticket: one int32 word, zero before and after.
+    grad = dict(eps= fp32 [B, Z] view, coef=, Wl= fp32 [2Z, De], dlat= fp32 [B, 2Z] contiguous, d_enc_out3= 16-bit [B, S, >= De]): the
+    launch also adds coef * dL/d[mu | sigma] to dlat and its product with Wl to position 0 of every sample of d_enc_out3"""
+    B, Z = z.shape
+    assert z.dtype == torch.float32 and classes.dtype == torch.int32 and classes.numel() == B and classes.is_contiguous()
+    assert rows.dtype == acc.dtype == torch.float64 and rows.is_contiguous() and rows.numel() >= B
+    assert acc.is_contiguous() and acc.numel() == len(CLASS_MMD_ACC) and ticket.dtype == torch.int32 and ticket.numel() == 1
+    if grad is None:
+        call("mst_class_mmd", 0, B, Z, 1, ptr(z), ld(z), None, 0, ptr(classes), s2, 0.0, None, None, None, 0, ptr(rows), ptr(ticket),
+             ptr(acc), stream())
+        return
+    eps, Wl, dlat, de3 = grad["eps"], grad["Wl"], grad["dlat"], grad["d_enc_out3"]
+    De = Wl.shape[1]
+    assert eps.dtype == Wl.dtype == dlat.dtype == torch.float32 and tuple(eps.shape) == (B, Z)
+    assert Wl.is_contiguous() and Wl.shape[0] == 2 * Z and dlat.is_contiguous() and tuple(dlat.shape) == (B, 2 * Z)
+    assert de3.dim() == 3 and de3.shape[0] == B and de3.shape[2] >= De and de3.stride(2) == 1
+    call("mst_class_mmd", dt(de3), B, Z, De, ptr(z), ld(z), ptr(eps), ld(eps), ptr(classes), s2, grad["coef"], ptr(Wl), ptr(dlat), ptr(de3),
+         de3.stride(0), ptr(rows), ptr(ticket), ptr(acc), stream())
+
+
 IW_STATE = ("m", "s", "s2", "sum_lw", "n", "n_bad")  # cells of iw_fold's per-sample state, in order
 IW_OUT = ("log_px", "elbo", "ess", "n")              # columns of iw_finish's per-sample rows
 IW_ACC = ("log_px", "elbo", "ess", "n", "pieces", "invalid")  # iw_finish's running sums

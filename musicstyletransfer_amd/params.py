@@ -150,6 +150,11 @@ class ParamStore:
         self.roll_counts = torch.zeros(ROLL_SLOTS, 4, dtype=torch.int64, device=device) if cfg.kind == "pianoroll" else None
         # lat_stats = per class and latent dimension {n, sum mu, sum mu^2, sum sigma^2, sum kl_d} (mst_latent_dim_stats; latent_scores)
         self.lat_stats = torch.zeros(cfg.num_classes, 5, cfg.latent_dim, dtype=torch.float64, device=device)
+        # class_mmd_acc = {sum of L over the launches whose L was finite, those launches, the others} of mst_class_mmd (class_mmd_score);
+        # beside it the launch's per-row terms (one per sample of the largest batch so far: class_mmd_rows) and its ticket word
+        self.class_mmd_acc = torch.zeros(3, dtype=torch.float64, device=device)
+        self._class_mmd_rows = [torch.zeros(256, dtype=torch.float64, device=device)]
+        self.class_mmd_ticket = torch.zeros(1, dtype=torch.int32, device=device)
         if params_np is None:
             params_np = xavier_init(cfg, np.random.default_rng(seed))
         self.load_numpy(params_np)
@@ -159,6 +164,13 @@ class ParamStore:
         if self._rng_state is None:
             self._rng_state = torch.tensor([0, 0, seed ^ 0x5DEECE66D, 0], dtype=torch.int64, device=self.device)
         return self._rng_state
+
+    def class_mmd_rows(self, B):
+        """the fp64 [>= B] buffer of mst_class_mmd's per-row terms; a batch larger than any so far gets a larger one, and none is ever
+        freed: captured graphs keep the pointer (call it where a plan is made, never inside a capture)"""
+        if self._class_mmd_rows[-1].numel() < B:
+            self._class_mmd_rows.append(torch.zeros(B, dtype=torch.float64, device=self.device))
+        return self._class_mmd_rows[-1]
 
     def grad_parts(self):
         """the per-workgroup sums of squares a step's mst_grad_sumsq launch leaves for its Adam launches (global-norm clipping), made
@@ -298,8 +310,10 @@ class ParamStore:
             c = self.roll_counts.cpu().sum(0).tolist()
             out.update(roll_tp=int(c[0]), roll_pred=int(c[1]), roll_pos=int(c[2]), roll_cells=int(c[3]))
         out["lat_stats"] = self.lat_stats.cpu().numpy()  # (all zero unless a plan with track_latent_stats ran; latent_scores)
+        out["class_mmd_acc"] = self.class_mmd_acc.cpu().numpy()  # (all zero unless a plan with class_mmd > 0 ran; class_mmd_score)
         if reset:
             o.zero(self.lat_stats)
+            o.zero(self.class_mmd_acc)
             o.zero(self.metric_acc)
             if g_steps > 0:
                 o.zero(self.gstat[2:6])

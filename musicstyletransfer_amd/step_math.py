@@ -49,6 +49,25 @@ def latent_scores(acc, threshold=0.01):
                 sigma_rms=float(np.sqrt((s_s2[seen] / n[seen]).mean())) if seen.any() else nan, class_leak=leak)
 
 
+def class_mmd_score(acc):
+    """the three running sums of ParamStore.read_metrics' 'class_mmd_acc' (mst_class_mmd: sum of L over the launches whose L was
+    finite, those launches, the launches whose L was not finite) as the reported figures: class_mmd = sum / count, the mean penalty
+    L = sum_c (n_c / n) MMD^2(q_c, q_pooled) per counted batch (NaN when none was counted), and class_mmd_bad, the other launches"""
+    acc = np.asarray(acc, np.float64).reshape(-1)
+    if acc.size != 3:
+        raise ValueError(f"class_mmd_score takes the three sums of mst_class_mmd, not {acc.size} values")
+    return dict(class_mmd=float(acc[0] / acc[1]) if acc[1] > 0 else float("nan"), class_mmd_bad=int(acc[2]))
+
+
+def check_class_mmd(class_mmd=0.0, class_mmd_s2=None):
+    """class_mmd: the penalty's multiplier lambda, 0 (off) or positive and finite; class_mmd_s2: the kernel's bandwidth s2, None or 0
+    (the latent width Z) or positive and finite; raises ValueError otherwise (a NaN too)"""
+    if not (0 <= class_mmd < float("inf")):
+        raise ValueError(f"class_mmd must be 0 (off) or a positive finite multiplier, not {class_mmd!r}")
+    if class_mmd_s2 is not None and not (0 <= class_mmd_s2 < float("inf")):
+        raise ValueError(f"class_mmd_s2 (class_mmd_bandwidth) must be 0 (the latent width) or a positive finite bandwidth, not {class_mmd_s2!r}")
+
+
 def iw_scores(acc, cells):
     """the six running sums of IWBound (ops.IW_ACC: sum log_px, sum elbo, sum ess, sum n, pieces counted, pieces invalid — mst_iw_finish)
     as the reported figures, stated once. cells: cells per piece (T * P for a piano-roll, T for a token sequence). Nats per piece:

@@ -9,6 +9,9 @@
 #                         kl_dims_used, kl_dim_max, sigma_rms and class_leak (how much of z's variation is between the classes)
 #   --iw-samples K        after every checkpoint's validation pass, score the validation set with the importance-weighted bound on
 #                         log p(x) from K posterior draws per piece: iw_nll, iw_elbo_nll, iw_gap, iw_ess, iw_bits_per_cell; 0: off
+#   --class-mmd LAMBDA    add LAMBDA times the class-conditional MMD of z (each class's z against the pooled batch, RBF kernel) to the
+#                         training objective, inside the step: the remedy when class_leak is near 1; class_mmd joins the log; 0: off
+#                         (--class-mmd-bandwidth S2: the kernel's bandwidth, 0: the latent width)
 cd "$(dirname "$0")/.." || exit 1
 
 python -m music_style_transfer.VarAutoEncoder.main \
