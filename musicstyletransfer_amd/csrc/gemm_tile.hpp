@@ -1,6 +1,6 @@
 // gemm_tile.hpp — the tile-level device code of the NT GEMM kernels (gemm_nt.hip, and the fused launches built on it: gemm_ln.hip,
 // ffn_ln.hip, gemm_bce.hip, dec_tail.hip): the K loop of one output tile and its epilogue.
-// A header so that launches of OTHER kernels can run GEMM tiles as extra workgroups (row_tail.hip: the idle XCDs of the
+// A header so that launches of OTHER kernels can run GEMM tiles as extra workgroups (row_tail.hpp, tail_ride_bm: the idle XCDs of the
 // one-launch position-0 tails take the decoder's K | Q | V projection and its input gradient off the step's dependent chain).
 #pragma once
 #include <math.h>

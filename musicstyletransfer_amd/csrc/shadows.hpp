@@ -48,7 +48,7 @@ __device__ __forceinline__ void shadow_tile_wg(const float* __restrict__ w, T* _
 }
 
 // FOUR consecutive tiles (tb0 .. tb0 + 3, those below n_total) by one group of 256 threads, every load of the four requested before
-// the first is used: a rider workgroup pays one memory round trip per 16 tiles instead of one per 4 (row_tail.hip). tiles: 4 x 32 x 33
+// the first is used: a rider workgroup pays one memory round trip per 16 tiles instead of one per 4 (row_tail.hpp: tail_shadow_ticket). tiles: 4 x 32 x 33
 // floats of LDS; every thread of the workgroup reaches the one barrier.
 template <typename T>
 __device__ __forceinline__ void shadow_tile_quad(const float* __restrict__ w, T* __restrict__ wt16, const int64_t* __restrict__ desc,

@@ -182,7 +182,7 @@ def row_tail_selfcheck(store, B=64, S=2):
     """One-time start-up check of the one-launch position-0 tails (mst_row_tail_fwd / _bwd) on THIS device, process and
     partition mode: both are run against the five launches the engine falls back to — row_block_fwd / row_block_bwd in both forms —
     on random rows and the store's own top-layer weights. Their grid barrier rests on properties no API guarantees (enough workgroups
-    of an oversubscribed launch landing on one XCD, L1 behaviour of write-through lines — csrc/row_tail.hip), so shape alone does not
+    of an oversubscribed launch landing on one XCD, L1 behaviour of write-through lines — csrc/row_tail.hpp), so shape alone does not
     decide whether the fused form is used: a mismatch, an unfinished barrier or a status flag pins the store to the five-launch form."""
     store.tail_checked = True
     cfg, dev, adt = store.cfg, store.device, store.act_dtype
